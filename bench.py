@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: lossless encode + decode of 640x512 uint16 IR frames on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W          (N = 1)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]          (N = 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one pass of the hot path over one device-resident batch: lossless encode (rir_codec_encode_packed_device: ONE
@@ -9,12 +9,16 @@ kernel that leaves the PACKED form of the encoded batch - record headers, a (pos
 and the payload without holes in a buffer of HALF the raw size; `encoded_footprint_bytes` says what it occupies) then decode
 (rir_codec_decode_packed_device) on BASELINE.json configs[1] (1 000-frame 640x512 uint16 stream, recipe S1) -
 per rank: two launches that move 4WH + 2C bytes (+ 6 % of the frames re-read where the waves of a segment meet in time).
-Beside it, as extra keys: `slotted_form` (round 3's step: the encoder's worst-case slots decoded in place - faster, but the
-encoded batch is larger than its input) and `dense_file_form` (the canonical ordered stream of the file format: one more
-pass).  Ranks hold independent shards (weak scaling, no collective in that data path): `value` = frames all ranks processed /
+Ranks hold independent shards (weak scaling, no collective in that data path): `value` = frames all ranks processed /
 the slowest rank's time.
 
-N > 1 additionally times, in the same run and with the same bracket, the step WITH the exchange north_star names
+A plain run sets up, warms up (W steps, K steps, one second of steps, W steps again), times exactly K steps, checks that they
+decoded their input bit for bit, writes the outputs of the last timed step when --dump-outputs DIR is given (dump_outputs) and
+prints the line.  Everything else is measured with --full only: the keys listed below, `slotted_form` (round 3's step: the
+encoder's worst-case slots decoded in place - faster, but the encoded batch is larger than its input), `dense_file_form` (the
+canonical ordered stream of the file format: one more pass), the single-pass encoder, `spread` and `value_from_idle`.
+
+N > 1 with --full additionally times, in the same run and with the same bracket, the step WITH the exchange north_star names
 (every GPU ends up holding the whole decoded stream), in both forms of librir_amd/distributed.py:
   value_with_exchange             encode, decode in sub-batches, all-gather of the DECODED frames per sub-batch on the
                                   communicator's stream while the next sub-batch decodes
@@ -22,11 +26,11 @@ N > 1 additionally times, in the same run and with the same bracket, the step WI
                                   rank's chunks on arrival into the reassembled stream
 each with the bytes a rank receives, its GB/s and the fraction of the per-GPU xGMI budget.
 
-One JSON line is printed by rank 0: whole-job frames/s, plus
+One JSON line is printed by rank 0: whole-job frames/s, plus with --full
   roofline      - the dominant kernel's algorithmic bytes / its HIP-event duration vs 8 TB/s
   cpu_baseline  - the oracle (plain-C port) timed on a bounded sample of the same workload: 1 core, and all cores of
-                  this process's CPU share over independent chunks; the compiled reference's filters when oracle/_ref
-                  travelled with the snapshot
+                  this process's CPU share over independent chunks; the compiled reference's filters where oracle/_ref
+                  was built
   per_frame_abi_fps / batched_h2d_d2h_fps - SURVEY §8d's other two numbers for the same configuration (N = 1)
 """
 import argparse
@@ -62,7 +66,13 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="the CPU oracle repeats passes until this much time is spent")
     p.add_argument("--exchange-piece", type=int, default=100, help="frames per sub-batch of the decoded all-gather (whole chunks)")
     p.add_argument("--exchange-chunks", type=int, default=4, help="chunks per piece of the compressed all-gather")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true", help="also the CPU baseline, the host-pointer numbers, the roofline, the other forms of the step, "
+                                                       "the spread and, N > 1, the exchange (a plain run measures the headline alone)")
+    p.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, 64 MB at most)")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ---- CPU baseline ------------------------------------------------------------------------------------------
@@ -375,6 +385,60 @@ def other_paths(D, frames, h, w):
     return res
 
 
+DUMP_SEED = 20240611
+
+
+def _sample_rows(nrows, row_bytes, budget):
+    """None (every row fits in `budget` bytes) or the sorted indices of a fixed, seeded sample of rows that does"""
+    if nrows * row_bytes <= budget:
+        return None
+    k = max(1, min(nrows, budget // row_bytes))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(nrows, k, replace=False))
+
+
+def _words_f64(words):
+    """int64 words -> float64 (..., 2): their low and high 32-bit halves, each exact in a float64"""
+    return np.ascontiguousarray(words).view(np.uint32).reshape(words.shape + (2,)).astype(np.float64)
+
+
+def dump_outputs(d, out, batch):
+    """What a caller of the step receives from its last launch pair, as DIR/<name>.npy (64 MB at most; a fixed, seeded sample of what is larger):
+      decoded          float32 (frames, H, W) - the decoder's output (a sample of the frames; of the pixels, should one frame be over its share)
+      headers          float64 (chunks, tiles, gop, 2) - the record headers, 32-bit halves of each word
+      segment_words    float64 (chunks, tiles) - the payload length of every (chunk, tile) segment
+      payload          float64 (words, 2) - the payload of a sample of the segments, in segment order, 32-bit halves of each word
+    The positions of the segments inside the stream buffer are left out: they follow the order in which the packing kernel's workgroups
+    finish, and differ from run to run; what each segment holds does not."""
+    import torch
+
+    os.makedirs(d, exist_ok=True)
+    n, h, w = out.shape
+    rows = _sample_rows(n, h * w * 4, 32 << 20)
+    v = out.view(torch.int16)  # (a uint16 tensor cannot be indexed on the device)
+    if rows is not None and h * w * 4 > 32 << 20:  # (one frame over its share: a sample of the pixels of the whole batch)
+        dec = v.reshape(-1)[torch.from_numpy(_sample_rows(n * h * w, 4, 32 << 20)).to(out.device)]
+    else:
+        dec = v if rows is None else v[torch.from_numpy(rows).to(out.device)]
+    np.save(os.path.join(d, "decoded.npy"), dec.cpu().numpy().view(np.uint16).astype(np.float32))
+    hdr = batch.hdr.cpu().numpy()
+    rows = _sample_rows(hdr.shape[0], hdr[0].nbytes * 2, 8 << 20)
+    np.save(os.path.join(d, "headers.npy"), _words_f64(hdr if rows is None else hdr[rows]))
+    seg = batch.seg_words.cpu().numpy().astype(np.int64)
+    rows = _sample_rows(seg.shape[0], seg[0].size * 8, 4 << 20)
+    np.save(os.path.join(d, "segment_words.npy"), (seg if rows is None else seg[rows]).astype(np.float64))
+    # the payload: whole segments of a seeded order, as many as 16 MB of halves hold (at least one), written in (chunk, tile) order
+    pos, seg = batch.seg_pos.cpu().numpy().reshape(-1), seg.reshape(-1)
+    take, words = [], 0
+    for s in np.random.default_rng(DUMP_SEED).permutation(seg.size):
+        if take and (words + seg[s]) * 16 > 16 << 20:
+            break
+        take.append(s)
+        words += seg[s]
+    take.sort()
+    pay = torch.cat([batch.stream[int(pos[s]):int(pos[s]) + int(seg[s])] for s in take]).cpu().numpy() if take else np.zeros(0, np.int64)
+    np.save(os.path.join(d, "payload.npy"), _words_f64(pay[:(16 << 20) // 16]))
+
+
 def check_world(ranks_seen, gpus, bus_ids, share_gpu):
     """The N > 1 line must be able to prove what it ran on: the communicator saw every rank, and no two ranks sat on one GPU.
     -> None, or the reason the run is refused (no `value` is printed then, exit status 3)."""
@@ -466,13 +530,13 @@ def main():
         return
     # the CPU path is timed beside the N=1 run only, before this process touches the GPU (forked workers)
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(frames_np, gop, args.cpu_frames, args.cpu_seconds)
     # The per-frame / batched host-pointer numbers come from a process of their own, run to completion before this one touches
     # the GPU: the per-frame path encodes and decodes chunk by chunk (50-frame launches of the same kernels), which would mix
     # into the per-kernel averages of a rocprofv3 --stats run of this command (profiles/: one stats file per process).
     extra_abi = {}
-    if world == 1 and not args.no_abi:
+    if args.full and world == 1 and not args.no_abi:
         import subprocess
 
         r = subprocess.run([sys.executable, os.path.abspath(__file__), "--abi-child", "--frames", str(n), "--width", str(w), "--height", str(h),
@@ -529,7 +593,7 @@ def main():
     from librir_amd.distributed import CompressedGather, FrameGather, shard_plan
 
     frames = torch.from_numpy(frames_np).to(dev)
-    ctx = D.CodecContext(w, h, n, gop, device=dev)  # (the slotted and the dense form, timed beside the step)
+    ctx = D.CodecContext(w, h, n, gop, device=dev) if args.full else None  # (the slotted and the dense form, timed beside the step)
     pc = D.PackedCodec(w, h, n, gop, device=dev)    # the step: stream buffer = the 8 bit-per-pixel budget (half the raw bytes)
     out = torch.empty_like(frames)
 
@@ -584,6 +648,53 @@ def main():
     code, low_words, high_words, arena_words = pc.status()
     if code != 0:
         raise SystemExit("bench.py: the encoded batch did not fit its budget (code %d) - refusing to report a number" % code)
+    # ---- parity gate before any number is reported: the timed steps decoded their input, bit-exact ----
+    batch = pc.finish()
+    payload_bytes = batch.payload_bytes()
+    if not torch.equal(out.view(torch.int16), frames.view(torch.int16)) or int(pc.error.item()) != 0:
+        raise SystemExit("bench.py: decode(encode(x)) != x - refusing to report a number")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, batch)
+
+    fps = n * K * world / dt
+    raw = 2.0 * h * w * n  # bytes of raw uint16 per batch
+    tables_bytes = batch.nbytes() - payload_bytes
+    line = {
+        "metric": "IR frames/sec encode+decode, 640x512 uint16",
+        "value": fps,
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": args.warmup,
+        "ms_per_step": dt / K * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u16",
+        "data": "synthetic",
+        "config": {"workload": "configs[1]: %d-frame %dx%d uint16 stream (S1 noisy background, seed 1234+rank), lossless RIRB1 "
+                               "encode+decode, device-resident, GOP %d, per GPU; two launches per step: the encoder leaves the PACKED "
+                               "form (headers + position and length per segment + the payload without holes: encoded_footprint_bytes, "
+                               "in a buffer of half the raw size), the decoder reads it as it is; the compressed payload (17 %% of a "
+                               "pass's bytes) is written and read back through the 256 MiB Infinity Cache, the raw frames (655 MB "
+                               "each way) stream from / to HBM" % (n, w, h, gop),
+                   "frames_per_gpu": n, "width": w, "height": h, "gop": gop, "sharding": "independent shard per rank"},
+        "bit_exact_roundtrip": True,
+        "value_excludes_exchange": True if dist_on else None,
+        "step_alg_bytes": 2.0 * raw + 2.0 * (payload_bytes + tables_bytes),
+        "step_alg_frac_of_hbm_peak": (2.0 * raw + 2.0 * (payload_bytes + tables_bytes)) / (dt / K) / 1e9 / HBM_PEAK_GBS,
+        "roundtrip_raw_GBs": fps * 4.0 * h * w / 1e9 / world,
+        "roundtrip_raw_frac_of_hbm_peak": fps * 4.0 * h * w / 1e9 / world / HBM_PEAK_GBS,
+    }
+    if identity:
+        line.update(identity)
+    if not args.full and not args.profile:
+        if rank == 0:
+            print(json.dumps(line))
+        if dist_on:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the same K steps once more with HIP events between the launches (on the stream the kernels run on): the per-kernel
     # durations of the roofline.  An event between two launches keeps the second kernel from starting under the tail of the
@@ -605,11 +716,8 @@ def main():
     ms_tiles = sum(ev[k][0].elapsed_time(ev[k][1]) for k in range(K)) / K
     ms_decode = sum(ev[k][1].elapsed_time(ev[k][2]) for k in range(K)) / K
 
-    # ---- parity gate before any number is reported: decoded stream == input, bit-exact ----
-    ok = torch.equal(out.view(torch.int16), frames.view(torch.int16)) and int(pc.error.item()) == 0
-    batch = pc.finish()
-    payload_bytes = batch.payload_bytes()
-    if not ok:
+    # ---- the same parity gate on what this region decoded ----
+    if not torch.equal(out.view(torch.int16), frames.view(torch.int16)) or int(pc.error.item()) != 0:
         raise SystemExit("bench.py: decode(encode(x)) != x - refusing to report a number")
 
     # ---- spread, and a GPU that is visibly busy: the same K-step region again and again until BUSY_S seconds of it have run (a utilisation
@@ -670,7 +778,6 @@ def main():
     if int(ctx.error.item()) != 0 or not torch.equal(out.view(torch.int16), frames.view(torch.int16)) or enc.total_words() * 8 != payload_bytes:
         raise SystemExit("bench.py: the dense form does not decode to the input - refusing to report a number")
 
-    tables_bytes = batch.nbytes() - payload_bytes
     extra = {"encoded_footprint_bytes": batch.nbytes(), "raw_bytes": int(2 * h * w * n),
              "value_from_idle": n * K * world / dt_idle,
              "value_from_idle_note": "the same K steps after the same W warm-up steps on a device that had been idle (no ramp): %d steps of set-up ran between "
@@ -715,7 +822,6 @@ def main():
         if not emitted.acquire(blocking=False):
             return
         if rank == 0:
-            raw = 2.0 * h * w * n  # bytes of raw uint16 per batch
             kernels = {
                 "rirb1_encode_packed": {"ms": ms_tiles, "alg_bytes": raw + payload_bytes + tables_bytes},
                 "rirb1_decode_tiles": {"ms": ms_decode, "alg_bytes": raw + payload_bytes + tables_bytes},
@@ -733,34 +839,9 @@ def main():
                     traffic = json.load(open(tpath)).get(dom, {}).get("hbm_bytes_per_launch")
                 except Exception:
                     traffic = None
-            fps = n * K * world / dt
-            res = {
-                "metric": "IR frames/sec encode+decode, 640x512 uint16",
-                "value": fps,
-                "unit": "frames/s",
-                "n_gpus": world,
-                "steps": K,
-                "warmup": args.warmup,
-                "ms_per_step": dt / K * 1e3,
-                "higher_is_better": True,
-                "scaling": "weak",
-                "vs_baseline": None,
-                "dtype": "u16",
-                "data": "synthetic",
-                "config": {"workload": "configs[1]: %d-frame %dx%d uint16 stream (S1 noisy background, seed 1234+rank), lossless RIRB1 "
-                                       "encode+decode, device-resident, GOP %d, per GPU; two launches per step: the encoder leaves the PACKED "
-                                       "form (headers + position and length per segment + the payload without holes: encoded_footprint_bytes, "
-                                       "in a buffer of half the raw size), the decoder reads it as it is; the compressed payload (17 %% of a "
-                                       "pass's bytes) is written and read back through the 256 MiB Infinity Cache, the raw frames (655 MB "
-                                       "each way) stream from / to HBM" % (n, w, h, gop),
-                           "frames_per_gpu": n, "width": w, "height": h, "gop": gop, "sharding": "independent shard per rank"},
-                "bit_exact_roundtrip": True,
-                "value_excludes_exchange": True if dist_on else None,
-                "step_alg_bytes": 2.0 * raw + 2.0 * (payload_bytes + tables_bytes),
-                "step_alg_frac_of_hbm_peak": (2.0 * raw + 2.0 * (payload_bytes + tables_bytes)) / (dt / K) / 1e9 / HBM_PEAK_GBS,
+            res = dict(line)
+            res.update({
                 "compression_ratio": raw / cbytes,
-                "roundtrip_raw_GBs": fps * 4.0 * h * w / 1e9 / world,
-                "roundtrip_raw_frac_of_hbm_peak": fps * 4.0 * h * w / 1e9 / world / HBM_PEAK_GBS,
                 "roofline": {"kernel": dom, "bound": "hbm", "achieved": kernels[dom]["GBs"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
                              "frac": kernels[dom]["GBs"] / HBM_PEAK_GBS, "traffic": traffic,
                              "traffic_source": ("%s (static: rocprofv3 --pmc passes of an earlier run of this command, not measured in this run)"
@@ -769,12 +850,11 @@ def main():
                              "measured": "HIP events between the launches of a K-step region that follows the timed one (ms_per_step_with_events)"},
                 "ms_per_step_with_events": dt_events / K * 1e3,
                 "kernels": kernels,
-            }
+            })
             res.update(extra)
             if exchange:
                 res.update(exchange)
             if identity:
-                res.update(identity)
                 ref1 = newest_n1_value()
                 res["n1_reference_value"] = ref1
                 res["scaling_factor_vs_n1_reference"] = (fps / ref1["value"]) if ref1 else None

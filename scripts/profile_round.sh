@@ -1,12 +1,13 @@
 #!/bin/bash
-# Round profile on the GPU box: kernel-trace stats of the default bench command + PMC passes.
+# Round profile on the GPU box: kernel-trace stats of the bench command with everything it measures (--full) + PMC passes.
 #   gpurun -- bash scripts/profile_round.sh r01
 set -u
 TAG=${1:-r01}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profile_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python $GRAFT_REPO_ROOT/bench.py > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python "$ROOT/bench.py" --full > $OUT/bench_under_rocprof.json 2> $OUT/stats.err
 # one stats file per process: bench.py measures its per-frame ABI numbers in a child process (50-frame launches of the same kernels);
 # the file of the bench process itself is the one with the most rirb1_decode_tiles time
 python - <<PY
@@ -22,7 +23,7 @@ PY
 cd $GRAFT_REPO_ROOT && bash scripts/pmc.sh $TAG > /dev/null 2>&1
 python scripts/pmc_summary.py gpurun_out/pmc_$TAG > $OUT/pmc_summary.json
 python scripts/pmc_traffic.py $OUT/pmc_summary.json > $OUT/pmc_traffic.json
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # the constant-budget form of the bounded-loss step (one 640x512 stream, 1 000 frames per call): kernel times and HBM bytes
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/lossy_const_stats -- python3 $GRAFT_REPO_ROOT/tests/perf/lossy_const_time.py 1000 1 > $OUT/lossy_const.log 2>&1

@@ -1,3 +1,4 @@
+import hashlib
 import json
 import os
 import subprocess
@@ -47,6 +48,57 @@ def ref():
     if not Ref.available():
         pytest.skip("oracle/_ref not built here (needs /root/reference)")
     return Ref()
+
+
+REF_ANSWERS = os.path.join(ROOT, "tests", "golden", "reference_answers.json")
+
+
+class RefAnswers:
+    """The compiled reference's answer to each case: asked live where oracle/_ref was built, else as recorded in
+    tests/golden/reference_answers.json (a sha256 of the answer's dtypes, shapes and bytes, per case).  With oracle/_ref built,
+    RIR_RECORD_REF_ANSWERS=1 rewrites the recorded answers of the cases that ran from the live ones."""
+
+    def __init__(self):
+        from oracle.pyoracle import Ref
+
+        self.ref = Ref() if Ref.available() else None
+        with open(REF_ANSWERS) as f:
+            self.recorded = json.load(f)
+        self.record = {} if os.environ.get("RIR_RECORD_REF_ANSWERS") and self.ref is not None else None
+
+    @staticmethod
+    def digest(arrays):
+        m = hashlib.sha256()
+        for a in arrays:
+            a = np.ascontiguousarray(a)
+            m.update(("%s %s|" % (a.dtype.str, a.shape)).encode())
+            m.update(a.tobytes())
+        return m.hexdigest()[:32]
+
+    def check(self, key, got, ask):
+        """`got` (an array or a tuple of arrays) equals `ask(ref)`, the reference's answer; `key` names the case within the suite"""
+        got = tuple(got) if isinstance(got, (tuple, list)) else (got,)
+        if self.ref is None:
+            assert key in self.recorded, "no recorded reference answer for %r" % key
+            assert self.digest(got) == self.recorded[key], key
+            return
+        want = ask(self.ref)
+        want = tuple(want) if isinstance(want, (tuple, list)) else (want,)
+        assert len(got) == len(want) and all(np.array_equal(a, b) for a, b in zip(got, want)), key
+        if self.record is not None:
+            assert self.digest(got) == self.digest(want), "equal but not bit for bit: %r" % key
+            self.record[key] = self.digest(want)
+
+
+@pytest.fixture(scope="session")
+def ref_answers():
+    r = RefAnswers()
+    yield r
+    if r.record:
+        r.recorded.update(r.record)
+        with open(REF_ANSWERS, "w") as f:
+            json.dump(r.recorded, f, indent=0, sort_keys=True)
+            f.write("\n")
 
 
 @pytest.fixture(scope="session")

@@ -133,19 +133,16 @@ def test_handle_registry_and_log(lib):
     assert lib.get_last_log_error(None, ct.byref(n)) == -1 and n.value > 0
 
 
-def test_hash_bytes_matches_reference(lib):
-    from oracle.pyoracle import Ref
+def test_hash_bytes_matches_reference(lib, ref_answers):
+    def hash_bytes(so, buf, n):
+        so.hash_bytes.argtypes = [ct.c_void_p, ct.c_size_t]
+        so.hash_bytes.restype = ct.c_size_t
+        return np.uint64(so.hash_bytes(buf.ctypes.data, n))
 
-    if not Ref.available():
-        pytest.skip("oracle/_ref not built here")
-    r = Ref()
-    for f in (lib.hash_bytes, r.lib.hash_bytes):
-        f.argtypes = [ct.c_void_p, ct.c_size_t]
-        f.restype = ct.c_size_t
     rng = np.random.default_rng(0)
     for n in [0, 1, 7, 8, 9, 15, 16, 31, 1000]:
         buf = rng.integers(0, 256, max(n, 1)).astype(np.uint8)
-        assert lib.hash_bytes(buf.ctypes.data, n) == r.lib.hash_bytes(buf.ctypes.data, n)
+        ref_answers.check("hash_bytes %d" % n, hash_bytes(lib, buf, n), lambda ref: hash_bytes(ref.lib, buf, n))
 
 
 def test_resident_capacity_rule_and_plan(lib):

@@ -18,7 +18,7 @@ def test_bench_exchange_runs_on_rccl_with_one_rank():
     env = dict(os.environ, RIR_BENCH_RCCL_SOLO="1")
     for k in ("RIR_BENCH_BACKEND", "RIR_BENCH_SHARE_GPU", "WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--no-abi", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-abi", "--no-cpu-baseline",
                         "--frames", "200"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-1500:])
     line = json.loads(r.stdout.strip().splitlines()[-1])
