@@ -107,6 +107,20 @@ extern "C"
 	 * open (another kind of file or geometry, a read-back filter switched on) and the caller goes image by image; -1 on failure. */
 	int rir_transcode_images(int camera, int saver, int first, int count, const int64_t *timestamps_ns, int keep_attributes);
 
+	/* Images first + k * step (k < count, step >= 1) of an open camera into d_out, [count][h][w] C-contiguous, in any memory the device can
+	 * write: dtype 'H' uint16, 'f' float32 (the uint16 value, exactly).  Bit for bit what load_image / load_imageF give for the same camera
+	 * state - bad-pixel repair, motion correction, MIN_T included - and the camera's per-read state (last image, its attributes, the value
+	 * get_last_image_raw_value reads, the read-ahead) is left as it was.  RIRB files are decoded on the device a batch of chunks at a time
+	 * (only their compressed form crosses the link); raw and ZFile images are read on the host and uploaded.  The work is ordered after what
+	 * is queued on `stream` (a hipStream_t, NULL: the null stream).  Returns count once the images are in d_out; -1 on failure: a bad
+	 * argument, out_bytes < count x h x w x element size, a corrupted chunk, no device. */
+	int rir_load_images_device(int camera, int first, int count, int step, int dtype, void *d_out, long long out_bytes, void *stream);
+	/* `count` uint16 frames [count][h][w] in device memory appended to an open lossless saver, after the frames added before them (host
+	 * frames staged by h264_add_image_lossless included), with the time stamps timestamps_ns[count] and no per-image attributes.  The
+	 * frames are read after the work queued on `stream`; the call returns when the caller may reuse d_frames (chunks are encoded and
+	 * written as for host frames).  Returns count; -2 for a saver that records with bounded loss (h264_add_image_lossy); -1 on failure. */
+	int rir_add_images_device(int saver, const unsigned short *d_frames, int count, const int64_t *timestamps_ns, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

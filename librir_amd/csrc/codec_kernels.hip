@@ -20,6 +20,7 @@
 //   * decode is the mirror image (the transpose is an involution);
 //   * 4 independent waves per 256-thread workgroup; grid = (ntiles/4) x nchunks >> 256 CUs.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -1586,17 +1587,37 @@ namespace rir
 		return o;
 	}
 
-	template <bool FAST>
-	__device__ __forceinline__ void decode_tile(const uint64_t *__restrict__ my_hdr, const uint64_t *__restrict__ in_ptr, uint32_t seg_len,
-												int64_t npx, int nf, int64_t frame0, int tile, int lane, uint16_t *__restrict__ frames,
-												int *__restrict__ error_flag)
+	// where decode_tile puts a reconstructed record: every frame of the chunk at its place in `frames`
+	struct ChunkSink
 	{
-		const int64_t p0 = (int64_t)tile * RIRB1_TILE_PX + lane * 8;
+		uint16_t *frames, *tile0;
+		int64_t npx, frame0, p0;
+		uint32_t lane_off;
+		__device__ __forceinline__ ChunkSink(uint16_t *frames_, int64_t npx_, int64_t frame0_, int tile, int lane)
+			: frames(frames_), tile0(frames_ + frame0_ * npx_ + (int64_t)tile * RIRB1_TILE_PX), npx(npx_), frame0(frame0_),
+			  p0((int64_t)tile * RIRB1_TILE_PX + lane * 8), lane_off((uint32_t)lane * 16u)
+		{
+		}
+		template <bool FAST>
+		__device__ __forceinline__ void put(int f, const Px8 &o)
+		{
+			if (FAST)
+				buf_store8(tile0 + (int64_t)f * npx, lane_off, o);
+			else
+				store8(frames, frame0 + f, npx, p0, false, o);
+		}
+	};
+
+	// The record walk of one tile over frames 0 .. nf - 1 of a chunk; sink.put<FAST>(f, pixels) takes each reconstructed frame.
+	// check_end: the walk covers the whole segment, so it must end exactly at its last word (a walk that stops early - the selective
+	// decode - checks every record it reads against the segment, not what lies behind the last one).
+	template <bool FAST, class Sink>
+	__device__ __forceinline__ void decode_tile(const uint64_t *__restrict__ my_hdr, const uint64_t *__restrict__ in_ptr, uint32_t seg_len,
+												int nf, bool check_end, int lane, Sink &sink, int *__restrict__ error_flag)
+	{
 		const TransposeConsts tc = make_transpose_consts(lane);
 		const LaneConsts lc = make_lane_consts(lane);
 		const __amdgpu_buffer_rsrc_t in = make_rsrc(in_ptr, seg_len * 8u);
-		const uint32_t lane_off = (uint32_t)lane * 16u;
-		uint16_t *tile0 = frames + frame0 * npx + (int64_t)tile * RIRB1_TILE_PX;
 
 		Px8 prev;
 		prev.d[0] = prev.d[1] = prev.d[2] = prev.d[3] = 0;
@@ -1648,10 +1669,7 @@ namespace rir
 			_Pragma("unroll") for (int k = 0; k < 4; ++k) o.d[k] = pk_add16(prev.d[k] & keep, o.d[k]);              \
 			err |= (mode == RIRB1_MODE_LEFT);                                                                        \
 		}                                                                                                            \
-		if (FAST)                                                                                                    \
-			buf_store8(tile0 + (int64_t)(f0 + fr) * npx, lane_off, o);                                               \
-		else                                                                                                         \
-			store8(frames, frame0 + f0 + fr, npx, p0, false, o);                                                     \
+		sink.template put<FAST>(f0 + fr, o);                                                                         \
 		prev = o;                                                                                                    \
 	}
 			for (int fb = 0; fb < nr; fb += 4)
@@ -1663,7 +1681,7 @@ namespace rir
 			}
 #undef RIR_DEC_STEP
 		}
-		if ((err || pos != seg_len) && lane == 0)
+		if ((err || (check_end && pos != seg_len)) && lane == 0)
 			atomicExch(error_flag, 1);
 	}
 
@@ -1741,10 +1759,131 @@ namespace rir
 			in = stream + c0 + t0;
 		}
 		const bool fast = ((npx & 7) == 0) && ((int64_t)(tile + 1) * RIRB1_TILE_PX <= npx) && ((((uintptr_t)frames) & 15) == 0);
+		ChunkSink sink(frames, npx, f_begin, tile, lane);
 		if (fast)
-			decode_tile<true>(my_hdr, in, seg_len, npx, nf, f_begin, tile, lane, frames, error_flag);
+			decode_tile<true>(my_hdr, in, seg_len, nf, true, lane, sink, error_flag);
 		else
-			decode_tile<false>(my_hdr, in, seg_len, npx, nf, f_begin, tile, lane, frames, error_flag);
+			decode_tile<false>(my_hdr, in, seg_len, nf, true, lane, sink, error_flag);
+	}
+
+	// ---- selective decode into the caller's buffer (rir_load_images_device) ----------------------------------------------
+	// Where decode_tile puts a record of the selective decode: frame f of the walk is stored when it is the next one the entry selects
+	// (first, first + step, ...), at its output slot - the store of a skipped frame points out of range (no branch around it, the walk
+	// keeps its counted waits).  MIN_T (IRFileLoader.cpp:1173-1179) is added to the first min_px pixels of every stored frame, after the
+	// reconstruction (the next frame is predicted from the stored value without it); F32: the value converted exactly (load_imageF).
+	template <bool F32>
+	struct SelectSink
+	{
+		char *cur;		 // this wave's tile in the output frame the next stored frame goes to
+		int64_t fbytes;	 // bytes of an output frame
+		int next, step;	 // next local frame to store, distance to the one after it
+		int npx, p0;	 // pixels of a frame (< 2^31: ChunkCodec::prepare), first pixel of this lane
+		uint32_t lane_off, min_t;
+		int nmin;		 // pixels of this lane's eight that get min_t
+		__device__ __forceinline__ Px8 add_min(Px8 o) const
+		{
+			if (min_t)
+			{
+#pragma unroll
+				for (int k = 0; k < 4; ++k)
+					o.d[k] = pk_add16(o.d[k], (2 * k < nmin ? min_t : 0u) | (2 * k + 1 < nmin ? min_t << 16 : 0u));
+			}
+			return o;
+		}
+		// (the walk ends at the last selected frame, so a skipped frame always lies before a selected one: `cur` is inside the output)
+		template <bool FAST>
+		__device__ __forceinline__ void put(int f, const Px8 &r)
+		{
+			const bool sel = f == next; // (wave-uniform)
+			const Px8 o = add_min(r);
+			if (FAST)
+			{
+				if (F32)
+				{
+					v4u32 a, b;
+					a.x = __builtin_bit_cast(uint32_t, (float)(o.d[0] & 0xffffu)), a.y = __builtin_bit_cast(uint32_t, (float)(o.d[0] >> 16));
+					a.z = __builtin_bit_cast(uint32_t, (float)(o.d[1] & 0xffffu)), a.w = __builtin_bit_cast(uint32_t, (float)(o.d[1] >> 16));
+					b.x = __builtin_bit_cast(uint32_t, (float)(o.d[2] & 0xffffu)), b.y = __builtin_bit_cast(uint32_t, (float)(o.d[2] >> 16));
+					b.z = __builtin_bit_cast(uint32_t, (float)(o.d[3] & 0xffffu)), b.w = __builtin_bit_cast(uint32_t, (float)(o.d[3] >> 16));
+					const __amdgpu_buffer_rsrc_t r4 = make_rsrc(cur, RIRB1_TILE_PX * 4);
+					__builtin_amdgcn_raw_buffer_store_b128(a, r4, sel ? lane_off * 2u : RIR_OOB, 0, RIR_FRAME_STORE_AUX);
+					__builtin_amdgcn_raw_buffer_store_b128(b, r4, sel ? lane_off * 2u + 16u : RIR_OOB, 0, RIR_FRAME_STORE_AUX);
+				}
+				else
+				{
+					v4u32 v;
+					v.x = o.d[0], v.y = o.d[1], v.z = o.d[2], v.w = o.d[3];
+					__builtin_amdgcn_raw_buffer_store_b128(v, make_rsrc(cur, RIRB1_TILE_PX * 2), sel ? lane_off : RIR_OOB, 0, RIR_FRAME_STORE_AUX);
+				}
+			}
+			else if (sel)
+			{
+#pragma unroll
+				for (int k = 0; k < 8; ++k)
+				{
+					const uint32_t v = (o.d[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+					if (p0 + k < npx)
+					{
+						if (F32)
+							reinterpret_cast<float *>(cur)[lane_off / 2u + k] = (float)v;
+						else
+							reinterpret_cast<uint16_t *>(cur)[lane_off / 2u + k] = (uint16_t)v;
+					}
+				}
+			}
+			if (sel)
+				next += step, cur += fbytes;
+		}
+	};
+
+	// grid = (ceil(ntiles/4), entries), block = 256.  Entry e (RirbSelect, filter_kernels.h) names a chunk of the batch - its tables at
+	// hdr_table + chunk * ntiles * gop, tile_off + chunk * (ntiles + 1), its payload at stream[chunk_off[chunk] ...) - and the frames
+	// of it to store.  Tables and entries are untrusted like the file they come from: every check of the dense form, plus the entry's
+	// own (a walk inside the chunk and inside the hdr table, output slots inside `out`); a failed check or a malformed record raises
+	// *error_flag.  The walk stops at the last selected frame: frames behind it are neither decoded nor read.
+	// FAST: tiles [tile0, tile_end) lie whole inside the frame, npx is a multiple of 8 and `out` 16-byte aligned (the host launches the
+	// tiles that do so with FAST, the rest - the frame's last, cut tile - without).
+	template <bool F32, bool FAST>
+	__attribute__((amdgpu_waves_per_eu(8, 8))) __global__ __launch_bounds__(256) void rirb1_decode_select(
+		const uint64_t *__restrict__ hdr_table, const uint32_t *__restrict__ tile_off, const uint64_t *__restrict__ chunk_off, const uint64_t *__restrict__ stream,
+		uint64_t stream_words, int64_t npx, int ntiles, int tile0, int tile_end, int gop, int nchunks, const RirbSelect *__restrict__ table, int out_frames,
+		void *__restrict__ out, int min_px, uint32_t min_t, int *__restrict__ error_flag)
+	{
+		const int lane = threadIdx.x & 63;
+		const int tile = tile0 + blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+		if (tile >= tile_end)
+			return;
+		const RirbSelect e = table[blockIdx.y];
+		if (e.count == 0)
+			return;
+		const int64_t walk = (int64_t)e.first + (int64_t)(e.count - 1) * e.step + 1;
+		if (e.chunk < 0 || e.chunk >= nchunks || e.nframes <= 0 || e.nframes > gop || e.first < 0 || e.count < 0 || e.step < 1 || walk > e.nframes ||
+			e.out_first < 0 || e.out_first > out_frames - e.count)
+		{
+			if (lane == 0)
+				atomicExch(error_flag, 1);
+			return;
+		}
+		const int chunk = e.chunk;
+		const uint32_t t0 = tile_off[(int64_t)chunk * (ntiles + 1) + tile];
+		const uint32_t t1 = tile_off[(int64_t)chunk * (ntiles + 1) + tile + 1];
+		const uint64_t c0 = chunk_off[chunk], c1 = chunk_off[chunk + 1];
+		if (c0 > c1 || c1 > stream_words || t1 < t0 || (uint64_t)t1 > c1 - c0)
+		{ // (the checks of rirb1_decode_tiles' dense form)
+			if (lane == 0)
+				atomicExch(error_flag, 1);
+			return;
+		}
+		const uint32_t seg_len = min(t1 - t0, (uint32_t)gop * RIRB1_REC_MAX_WORDS);
+		const int tpx = tile * RIRB1_TILE_PX;
+		SelectSink<F32> sink;
+		sink.fbytes = npx * (F32 ? 4 : 2);
+		sink.cur = static_cast<char *>(out) + (int64_t)e.out_first * sink.fbytes + (int64_t)tpx * (F32 ? 4 : 2);
+		sink.next = e.first, sink.step = e.step;
+		sink.npx = (int)npx, sink.p0 = tpx + lane * 8;
+		sink.lane_off = (uint32_t)lane * 16u, sink.min_t = min_t & 0xffffu;
+		sink.nmin = max(0, min(8, min_px - sink.p0));
+		decode_tile<FAST>(hdr_table + ((int64_t)chunk * ntiles + tile) * gop, stream + c0 + t0, seg_len, (int)walk, walk == e.nframes, lane, sink, error_flag);
 	}
 
 	// ---- host launchers --------------------------------------------------------------------------------
@@ -1892,6 +2031,26 @@ namespace rir
 		dim3 grid((ntiles + 3) / 4, nchunks), block(256);
 		hipLaunchKernelGGL(rirb1_decode_tiles, grid, block, 0, st, d_hdr, (const uint32_t *)nullptr, (const uint64_t *)nullptr, d_stream, stream_words, npx,
 						   ntiles, nframes, gop, (const int64_t *)nullptr, d_seg_words, d_seg_pos, d_frames, d_error);
+		return hipGetLastError();
+	}
+
+	hipError_t launch_decode_select(const uint64_t *hdr, const uint32_t *tile_off, const uint64_t *chunk_off, const uint64_t *stream, uint64_t stream_words,
+									int64_t npx, int ntiles, int gop, int nchunks, const RirbSelect *table, int entries, int out_frames, bool f32, void *out,
+									int min_px, uint32_t min_t, int *d_error, hipStream_t st)
+	{
+		if (entries <= 0)
+			return hipSuccess;
+		const bool aligned = ((npx & 7) == 0) && ((((uintptr_t)out) & 15) == 0);
+		const int nfast = aligned ? (int)std::min<int64_t>(ntiles, npx / RIRB1_TILE_PX) : 0; // tiles that lie whole inside the frame
+		auto go = [&](auto kernel, int t0, int t1) {
+			if (t1 > t0)
+				hipLaunchKernelGGL(kernel, dim3((t1 - t0 + 3) / 4, entries), dim3(256), 0, st, hdr, tile_off, chunk_off, stream, stream_words, npx, ntiles, t0, t1,
+								   gop, nchunks, table, out_frames, out, min_px, min_t, d_error);
+		};
+		if (f32)
+			go(rirb1_decode_select<true, true>, 0, nfast), go(rirb1_decode_select<true, false>, nfast, ntiles);
+		else
+			go(rirb1_decode_select<false, true>, 0, nfast), go(rirb1_decode_select<false, false>, nfast, ntiles);
 		return hipGetLastError();
 	}
 } // namespace rir

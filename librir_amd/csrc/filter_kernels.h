@@ -52,6 +52,17 @@ namespace rir
 	hipError_t launch_decode(const uint64_t *d_hdr, const uint32_t *d_tile_off, const uint64_t *d_chunk_off, const uint64_t *d_stream,
 							 uint64_t stream_words, int64_t npx, int ntiles, int nframes, int gop, const int64_t *d_chunk_frames, int nchunks_tab,
 							 uint16_t *d_frames, int *d_error, hipStream_t st);
+	// The selective decode (rirb1_decode_select): one entry per (chunk, frames of it) - local frames first, first + step, ... (count of them,
+	// step >= 1) of chunk `chunk` of the batch (nframes frames), stored at output frames out_first, out_first + 1, ... of `out` ([out_frames][npx],
+	// uint16 or float32).  The walk of a chunk goes from its key frame to its last selected frame.  min_t is added (mod 2^16) to the
+	// first min_px pixels of every stored frame.  Tables, entries and payload may be in device memory or in page-locked host memory.
+	struct RirbSelect
+	{
+		int32_t chunk, nframes, first, count, step, out_first;
+	};
+	hipError_t launch_decode_select(const uint64_t *hdr, const uint32_t *tile_off, const uint64_t *chunk_off, const uint64_t *stream, uint64_t stream_words,
+									int64_t npx, int ntiles, int gop, int nchunks, const RirbSelect *table, int entries, int out_frames, bool f32, void *out,
+									int min_px, uint32_t min_t, int *d_error, hipStream_t st);
 	hipError_t launch_decode_slots(const uint64_t *d_hdr, const uint32_t *d_seg_words, const uint64_t *d_slots, int64_t npx, int ntiles, int nframes,
 								   int gop, uint16_t *d_frames, int *d_error, hipStream_t st);
 	// the packed form (codec_kernels.hip: rirb1_encode_packed)

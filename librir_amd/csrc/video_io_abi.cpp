@@ -654,6 +654,9 @@ namespace
 			stop_writer();
 			if (fly_ev)
 				(void)hipEventDestroy(fly_ev);
+			for (hipEvent_t e : {dev_in_ev, dev_out_ev})
+				if (e)
+					(void)hipEventDestroy(e);
 			if (copy_st)
 			{
 				(void)hipStreamSynchronize(copy_st);
@@ -1252,6 +1255,37 @@ namespace
 			return take;
 		}
 
+		// rir_add_images_device: `count` frames [count][h][w] of the caller's device memory, queued on the caller's stream, appended without
+		// attributes.  The library's stream waits for what the caller queued before (an event), the frames go device-to-device into the
+		// chunks being assembled (add_images_device), and the call returns once those copies are through: the caller may reuse its buffer.
+		hipEvent_t dev_in_ev = nullptr, dev_out_ev = nullptr;
+		bool add_caller_frames(const unsigned short *d_frames, int count, const int64_t *ts, hipStream_t caller)
+		{
+			if (!usable() || !open())
+				return false;
+			for (hipEvent_t *e : {&dev_in_ev, &dev_out_ev})
+				if (!*e && !hip_ok(hipEventCreateWithFlags(e, hipEventDisableTiming), "hipEventCreate"))
+				{
+					*e = nullptr;
+					return false;
+				}
+			hipStream_t st = default_stream();
+			if (!hip_ok(hipEventRecord(dev_in_ev, caller), "hipEventRecord") || !hip_ok(hipStreamWaitEvent(st, dev_in_ev, 0), "hipStreamWaitEvent"))
+				return false;
+			const size_t npx = (size_t)width * height;
+			const std::vector<AttrMap> none((size_t)std::min(count, std::max(1, chunk_gop)));
+			bool ok = true;
+			for (int k = 0; k < count && ok;)
+			{
+				const int took = add_images_device(d_frames + (size_t)k * npx, count - k, ts + k, none.data());
+				ok = took > 0;
+				k += took;
+			}
+			// (also after a failure: copies already queued still read the caller's frames)
+			const bool drained = hip_ok(hipEventRecord(dev_out_ev, st), "hipEventRecord") && hip_ok(wait_event(dev_out_ev), "sync");
+			return ok && drained;
+		}
+
 		bool frame_added(int64_t ts, const AttrMap &attrs)
 		{
 			++pending;
@@ -1422,6 +1456,7 @@ namespace
 		{
 			stop_prefetch();
 			stop_zfile_ahead();
+			dio_release();
 			if (fp)
 				std::fclose(fp);
 			if (bp_handle > 0)
@@ -1840,6 +1875,25 @@ namespace
 			return true;
 		}
 
+		// The header of chunk c, checked against the file header and the index (nothing of it is trusted before)
+		// (ctx: a buffer set prepared for this file's geometry - the caller's own, the read-ahead lanes run this too)
+		bool read_chunk_header(int c, ChunkHeader &ch, const ChunkCodec &ctx)
+		{
+			const IndexEntry &e = index[c];
+			return read_at(e.file_offset, &ch, sizeof(ch)) && std::memcmp(ch.magic, "CHNK", 4) == 0 && (int)ch.gop == ctx.gop && (int)ch.ntiles == ctx.L.ntiles &&
+				   ch.nframes != 0 && (int)ch.nframes <= ctx.gop && ch.nframes == e.nframes && ch.first_frame == e.first_frame &&
+				   ch.payload_words <= (uint64_t)ctx.L.stream_max_bytes / 8;
+		}
+		// the offsets table comes from the file: monotone and ending exactly at the payload length, or the chunk is refused before anything
+		// reaches the device (the kernel checks again against the stream length it is given)
+		static bool tile_offsets_ok(const ChunkHeader &ch, const uint32_t *toff)
+		{
+			bool ok = toff[0] == 0 && (uint64_t)toff[ch.ntiles] == ch.payload_words;
+			for (size_t t = 0; t < (size_t)ch.ntiles && ok; ++t)
+				ok = toff[t] <= toff[t + 1];
+			return ok;
+		}
+
 		// Chunk c of the file -> ctx.d_frames (decoded, MIN_T added back) on stream st; with to_host the decoded images follow
 		// into ctx.h_frames (one asynchronous copy).  Waits for the stream.  quiet: failures are not logged (the read-ahead
 		// thread: the caller's own attempt will say what is wrong).
@@ -1852,9 +1906,7 @@ namespace
 			};
 			const IndexEntry &e = index[c];
 			ChunkHeader ch;
-			if (!read_at(e.file_offset, &ch, sizeof(ch)) || std::memcmp(ch.magic, "CHNK", 4) != 0 || (int)ch.gop != ctx.gop ||
-				(int)ch.ntiles != ctx.L.ntiles || ch.nframes == 0 || (int)ch.nframes > ctx.gop || ch.nframes != e.nframes ||
-				ch.first_frame != e.first_frame || ch.payload_words > (uint64_t)ctx.L.stream_max_bytes / 8)
+			if (!read_chunk_header(c, ch, ctx))
 				return fail("RIRB file: corrupted chunk header");
 			// tables and payload are read straight into page-locked memory (kept for the life of the object): no page faults of a
 			// fresh 7 MB vector per chunk, and the uploads below run at the PCIe rate instead of through the runtime's staging
@@ -1882,10 +1934,7 @@ namespace
 			payload[ch.payload_words] = 0;
 			// the offsets table comes from the file: monotone and ending exactly at the payload length, or the chunk is
 			// refused before anything reaches the device (the kernel checks again against the stream length it is given)
-			bool toff_ok = toff[0] == 0 && (uint64_t)toff[ch.ntiles] == ch.payload_words;
-			for (size_t t = 0; t < (size_t)ch.ntiles && toff_ok; ++t)
-				toff_ok = toff[t] <= toff[t + 1];
-			if (!toff_ok)
+			if (!tile_offsets_ok(ch, toff))
 				return fail("RIRB file: corrupted tile offsets");
 			uint64_t *coff = reinterpret_cast<uint64_t *>(payload + pay_n); // (page-locked too: the copy below is asynchronous)
 			coff[0] = 0, coff[1] = ch.payload_words;
@@ -1910,10 +1959,11 @@ namespace
 					return fail("RIRB file: malformed chunk payload");
 				return true;
 			}
+			// (the payload without the host's guard word behind it: a chunk of incompressible frames fills d_stream to its last word)
 			if (!hip_ok(hipMemcpyAsync(ctx.d_hdr.ptr, hdr, hdr_b, hipMemcpyHostToDevice, st), "H2D") ||
 				!hip_ok(hipMemcpyAsync(ctx.d_tile_off.ptr, toff, toff_n * 4, hipMemcpyHostToDevice, st), "H2D") ||
 				!hip_ok(hipMemcpyAsync(ctx.d_chunk_off.ptr, coff, 16, hipMemcpyHostToDevice, st), "H2D") ||
-				!hip_ok(hipMemcpyAsync(ctx.d_stream.ptr, payload, pay_n * 8, hipMemcpyHostToDevice, st), "H2D"))
+				!hip_ok(hipMemcpyAsync(ctx.d_stream.ptr, payload, (size_t)ch.payload_words * 8, hipMemcpyHostToDevice, st), "H2D"))
 				return false;
 			if (rir_codec_decode_device(ctx.d_hdr.as<unsigned long long>(), ctx.d_tile_off.as<unsigned int>(), ctx.d_chunk_off.as<unsigned long long>(),
 										ctx.d_stream.as<unsigned long long>(), (long long)ch.payload_words, width, height, (int)ch.nframes, ctx.gop,
@@ -2166,6 +2216,10 @@ namespace
 			return true;
 		}
 
+		// the read-back filters a read applies (IRFileLoader.cpp:1190-1220): every path that hands out images asks these two
+		bool filter_bad_pixels() const { return bp_enabled && bp_handle > 0 && global_attrs.count("Type") == 0; }
+		bool filter_motion() const { return motion_enabled && !shifts.empty(); }
+
 		// IRFileLoader::readImage (IRFileLoader.cpp:1148-1247), calibration 0 = digital levels.  Decode, bad-pixel
 		// repair and motion correction all run on the device; one D2H copy hands the finished frame over.
 		bool read_image(int pos, int calibration, unsigned short *pixels)
@@ -2174,8 +2228,7 @@ namespace
 				return false;
 			if (calibration != 0)
 				return false; // no calibration plugin is shipped
-			const bool do_bp = bp_enabled && bp_handle > 0 && global_attrs.count("Type") == 0;
-			const bool do_motion = motion_enabled && !shifts.empty();
+			const bool do_bp = filter_bad_pixels(), do_motion = filter_motion();
 			if (!do_bp && !do_motion)
 			{
 				if (!read_raw(pos, pixels))
@@ -2257,6 +2310,290 @@ namespace
 				res = d_b;
 			}
 			return hip_ok(hipMemcpyAsync(pixels, res, fbytes, hipMemcpyDeviceToHost, st), "D2H") && hip_ok(wait_stream(st), "sync");
+		}
+
+		// ---- rir_load_images_device: images first + k * step (k < count) into the caller's device buffer --------------------------------
+		// Everything here has buffers, a stream and events of its own (dio_*): the camera's per-read state - the cached chunk
+		// get_last_image_raw_value reads, last_pos and the sequential-read detector, the read-ahead lanes, the current image's
+		// attributes - is neither read nor changed.
+		// RIRB files go in batches of chunks: a batch's tables and payload are read into one of two page-locked buffers while the batch
+		// before it is decoded (one rirb1_decode_select launch a batch: only the selected frames are stored, MIN_T added on the way).
+		// Raw and ZFile images are read on the host and go up in batches.  With a read-back filter on, the batch is decoded into a
+		// scratch buffer and the batched filter kernels run on it before it goes to the output.
+#ifndef RIR_DIO_BATCH_CHUNKS
+#define RIR_DIO_BATCH_CHUNKS 8
+#endif
+		static constexpr int kDioBatchChunks = RIR_DIO_BATCH_CHUNKS;
+		static constexpr size_t kDioBatchBytes = (size_t)64 << 20; // page-locked bytes of a batch (compressed chunks, or raw images)
+		static constexpr size_t kDioScratchBytes = (size_t)256 << 20; // device scratch of a filtered batch
+		hipStream_t dio_st = nullptr;
+		hipEvent_t dio_ev[2] = {nullptr, nullptr}, dio_in_ev = nullptr;
+		bool dio_ev_set[2] = {false, false};
+		PinnedBuffer dio_h[2], dio_err_h;
+		DeviceBuffer dio_d[2], dio_scr, dio_shift, dio_err;
+
+		void dio_release()
+		{
+			if (dio_st)
+			{
+				(void)hipStreamSynchronize(dio_st);
+				(void)hipStreamDestroy(dio_st);
+			}
+			for (hipEvent_t e : {dio_ev[0], dio_ev[1], dio_in_ev})
+				if (e)
+					(void)hipEventDestroy(e);
+		}
+
+		// Batches of RIRB chunks are decoded straight from page-locked memory (the kernel reads tables and payload over the link) or
+		// after an upload into device memory.  Default: the faster of the two on the MI355X; RIR_DIO_UPLOAD=0 / 1 forces one.
+		static bool dio_upload()
+		{
+			static const int v = [] {
+				const char *e = getenv("RIR_DIO_UPLOAD");
+				return e ? (std::atoi(e) != 0 ? 1 : 0) : 0;
+			}();
+			return v != 0;
+		}
+
+		// frames [k0, k0 + n) of the selection, uint16 in dio_scr, go to the output: read-back filters, then a copy or the conversion
+		bool dio_finish(int k0, int n, bool f32, void *d_out, bool do_bp, bool do_motion, hipStream_t st)
+		{
+			const size_t npx = (size_t)width * height;
+			unsigned short *src = dio_scr.as<unsigned short>(), *res = src;
+			unsigned short *out16 = static_cast<unsigned short *>(d_out) + (size_t)k0 * npx;
+			if (do_bp && rir_remove_bad_pixels_device(bp_handle, src, height - 3, n, st) != 0)
+				return false;
+			if (do_motion)
+			{
+				unsigned short *dst = f32 ? src + (size_t)n * npx : out16;
+				if (rir_remove_motion_device(src, dst, width, height, height - 3, n, dio_shift.as<float>() + 2 * (size_t)k0, st) != 0)
+					return false;
+				res = dst;
+			}
+			if (f32)
+				return hip_ok(launch_u16_to_f32(res, static_cast<float *>(d_out) + (size_t)k0 * npx, (int64_t)n * npx, st), "u16 -> f32");
+			return res == out16 || hip_ok(hipMemcpyAsync(out16, res, (size_t)n * npx * 2, hipMemcpyDefault, st), "D2D");
+		}
+
+		bool load_images_device(int first, int count, int step, bool f32, void *d_out, hipStream_t caller)
+		{
+			const bool do_bp = filter_bad_pixels(), do_motion = filter_motion(), filtered = do_bp || do_motion;
+			if (filtered && height <= 3)
+				return false;
+			const size_t npx = (size_t)width * height, fbytes = npx * 2;
+			if (!dio_st && !hip_ok(hipStreamCreateWithFlags(&dio_st, hipStreamNonBlocking), "hipStreamCreate"))
+			{
+				dio_st = nullptr;
+				return false;
+			}
+			for (hipEvent_t *e : {&dio_ev[0], &dio_ev[1], &dio_in_ev})
+				if (!*e && !hip_ok(hipEventCreateWithFlags(e, hipEventDisableTiming), "hipEventCreate"))
+				{
+					*e = nullptr;
+					return false;
+				}
+			hipStream_t st = dio_st;
+			// whatever happens below, nothing of this call is left running when it returns (its buffers are reused by the next one)
+			struct Drain
+			{
+				hipStream_t st;
+				~Drain() { (void)wait_stream(st); }
+			} drain{st};
+			// the caller's work queued before this call (what writes d_out, say) goes first
+			if (!hip_ok(hipEventRecord(dio_in_ev, caller), "hipEventRecord") || !hip_ok(hipStreamWaitEvent(st, dio_in_ev, 0), "hipStreamWaitEvent"))
+				return false;
+			dio_ev_set[0] = dio_ev_set[1] = false;
+			if (!dio_err.reserve(sizeof(int)) || !dio_err_h.reserve(sizeof(int)) || !hip_ok(hipMemsetAsync(dio_err.ptr, 0, sizeof(int), st), "memset"))
+				return false;
+			std::vector<float> sel_shifts;
+			if (do_motion)
+			{ // the shifts of the selected images, in selection order
+				sel_shifts.resize(2 * (size_t)count);
+				for (int k = 0; k < count; ++k)
+				{
+					const size_t p = (size_t)first + (size_t)k * step;
+					sel_shifts[2 * (size_t)k] = shifts[2 * p], sel_shifts[2 * (size_t)k + 1] = shifts[2 * p + 1];
+				}
+				if (!dio_shift.reserve(sel_shifts.size() * 4) ||
+					!hip_ok(hipMemcpyAsync(dio_shift.ptr, sel_shifts.data(), sel_shifts.size() * 4, hipMemcpyHostToDevice, st), "H2D"))
+					return false;
+			}
+			// a page-locked buffer is refilled once the work that read it has passed
+			auto take_buffer = [&](int b) {
+				if (dio_ev_set[b] && !hip_ok(wait_event(dio_ev[b]), "sync"))
+					return false;
+				dio_ev_set[b] = false;
+				return true;
+			};
+			auto release_buffer = [&](int b) {
+				if (!hip_ok(hipEventRecord(dio_ev[b], st), "hipEventRecord"))
+					return false;
+				dio_ev_set[b] = true;
+				return true;
+			};
+			const size_t scratch_frames_per = (filtered || f32) ? ((f32 && do_motion) ? 2 : 1) : 0;
+			if (kind != RIRB)
+			{ // raw frames (PCR, BIN) / one zstd frame per image (ZFile): read on the host, up in batches
+				const int per = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, kDioBatchBytes / fbytes,
+																			 scratch_frames_per ? kDioScratchBytes / (fbytes * scratch_frames_per) : (size_t)count}));
+				std::vector<char> comp(kind == ZFILE ? z_buf.size() : 0);
+				if (scratch_frames_per && !dio_scr.reserve((size_t)per * fbytes * scratch_frames_per))
+					return false;
+				for (int k0 = 0, bi = 0; k0 < count; k0 += per, ++bi)
+				{
+					const int b = bi & 1, n = std::min(per, count - k0);
+					if (!take_buffer(b) || !dio_h[b].reserve((size_t)n * fbytes))
+						return false;
+					for (int k = 0; k < n; ++k)
+					{
+						const int pos = first + (k0 + k) * step;
+						unsigned short *dst = dio_h[b].as<unsigned short>() + (size_t)k * npx;
+						const bool ok = kind == PCR ? read_at(pcr_start + pcr_transfer * (int64_t)pos, dst, fbytes) : zfile_image(pos, dst, comp);
+						if (!ok)
+						{
+							log_error("rir_load_images_device: image " + std::to_string(pos) + " could not be read");
+							return false;
+						}
+					}
+					void *up = scratch_frames_per ? dio_scr.ptr : static_cast<void *>(static_cast<char *>(d_out) + (size_t)k0 * fbytes);
+					if (!hip_ok(hipMemcpyAsync(up, dio_h[b].ptr, (size_t)n * fbytes, hipMemcpyDefault, st), "H2D") ||
+						(scratch_frames_per && !dio_finish(k0, n, f32, d_out, do_bp, do_motion, st)) || !release_buffer(b))
+						return false;
+				}
+				return hip_ok(wait_stream(st), "sync");
+			}
+			// RIRB: what each chunk of the range gives
+			struct Job
+			{
+				int c;
+				ChunkHeader ch;
+				RirbSelect e;
+			};
+			std::vector<Job> jobs;
+			const int64_t last = (int64_t)first + (int64_t)(count - 1) * step;
+			const int c_lo = chunk_of(first), c_hi = chunk_of((int)last);
+			if (c_lo < 0 || c_hi < c_lo)
+				return false;
+			int64_t covered = 0;
+			for (int c = c_lo; c <= c_hi; ++c)
+			{
+				const int64_t cf = (int64_t)index[c].first_frame, cn = index[c].nframes;
+				const int64_t k_lo = std::max<int64_t>(0, (cf - first + step - 1) / step), k_hi = std::min<int64_t>(count, (cf + cn - first + step - 1) / step);
+				if (cf + cn <= first || k_hi <= k_lo)
+					continue;
+				Job j;
+				j.c = c;
+				if (!read_chunk_header(c, j.ch, cc))
+				{
+					log_error("RIRB file: corrupted chunk header");
+					return false;
+				}
+				j.e.chunk = 0, j.e.nframes = (int)cn, j.e.first = (int)(first + k_lo * step - cf), j.e.count = (int)(k_hi - k_lo), j.e.step = step;
+				j.e.out_first = (int)k_lo;
+				covered += k_hi - k_lo;
+				jobs.push_back(j);
+			}
+			if (covered != count)
+			{
+				log_error("RIRB file: the chunk index does not cover the images asked for");
+				return false;
+			}
+			const int ntiles = cc.L.ntiles, gop = (int)hd.gop;
+			const size_t hdr_per = (size_t)ntiles * gop * 8, toff_per = ((size_t)ntiles + 1) * 4;
+			const bool upload = dio_upload();
+			// the batches: chunks j0 .. j1 - 1, as many as kDioBatchChunks, kDioBatchBytes and (filtered) the scratch allow
+			struct Batch
+			{
+				size_t j0, j1, pay_words;
+				int sel_frames;
+			};
+			std::vector<Batch> plan;
+			int max_sel = 0;
+			for (size_t j0 = 0; j0 < jobs.size();)
+			{
+				Batch bt{j0, j0, 0, 0};
+				while (bt.j1 < jobs.size() && (int)(bt.j1 - j0) < kDioBatchChunks)
+				{
+					const size_t more = (bt.j1 - j0 + 1) * (hdr_per + toff_per + 32) + (bt.pay_words + jobs[bt.j1].ch.payload_words) * 8;
+					const size_t scr = (size_t)(bt.sel_frames + jobs[bt.j1].e.count) * fbytes * scratch_frames_per;
+					if (bt.j1 > j0 && (more > kDioBatchBytes || scr > kDioScratchBytes))
+						break;
+					bt.pay_words += jobs[bt.j1].ch.payload_words, bt.sel_frames += jobs[bt.j1].e.count;
+					++bt.j1;
+				}
+				max_sel = std::max(max_sel, bt.sel_frames);
+				plan.push_back(bt);
+				j0 = bt.j1;
+			}
+			// (sized once: a buffer that grew under work in flight would be freed beneath it)
+			if (filtered && !dio_scr.reserve((size_t)max_sel * fbytes * scratch_frames_per))
+				return false;
+			for (size_t bi = 0; bi < plan.size(); ++bi)
+			{
+				const size_t j0 = plan[bi].j0, pay_words = plan[bi].pay_words;
+				const int sel_frames = plan[bi].sel_frames;
+				const int nb = (int)(plan[bi].j1 - j0), b = (int)(bi & 1);
+				const int k0 = jobs[j0].e.out_first; // first output slot of the batch
+				// layout: entries | chunk offsets | record headers | tile offsets | payload (8-byte aligned parts)
+				const size_t o_coff = ((size_t)nb * sizeof(RirbSelect) + 7) & ~(size_t)7, o_hdr = o_coff + ((size_t)nb + 1) * 8;
+				const size_t o_toff = o_hdr + (size_t)nb * hdr_per, o_pay = o_toff + (((size_t)nb * toff_per + 7) & ~(size_t)7);
+				const size_t used = o_pay + pay_words * 8 + 8;
+				if (!take_buffer(b) || !dio_h[b].reserve(used))
+					return false;
+				char *h = dio_h[b].as<char>();
+				RirbSelect *tab = reinterpret_cast<RirbSelect *>(h);
+				uint64_t *coff = reinterpret_cast<uint64_t *>(h + o_coff), words = 0;
+				for (int i = 0; i < nb; ++i)
+				{
+					const Job &jb = jobs[j0 + i];
+					uint64_t off = index[jb.c].file_offset + sizeof(ChunkHeader);
+					uint64_t *hdr = reinterpret_cast<uint64_t *>(h + o_hdr + (size_t)i * hdr_per);
+					uint32_t *toff = reinterpret_cast<uint32_t *>(h + o_toff + (size_t)i * toff_per);
+					if (!read_at_large(off, hdr, hdr_per) || !read_at(off + hdr_per, toff, toff_per) ||
+						(jb.ch.payload_words && !read_at_large(off + hdr_per + toff_per, h + o_pay + words * 8, (size_t)jb.ch.payload_words * 8)))
+						return false;
+					if (!tile_offsets_ok(jb.ch, toff))
+					{
+						log_error("RIRB file: corrupted tile offsets");
+						return false;
+					}
+					tab[i] = jb.e;
+					tab[i].chunk = i;
+					tab[i].out_first = filtered ? jb.e.out_first - k0 : jb.e.out_first;
+					coff[i] = words;
+					words += jb.ch.payload_words;
+				}
+				coff[nb] = words;
+				reinterpret_cast<uint64_t *>(h + o_pay)[words] = 0;
+				const char *src = h;
+				if (upload)
+				{
+					if (!dio_d[b].reserve(used) || !hip_ok(hipMemcpyAsync(dio_d[b].ptr, h, used, hipMemcpyHostToDevice, st), "H2D"))
+						return false;
+					src = dio_d[b].as<char>();
+				}
+				void *out = d_out;
+				int out_frames = count;
+				if (filtered)
+					out = dio_scr.ptr, out_frames = sel_frames;
+				const bool add_min = min_T && min_T_rows > 0;
+				if (!hip_ok(launch_decode_select(reinterpret_cast<const uint64_t *>(src + o_hdr), reinterpret_cast<const uint32_t *>(src + o_toff),
+												 reinterpret_cast<const uint64_t *>(src + o_coff), reinterpret_cast<const uint64_t *>(src + o_pay), words, (int64_t)npx,
+												 ntiles, gop, nb, reinterpret_cast<const RirbSelect *>(src), nb, out_frames, f32 && !filtered, out,
+												 add_min ? width * std::min(min_T_rows, height) : 0, add_min ? (uint32_t)min_T : 0u, dio_err.as<int>(), st),
+							"decode"))
+					return false;
+				if ((filtered && !dio_finish(k0, sel_frames, f32, d_out, do_bp, do_motion, st)) || !release_buffer(b))
+					return false;
+			}
+			if (!hip_ok(hipMemcpyAsync(dio_err_h.ptr, dio_err.ptr, sizeof(int), hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(wait_stream(st), "sync"))
+				return false;
+			if (*dio_err_h.as<int>())
+			{
+				log_error("RIRB file: malformed chunk payload");
+				return false;
+			}
+			return true;
 		}
 
 		// IRFileLoader::setBadPixelsEnabled (IRFileLoader.cpp:693-716): detector on the first image, rows < H-3, once
@@ -2801,7 +3138,7 @@ RIR_EXPORT int rir_transcode_images(int cam, int file, int first, int count, con
 	if (first < 0 || count < 0 || (count > 0 && !timestamps_ns) || (int64_t)first + count > c->count)
 		return -1;
 	return guarded("rir_transcode_images", -1, [&] {
-		const bool filtered = (c->bp_enabled && c->bp_handle > 0 && c->global_attrs.count("Type") == 0) || (c->motion_enabled && !c->shifts.empty());
+		const bool filtered = c->filter_bad_pixels() || c->filter_motion();
 		if (c->kind != CameraObject::RIRB || c->width != s->width || c->height != s->height || filtered)
 			return -2;
 		const size_t npx = (size_t)c->width * c->height;
@@ -2843,6 +3180,62 @@ RIR_EXPORT int rir_transcode_images(int cam, int file, int first, int count, con
 		}
 		return count;
 	});
+}
+
+// Extension: images first + k * step (k < count) of an open camera into the caller's buffer d_out ([count][h][w], 'H' uint16 or 'f' float32),
+// bit for bit what load_image / load_imageF give (read-back filters and MIN_T included), without the camera's per-read state changing.
+// Ordered after the work queued on `stream`; returns count once the images are there, -1 on failure (logged).
+RIR_EXPORT int rir_load_images_device(int cam, int first, int count, int step, int dtype, void *d_out, long long out_bytes, void *stream)
+{
+	auto c = camera(cam);
+	if (!c)
+	{
+		log_error("rir_load_images_device: NULL camera");
+		return -1;
+	}
+	const long long esz = dtype == 'H' ? 2 : dtype == 'f' ? 4 : 0;
+	const int64_t last = (int64_t)first + (int64_t)(count - 1) * step;
+	if (esz == 0 || count < 0 || step < 1 || (count > 0 && (first < 0 || last >= c->count || !d_out)) ||
+		out_bytes < (long long)count * c->width * c->height * esz)
+	{
+		log_error("rir_load_images_device: invalid argument (dtype 'H' or 'f', step >= 1, images inside the file, an output of count images)");
+		return -1;
+	}
+	if (count == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	return guarded("rir_load_images_device", -1,
+				   [&] { return c->load_images_device(first, count, step, esz == 4, d_out, static_cast<hipStream_t>(stream)) ? count : -1; });
+}
+
+// Extension: `count` uint16 frames [count][h][w] of device memory, queued on `stream`, appended to an open lossless saver without
+// per-image attributes.  Returns count once the caller may reuse d_frames (encoding and writing go on as for host frames); -2 for a
+// saver that records with bounded loss; -1 on failure (logged).
+RIR_EXPORT int rir_add_images_device(int file, const unsigned short *d_frames, int count, const int64_t *timestamps_ns, void *stream)
+{
+	auto s = saver(file);
+	if (!s)
+	{
+		log_error("rir_add_images_device: NULL identifier");
+		return -1;
+	}
+	if (count < 0 || (count > 0 && (!d_frames || !timestamps_ns)))
+	{
+		log_error("rir_add_images_device: invalid argument");
+		return -1;
+	}
+	if (s->lossy)
+	{
+		log_error("rir_add_images_device: this saver records with bounded loss (add_image_lossy); device frames go to lossless savers only");
+		return -2;
+	}
+	if (count == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	return guarded("rir_add_images_device", -1,
+				   [&] { return s->add_caller_frames(d_frames, count, timestamps_ns, static_cast<hipStream_t>(stream)) ? count : -1; });
 }
 
 // video_io.cpp:377-391: the uint16 image cast to float (IRVideoLoader.h:109-117)

@@ -265,6 +265,43 @@ class IRMovie(object):
         self._current = pos
         return image
 
+    def to_tensor(self, selection=slice(None), dtype=None, out=None):
+        """Images of ``selection`` (an int, or a slice with a positive step; negative bounds as ``movie[...]`` takes them) as a CUDA
+        tensor ``[n][h][w]`` of ``dtype`` (``torch.uint16``, the default, or ``torch.float32``) on the current CUDA device - the images
+        ``movie[selection]`` gives, bit for bit, decoded on the device: only the compressed chunks of a recording of this library cross
+        the link.  ``out``: a preallocated C-contiguous CUDA tensor of that shape and dtype.  The current image (``load_pos``) and its
+        attributes stay what they were."""
+        import torch
+
+        dtype = torch.uint16 if dtype is None else dtype
+        if dtype not in (torch.uint16, torch.float32):
+            raise ValueError("to_tensor: dtype torch.uint16 or torch.float32 expected, not %s" % (dtype,))
+        if self._calibration_index != 0:
+            raise ValueError("to_tensor: only digital levels (DL) are read to the device")
+        total = self.images
+        if isinstance(selection, (int, np.integer)):
+            pos = int(selection) + (total if selection < 0 else 0)
+            if not 0 <= pos < total:
+                raise IndexError("image %d out of range (%d images)" % (int(selection), total))
+            positions = range(pos, pos + 1)
+        elif isinstance(selection, slice):
+            if selection.step is not None and selection.step <= 0:
+                raise ValueError("to_tensor: a slice with a positive step expected")
+            positions, _ = self._positions(selection)
+        else:
+            raise TypeError("to_tensor: an int or a slice expected")
+        h, w = self.image_size
+        shape = (len(positions), h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
+        elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise RuntimeError("to_tensor: 'out' must be a C-contiguous CUDA tensor of shape %s and dtype %s" % (shape, dtype))
+        if len(positions):
+            if positions.start < 0 or positions[-1] >= total:
+                raise IndexError("to_tensor: images %s out of range (%d images)" % (positions, total))
+            _abi.load_images_device(self.handle, positions.start, len(positions), positions.step, out)
+        return out
+
     def load_secs(self, time, calibration=None):
         """The image whose time stamp is closest to ``time`` (seconds)."""
         if self.times is None:

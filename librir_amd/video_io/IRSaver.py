@@ -109,6 +109,19 @@ class IRSaver(object):
         """Lossless: the image read back is the image given.  ``timestamp`` in nanoseconds."""
         _abi.h264_add_image_lossless(self._handle, self._frame(image, "wrong image dimension"), timestamp, attributes)
 
+    def add_images(self, frames, timestamps):
+        """Lossless, from the device: ``frames`` a CUDA ``torch.uint16`` tensor ``[n][h][w]`` (made contiguous once when it is not),
+        ``timestamps`` n time stamps in nanoseconds, as ``add_image`` takes them; no per-image attributes.  Ordered after the work
+        queued on the current CUDA stream; ``frames`` may be overwritten once this returns.  The file is the one ``add_image`` of the same
+        frames would make, byte for byte."""
+        import torch
+
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint16:
+            raise RuntimeError("add_images: a CUDA torch.uint16 tensor expected")
+        if frames.dim() != 3 or tuple(frames.shape[1:]) != self._shape:
+            raise RuntimeError("wrong image dimension")
+        _abi.add_images_device(self._handle, frames.contiguous(), timestamps)
+
     def add_image_lossy(self, image_DL, timestamp, attributes=None):
         """Bounded loss: pixels may move by at most lowValueError / highValueError around their reference value
         (rows below ``lossy_height`` only), which makes the temporal residuals smaller."""

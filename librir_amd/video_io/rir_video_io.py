@@ -21,6 +21,8 @@ _v.open_camera_file.argtypes = [ct.c_char_p, _ip]
 _v.open_camera_from_memory.argtypes = [_vp, ct.c_int64, _ip]
 _v.video_file_format.argtypes = [ct.c_char_p]
 _v.rir_transcode_images.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p, ct.c_int]
+_v.rir_load_images_device.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p, ct.c_longlong, ct.c_void_p]
+_v.rir_add_images_device.argtypes = [ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_void_p]
 _v.get_image_time.argtypes = [ct.c_int, ct.c_int, ct.POINTER(ct.c_int64)]
 _v.get_image_size.argtypes = [ct.c_int, _ip, _ip]
 _v.get_filename.argtypes = [ct.c_int, ct.c_char_p]
@@ -376,6 +378,38 @@ def transcode_images(camera, saver, first, count, timestamps_ns, keep_attributes
     if r != count:
         _fail("transcode_images")
     return True
+
+
+def load_images_device(camera, first, count, step, out, stream=None):
+    """Extension (``rir_load_images_device``): images ``first + k * step`` (``k < count``) into ``out``, a C-contiguous CUDA tensor
+    ``[count][h][w]`` of ``torch.uint16`` or ``torch.float32`` - what ``load_image`` gives, with the camera's read state left alone.
+    ``stream``: the CUDA stream the call is ordered after (default: the current one)."""
+    import torch
+
+    code = {torch.uint16: ord("H"), torch.float32: ord("f")}[out.dtype]
+    st = torch.cuda.current_stream(out.device) if stream is None else stream
+    r = _v.rir_load_images_device(camera, int(first), int(count), int(step), code, out.data_ptr(), out.numel() * out.element_size(), st.cuda_stream)
+    if r != count:
+        _fail("rir_load_images_device")
+    return out
+
+
+def add_images_device(saver, frames, timestamps_ns, stream=None):
+    """Extension (``rir_add_images_device``): the frames of ``frames`` (C-contiguous CUDA ``torch.uint16`` tensor ``[n][h][w]``) appended
+    to a lossless saver with time stamps ``timestamps_ns`` (n of them), ordered after the work queued on ``stream`` (default: the current
+    one).  Returns when ``frames`` may be overwritten."""
+    import torch
+
+    stamps = np.ascontiguousarray(timestamps_ns, dtype=np.int64)
+    n = int(frames.shape[0])
+    if stamps.shape != (n,):
+        raise RuntimeError("add_images_device: one time stamp per image expected")
+    st = torch.cuda.current_stream(frames.device) if stream is None else stream
+    r = _v.rir_add_images_device(saver, frames.data_ptr(), n, stamps.ctypes.data, st.cuda_stream)
+    if r == -2:
+        raise RuntimeError("add_images_device: device frames go to lossless savers only (this one records with bounded loss)")
+    if r != n:
+        _fail("rir_add_images_device")
 
 
 def h264_add_image_lossy(saver, image_DL, timestamp, attributes=None):
