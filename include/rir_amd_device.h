@@ -141,8 +141,10 @@ extern "C"
 									   unsigned long long *d_seg_pos, unsigned int *d_seg_words, unsigned long long *d_stream,
 									   long long stream_capacity_words, void *d_workspace, long long workspace_bytes, void *stream);
 	int rir_codec_encode_packed_status(const void *d_workspace, unsigned long long *out3, void *stream);
-	/* rir_codec_encode_packed_device in its two halves (the reset of the workspace's control block is a fill launch of its own): for callers
-	 * that time the packing kernel alone.  _launch_ packs into a workspace that has just been reset on the same stream. */
+	/* rir_codec_encode_packed_device in its two halves (the reset of the workspace's control block is a fill launch of its own).  _launch_
+	 * packs into a workspace whose control block is zero: just reset on the same stream, or left so by the packed encode before it on that
+	 * stream - a launch that runs to its end zeroes the block again and leaves its result for rir_codec_encode_packed_status, so a caller
+	 * that knows its workspace is clean encodes with one launch. */
 	int rir_codec_packed_reset_device(void *d_workspace, long long workspace_bytes, void *stream);
 	int rir_codec_encode_packed_launch_device(const unsigned short *d_frames, int width, int height, int nframes, int gop, unsigned long long *d_hdr,
 											  unsigned long long *d_seg_pos, unsigned int *d_seg_words, unsigned long long *d_stream,

@@ -483,8 +483,9 @@ RIR_EXPORT int rir_codec_encode_packed_device(const unsigned short *d_frames, in
 	return encode_packed(d_frames, width, height, nframes, gop, d_hdr, d_seg_pos, d_seg_words, d_stream, stream_capacity_words, d_workspace, workspace_bytes, true, stream);
 }
 // The two halves of the call above, for a caller that wants them apart (bench.py's per-kernel HIP events: the reset is a fill launch of its own):
-// rir_codec_packed_reset_device zeroes the control block of a workspace, rir_codec_encode_packed_launch_device packs into a workspace that has
-// just been reset on the same stream.
+// rir_codec_packed_reset_device zeroes the control block of a workspace, rir_codec_encode_packed_launch_device packs into a workspace whose
+// control block is zero: just reset on the same stream, or left so by the packed encode before it on that stream (every launch that runs
+// to its end leaves the block zero and its result on the status line).
 RIR_EXPORT int rir_codec_packed_reset_device(void *d_workspace, long long workspace_bytes, void *stream)
 {
 	if (!device_ready())
@@ -519,6 +520,12 @@ int encode_packed(const unsigned short *d_frames, int width, int height, int nfr
 		log_error("rir_codec_encode_packed_device: null buffer, negative capacity, or a workspace that is too small or not 128-byte aligned");
 		return -1;
 	}
+	// (the kernel counts a side's segments in the top 24 bits of its cursor, the words in the low 40)
+	if ((int64_t)L.nchunks * L.ntiles > (1ll << 24) || stream_capacity_words >= (1ll << 40))
+	{
+		log_error("rir_codec_encode_packed_device: more than 2^24 segments or a stream of 2^40 words or more");
+		return -1;
+	}
 	uint64_t *ctrl = static_cast<uint64_t *>(d_workspace);
 	uint64_t *arena = ctrl + RIRB1_PACKED_CTRL_BYTES / 8;
 	const uint64_t arena_words = (uint64_t)(workspace_bytes - RIRB1_PACKED_CTRL_BYTES) / 8;
@@ -539,9 +546,10 @@ RIR_EXPORT int rir_codec_encode_packed_status(const void *d_workspace, unsigned 
 	if (!hip_ok(hipMemcpyAsync(c, d_workspace, sizeof(c), hipMemcpyDeviceToHost, as_stream(stream)), "D2H") ||
 		!hip_ok(hipStreamSynchronize(as_stream(stream)), "sync"))
 		return -1;
+	// the status line the last workgroup of the launch wrote (rirb1_encode_packed, packed_finish)
 	if (out3)
-		out3[0] = c[0], out3[1] = c[16], out3[2] = c[32];
-	return (int)(c[48] & 3u) | (c[0] + c[16] > c[64] ? 1 : 0);
+		out3[0] = c[64], out3[1] = c[65], out3[2] = c[66];
+	return (int)(c[67] & 2u) | (c[64] + c[65] > c[68] ? 1 : 0);
 }
 
 RIR_EXPORT int rir_codec_decode_packed_device(const unsigned long long *d_hdr, const unsigned long long *d_seg_pos, const unsigned int *d_seg_words,

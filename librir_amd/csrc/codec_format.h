@@ -16,6 +16,6 @@
 #endif
 #define RIRB1_SLOT_WORDS(gop) ((int64_t)(gop) * RIRB1_REC_MAX_WORDS + RIRB1_SLOT_PAD_WORDS)
 
-// Control block of the packed form's encoder (rirb1_encode_packed), at the start of its workspace: three 128-byte lines -
-// stream cursor, spill cursor, error word - and a spare one.
+// Control block of the packed form's encoder (rirb1_encode_packed), at the start of its workspace: 128-byte lines for the two stream
+// cursors, the spill cursor, the error word, the status line of the last launch and the word where its last workgroups meet.
 #define RIRB1_PACKED_CTRL_BYTES 4096

@@ -1318,9 +1318,34 @@ namespace rir
 	// they share the caller's capacity instead of halving it they work from its two ends: segments with an even (tile + chunk)
 	// are placed upwards from word 0, the others downwards from word `capacity`.  The batch is two extents without holes,
 	// [0, low) and [capacity - high, capacity); it fits when low + high <= capacity.
-	// ctrl (zeroed before the launch, a line each): [0] low cursor, [16] high cursor, [32] spill cursor, [48] error word (u32): bit 0
-	// = a segment did not fit its side (the cursors still say how many words the batch needs), bit 1 = the spill arena was
-	// exceeded; [64] the capacity the launch was given (for the status call: the extents cross when low + high > capacity).
+	// ctrl (a line each): [0] low cursor, [16] high cursor, [32] spill cursor, [48] error word (u32): bit 1 = the spill arena was
+	// exceeded; [64..68] the status line; [80] the meeting word (u32).
+	// The launch leaves its control block as it found it - zero - so the next launch needs no fill before it: a stream cursor counts
+	// its segments in its top bits (each add is `words | 1 << 40`), and the workgroup that brings a cursor's count to the number of
+	// segments on that side knows it is the last there (no ticket of its own: 12 800 more returning atomics on few addresses would
+	// cost what the second cursor saved).  The last of each side meets the other at [80]; the second to arrive swaps every word of the
+	// block with 0 and writes what it took to the status line: [64] low, [65] high, [66] spill words asked for, [67] error word, [68]
+	// the capacity the launch was given (rir_codec_encode_packed_status: a segment did not fit its side, or the extents cross, when
+	// low + high > capacity).  Each workgroup's spill atomics are complete before its cursor add (returning, or waited for), so the
+	// swaps see every one.
+#define RIR_PACKED_COUNT_SHIFT 40
+#define RIR_PACKED_WORDS_MASK ((1ull << RIR_PACKED_COUNT_SHIFT) - 1)
+	// the last workgroup of one side (wave-uniform call): meet the other side's last, and the second of the two empties the block
+	__device__ __noinline__ void packed_finish(uint64_t *ctrl, uint64_t capacity_words, uint32_t sides)
+	{
+		if ((threadIdx.x & 63u) != 0)
+			return;
+		uint32_t *meet = reinterpret_cast<uint32_t *>(ctrl + 80);
+		if (sides > 1 && __hip_atomic_fetch_add(meet, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1 < sides)
+			return;
+		unsigned long long *c = reinterpret_cast<unsigned long long *>(ctrl);
+		const uint64_t low = __hip_atomic_exchange(c, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & RIR_PACKED_WORDS_MASK;
+		const uint64_t high = __hip_atomic_exchange(c + 16, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & RIR_PACKED_WORDS_MASK;
+		const uint64_t spill = __hip_atomic_exchange(c + 32, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		const uint32_t err = __hip_atomic_exchange(reinterpret_cast<uint32_t *>(ctrl + 48), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		__hip_atomic_store(meet, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		ctrl[64] = low, ctrl[65] = high, ctrl[66] = spill, ctrl[67] = err, ctrl[68] = capacity_words;
+	}
 #ifndef RIR_PACKED_COPY_ALL_WAVES
 #define RIR_PACKED_COPY_ALL_WAVES 0
 #endif
@@ -1340,14 +1365,12 @@ namespace rir
 		uint32_t *sh_u32 = reinterpret_cast<uint32_t *>(sh_u64 + 1 + WAVES); // [0..WAVES) words of each wave, [WAVES..2 WAVES) of them in LDS
 		const int lane = threadIdx.x & 63;
 		const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-		const bool downwards = ((blockIdx.x + blockIdx.y) & 1u) != 0 && diag != 1; // (diag 1: one cursor)
+		const int chunk = blockIdx.y, tile = tile_first + blockIdx.x;
+		const bool downwards = ((tile + chunk) & 1) != 0 && diag != 1; // (diag 1: one cursor)
 		unsigned long long *cursor = reinterpret_cast<unsigned long long *>(ctrl) + (downwards ? 16 : 0);
 		unsigned long long *spill_cursor = reinterpret_cast<unsigned long long *>(ctrl + 32);
 		uint32_t *error_word = reinterpret_cast<uint32_t *>(ctrl + 48);
-		if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
-			ctrl[64] = capacity_words;
 
-		const int chunk = blockIdx.y, tile = tile_first + blockIdx.x;
 		const int64_t seg = (int64_t)chunk * ntiles + tile;
 		const int f_begin = chunk * gop;
 		const int nf = min(gop, nframes - f_begin);
@@ -1400,19 +1423,24 @@ namespace rir
 		{
 			unsigned long long at = 0;
 			if (lane == 0)
-				at = __hip_atomic_fetch_add(cursor, (unsigned long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+				at = __hip_atomic_fetch_add(cursor, (unsigned long long)total | (1ull << RIR_PACKED_COUNT_SHIFT), __ATOMIC_RELAXED,
+											__HIP_MEMORY_SCOPE_AGENT);
 			const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)at);
 			const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(at >> 32));
-			at = ((unsigned long long)hi << 32) | lo;
-			const bool fits = at + total <= capacity_words;
+			// segments placed on this side before this one: the last of them all leaves the control block clean
+			const uint32_t arrived = hi >> (RIR_PACKED_COUNT_SHIFT - 32);
+			const uint64_t nseg = (uint64_t)gridDim.y * (uint32_t)ntiles; // (both launches: every segment of the batch)
+			const uint64_t on_side = diag == 1 ? nseg : downwards ? nseg / 2 : (nseg + 1) / 2; // (tile + chunk) odd / even
+			if ((uint64_t)arrived + 1 == on_side)
+				packed_finish(ctrl, capacity_words, diag == 1 || nseg < 2 ? 1u : 2u);
+			at = ((unsigned long long)hi << 32 | lo) & RIR_PACKED_WORDS_MASK;
+			const bool fits = at + total <= capacity_words; // (a segment that does not fit leaves its cursor beyond the capacity)
 			if (downwards)
 				at = capacity_words - at - total; // (unused when it does not fit)
 			if (lane == 0)
 			{
 				seg_pos[seg] = at;
 				seg_words[seg] = total;
-				if (!fits)
-					__hip_atomic_fetch_or(error_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 				sh_u64[0] = (fits && !lost) ? at : ~0ull;
 			}
 #if !RIR_PACKED_COPY_ALL_WAVES
@@ -1686,19 +1714,16 @@ namespace rir
 	}
 
 	// grid = (ceil(ntiles/4), nchunks), block = 256 (4 independent waves)
-	// Two layouts of the payload, one record format:
+	// Two layouts of the payload, one record format (the third, packed, has a kernel of its own: rirb1_decode_packed):
 	//   dense   (seg_words == NULL)  segment (c, t) = stream[chunk_off[c] + tile_off[c][t] ...) - the file form, tables untrusted
 	//   slotted (seg_words != NULL)  segment (c, t) = stream[(c * ntiles + t) * RIRB1_SLOT_WORDS(gop) ...), seg_words[c][t] words
 	//            long - what rirb1_encode_tiles leaves in its workspace: every segment's place is known before anything is
 	//            packed, so the encoder needs no second pass and the decoder no offsets (tile_off / chunk_off unused).
-	//   packed  (seg_pos != NULL too) segment (c, t) = stream[seg_pos[c][t] ...), seg_words[c][t] words long - what rirb1_encode_packed
-	//            leaves: a stream without holes whose segments lie in order of arrival.
 	__global__ __launch_bounds__(256) void rirb1_decode_tiles(const uint64_t *__restrict__ hdr_table, const uint32_t *__restrict__ tile_off,
 															 const uint64_t *__restrict__ chunk_off, const uint64_t *__restrict__ stream,
 															 uint64_t stream_words, int64_t npx, int ntiles, int nframes, int gop,
 															 const int64_t *__restrict__ chunk_frames, const uint32_t *__restrict__ seg_words,
-															 const uint64_t *__restrict__ seg_pos, uint16_t *__restrict__ frames,
-															 int *__restrict__ error_flag)
+															 uint16_t *__restrict__ frames, int *__restrict__ error_flag)
 	{
 		const int lane = threadIdx.x & 63;
 		const int tile = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1728,10 +1753,8 @@ namespace rir
 		uint32_t seg_len;
 		const uint64_t *in;
 		if (seg_words)
-		{ // slotted: the slot's place is fixed, its length comes from the encoder's table (clamped to the slot all the same);
-		  // packed (seg_pos != NULL): the place comes from a table too - untrusted like the length (a batch received from another
-		  // device), so the segment must lie inside the stream before a descriptor is built on it
-			const uint64_t base = seg_pos ? seg_pos[slot] : (uint64_t)slot * (uint64_t)RIRB1_SLOT_WORDS(gop);
+		{ // slotted: the slot's place is fixed, its length comes from the encoder's table (clamped to the slot all the same)
+			const uint64_t base = (uint64_t)slot * (uint64_t)RIRB1_SLOT_WORDS(gop);
 			seg_len = min(seg_words[slot], (uint32_t)gop * RIRB1_REC_MAX_WORDS);
 			if (base > stream_words || (uint64_t)seg_len > stream_words - base)
 			{
@@ -1764,6 +1787,39 @@ namespace rir
 			decode_tile<true>(my_hdr, in, seg_len, nf, true, lane, sink, error_flag);
 		else
 			decode_tile<false>(my_hdr, in, seg_len, nf, true, lane, sink, error_flag);
+	}
+
+	// The packed layout: segment (c, t) = stream[seg_pos[c][t] ...), seg_words[c][t] words long - what rirb1_encode_packed leaves, a stream
+	// without holes whose segments lie in order of arrival.  Both tables are untrusted (a batch received from another device): the segment
+	// must lie inside the stream before a descriptor is built on it.  A kernel of its own, specialised like the encoder: FAST for tiles
+	// [tile0, tile_end) that lie whole inside the frame of 16-byte aligned frames, the ragged form for the rest.  Without the other
+	// layouts' tables and branches its registers admit 8 workgroups per CU (<= 80 SGPRs) where rirb1_decode_tiles' admit 6; how many
+	// run at once is set by the launch (launch_decode_packed).
+	// grid = (ceil((tile_end - tile0) / 4), nchunks), block = 256 (4 independent waves)
+	template <bool FAST>
+	__attribute__((amdgpu_waves_per_eu(8, 8))) __global__ __launch_bounds__(256) void rirb1_decode_packed(
+		const uint64_t *__restrict__ hdr_table, const uint64_t *__restrict__ seg_pos, const uint32_t *__restrict__ seg_words,
+		const uint64_t *__restrict__ stream, uint64_t stream_words, int64_t npx, int ntiles, int tile0, int tile_end, int nframes, int gop,
+		uint16_t *__restrict__ frames, int *__restrict__ error_flag)
+	{
+		const int lane = threadIdx.x & 63;
+		const int tile = tile0 + blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+		if (tile >= tile_end)
+			return;
+		const int chunk = blockIdx.y;
+		const int64_t f_begin = (int64_t)chunk * gop;
+		const int nf = (int)min((int64_t)gop, (int64_t)nframes - f_begin);
+		const int64_t slot = (int64_t)chunk * ntiles + tile;
+		const uint64_t base = seg_pos[slot];
+		const uint32_t seg_len = min(seg_words[slot], (uint32_t)gop * RIRB1_REC_MAX_WORDS);
+		if (base > stream_words || (uint64_t)seg_len > stream_words - base)
+		{
+			if (lane == 0)
+				atomicExch(error_flag, 1);
+			return;
+		}
+		ChunkSink sink(frames, npx, f_begin, tile, lane);
+		decode_tile<FAST>(hdr_table + slot * gop, stream + base, seg_len, nf, true, lane, sink, error_flag);
 	}
 
 	// ---- selective decode into the caller's buffer (rir_load_images_device) ----------------------------------------------
@@ -1962,7 +2018,7 @@ namespace rir
 		const int nchunks = d_chunk_frames ? nchunks_tab : (nframes + gop - 1) / gop;
 		dim3 grid((ntiles + 3) / 4, nchunks), block(256);
 		hipLaunchKernelGGL(rirb1_decode_tiles, grid, block, 0, st, d_hdr, d_tile_off, d_chunk_off, d_stream, stream_words, npx, ntiles, nframes, gop,
-						   d_chunk_frames, (const uint32_t *)nullptr, (const uint64_t *)nullptr, d_frames, d_error);
+						   d_chunk_frames, (const uint32_t *)nullptr, d_frames, d_error);
 		return hipGetLastError();
 	}
 	// the slotted form: d_slots = the encoder's slot array ([nchunks][ntiles] slots of RIRB1_SLOT_WORDS(gop) words), d_seg_words its lengths
@@ -1973,11 +2029,12 @@ namespace rir
 		dim3 grid((ntiles + 3) / 4, nchunks), block(256);
 		hipLaunchKernelGGL(rirb1_decode_tiles, grid, block, 0, st, d_hdr, (const uint32_t *)nullptr, (const uint64_t *)nullptr, d_slots,
 						   (uint64_t)nchunks * ntiles * (uint64_t)RIRB1_SLOT_WORDS(gop), npx, ntiles, nframes, gop, (const int64_t *)nullptr,
-						   d_seg_words, (const uint64_t *)nullptr, d_frames, d_error);
+						   d_seg_words, d_frames, d_error);
 		return hipGetLastError();
 	}
 
-	// the packed form.  d_ctrl: RIRB1_PACKED_CTRL_BYTES at the start of the workspace (zeroed here), d_arena: the rest of it.
+	// the packed form.  d_ctrl: RIRB1_PACKED_CTRL_BYTES at the start of the workspace (zeroed here when `reset`; the kernel leaves it
+	// zero), d_arena: the rest of it.
 	int packed_lds_words(int gop)
 	{
 		constexpr int WAVES = RIR_PACKED_WAVES;
@@ -2028,9 +2085,19 @@ namespace rir
 									uint64_t stream_words, int64_t npx, int ntiles, int nframes, int gop, uint16_t *d_frames, int *d_error, hipStream_t st)
 	{
 		const int nchunks = (nframes + gop - 1) / gop;
-		dim3 grid((ntiles + 3) / 4, nchunks), block(256);
-		hipLaunchKernelGGL(rirb1_decode_tiles, grid, block, 0, st, d_hdr, (const uint32_t *)nullptr, (const uint64_t *)nullptr, d_stream, stream_words, npx,
-						   ntiles, nframes, gop, (const int64_t *)nullptr, d_seg_words, d_seg_pos, d_frames, d_error);
+		const bool aligned = ((npx & 7) == 0) && ((((uintptr_t)d_frames) & 15) == 0);
+		const int nfast = aligned ? (int)std::min<int64_t>(ntiles, npx / RIRB1_TILE_PX) : 0; // tiles that lie whole inside the frame
+		// The kernel uses no LDS and its registers admit 8 workgroups per CU, but the decoder is bound by the HBM writes of the frames,
+		// not by latency: with more of its waves writing at once the step is slower (DESIGN.md §3, 8 / 7 / 6 / 5 / 4 / 3 / 2 workgroups
+		// per CU measured).  The launch reserves LDS it does not use so that 5 share a CU: 160 KiB / 32 KiB.
+		constexpr unsigned lds_reserve = 32768;
+		auto go = [&](auto kernel, int t0, int t1) {
+			if (t1 > t0)
+				hipLaunchKernelGGL(kernel, dim3((t1 - t0 + 3) / 4, nchunks), dim3(256), lds_reserve, st, d_hdr, d_seg_pos, d_seg_words, d_stream, stream_words, npx,
+								   ntiles, t0, t1, nframes, gop, d_frames, d_error);
+		};
+		go(rirb1_decode_packed<true>, 0, nfast);
+		go(rirb1_decode_packed<false>, nfast, ntiles);
 		return hipGetLastError();
 	}
 

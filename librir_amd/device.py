@@ -375,26 +375,37 @@ class PackedCodec:
         self.workspace = torch.empty((max(wb, 4096),), dtype=torch.uint8, device=dev)
         self.error = torch.zeros((1,), dtype=torch.int32, device=dev)
         self.raw_bytes = self.width * self.height * self.nframes * 2
+        # the packing kernel leaves the workspace's control block zero when it runs to its end: only a block not known to be so (a new
+        # workspace, after grow(), after an encode whose status was not 0) is zeroed before the next encode - a fill launch of its own.
+        # (the address of the workspace whose block is known to be zero: a workspace put in its place is not)
+        self._clean_ws = None
 
     def reset(self):
         """the first half of encode(): zero the workspace's control block (a fill launch of its own)"""
         _check(_lib.rir_codec_packed_reset_device(self.workspace.data_ptr(), self.workspace.numel(), _stream()), "rir_codec_packed_reset_device")
+        self._clean_ws = self.workspace.data_ptr()
 
     def encode(self, frames, check=False, reset=True):
-        """Asynchronous; ``check=True`` (or a later ``finish()``) waits and returns the PackedBatch.  ``reset=False``: the caller has just
-        called reset() on the same stream (the packing kernel alone, for timings)."""
+        """Asynchronous; ``check=True`` (or a later ``finish()``) waits and returns the PackedBatch.  One launch when the control block is
+        known to be clean (the previous encode on this stream left it so), else a fill launch before it.  ``reset=False``: the caller has
+        just called reset() on the same stream (the packing kernel alone, for timings)."""
         fr = _frames3(frames, torch.uint16)
         if tuple(fr.shape) != (self.nframes, self.height, self.width):
             raise RuntimeError("encode: frames do not match the codec geometry")
-        _check((_lib.rir_codec_encode_packed_device if reset else _lib.rir_codec_encode_packed_launch_device)(fr.data_ptr(), self.width, self.height, self.nframes, self.gop, self.hdr.data_ptr(), self.seg_pos.data_ptr(),
+        fill = reset and self._clean_ws != self.workspace.data_ptr()
+        _check((_lib.rir_codec_encode_packed_device if fill else _lib.rir_codec_encode_packed_launch_device)(fr.data_ptr(), self.width, self.height, self.nframes, self.gop, self.hdr.data_ptr(), self.seg_pos.data_ptr(),
                                                    self.seg_words.data_ptr(), self.stream.data_ptr(), self.stream.numel(), self.workspace.data_ptr(),
                                                    self.workspace.numel(), _stream()), "rir_codec_encode_packed_device")
+        self._clean_ws = self.workspace.data_ptr()
         return self.finish() if check else None
 
     def status(self):
-        """(code, low words, high words, arena words asked for): code 0 complete, bit 0 stream capacity, bit 1 arena exceeded; waits."""
+        """(code, low words, high words, arena words asked for) of the last encode: code 0 complete, bit 0 stream capacity, bit 1 arena
+        exceeded; waits."""
         out = (ct.c_ulonglong * 3)()
         r = int(_lib.rir_codec_encode_packed_status(self.workspace.data_ptr(), out, _stream()))
+        if r != 0:
+            self._clean_ws = None  # (the kernel leaves the block zero all the same; it is not relied upon after a failure)
         if r < 0:
             raise RuntimeError("rir_codec_encode_packed_status failed: %s" % last_error())
         return r, int(out[0]), int(out[1]), int(out[2])
@@ -410,6 +421,7 @@ class PackedCodec:
         """room for any data (after a batch did not fit)"""
         self.stream = torch.empty((self.P.stream_max_bytes // 8,), dtype=torch.int64, device=self.device)
         self.workspace = torch.empty((self.P.workspace_max_bytes,), dtype=torch.uint8, device=self.device)
+        self._clean_ws = None
 
     def decode(self, batch=None, out=None, check=True):
         hdr, pos, seg, st = (batch.hdr, batch.seg_pos, batch.seg_words, batch.stream) if batch is not None else (self.hdr, self.seg_pos, self.seg_words, self.stream)
