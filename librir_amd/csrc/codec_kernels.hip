@@ -22,39 +22,24 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "codec_format.h"
 #include "filter_kernels.h"
 #include "runtime.h"
 
-// Cache policy of each traffic class (aux operand of the buffer instructions: 2 = nt, "streaming").
-// Raw frames are read once by the encoder and written once by the decoder, the sparse slots are read once by
-// the compaction: marking those accesses non-temporal keeps them from evicting what the NEXT kernel of the
-// pipeline reads (the dense stream, which should stay in L2 / Infinity Cache between compaction and decode).
-// Measured on the headline workload (scripts/variants.py): all-default 438 us per encode+decode pass,
-// frames nt 391 us, + compaction loads nt 351 us; nt on the stream loads or the sparse stores is worse.
-#ifndef RIR_FRAME_LOAD_AUX
-#define RIR_FRAME_LOAD_AUX 2
-#endif
-#ifndef RIR_FRAME_STORE_AUX
-#define RIR_FRAME_STORE_AUX 2
-#endif
-#ifndef RIR_SPARSE_STORE_AUX
-#define RIR_SPARSE_STORE_AUX 0
-#endif
-#ifndef RIR_STREAM_LOAD_AUX
-#define RIR_STREAM_LOAD_AUX 0
-#endif
-#ifndef RIR_COMPACT_NT_LOAD
-#define RIR_COMPACT_NT_LOAD 1
-#endif
-#ifndef RIR_COMPACT_NT_STORE
-#define RIR_COMPACT_NT_STORE 0
-#endif
-
 namespace rir
 {
+
+	// Cache policy of each traffic class (aux operand of the buffer instructions: 2 = nt, "streaming").
+	// Raw frames are read once by the encoder and written once by the decoder, the sparse slots are read once by
+	// the compaction (nt loads there): marking those accesses non-temporal keeps them from evicting what the NEXT kernel
+	// of the pipeline reads (the dense stream, which should stay in L2 / Infinity Cache between compaction and decode).
+	// Measured on the headline workload (scripts/variants.py): all-default 438 us per encode+decode pass,
+	// frames nt 391 us, + compaction loads nt 351 us; nt on the stream loads or the sparse stores is worse.
+	constexpr int FRAME_LOAD_AUX = 2;
+	constexpr int FRAME_STORE_AUX = 2;
+	constexpr int SPARSE_STORE_AUX = 0;
+	constexpr int STREAM_LOAD_AUX = 0;
 
 	typedef short short2v __attribute__((ext_vector_type(2)));
 	typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
@@ -267,7 +252,7 @@ namespace rir
 	}
 	__device__ __forceinline__ Px8 buf_load8(const void *tile_base, uint32_t lane_off)
 	{
-		const v4u32 v = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(tile_base, RIRB1_TILE_PX * 2), lane_off, 0, RIR_FRAME_LOAD_AUX);
+		const v4u32 v = __builtin_amdgcn_raw_buffer_load_b128(make_rsrc(tile_base, RIRB1_TILE_PX * 2), lane_off, 0, FRAME_LOAD_AUX);
 		Px8 r;
 		r.d[0] = v.x;
 		r.d[1] = v.y;
@@ -282,7 +267,7 @@ namespace rir
 		v.y = r.d[1];
 		v.z = r.d[2];
 		v.w = r.d[3];
-		__builtin_amdgcn_raw_buffer_store_b128(v, make_rsrc(tile_base, RIRB1_TILE_PX * 2), lane_off, 0, RIR_FRAME_STORE_AUX);
+		__builtin_amdgcn_raw_buffer_store_b128(v, make_rsrc(tile_base, RIRB1_TILE_PX * 2), lane_off, 0, FRAME_STORE_AUX);
 	}
 
 	// tile minimum of the 8 packed values of every lane -> wave-uniform 16-bit base
@@ -507,8 +492,8 @@ namespace rir
 			h = emit_record_narrow(r, mode, base, rs, pos, lc, tc, words);
 		else
 			h = emit_record_wide(r, mode, base, rs, pos, lc, tc, words);
-		__builtin_amdgcn_raw_buffer_store_b64(rs.va, out, rs.oa, 0, RIR_SPARSE_STORE_AUX);
-		__builtin_amdgcn_raw_buffer_store_b64(rs.vb, out, rs.ob, 0, RIR_SPARSE_STORE_AUX);
+		__builtin_amdgcn_raw_buffer_store_b64(rs.va, out, rs.oa, 0, SPARSE_STORE_AUX);
+		__builtin_amdgcn_raw_buffer_store_b64(rs.vb, out, rs.ob, 0, SPARSE_STORE_AUX);
 		return h;
 	}
 
@@ -752,14 +737,14 @@ namespace rir
 		uint32_t i = tid;
 		for (; i + 768 < n; i += 1024)
 		{ // four independent 8-byte copies per thread and iteration
-			const uint64_t v0 = RIR_COMPACT_NT_LOAD ? __builtin_nontemporal_load(src + i) : src[i];
-			const uint64_t v1 = RIR_COMPACT_NT_LOAD ? __builtin_nontemporal_load(src + i + 256) : src[i + 256];
-			const uint64_t v2 = RIR_COMPACT_NT_LOAD ? __builtin_nontemporal_load(src + i + 512) : src[i + 512];
-			const uint64_t v3 = RIR_COMPACT_NT_LOAD ? __builtin_nontemporal_load(src + i + 768) : src[i + 768];
+			const uint64_t v0 = __builtin_nontemporal_load(src + i);
+			const uint64_t v1 = __builtin_nontemporal_load(src + i + 256);
+			const uint64_t v2 = __builtin_nontemporal_load(src + i + 512);
+			const uint64_t v3 = __builtin_nontemporal_load(src + i + 768);
 			dst[i] = v0, dst[i + 256] = v1, dst[i + 512] = v2, dst[i + 768] = v3;
 		}
 		for (; i < n; i += 256)
-			dst[i] = RIR_COMPACT_NT_LOAD ? __builtin_nontemporal_load(src + i) : src[i];
+			dst[i] = __builtin_nontemporal_load(src + i);
 	}
 
 	// ==== single-pass dense encoder ===================================================================
@@ -792,6 +777,7 @@ namespace rir
 	// raises the error instead of hanging.
 #define RIR_LB_TAG (1ull << 63)
 #define RIR_LB_TIMEOUT_TICKS 200000000ull /* s_memrealtime runs at 100 MHz: 2 s */
+	constexpr int LB_SLEEP = 8; // s_sleep between two polls of a look-back
 #define RIR_NONE 0xffffffffu
 
 	struct RecordWords
@@ -918,8 +904,8 @@ namespace rir
 		const uint32_t add = sg.spilling ? 0u - sg.lds_used * 8u : RIR_OOB;
 		const uint32_t oa = rw.ia != RIR_NONE ? rw.ia * 8u + add : RIR_OOB;
 		const uint32_t ob = rw.ib != RIR_NONE ? rw.ib * 8u + add : RIR_OOB;
-		__builtin_amdgcn_raw_buffer_store_b64(rw.va, sg.spill, oa, 0, RIR_SPARSE_STORE_AUX);
-		__builtin_amdgcn_raw_buffer_store_b64(rw.vb, sg.spill, ob, 0, RIR_SPARSE_STORE_AUX);
+		__builtin_amdgcn_raw_buffer_store_b64(rw.va, sg.spill, oa, 0, SPARSE_STORE_AUX);
+		__builtin_amdgcn_raw_buffer_store_b64(rw.vb, sg.spill, ob, 0, SPARSE_STORE_AUX);
 		return h;
 	}
 
@@ -1050,9 +1036,10 @@ namespace rir
 	}
 
 	// Look-back of workgroup (c, t), run by ONE wave.  A = sum of the lengths of tiles < t of chunk c, Pc = first word of
-	// chunk c.  false: gave up (clock or error word); the error word is raised.
+	// chunk c.  false: gave up (clock or error word); the error word is raised.  The last argument is unused (the diagnostic
+	// build of 02807a8 wrote its timings there); dropping it would rename the device function.
 	__device__ __noinline__ bool encode_lookback(const uint64_t *P, const uint64_t *gtotal, const uint64_t *gran, uint32_t *error_word, int c, int t,
-												 int ntiles, int ngroups, int lane, uint64_t *A_out, uint64_t *P_out, uint64_t *dbg_words)
+												 int ntiles, int ngroups, int lane, uint64_t *A_out, uint64_t *P_out, uint64_t * /* unused */)
 	{
 		const int g = t >> 6, e1 = t & 63, E = e1 + g + (c > 0 ? 1 : 0);
 		uint64_t accA = 0, accP = 0;
@@ -1088,10 +1075,7 @@ namespace rir
 						return false;
 					}
 				}
-#ifndef RIR_LB_SLEEP
-#define RIR_LB_SLEEP 8
-#endif
-				__builtin_amdgcn_s_sleep(RIR_LB_SLEEP);
+				__builtin_amdgcn_s_sleep(LB_SLEEP);
 			}
 			if (valid)
 			{
@@ -1101,13 +1085,6 @@ namespace rir
 					accA += v & ~RIR_LB_TAG;
 			}
 		}
-#ifdef RIR_DIAG_LB_STATS
-		if (lane == 0)
-		{ // diagnostic build only: time spent looking back, into the pad at the end of the control block (nothing reads it in the kernel)
-			dbg_words[0] = __builtin_amdgcn_s_memrealtime() - t_start; // (the pad word of this segment's spill slot)
-			dbg_words[1] = t_start;
-		}
-#endif
 		*A_out = wave_sum_u64(accA);
 		*P_out = wave_sum_u64(accP);
 		return true;
@@ -1152,9 +1129,6 @@ namespace rir
 		uint64_t *gcount = gran + (((int64_t)nchunks * ntiles + 15) & ~(int64_t)15); // counters: on lines of their own
 		uint64_t *ccount = gcount + (int64_t)nchunks * ngroups;
 
-#ifdef RIR_DIAG_NO_TICKET
-		const int seg = blockIdx.x;
-#else
 		if (threadIdx.x == 0)
 		{
 			const uint32_t head = blockIdx.x & 7u;
@@ -1163,10 +1137,6 @@ namespace rir
 		}
 		__syncthreads();
 		const int seg = __builtin_amdgcn_readfirstlane((int)sh_u32[WAVES]);
-#endif
-#ifdef RIR_DIAG_LB_STATS
-		const uint64_t dbg_t0 = __builtin_amdgcn_s_memrealtime();
-#endif
 		const int chunk = seg / ntiles, tile = seg - chunk * ntiles;
 		const int f_begin = chunk * gop;
 		const int nf = min(gop, nframes - f_begin);
@@ -1232,17 +1202,9 @@ namespace rir
 			}
 		}
 		uint64_t A = 0, Pc = 0;
-#ifdef RIR_DIAG_NO_LOOKBACK
-		const bool ok = true;
-#else
-		const bool ok = encode_lookback(P, gtotal, gran, error_word, chunk, tile, ntiles, ngroups, lane, &A, &Pc,
-										spill + (int64_t)seg * RIRB1_SLOT_WORDS(gop) + (int64_t)gop * RIRB1_REC_MAX_WORDS);
-#endif
+		const bool ok = encode_lookback(P, gtotal, gran, error_word, chunk, tile, ntiles, ngroups, lane, &A, &Pc, nullptr);
 		if (!ok)
 			return; // the look-back gave up: the error word is raised, nothing is copied
-#ifdef RIR_DIAG_LB_STATS
-		const uint64_t dbg_t2 = __builtin_amdgcn_s_memrealtime();
-#endif
 		if (lane == 0)
 		{
 			tile_off[(int64_t)chunk * (ntiles + 1) + tile] = (uint32_t)A;
@@ -1255,9 +1217,6 @@ namespace rir
 				chunk_off[chunk + 1] = Pc + chunk_words;
 			}
 		}
-#ifdef RIR_DIAG_NO_COPY
-		return;
-#endif
 		uint64_t *dst = stream + (Pc + A);
 		for (int i = 0; i < WAVES; ++i)
 		{
@@ -1284,19 +1243,6 @@ namespace rir
 			}
 			dst += n_all;
 		}
-#ifdef RIR_DIAG_LB_STATS
-		if (lane == 0)
-		{
-			uint64_t *dbg = spill + (int64_t)seg * RIRB1_SLOT_WORDS(gop) + (int64_t)gop * RIRB1_REC_MAX_WORDS;
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-			dbg[2] = dbg_t0, dbg[3] = dbg_t2, dbg[4] = __builtin_amdgcn_s_memrealtime();
-			unsigned xcc;
-			asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
-			unsigned hwid;
-			asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID, 0, 32)" : "=s"(hwid));
-			dbg[5] = ((uint64_t)xcc << 32) | hwid;
-		}
-#endif
 	}
 
 	// ==== packed form: the dense stream without the order ===============================================
@@ -1346,12 +1292,6 @@ namespace rir
 		__hip_atomic_store(meet, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		ctrl[64] = low, ctrl[65] = high, ctrl[66] = spill, ctrl[67] = err, ctrl[68] = capacity_words;
 	}
-#ifndef RIR_PACKED_COPY_ALL_WAVES
-#define RIR_PACKED_COPY_ALL_WAVES 0
-#endif
-#ifndef RIR_PACKED_WAVES
-#define RIR_PACKED_WAVES 4
-#endif
 	// Two kernels, as for rirb1_encode_tiles: FAST for the tiles that lie whole inside 16-byte aligned frames, the ragged form for
 	// the last tile of a frame whose size is not a multiple of 512 pixels.  grid = (tile_count, nchunks).
 	template <int WAVES, bool FAST>
@@ -1404,18 +1344,16 @@ namespace rir
 		if (sg.spilling)
 			asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the spilled words have left this wave before another wave reads them
 		__syncthreads();
-#if !RIR_PACKED_COPY_ALL_WAVES
+		// the segment is complete in LDS (+ extents): one wave places and copies it, the others make room (the alternative, every
+		// wave copying its own words after one more barrier, is RIR_PACKED_COPY_ALL_WAVES in 02807a8)
 		if (w != 0)
-			return; // the segment is complete in LDS (+ extents): one wave places and copies it, the others make room
-#endif
-		uint32_t total = 0, before = 0;
+			return;
+		uint32_t total = 0;
 		bool lost = false; // a wave of this segment wanted an extent and got none
-		(void)before;
 #pragma unroll
 		for (int i = 0; i < WAVES; ++i)
 		{
 			const uint32_t n = sh_u32[i];
-			before += i < w ? n : 0u;
 			total += n;
 			lost |= n > sh_u32[WAVES + i] && sh_u64[1 + i] == ~0ull;
 		}
@@ -1443,7 +1381,6 @@ namespace rir
 				seg_words[seg] = total;
 				sh_u64[0] = (fits && !lost) ? at : ~0ull;
 			}
-#if !RIR_PACKED_COPY_ALL_WAVES
 			if (!fits || lost)
 				return;
 			uint64_t *dst = stream + at;
@@ -1471,36 +1408,7 @@ namespace rir
 				}
 				dst += n_all;
 			}
-#endif
 		}
-#if RIR_PACKED_COPY_ALL_WAVES
-		__syncthreads();
-		const uint64_t at = sh_u64[0];
-		if (at == ~0ull)
-			return;
-		{ // every wave moves its own words
-			uint64_t *dst = stream + at + before;
-			const uint64_t *src = enc_lds + (size_t)w * cap;
-			const uint32_t n_all = sh_u32[w], n_lds = sh_u32[WAVES + w];
-			uint32_t j = (uint32_t)lane;
-			for (; j + 192 < n_lds; j += 256)
-			{
-				const uint64_t v0 = src[j], v1 = src[j + 64], v2 = src[j + 128], v3 = src[j + 192];
-				dst[j] = v0, dst[j + 64] = v1, dst[j + 128] = v2, dst[j + 192] = v3;
-			}
-			for (; j < n_lds; j += 64)
-				dst[j] = src[j];
-			if (n_all > n_lds)
-			{
-				const __amdgpu_buffer_rsrc_t sp = make_rsrc(arena + sh_u64[1 + w], (uint32_t)nrec * RIRB1_REC_MAX_WORDS * 8u);
-				for (uint32_t q = (uint32_t)lane; q < n_all - n_lds; q += 64)
-				{
-					const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(sp, q * 8u, 0, 16 /* sc1 */);
-					dst[n_lds + q] = ((uint64_t)v.y << 32) | v.x;
-				}
-			}
-		}
-#endif
 	}
 
 	// ---- decode -----------------------------------------------------------------------------
@@ -1558,8 +1466,8 @@ namespace rir
 			ob = (!r.bad && lc.bit < wb) ? (pos + tot_a + ib - wb + lc.bit) * 8u : RIR_OOB;
 		}
 		// exactly two loads per record, whatever the tier (the consumer's wait counts younger loads)
-		r.a = __builtin_amdgcn_raw_buffer_load_b64(in, oa, 0, RIR_STREAM_LOAD_AUX);
-		r.b = __builtin_amdgcn_raw_buffer_load_b64(in, ob, 0, RIR_STREAM_LOAD_AUX);
+		r.a = __builtin_amdgcn_raw_buffer_load_b64(in, oa, 0, STREAM_LOAD_AUX);
+		r.b = __builtin_amdgcn_raw_buffer_load_b64(in, ob, 0, STREAM_LOAD_AUX);
 		return r;
 	}
 
@@ -1862,14 +1770,14 @@ namespace rir
 					b.x = __builtin_bit_cast(uint32_t, (float)(o.d[2] & 0xffffu)), b.y = __builtin_bit_cast(uint32_t, (float)(o.d[2] >> 16));
 					b.z = __builtin_bit_cast(uint32_t, (float)(o.d[3] & 0xffffu)), b.w = __builtin_bit_cast(uint32_t, (float)(o.d[3] >> 16));
 					const __amdgpu_buffer_rsrc_t r4 = make_rsrc(cur, RIRB1_TILE_PX * 4);
-					__builtin_amdgcn_raw_buffer_store_b128(a, r4, sel ? lane_off * 2u : RIR_OOB, 0, RIR_FRAME_STORE_AUX);
-					__builtin_amdgcn_raw_buffer_store_b128(b, r4, sel ? lane_off * 2u + 16u : RIR_OOB, 0, RIR_FRAME_STORE_AUX);
+					__builtin_amdgcn_raw_buffer_store_b128(a, r4, sel ? lane_off * 2u : RIR_OOB, 0, FRAME_STORE_AUX);
+					__builtin_amdgcn_raw_buffer_store_b128(b, r4, sel ? lane_off * 2u + 16u : RIR_OOB, 0, FRAME_STORE_AUX);
 				}
 				else
 				{
 					v4u32 v;
 					v.x = o.d[0], v.y = o.d[1], v.z = o.d[2], v.w = o.d[3];
-					__builtin_amdgcn_raw_buffer_store_b128(v, make_rsrc(cur, RIRB1_TILE_PX * 2), sel ? lane_off : RIR_OOB, 0, RIR_FRAME_STORE_AUX);
+					__builtin_amdgcn_raw_buffer_store_b128(v, make_rsrc(cur, RIRB1_TILE_PX * 2), sel ? lane_off : RIR_OOB, 0, FRAME_STORE_AUX);
 				}
 			}
 			else if (sel)
@@ -1991,14 +1899,6 @@ namespace rir
 		int cap = 448; // 14.4 KB per workgroup: 11 workgroups per CU, 7 packing (28 waves) while 4 wait for their offsets (1 wave each)
 		if (cap > share * RIRB1_REC_MAX_WORDS)
 			cap = share * RIRB1_REC_MAX_WORDS;
-		static int cap_env = -1;
-		if (cap_env < 0)
-		{
-			const char *ev = getenv("RIR_ENC_LDS_WORDS"); // tuning aid
-			cap_env = ev ? atoi(ev) : 0;
-		}
-		if (cap_env > 0)
-			cap = cap_env;
 		const size_t lds = (size_t)WAVES * cap * 8 + 8 + (2 * WAVES + 2) * 4;
 		const int64_t total = (int64_t)nchunks * ntiles;
 		// its workgroups wait for the segments in front of them (dealt by tickets, so any grid size makes progress on its own - but
@@ -2035,20 +1935,15 @@ namespace rir
 
 	// the packed form.  d_ctrl: RIRB1_PACKED_CTRL_BYTES at the start of the workspace (zeroed here when `reset`; the kernel leaves it
 	// zero), d_arena: the rest of it.
+	constexpr int PACKED_WAVES = 4; // waves that pack one segment between them
 	int packed_lds_words(int gop)
 	{
-		constexpr int WAVES = RIR_PACKED_WAVES;
+		constexpr int WAVES = PACKED_WAVES;
 		const int share = (gop + 1 + WAVES - 1) / WAVES + 1;
 		int cap = 448 * 4 / WAVES; // 14.4 KB per workgroup, as the dense kernel: the reference's recipe needs 290-355 words per wave of four
 		if (cap > share * RIRB1_REC_MAX_WORDS)
 			cap = share * RIRB1_REC_MAX_WORDS;
-		static int cap_env = -1;
-		if (cap_env < 0)
-		{
-			const char *ev = getenv("RIR_ENC_LDS_WORDS"); // tuning aid
-			cap_env = ev ? atoi(ev) : 0;
-		}
-		return cap_env > 0 ? cap_env : cap;
+		return cap;
 	}
 	hipError_t launch_encode_packed(const uint16_t *d_frames, int64_t npx, int ntiles, int nframes, int gop, uint64_t *d_hdr, uint64_t *d_seg_pos,
 									uint32_t *d_seg_words, uint64_t *d_stream, uint64_t capacity_words, uint64_t *d_ctrl, uint64_t *d_arena,
@@ -2061,15 +1956,10 @@ namespace rir
 			if (e != hipSuccess)
 				return e;
 		}
-		constexpr int WAVES = RIR_PACKED_WAVES;
+		constexpr int WAVES = PACKED_WAVES;
 		const int cap = packed_lds_words(gop);
-		// (a build with -DRIR_PACKED_ONE_CURSOR sends every segment through the low cursor: the measurement of DESIGN.md §3 - 207 us a launch
-		// against 162-165 with two; the product library reads no such switch)
-#ifdef RIR_PACKED_ONE_CURSOR
-		constexpr int diag = 1;
-#else
+		// two stream cursors: diag 1 sends every segment through the low one, 207 us a launch against 162-165 with two
 		constexpr int diag = 0;
-#endif
 		const size_t lds = (size_t)WAVES * cap * 8 + (1 + WAVES) * 8 + 2 * WAVES * 4;
 		const bool aligned = ((npx & 7) == 0) && ((((uintptr_t)d_frames) & 15) == 0);
 		const int nfast = aligned ? (int)(npx / RIRB1_TILE_PX) : 0; // tiles that lie whole inside the frame

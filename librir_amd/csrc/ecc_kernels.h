@@ -5,18 +5,13 @@
 
 namespace rir
 {
-#ifndef RIR_ECC_BLOCK
-#define RIR_ECC_BLOCK 256
-#endif
-#ifndef RIR_ECC_MAX_BLOCKS
-#define RIR_ECC_MAX_BLOCKS 256
-#endif
 	enum
 	{
 		ECC_NSUMS = 15,
-		ECC_BLOCK = RIR_ECC_BLOCK,
+		ECC_BLOCK = 256,
 		ECC_SOLVE_BLOCK = 256
 	};
+	constexpr int ECC_MAX_BLOCKS = 256; // workgroups of one sequence's sums: one per CU, all resident
 	// Lives in device memory; one per alignment in flight.
 	struct EccState
 	{

@@ -25,7 +25,7 @@ namespace rir
 	static int ecc_blocks(int w, int h)
 	{
 		const int64_t b = ((int64_t)w * h + ECC_BLOCK - 1) / ECC_BLOCK;
-		return (int)(b < RIR_ECC_MAX_BLOCKS ? b : RIR_ECC_MAX_BLOCKS);
+		return (int)(b < ECC_MAX_BLOCKS ? b : ECC_MAX_BLOCKS);
 	}
 	size_t ecc_workspace_bytes(int w, int h) { return (size_t)ecc_blocks(w, h) * 16 * sizeof(double); }
 
@@ -93,29 +93,17 @@ namespace rir
 		__builtin_amdgcn_wave_barrier();
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 	}
-#ifdef RIR_ECC_DIAG
-	static __shared__ unsigned long long ecc_diag_loop_end, ecc_diag_reduced; // (written by every thread with about the same value)
-#endif
-#ifndef RIR_ECC_GRAD_ON_THE_FLY
-#define RIR_ECC_GRAD_ON_THE_FLY 0 /* measured: slower (81 k against 90 k frames/s over 8 sequences) although the L2 then holds a sequence - DESIGN.md */
-#endif
-#ifndef RIR_ECC_PIXELS_PER_ROUND
-#define RIR_ECC_PIXELS_PER_ROUND 3 /* one sequence, one wave per SIMD: 19.3 k frames/s; 2: 18.8 k, 6: 19.3 k at 226 VGPRs */
-#endif
-#ifndef RIR_ECC_MULTI_PIXELS_PER_ROUND
-#define RIR_ECC_MULTI_PIXELS_PER_ROUND 1 /* several sequences: latency is hidden by waves (RIR_ECC_MULTI_WAVES per SIMD), not by pixels in flight */
-#endif
-#ifndef RIR_ECC_MULTI_WAVES
-#define RIR_ECC_MULTI_WAVES 5 /* 96 VGPRs, 23 KB of LDS: five workgroups to a CU, 1 280 places - the 1 024 compute workgroups of 8 sequences (4 pairs x
-                                 256 slices of one row each: four to every CU, the dispatcher deals them evenly - scripts/ubench/wg_placement.hip) and
-                                 their 8 service workgroups.  (The first form of the kernel - no service workgroups, the adding done by each sequence's
-                                 slice 0 - at 128 VGPRs, 4 workgroups per CU, (pixels per round, waves per SIMD): (1, 4) 70-75 k frames/s over 8
-                                 sequences, (2, 4) 65-69, (3, 4) 62-66, (5, 3) 62-65.)  The pixel loop is bound by latency - 44 % of its L2 accesses miss:
-                                 a sequence's four arrays are 5.2 MB, an XCD's L2 4 MB (profiles/r04_pmc_ecc.json) - which more pixels per round did not hide */
-#endif
-#ifndef RIR_ECC_MULTI_MARGIN
-#define RIR_ECC_MULTI_MARGIN 0
-#endif
+	// pixels per round of the one-sequence kernels (one wave per SIMD): 3 gives 19.3 k frames/s; 2: 18.8 k, 6: 19.3 k at 226 VGPRs
+	constexpr int ECC_PIXELS_PER_ROUND = 3;
+	// several sequences: latency is hidden by waves (ECC_MULTI_WAVES per SIMD), not by pixels in flight
+	constexpr int ECC_MULTI_PIXELS_PER_ROUND = 1;
+	// 96 VGPRs, 23 KB of LDS: five workgroups to a CU, 1 280 places - the 1 024 compute workgroups of 8 sequences (4 pairs x 256 slices
+	// of one row each: four to every CU, the dispatcher deals them evenly - scripts/ubench/wg_placement.hip) and their 8 service
+	// workgroups.  (The first form of the kernel - no service workgroups, the adding done by each sequence's slice 0 - at 128 VGPRs,
+	// 4 workgroups per CU, (pixels per round, waves per SIMD): (1, 4) 70-75 k frames/s over 8 sequences, (2, 4) 65-69, (3, 4) 62-66,
+	// (5, 3) 62-65.)  The pixel loop is bound by latency - 44 % of its L2 accesses miss: a sequence's four arrays are 5.2 MB, an XCD's
+	// L2 4 MB (profiles/r04_pmc_ecc.json) - which more pixels per round did not hide.
+	constexpr int ECC_MULTI_WAVES = 5;
 	// the 15 sums of workgroup `blk` of `nblk` at translation (tx, ty), reduced over the workgroup (fixed order); valid in threads < ECC_NSUMS
 	template <int R> // pixels per round: their 13 R loads are in flight together; the sums are taken in pixel order whatever R is
 	__device__ __forceinline__ double ecc_block_sums(const float *__restrict__ templ, const float *__restrict__ image, const float *__restrict__ gximg,
@@ -126,7 +114,7 @@ namespace rir
 #pragma unroll
 		for (int k = 0; k < ECC_NSUMS; ++k)
 			s[k] = 0.0;
-		// grid-stride over the pixels (at most RIR_ECC_MAX_BLOCKS workgroups: one row of partials each), two pixels per round: the
+		// grid-stride over the pixels (at most ECC_MAX_BLOCKS workgroups: one row of partials each), two pixels per round: the
 		// 26 loads of both are in flight together (a thread has 5 pixels at 640x512 and one wave per SIMD: one pixel per round was
 		// five exposed L2 latencies); sums are taken in pixel order as before
 		struct Px
@@ -141,7 +129,6 @@ namespace rir
 		const int dy = stride / w, dx = stride - dy * w;
 		const uint32_t bytes = (uint32_t)npx * 4u;
 		const __amdgpu_buffer_rsrc_t r_img = ecc_rsrc(image, bytes), r_gx = ecc_rsrc(gximg, bytes), r_gy = ecc_rsrc(gyimg, bytes), r_t = ecc_rsrc(templ, bytes);
-		(void)r_gx, (void)r_gy;
 		auto ld = [](__amdgpu_buffer_rsrc_t r, uint32_t off) { return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0)); };
 		auto sample = [&](int i, int x, int y, bool inside) {
 			const float sx = (float)x + tx, sy = (float)y + ty;
@@ -152,11 +139,7 @@ namespace rir
 			// past the end - the validity test, the four range tests of the taps and the four selects on their offsets are left out: same
 			// values, bit for bit, a sixth of the loop's vector instructions fewer, and the loop is bound by those (profiles/r04_pmc_ecc.json).
 			// Decided per WAVE (64 consecutive pixels of a line): with a translation of t pixels every wave but those within t of two borders.
-#if !RIR_ECC_GRAD_ON_THE_FLY && !defined(RIR_ECC_NO_INTERIOR_PATH)
 			const bool interior = mask == nullptr && __builtin_amdgcn_ballot_w64(!(inside && (unsigned)x0 < (unsigned)(w - 1) && (unsigned)y0 < (unsigned)(h - 1))) == 0;
-#else
-			const bool interior = false;
-#endif
 			bool valid = true;
 			if (!interior)
 			{ // validity: the nearest source pixel lies inside the image and inside the caller's mask
@@ -181,34 +164,9 @@ namespace rir
 			Px p;
 			// (The two taps of an image row as ONE 8-byte load - 7 loads per pixel instead of 13, the lanes at the image's left and right edge
 			// fixed up afterwards - was measured: the loop took 5.4 us a row instead of 3.6.  8-byte loads at addresses that are only
-			// 4-byte aligned are not what the memory pipeline likes.)
-#if RIR_ECC_GRAD_ON_THE_FLY
-			// The gradient taps are COMPUTED from the image instead of loaded from the gradient arrays: the same twelve loads per pixel, but
-			// all of them from ONE array - a sequence's working set is its image and its template, 2.6 MB instead of 5.2, under an XCD's 4 MB
-			// L2 (with four arrays 44 % of the L2 accesses of the sequence kernels missed: profiles/r03_pmc_ecc_caches.json).  Same values,
-			// bit for bit: a stored gradient is 0.5f * right - 0.5f * left of the stored image (ecc_gradient_kernel,
-			// minmax_apply_grad_frames_kernel), two exact products and one rounding, and at the image's edge, where reflection makes both
-			// neighbours the same pixel, it is 0.5f a - 0.5f a = +0.
-			{
-				const bool xm = (unsigned)(x0 - 1) < (unsigned)w, xp = (unsigned)(x0 + 2) < (unsigned)w, ym = (unsigned)(y0 - 1) < (unsigned)h,
-						   yp = (unsigned)(y0 + 2) < (unsigned)h;
-				const float i00 = ld(r_img, xa && ya ? lin : kOutside), i01 = ld(r_img, xb && ya ? lin + 4u : kOutside);
-				const float i10 = ld(r_img, xa && yb ? lin + w4 : kOutside), i11 = ld(r_img, xb && yb ? lin + w4 + 4u : kOutside);
-				const float im0 = ld(r_img, xm && ya ? lin - 4u : kOutside), ip0 = ld(r_img, xp && ya ? lin + 8u : kOutside);
-				const float im1 = ld(r_img, xm && yb ? lin + w4 - 4u : kOutside), ip1 = ld(r_img, xp && yb ? lin + w4 + 8u : kOutside);
-				const float iu0 = ld(r_img, xa && ym ? lin - w4 : kOutside), iu1 = ld(r_img, xb && ym ? lin - w4 + 4u : kOutside);
-				const float id0 = ld(r_img, xa && yp ? lin + 2u * w4 : kOutside), id1 = ld(r_img, xb && yp ? lin + 2u * w4 + 4u : kOutside);
-				// a tap (c, r) has a horizontal gradient when it is inside the image and not in its first or last column (there: + 0)
-				const bool cx0 = x0 > 0 && x0 < w - 1, cx1 = x0 + 1 > 0 && x0 + 1 < w - 1, cy0 = y0 > 0 && y0 < h - 1, cy1 = y0 + 1 > 0 && y0 + 1 < h - 1;
-				const float gx00 = cx0 && ya ? 0.5f * i01 - 0.5f * im0 : 0.0f, gx01 = cx1 && ya ? 0.5f * ip0 - 0.5f * i00 : 0.0f;
-				const float gx10 = cx0 && yb ? 0.5f * i11 - 0.5f * im1 : 0.0f, gx11 = cx1 && yb ? 0.5f * ip1 - 0.5f * i10 : 0.0f;
-				const float gy00 = cy0 && xa ? 0.5f * i10 - 0.5f * iu0 : 0.0f, gy01 = cy0 && xb ? 0.5f * i11 - 0.5f * iu1 : 0.0f;
-				const float gy10 = cy1 && xa ? 0.5f * id0 - 0.5f * i00 : 0.0f, gy11 = cy1 && xb ? 0.5f * id1 - 0.5f * i01 : 0.0f;
-				p.I = lerp2(i00, i01, i10, i11);
-				p.gx = lerp2(gx00, gx01, gx10, gx11);
-				p.gy = lerp2(gy00, gy01, gy10, gy11);
-			}
-#else
+			// 4-byte aligned are not what the memory pipeline likes.)  Computing the gradient taps from the image instead of loading
+			// them (a working set of 2.6 MB instead of 5.2, under an XCD's L2) gave the same bits but was slower: 81 k against 90 k frames/s
+			// over 8 sequences (RIR_ECC_GRAD_ON_THE_FLY in 02807a8).
 			{
 				uint32_t o00 = lin, o01 = lin + 4u, o10 = lin + w4, o11 = lin + w4 + 4u;
 				if (!interior)
@@ -218,7 +176,6 @@ namespace rir
 				p.gx = blend(r_gx);
 				p.gy = blend(r_gy);
 			}
-#endif
 			p.T = ld(r_t, (uint32_t)i * 4u);
 			p.valid = valid;
 			return p;
@@ -254,9 +211,6 @@ namespace rir
 				x = xx, y = yy;
 			}
 		}
-#ifdef RIR_ECC_DIAG
-		ecc_diag_loop_end = __builtin_amdgcn_s_memrealtime();
-#endif
 		// Reduction over the workgroup through LDS, in a fixed order and without cross-lane operations (fifteen 64-bit butterflies of
 		// six ds_bpermute steps each took 3.3 us of a 14 us iteration): every thread leaves its 15 sums in LDS; thread t then adds, for
 		// sum k = t % 16, the 16 threads of chunk c = t / 16 in order; thread k < 15 finally adds the chunks in order.
@@ -284,9 +238,6 @@ namespace rir
 			}
 		}
 		ecc_lds_barrier();
-#ifdef RIR_ECC_DIAG
-		ecc_diag_reduced = __builtin_amdgcn_s_memrealtime();
-#endif
 		double v = 0.0;
 		if (threadIdx.x < ECC_NSUMS)
 #pragma unroll 4
@@ -303,7 +254,7 @@ namespace rir
 		if (state->done)
 			return;
 		__shared__ EccReduceLds red;
-		const double v = ecc_block_sums<RIR_ECC_PIXELS_PER_ROUND>(templ, image, gximg, gyimg, mask, w, h, state->tx, state->ty, blockIdx.x, gridDim.x, red, 0);
+		const double v = ecc_block_sums<ECC_PIXELS_PER_ROUND>(templ, image, gximg, gyimg, mask, w, h, state->tx, state->ty, blockIdx.x, gridDim.x, red, 0);
 		if (threadIdx.x < ECC_NSUMS)
 			partials[(size_t)blockIdx.x * 16 + threadIdx.x] = v; // rows of 16 doubles (ecc_rows_total)
 	}
@@ -460,7 +411,7 @@ namespace rir
 
 	// ---- all iterations of an alignment in ONE launch -----------------------------------------------------------------
 	//
-	// grid = nblk (<= RIR_ECC_MAX_BLOCKS = 256: one workgroup per CU, all resident), block = 256.  Per iteration every workgroup
+	// grid = nblk (<= ECC_MAX_BLOCKS = 256: one workgroup per CU, all resident), block = 256.  Per iteration every workgroup
 	// leaves its row of 15 sums as granules {value, flag}; workgroup 0 waits for all of them, adds
 	// the rows in the order ecc_solve_kernel does - the results are the same bits as with two launches per iteration - solves,
 	// and publishes the new translation with a flag the other workgroups wait for.  Two hops across the chip per iteration
@@ -510,24 +461,14 @@ namespace rir
 		for (int it = 1; !done; ++it)
 		{
 			const unsigned long long flag = ((unsigned long long)(epoch & 0x3fffffffu) << 32) | ((unsigned long long)(unsigned int)f << 20) | (unsigned long long)((unsigned int)it & 0xfffffu);
-#ifdef RIR_ECC_DIAG
-			const unsigned long long dg0 = __builtin_amdgcn_s_memrealtime();
-			unsigned long long dg1 = 0, dg2 = 0, dg3 = 0;
-#endif
-			const double v = ecc_block_sums<RIR_ECC_PIXELS_PER_ROUND>(templ, image, gximg, gyimg, mask, w, h, tx, ty, b, nblk, red, it & 1);
+			const double v = ecc_block_sums<ECC_PIXELS_PER_ROUND>(templ, image, gximg, gyimg, mask, w, h, tx, ty, b, nblk, red, it & 1);
 			// hand-off without fences (a release / acquire pair at agent scope writes back and invalidates whole caches: 227 us per
 			// frame against 139 with two launches per iteration) and without a drain: every sum travels as a granule {value, flag}
 			if (tid < ECC_NSUMS)
 				ecc_granule_store(rows_rs, (uint32_t)b * 256u + (uint32_t)tid * 16u, (unsigned long long)__double_as_longlong(v), flag);
-#ifdef RIR_ECC_DIAG
-			dg1 = __builtin_amdgcn_s_memrealtime();
-#endif
 			if (b == 0)
 			{
 				const bool all_ok = ecc_rows_total<true>(rows, nblk, flag, part, tot);
-#ifdef RIR_ECC_DIAG
-				dg2 = __builtin_amdgcn_s_memrealtime();
-#endif
 				if (tid == 0)
 				{
 					done = all_ok ? ecc_solve_step(tot, st) : 2;
@@ -562,15 +503,6 @@ namespace rir
 			__syncthreads();
 			tx = sh_t[0], ty = sh_t[1];
 			done = sh_done;
-#ifdef RIR_ECC_DIAG
-			if (tid == 0 && (b == 0 || b == nblk - 1))
-			{ // ticks (10 ns): sums + publish | wait for the rows | add + solve + publish (workgroup 0) or the whole wait (last workgroup)
-				dg3 = __builtin_amdgcn_s_memrealtime();
-				unsigned long long *dg = pub + 8 + (b == 0 ? 0 : 8);
-				dg[0] += dg1 - dg0, dg[1] += (b == 0 ? dg2 : dg3) - dg1, dg[2] += b == 0 ? dg3 - dg2 : 0, dg[3] += 1;
-				dg[4] += ecc_diag_loop_end - dg0, dg[5] += ecc_diag_reduced - ecc_diag_loop_end;
-			}
-#endif
 			__syncthreads(); // (red / tot / sh_* are reused by the next iteration)
 		}
 		if (b == 0 && tid == 0 && results)
@@ -654,9 +586,6 @@ namespace rir
 			for (int it = 1; !done; ++it)
 			{
 				const unsigned long long flag = ecc_flag(epoch, f, it);
-#ifdef RIR_ECC_DIAG
-				const unsigned long long dg0 = __builtin_amdgcn_s_memrealtime();
-#endif
 				// While the rows are being computed only a few of them are watched - every 16th, one granule each, by 16 lanes - and
 				// the whole set (61 KB of write-through granules per look) is asked for when those have come: the rows of a turn are
 				// finished within a microsecond of each other, and eight service workgroups that look at everything all the time
@@ -677,22 +606,12 @@ namespace rir
 				}
 				__syncthreads();
 				const bool all_ok = ecc_rows_total<true>(sq.rows, V, flag, part, tot);
-#ifdef RIR_ECC_DIAG
-				const unsigned long long dg1 = __builtin_amdgcn_s_memrealtime();
-#endif
 				if (tid == 0)
 				{
 					done = all_ok ? ecc_solve_step(tot, st) : 2;
 					sh_done = done;
 					ecc_granule_store(pub_rs, 0, (unsigned long long)__float_as_uint(st.tx) | ((unsigned long long)__float_as_uint(st.ty) << 32),
 									  flag | ((unsigned long long)done << 62));
-#ifdef RIR_ECC_DIAG
-					if (q == 0)
-					{ // ticks (10 ns): waiting for + adding the rows | solve + publish
-						unsigned long long *dg = pub + 8;
-						dg[0] += dg1 - dg0, dg[1] += __builtin_amdgcn_s_memrealtime() - dg1, dg[2] += 1;
-					}
-#endif
 				}
 				__syncthreads();
 				done = sh_done;
@@ -710,7 +629,7 @@ namespace rir
 			table[q].frames_done = frames_done;
 	}
 
-	__attribute__((amdgpu_waves_per_eu(RIR_ECC_MULTI_WAVES, RIR_ECC_MULTI_WAVES))) __global__ __launch_bounds__(ECC_BLOCK) void ecc_run_multi_kernel(EccSeq *__restrict__ table, int S, int w, int h, int V, int max_iter, double eps,
+	__attribute__((amdgpu_waves_per_eu(ECC_MULTI_WAVES, ECC_MULTI_WAVES))) __global__ __launch_bounds__(ECC_BLOCK) void ecc_run_multi_kernel(EccSeq *__restrict__ table, int S, int w, int h, int V, int max_iter, double eps,
 																	  unsigned int epoch, unsigned int *__restrict__ ctl, unsigned int arrivals_before,
 																	  unsigned int *host_go)
 	{
@@ -773,9 +692,6 @@ namespace rir
 		int red_calls = 0;
 		// (Asking for the decision a turn starts with already between the pixel loop and the reduction of the turn before - its answer
 		// kept in flight across the reduction's barrier - was tried: no faster; the decision is rarely there that early.)
-#ifdef RIR_ECC_DIAG
-		unsigned long long dg_rows = 0, dg_wait = 0, dg_n = 0, dg_loop = 0;
-#endif
 		for (bool any = true; any;)
 		{
 			any = false;
@@ -787,9 +703,6 @@ namespace rir
 					continue;
 				if (t.asked)
 				{ // the decision on the rows this workgroup left a turn ago
-#ifdef RIR_ECC_DIAG
-					const unsigned long long w0 = __builtin_amdgcn_s_memrealtime();
-#endif
 					const unsigned long long flag = ecc_flag(epoch, t.f, t.it);
 					if (tid == 0)
 					{
@@ -815,9 +728,6 @@ namespace rir
 					if (done != 2)
 						t.tx = ecc_uni(sh_t[0]), t.ty = ecc_uni(sh_t[1]);
 					__syncthreads(); // (sh_* are reused by the next turn)
-#ifdef RIR_ECC_DIAG
-					dg_wait += __builtin_amdgcn_s_memrealtime() - w0;
-#endif
 					t.asked = false;
 					if (done == 0)
 						++t.it;
@@ -833,36 +743,20 @@ namespace rir
 					}
 				}
 				any = true;
-#ifdef RIR_ECC_DIAG
-				const unsigned long long r0 = __builtin_amdgcn_s_memrealtime();
-#endif
 				const unsigned long long flag = ecc_flag(epoch, t.f, t.it);
 				for (int b = slice; b < V; b += nslices)
 				{
-					const double v = ecc_block_sums<RIR_ECC_MULTI_PIXELS_PER_ROUND>(t.templ, t.image, t.gx, t.gy, nullptr, w, h, t.tx, t.ty, b, V, red, (red_calls++) & 1);
+					const double v = ecc_block_sums<ECC_MULTI_PIXELS_PER_ROUND>(t.templ, t.image, t.gx, t.gy, nullptr, w, h, t.tx, t.ty, b, V, red, (red_calls++) & 1);
 					if (tid < ECC_NSUMS)
 						ecc_granule_store(t.rows_rs, (uint32_t)b * 256u + (uint32_t)tid * 16u, (unsigned long long)__double_as_longlong(v), flag);
-#ifdef RIR_ECC_DIAG
-					dg_loop += ecc_diag_loop_end - r0; // (one row per turn: r0 is the row's start)
-#endif
 				}
 				t.asked = true;
-#ifdef RIR_ECC_DIAG
-				dg_rows += __builtin_amdgcn_s_memrealtime() - r0, dg_n += 1;
-#endif
 			}
 		}
-#ifdef RIR_ECC_DIAG
-		if (g == 0 && tid == 0 && (slice == 0 || slice == nslices - 1))
-		{ // ticks (10 ns), per turn: rows | waiting for a decision
-			unsigned long long *dg = reinterpret_cast<unsigned long long *>(table[0].rows + (size_t)V * 32) + 8 + (slice == 0 ? 4 : 8);
-			dg[0] += dg_rows, dg[1] += dg_wait, dg[2] += dg_n, dg[3] += dg_loop;
-		}
-#endif
 	}
 
 	int ecc_run_grid(int w, int h) { return ecc_blocks(w, h); }
-	int ecc_run_multi_capacity() { return resident_capacity(reinterpret_cast<const void *>(ecc_run_multi_kernel), ECC_BLOCK, 0, RIR_ECC_MULTI_MARGIN != 0); }
+	int ecc_run_multi_capacity() { return resident_capacity(reinterpret_cast<const void *>(ecc_run_multi_kernel), ECC_BLOCK, 0, false); } // every place of the device: the kernel checks its own residency
 	int ecc_rows(int w, int h) { return ecc_blocks(w, h); }
 	// d_table: nseq entries (device); nslices compute workgroups per PAIR of sequences (1 .. ecc_rows(w, h)), one service workgroup per
 	// sequence: ecc_run_multi_grid(nseq, nslices) <= ecc_run_multi_capacity()
@@ -900,7 +794,7 @@ namespace rir
 	// the alignment's grid fits - otherwise two launches per iteration (same sums in the same order, same results)
 	int ecc_run_capacity() { return resident_capacity(reinterpret_cast<const void *>(ecc_run_kernel), ECC_BLOCK, 0); }
 	bool ecc_run_fits(int w, int h) { return ecc_blocks(w, h) <= ecc_run_capacity(); }
-	size_t ecc_run_workspace_bytes(int w, int h) { return (size_t)ecc_blocks(w, h) * 256 + 256; } // rows of 16 granules, then pub (+ diagnostics)
+	size_t ecc_run_workspace_bytes(int w, int h) { return (size_t)ecc_blocks(w, h) * 256 + 256; } // rows of 16 granules, then pub
 	hipError_t launch_ecc_run(const float *d_templ, const float *d_image, const float *d_gx, const float *d_gy, const uint8_t *d_mask, int w, int h,
 							  double *d_rows, EccState *d_state, EccHostView *host_view, float tx, float ty, int max_iter, double eps, unsigned int epoch,
 							  int nframes, EccFrameResult *d_results, unsigned int *d_ctl, unsigned int arrivals_before, hipStream_t st)

@@ -198,9 +198,7 @@ namespace rir
 	// row (r == w -> l, b == h -> t) and columns left or right of the source under "nearest" / "background" /
 	// "noborder" are handled in place.  Every other tile (rows above / below the source, "wrap", ...) runs
 	// translate_px pixel by pixel.  Bit-identical to the reference.  (0.135 -> 0.097 ms per 256 frames 640x512 uint16; the XCD-major order is a quarter of that.)
-#ifndef RIR_TR_TY
-#define RIR_TR_TY 16
-#endif
+	constexpr int TR_TY = 16; // output rows per wave tile
 	template <class T>
 	__device__ __forceinline__ T buffer_load_px(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff)
 	{
@@ -228,7 +226,7 @@ namespace rir
 																 const float *__restrict__ offsets, int per_frame_offsets, float sign, int strategy, int rows,
 																 int copy_tail)
 	{
-		constexpr int OW = 63, OH = RIR_TR_TY;
+		constexpr int OW = 63, OH = TR_TY;
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 		// XCD-major tile order with the column index fastest: tiles that are neighbours along x split cache lines of the
@@ -445,7 +443,7 @@ namespace rir
 										 int per_frame, float sign, int strategy, int rows, hipStream_t st)
 	{
 		U back = *reinterpret_cast<const U *>(background);
-		dim3 block(256), grid((unsigned)((w + 62) / 63), (unsigned)((rows + 4 * RIR_TR_TY - 1) / (4 * RIR_TR_TY)), nframes);
+		dim3 block(256), grid((unsigned)((w + 62) / 63), (unsigned)((rows + 4 * TR_TY - 1) / (4 * TR_TY)), nframes);
 		hipLaunchKernelGGL((translate_tile_kernel<T, U>), grid, block, 0, st, (const T *)src, (U *)dst, back, w, h, d_offsets, per_frame, sign, strategy, rows,
 						   0);
 		return hipGetLastError();
@@ -491,7 +489,7 @@ namespace rir
 	// are copied.
 	hipError_t launch_remove_motion(const uint16_t *src, uint16_t *dst, int w, int h, int rows, int nframes, const float *d_shifts, hipStream_t st)
 	{
-		dim3 block(256), grid((unsigned)((w + 62) / 63), (unsigned)((h + 4 * RIR_TR_TY - 1) / (4 * RIR_TR_TY)), nframes);
+		dim3 block(256), grid((unsigned)((w + 62) / 63), (unsigned)((h + 4 * TR_TY - 1) / (4 * TR_TY)), nframes);
 		hipLaunchKernelGGL((translate_tile_kernel<uint16_t, u16_via_f32>), grid, block, 0, st, src, reinterpret_cast<u16_via_f32 *>(dst), u16_via_f32{0}, w, h,
 						   d_shifts, 1, -1.f, (int)TRANSLATE_NEAREST, rows, 1);
 		return hipGetLastError();
@@ -557,9 +555,7 @@ namespace rir
 	// lanes with DPP wave shifts.  No LDS, no barrier.  (History: the tile-staging version took 0.25 ms per 256
 	// frames whatever the radius, set by its load / barrier / compute phases; the version with a wave-private LDS
 	// strip for the row pass and loads under conditions 0.136 ms.)
-#ifndef RIR_GAUSS_TY
-#define RIR_GAUSS_TY 16 /* output rows per wave tile */
-#endif
+	constexpr int GAUSS_TY = 16; // output rows per wave tile
 	// TIN = float, or uint16_t (the integer -> float conversion of a u16 frame folded into the load).
 	typedef float v2f __attribute__((ext_vector_type(2)));
 	__device__ __forceinline__ float wave_shl1(float f) // lane i <- lane i + 1 (0 into lane 63)
@@ -575,7 +571,7 @@ namespace rir
 	__global__ __launch_bounds__(256) void gaussian_sep_kernel(const TIN *__restrict__ src, float *__restrict__ dst, int w, int h,
 															   const float *__restrict__ kern)
 	{
-		constexpr int TY = RIR_GAUSS_TY, HY = TY / 2, KW = 2 * R + 1, OUTW = 64 - 2 * R, NR = TY + 2 * R;
+		constexpr int TY = GAUSS_TY, HY = TY / 2, KW = 2 * R + 1, OUTW = 64 - 2 * R, NR = TY + 2 * R;
 		static_assert(TY % 2 == 0, "rows are processed in pairs (packed FMAs)");
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -735,7 +731,7 @@ namespace rir
 	template <int R, class TIN>
 	__global__ __launch_bounds__(256) void gaussian_exact_kernel(const TIN *__restrict__ src, float *__restrict__ dst, int w, int h, const float *__restrict__ kern)
 	{
-		constexpr int TY = RIR_GAUSS_TY, KW = 2 * R + 1, OUTW = 64 - 2 * R, NR = TY + 2 * R;
+		constexpr int TY = GAUSS_TY, KW = 2 * R + 1, OUTW = 64 - 2 * R, NR = TY + 2 * R;
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 		int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
@@ -872,7 +868,7 @@ namespace rir
 		if (radius < 1 || radius > 4)
 			return false;
 		const int outw = 64 - 2 * radius;
-		dim3 block(256), tgrid((w + outw - 1) / outw, (h + 4 * RIR_GAUSS_TY - 1) / (4 * RIR_GAUSS_TY), nframes);
+		dim3 block(256), tgrid((w + outw - 1) / outw, (h + 4 * GAUSS_TY - 1) / (4 * GAUSS_TY), nframes);
 		switch (radius)
 		{
 		case 1:
@@ -896,7 +892,7 @@ namespace rir
 		if (radius < 1 || radius > 4)
 			return false;
 		const int outw = 64 - 2 * radius;
-		dim3 block(256), tgrid((w + outw - 1) / outw, (h + 4 * RIR_GAUSS_TY - 1) / (4 * RIR_GAUSS_TY), nframes);
+		dim3 block(256), tgrid((w + outw - 1) / outw, (h + 4 * GAUSS_TY - 1) / (4 * GAUSS_TY), nframes);
 		switch (radius)
 		{
 		case 1:
@@ -968,23 +964,18 @@ namespace rir
 		const uint32_t f2 = floor_v | (floor_v << 16);
 		if (i8 + 8 <= total && ((((uintptr_t)in) | ((uintptr_t)out)) & 15) == 0)
 		{
-#ifndef RIR_CLAMP_COPY_NT
-#define RIR_CLAMP_COPY_NT 2 /* 1: non-temporal load, 2: non-temporal store, 3: both.  Measured (256 frames 640x512): store alone 0.069 -> 0.0635 ms, load alone or both slower (the repair launch reads the neighbours of the flagged pixels from the cache) */
-#endif
 			typedef unsigned int clamp_v4u __attribute__((ext_vector_type(4)));
 			const clamp_v4u *src4 = reinterpret_cast<const clamp_v4u *>(in + i8);
-			clamp_v4u v = (RIR_CLAMP_COPY_NT & 1) ? __builtin_nontemporal_load(src4) : *src4;
+			clamp_v4u v = *src4;
 #pragma unroll
 			for (int k = 0; k < 4; ++k)
 			{
 				const uint32_t lo = max(v[k] & 0xffffu, f2 & 0xffffu), hi = max(v[k] >> 16, f2 >> 16);
 				v[k] = lo | (hi << 16);
 			}
-			clamp_v4u *dst4 = reinterpret_cast<clamp_v4u *>(out + i8);
-			if (RIR_CLAMP_COPY_NT & 2)
-				__builtin_nontemporal_store(v, dst4);
-			else
-				*dst4 = v;
+			// non-temporal store, plain load.  Measured (256 frames 640x512): the nt store alone 0.069 -> 0.0635 ms, an nt load alone or
+			// both slower (the repair launch reads the neighbours of the flagged pixels from the cache)
+			__builtin_nontemporal_store(v, reinterpret_cast<clamp_v4u *>(out + i8));
 		}
 		else
 		{
@@ -1069,12 +1060,8 @@ namespace rir
 // 244 MB for 168 MB of output (1.45x), and the encoder that reads the frames next found nothing cached.  With the default
 // policy the lines are completed in L2: 172 MB (1.02x); the kernel alone is 3 % slower (0.149 vs 0.145 ms per 256 frames),
 // chain + encode 3 % faster (0.198 vs 0.204 ms) - scripts/chain_variants.sh, profiles/r02_pmc_filters.json.
-#ifndef RIR_CHAIN_STORE_AUX
-#define RIR_CHAIN_STORE_AUX 0
-#endif
-#ifndef RIR_CHAIN_TY
-#define RIR_CHAIN_TY 16 /* rows of the gaussian block per wave; OH = TY - 2 output rows */
-#endif
+	constexpr int CHAIN_STORE_AUX = 0;
+	constexpr int CHAIN_TY = 16; // rows of the gaussian block per wave; OH = TY - 2 output rows
 	typedef unsigned int v2u32 __attribute__((ext_vector_type(2)));
 	struct ChainBadPixels
 	{
@@ -1173,7 +1160,7 @@ namespace rir
 												uint32_t background, int bx, int byw, int n, int lane, float (*tile_w)[64], unsigned long long *__restrict__ worklist,
 												unsigned int *__restrict__ work_count)
 	{
-		constexpr int TY = RIR_CHAIN_TY, KW = 2 * R + 1, OUTW = 64 - 2 * R, OW = OUTW - 2, OH = TY - 2, NR = TY + 2 * R;
+		constexpr int TY = CHAIN_TY, KW = 2 * R + 1, OUTW = 64 - 2 * R, OW = OUTW - 2, OH = TY - 2, NR = TY + 2 * R;
 		static_assert(TY % 2 == 0 && (R != 1 || OW % 4 == 0), "rows in pairs (packed FMAs); 4-pixel output pieces in the register path");
 		static_assert(MODE == 0 || R == 1, "the regular / listed split exists for radius 1");
 		const int x0 = bx * OW, y0 = byw * OH;
@@ -1433,7 +1420,7 @@ namespace rir
 #pragma unroll
 					for (int j = 0; j < OH; ++j)
 						__builtin_amdgcn_raw_buffer_store_b16(res[j], rd,
-															  (int)((act_x && y0 + j < h) ? (uint32_t)((y0 * w + x) * 2) + (uint32_t)j * dstep : 0x80000000u), 0, RIR_CHAIN_STORE_AUX);
+															  (int)((act_x && y0 + j < h) ? (uint32_t)((y0 * w + x) * 2) + (uint32_t)j * dstep : 0x80000000u), 0, CHAIN_STORE_AUX);
 				}
 				else
 				{
@@ -1452,7 +1439,7 @@ namespace rir
 						const int ox = x0 + 4 * k, oy = y0 + row; // x0 and w are multiples of 4: a piece is inside the row or outside, never across
 						const v2u32 px4 = *reinterpret_cast<const v2u32 *>(ot + (row < OH ? row : 0) * 64 + 4 * k);
 						const bool st = c < PPR * OH && ox < w && oy < h;
-						__builtin_amdgcn_raw_buffer_store_b64(px4, rd, (int)(st ? (uint32_t)((oy * w + ox) * 2) : 0x80000000u), 0, RIR_CHAIN_STORE_AUX);
+						__builtin_amdgcn_raw_buffer_store_b64(px4, rd, (int)(st ? (uint32_t)((oy * w + ox) * 2) : 0x80000000u), 0, CHAIN_STORE_AUX);
 					}
 				}
 				return;
@@ -1575,7 +1562,7 @@ namespace rir
 															   ChainBadPixels bp, const float *__restrict__ kern, const float *__restrict__ offsets,
 															   int per_frame_offsets, int strategy, uint32_t background)
 	{
-		__shared__ float tile[4][RIR_CHAIN_TY][64];
+		__shared__ float tile[4][CHAIN_TY][64];
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 		// XCD-major tile order, row bands fastest (see gaussian_sep_kernel)
@@ -1590,7 +1577,7 @@ namespace rir
 		const float *__restrict__ offsets, int per_frame_offsets, int strategy, uint32_t background, unsigned long long *__restrict__ worklist,
 		unsigned int *__restrict__ work_count)
 	{
-		__shared__ float tile[4][RIR_CHAIN_TY][64];
+		__shared__ float tile[4][CHAIN_TY][64];
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 		const unsigned gx = gridDim.x, gy = gridDim.y;
@@ -1606,7 +1593,7 @@ namespace rir
 																	  const unsigned long long *__restrict__ worklist, const unsigned int *__restrict__ work_count,
 																	  unsigned int *__restrict__ other_count)
 	{
-		__shared__ float tile[4][RIR_CHAIN_TY][64];
+		__shared__ float tile[4][CHAIN_TY][64];
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 		const unsigned int count = __hip_atomic_load(work_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1680,17 +1667,14 @@ namespace rir
 			hipLaunchKernelGGL(bad_pixels_fix_kernel, dim3((nbad + 63) / 64, nframes), dim3(64), 0, st, src, (uint16_t *)nullptr, w, h, d_xy, nbad, fl,
 							   d_fix);
 		ChainBadPixels bp{d_xy, d_row_start, d_fix, nbad, fl};
-		const int ow = 64 - 2 * radius - 2, oh = RIR_CHAIN_TY - 2;
+		const int ow = 64 - 2 * radius - 2, oh = CHAIN_TY - 2;
 		dim3 block(256), grid((w + ow - 1) / ow, (h + 4 * oh - 1) / (4 * oh), nframes);
 		switch (radius)
 		{
 		case 1:
-#ifdef RIR_CHAIN_ONE_KERNEL /* (measurements: round 2's form, both paths in one kernel at 7 waves per SIMD) */
-			hipLaunchKernelGGL((filter_chain_kernel<1>), grid, block, 0, st, src, dst, w, h, bp, d_kernel, d_offsets, per_frame, strategy, (uint32_t)background);
-			break;
-#endif
 		{
-			// regular tiles in registers; the rest through a list (stream-ordered scratch: [count | pad to 8 bytes][one entry per tile])
+			// regular tiles in registers; the rest through a list (stream-ordered scratch: [count | pad to 8 bytes][one entry per tile]).
+			// (Round 2's form, both paths in one kernel at 7 waves per SIMD, is RIR_CHAIN_ONE_KERNEL in 02807a8.)
 			const size_t ntile = (size_t)grid.x * grid.y * 4 * grid.z;
 			int par = 0;
 			unsigned int *counters = chain_list_of(st, ntile, &par);
@@ -2153,15 +2137,13 @@ namespace rir
 	// corners) take median3x3_px.  XCD-major tile order with x fastest (60-pixel rows are not line-aligned).
 	// (The first version - 8 consecutive outputs per thread, 3 x 10 windows fetched with dword loads - was bound by its
 	// instruction count at 0.134 ms per 256 frames 640x512.)
-#ifndef RIR_MEDIAN_TY
-#define RIR_MEDIAN_TY 16
-#endif
+	constexpr int MEDIAN_TY = 16; // output rows per wave tile
 	__device__ __forceinline__ uint32_t wave_shl1_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true); }
 	__device__ __forceinline__ uint32_t wave_shr1_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true); }
 
 	__global__ __launch_bounds__(256) void median3x3_kernel(const uint16_t *__restrict__ src, uint16_t *__restrict__ dst, int w, int h)
 	{
-		constexpr int TY = RIR_MEDIAN_TY, OW = 60; // (62 outputs fit a wave; 60 keeps the tiles 8-byte aligned for the stores)
+		constexpr int TY = MEDIAN_TY, OW = 60; // (62 outputs fit a wave; 60 keeps the tiles 8-byte aligned for the stores)
 		__shared__ uint16_t strip[4][TY][64];
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -2253,14 +2235,14 @@ namespace rir
 				const int ox = x0 + 4 * k, oy = y0 + row;
 				const v2u32 px4 = *reinterpret_cast<const v2u32 *>(&strip[wv][row < TY ? row : 0][4 * k]);
 				const bool st = c < PPR * TY && ox < w && oy < h;
-				__builtin_amdgcn_raw_buffer_store_b64(px4, rd, (int)(st ? (uint32_t)((oy * w + ox) * 2) : 0x80000000u), 0, RIR_CHAIN_STORE_AUX);
+				__builtin_amdgcn_raw_buffer_store_b64(px4, rd, (int)(st ? (uint32_t)((oy * w + ox) * 2) : 0x80000000u), 0, CHAIN_STORE_AUX);
 			}
 		}
 	}
 
 	hipError_t launch_median3x3(const uint16_t *src, uint16_t *dst, int w, int h, int nframes, hipStream_t st)
 	{
-		dim3 block(256), grid((unsigned)((w + 59) / 60), (unsigned)((h + 4 * RIR_MEDIAN_TY - 1) / (4 * RIR_MEDIAN_TY)), nframes);
+		dim3 block(256), grid((unsigned)((w + 59) / 60), (unsigned)((h + 4 * MEDIAN_TY - 1) / (4 * MEDIAN_TY)), nframes);
 		hipLaunchKernelGGL(median3x3_kernel, grid, block, 0, st, src, dst, w, h);
 		return hipGetLastError();
 	}

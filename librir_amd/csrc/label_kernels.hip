@@ -31,17 +31,11 @@ namespace rir
 	{
 		constexpr int kBlock = 256;		 // 4 wavefronts
 		constexpr int kScanBlock = 1024; // the one workgroup that turns per-block root counts into offsets
-// Tile of the first launch: 64 columns (a wavefront per row piece) x RIR_LABEL_TILE_H rows, RIR_LABEL_TILE_THREADS threads.  Measured on 640x512
-// images (scripts/variants.py; profiles/r05_label_time.txt): heights 8 / 16 / 32 / 64 with 256 / 512 / 1024 threads are within 8 % of each other on
-// every kind of image; 32 rows with 1024 threads (two rows a wavefront) is the best by a few per cent (regions 25.4 us against 27.3 for 16 rows
-// and 256 threads, vertical stripes 31.6 against 36.0, the spiral 183 against 206).
-#ifndef RIR_LABEL_TILE_H
-#define RIR_LABEL_TILE_H 32
-#endif
-#ifndef RIR_LABEL_TILE_THREADS
-#define RIR_LABEL_TILE_THREADS 1024
-#endif
-		constexpr int kTileW = 64, kTileH = RIR_LABEL_TILE_H, kTileThreads = RIR_LABEL_TILE_THREADS, kRowsPerWave = kTileH / (kTileThreads / 64);
+		// Tile of the first launch: 64 columns (a wavefront per row piece) x kTileH rows, kTileThreads threads.  Measured on 640x512 images
+		// (scripts/variants.py; profiles/r05_label_time.txt): heights 8 / 16 / 32 / 64 with 256 / 512 / 1024 threads are within 8 % of each
+		// other on every kind of image; 32 rows with 1024 threads (two rows a wavefront) is the best by a few per cent (regions 25.4 us
+		// against 27.3 for 16 rows and 256 threads, vertical stripes 31.6 against 36.0, the spiral 183 against 206).
+		constexpr int kTileW = 64, kTileH = 32, kTileThreads = 1024, kRowsPerWave = kTileH / (kTileThreads / 64);
 		static_assert(kRowsPerWave * (kTileThreads / 64) == kTileH && kRowsPerWave >= 1, "tile rows divide over the wavefronts");
 
 		// The forests are read and written by many waves at once: a link is loaded and stored as one 32-bit access at the scope that

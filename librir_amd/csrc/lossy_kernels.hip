@@ -528,7 +528,7 @@ namespace rir
 	// window - 40 dependent additions that do not involve the new frame - is out of the way before the frame's sums arrive:
 	// lossy_budget2_prepare (any time after the previous frame's finish), then lossy_budget2_finish.  Both lanes call; b in LDS.
 	// (The 39 additions in a row - the ORDER is the reference's and cannot change - are 1.1-1.5 us of the leader's 6 us per frame
-	// (RIR_LOSSY_DIAG: "window sum").  Asking for 13 window entries at a time instead of one brought the sum itself from 1.5 to 1.1 us and cost
+	// (RIR_LOSSY_DIAG build of 02807a8: "window sum").  Asking for 13 window entries at a time instead of one brought the sum itself from 1.5 to 1.1 us and cost
 	// the rest of the frame more - 155 k frames/s against 163 k: the kernel has no registers to spare.  Not kept.)
 	__device__ __forceinline__ double lossy_budget2_prepare(const LossyBudget &b, int c)
 	{
@@ -1050,17 +1050,13 @@ namespace rir
 	// per half: 0xffff where the half of x is not 0, else 0
 	__device__ __forceinline__ uint32_t lossy_nz_mask(lossy_u16x2 x)
 	{
-#ifndef RIR_LOSSY_NZ_MASK_PLAIN
 		// min(x, 1) and 0 - that, two packed instructions.  Spelled as such: written in C (min(x, 1) * 0xffff) the compiler sees through
-		// the mask and turns every select under it into two 16-bit compares, two conditional moves and a byte permute.
+		// the mask and turns every select under it into two 16-bit compares, two conditional moves and a byte permute (the plain C form is
+		// RIR_LOSSY_NZ_MASK_PLAIN in 02807a8).
 		uint32_t t, r;
 		asm("v_pk_min_u16 %0, %1, %2" : "=v"(t) : "v"(lu1(x)), "s"(0x00010001u));
 		asm("v_pk_sub_u16 %0, 0, %1" : "=v"(r) : "v"(t));
 		return r;
-#else
-		const lossy_u16x2 one = {1, 1}, ffff = {0xffff, 0xffff};
-		return lu1(__builtin_elementwise_min(x, one) * ffff);
-#endif
 	}
 	__device__ __forceinline__ uint32_t lossy_bfi(uint32_t mask, uint32_t a, uint32_t b) { return (a & mask) | (b & ~mask); } // mask ? a : b, bit by bit
 	struct LossyPairConsts
@@ -1113,36 +1109,6 @@ namespace rir
 			out2 = lossy_bfi(NM, lu1(t), ref2);
 		ref2 = lossy_bfi(NM, lu1(t), ref2);
 	}
-	// the sums of a frame over the 8 pixels of a thread against the previous output: totals and foreground parts
-	//   a[0] = sum d (fg) + (fg pixels << 32), a[1] = sum d2 (fg), a[2] = sum d (all) + (8 << 32), a[3] = sum d2 (all)
-	// (the background parts are the differences; d2 = the wrapped 32-bit square, sign-extended, as the reference's int arithmetic has it)
-	__device__ __forceinline__ void lossy_sums8_packed(const U16x8 &v8, const U16x8 &o8, uint32_t min2, uint32_t bg2, long long *a)
-	{
-		const lossy_u16x2 one = {1, 1};
-		uint32_t fd = 0, fn = 0, dall = 0;
-		long long f2 = 0, t2 = 0;
-#pragma unroll
-		for (int p = 0; p < 4; ++p)
-		{
-			const lossy_u16x2 v = lp2(v8.d[p]), o = lp2(o8.d[p]);
-			const lossy_u16x2 t = __builtin_elementwise_sub_sat(v, lp2(min2));
-			const lossy_u16x2 d = __builtin_elementwise_max(t, o) - __builtin_elementwise_min(t, o);
-			const lossy_u16x2 fg = __builtin_elementwise_min(__builtin_elementwise_sub_sat(v, lp2(bg2)), one); // 1 where v > background
-			fd = __builtin_amdgcn_udot2(d, fg, fd, false);
-			dall = __builtin_amdgcn_udot2(d, one, dall, false);
-			fn = __builtin_amdgcn_udot2(fg, one, fn, false);
-			const uint32_t d_lo = lu1(d) & 0xffffu, d_hi = lu1(d) >> 16;
-			const int32_t q_lo = (int32_t)__umul24(d_lo, d_lo), q_hi = (int32_t)__umul24(d_hi, d_hi); // (d < 2^16: the 24-bit multiplier gives the low 32 bits of d * d)
-			const uint32_t m = lu1(fg);
-			t2 += (long long)q_lo + (long long)q_hi;
-			f2 += (long long)((m & 1u) ? q_lo : 0) + (long long)((m >> 16) ? q_hi : 0);
-		}
-		a[0] = (long long)(((unsigned long long)fn << 32) | fd);
-		a[1] = f2;
-		a[2] = (long long)((8ull << 32) | dall);
-		a[3] = t2;
-	}
-
 	// ---- a run of frames in one launch ---------------------------------------------------------------------------
 	//
 	// grid = workgroups of a stream (nb = lossy_run_workgroups(full)) x streams, 1-D, all resident at once (lossy_run_capacity(),
@@ -1270,18 +1236,14 @@ namespace rir
 		bool gave_up = false;
 		for (int k = 0; k < rp.nsteps; ++k)
 		{
-#ifdef RIR_LOSSY_DIAG
-			const unsigned long long dgA = __builtin_amdgcn_s_memrealtime();
-#endif
 			// the next frame's pixels are requested now: they arrive while this frame's sums go round
 			U16x8 vn{};
 			if (inside && k + 1 < rp.nsteps)
 				vn = ld8(in + (size_t)(k + 1) * rp.frame_px, i8);
 			const long long background = as_global(rp.bg)[(size_t)k * rp.bg_stride];
-			// 1. this workgroup's share of the frame's sums (the packed form of the sums - lossy_sums8_packed, four reductions instead of
-			// six - is kept behind RIR_LOSSY_PACKED_SUMS: same values, but its extra live registers cost more than its instructions save:
-			// 7 streams 509 k frames/s against 593 k; scripts/lossy_ab.sh)
-#ifndef RIR_LOSSY_PACKED_SUMS
+			// 1. this workgroup's share of the frame's sums (a packed form of the sums, four reductions instead of six, gave the same values,
+			// but its extra live registers cost more than its instructions save: 7 streams 509 k frames/s against 593 k; scripts/lossy_ab.sh,
+			// RIR_LOSSY_PACKED_SUMS in 02807a8)
 			int32_t fd = 0, fn = 0, bd = 0, bn = 0;
 			long long f2 = 0, b2 = 0;
 			if (lossy)
@@ -1299,17 +1261,7 @@ namespace rir
 						bd += d, b2 += d2, bn += 1;
 				}
 			}
-#else
-			long long ps[4] = {0, 0, 0, 0};
-			if (lossy)
-				lossy_sums8_packed(v8, o8, st.subtract_min ? lossy_both(st.min) : 0u, lossy_both((uint32_t)background), ps);
-#endif
-#ifdef RIR_LOSSY_DIAG
-			const unsigned long long dg0 = __builtin_amdgcn_s_memrealtime();
-			unsigned long long dg1 = 0, dg2 = 0, dg3 = 0, dgB = 0, dgC = 0;
-#endif
 			// wave sums -> LDS; wave 0 adds the waves up, publishes, collects everybody's words and decides
-#ifndef RIR_LOSSY_PACKED_SUMS
 			// (The per-pixel sums above as totals + foreground parts without the branch - |t - o| as one v_sad_u16, selects instead of the two
 			// sides under exec masks - were measured: 7 streams 589 k frames/s against 635 k; two 64-bit adds per pixel cost more than the exec
 			// switches.)
@@ -1321,25 +1273,10 @@ namespace rir
 				ws[0] = (long long)wfd, ws[1] = lossy_wave_sum(f2), ws[2] = (long long)(wn & 0xffffu), ws[3] = (long long)wbd, ws[4] = lossy_wave_sum(b2),
 				ws[5] = (long long)(wn >> 16);
 			}
-#else
-			// four reductions instead of six: counts ride in the high halves of the sums of d (a wave's sum of d stays below 2^26),
-			// the background parts are totals minus foreground
-			long long ws[6];
-			{
-#pragma unroll
-				for (int j = 0; j < 4; ++j)
-					ps[j] = lossy_wave_sum(ps[j]);
-				const long long wfd = ps[0] & 0xffffffffll, wfn = ps[0] >> 32, wd = ps[2] & 0xffffffffll, wn = ps[2] >> 32;
-				ws[0] = wfd, ws[1] = ps[1], ws[2] = wfn, ws[3] = wd - wfd, ws[4] = ps[3] - ps[1], ws[5] = wn - wfn;
-			}
-#endif
 			const int lane = tid & 63, wave = tid >> 6;
 			if (lane < 6)
 				red[wave][lane] = lane == 0 ? ws[0] : lane == 1 ? ws[1] : lane == 2 ? ws[2] : lane == 3 ? ws[3] : lane == 4 ? ws[4] : ws[5];
 			__syncthreads();
-#ifdef RIR_LOSSY_DIAG
-			dgB = __builtin_amdgcn_s_memrealtime();
-#endif
 			const unsigned long long tag = (unsigned long long)(((unsigned)k & 0x7fffu) | 0x8000u) << 48;
 			const unsigned long long vmask = 0x0000ffffffffffffull;
 			RIR_GLOBAL(unsigned long long) *bank = exch + (size_t)(k & 1) * nb * rp.slot_words;
@@ -1364,16 +1301,10 @@ namespace rir
 															 : (unsigned long long)ws[4] & vmask;
 					__hip_atomic_store(bank + (size_t)b * rp.slot_words + lane, tag | w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 				}
-#ifdef RIR_LOSSY_DIAG
-				dgC = __builtin_amdgcn_s_memrealtime();
-#endif
 				// while the words travel: the part of the budget that does not need them
 				if (lane < 2 && (!rp.leader || b == 0))
 					part = lossy_budget2_prepare(bl, lane);
 			}
-#ifdef RIR_LOSSY_DIAG
-			dg1 = __builtin_amdgcn_s_memrealtime();
-#endif
 			// 2. everybody's shares: thread p takes workgroup p (p + 256, ...).  With many streams in the launch only workgroup 0 of a
 			// stream does that (every workgroup reading every slot is nb^2 polled lines per stream and frame: with 6 streams the polls
 			// took 5.8 us instead of 2) and hands the decision on in one word; the others poll that word - one more hop, 1/nb of the traffic.
@@ -1381,7 +1312,7 @@ namespace rir
 			long long acc[6] = {0, 0, 0, 0, 0, 0};
 			if (rp.leader && b == 0)
 				__builtin_amdgcn_s_setprio(3); // (the whole stream waits for what this workgroup does next, and it shares its CU with four others: 7 streams 561 -> 579 k frames/s)
-			// (wave 0 of a collecting workgroup is in the window sum for another microsecond - RIR_LOSSY_DIAG: "window sum" - so the other three
+			// (wave 0 of a collecting workgroup is in the window sum for another microsecond - RIR_LOSSY_DIAG build of 02807a8: "window sum" - so the other three
 			// waves take the slots between them when they can: 192 threads for the 160 workgroups of a 640x512 stream.  The round trip of the
 			// polls then runs under the window sum instead of behind it.)
 			const bool three_waves = nb <= kLossyRunThreads - 64;
@@ -1423,9 +1354,6 @@ namespace rir
 				if (lane < 6)
 					red2[wave][lane] = lane == 0 ? acc[0] : lane == 1 ? acc[1] : lane == 2 ? acc[2] : lane == 3 ? acc[3] : lane == 4 ? acc[4] : acc[5];
 				__syncthreads();
-#ifdef RIR_LOSSY_DIAG
-				dg2 = __builtin_amdgcn_s_memrealtime();
-#endif
 				if (wave == 0)
 				{
 					long long val = 0;
@@ -1478,9 +1406,6 @@ namespace rir
 				d.reserved = 0;
 				dec = d;
 			}
-#ifdef RIR_LOSSY_DIAG
-			dg3 = __builtin_amdgcn_s_memrealtime();
-#endif
 			if (rp.leader && b == 0)
 				__builtin_amdgcn_s_setprio(0);
 			__syncthreads(); // (also keeps the other waves off red / red2 until wave 0 has read them)
@@ -1491,18 +1416,8 @@ namespace rir
 			{
 				const LossyFrameConsts fc = {st.min, dec.background, st.subtract_min, ra, full_ring ? 1 : 0, n_after, add_loss, dec.low_error, dec.high_error,
 											 lossy_div_magic(n_after)};
-#ifdef RIR_LOSSY_SCALAR_UPDATE /* (round 2's form, one pixel at a time: 7 streams 570 k frames/s against 593 k with pairs) */
-				bool rc = false, ccg = false;
-#pragma unroll
-				for (int q = 0; q < 8; ++q)
-				{
-					uint32_t ref = ref8.get(q), cc = cc8.get(q), cv = cv8.get(q), t_in;
-					const uint32_t t = lossy_pixel(fc, v8.get(q), old8.get(q), last8.get(q), ref, sum[q], cc, cv, &t_in, rc, ccg);
-					ref8.set(q, ref), cc8.set(q, cc), cv8.set(q, cv);
-					t8.set(q, t_in);
-					o8.set(q, t);
-				}
-#else
+				// (round 2's form, one pixel at a time, was slower: 7 streams 570 k frames/s against 593 k with pairs; RIR_LOSSY_SCALAR_UPDATE
+				// in 02807a8)
 				const LossyPairConsts pc = lossy_pair_consts(fc);
 				if constexpr (PARKED)
 				{
@@ -1524,7 +1439,6 @@ namespace rir
 					for (int p = 0; p < 4; ++p)
 						lossy_pixel_pair(fc, pc, v8.d[p], old8.d[p], last8.d[p], ref8.d[p], sum[2 * p], sum[2 * p + 1], cc8.d[p], cv8.d[p], t8.d[p], o8.d[p]);
 				}
-#endif
 				if constexpr (!PARKED)
 					last8 = v8;
 				st8(out + (size_t)k * rp.frame_px, i8, o8);
@@ -1548,14 +1462,6 @@ namespace rir
 			}
 			if (k + 1 < rp.nsteps)
 				v8 = vn;
-#ifdef RIR_LOSSY_DIAG
-			if (b == 0 && tid == 0)
-			{ // ticks (10 ns) of: sums + reduce + publish | poll | reduce | budget | barrier + update, summed over the frames
-				RIR_GLOBAL(unsigned long long) *dg = (RIR_GLOBAL(unsigned long long) *)as_global(rp.error_word) + 8;
-				const unsigned long long dg4 = __builtin_amdgcn_s_memrealtime();
-				dg[0] += dg1 - dg0, dg[1] += dg2 - dg1, dg[2] += dg3 - dg2, dg[3] += dg4 - dg3, dg[4] += 1, dg[5] += dg0 - dgA, dg[6] += dgB - dg0, dg[7] += dgC - dgB;
-			}
-#endif
 		}
 		// registers -> state
 		if constexpr (PARKED)
@@ -1671,13 +1577,7 @@ namespace rir
 		return k >= tail0 ? 1 + (k - tail0) : (k == 0 ? 0 : -1);
 	}
 
-#ifndef RIR_LOSSY_CONST_DEPTH
-#define RIR_LOSSY_CONST_DEPTH 4
-#endif
-#ifndef RIR_LOSSY_CONST_PIN_STEPS
-#define RIR_LOSSY_CONST_PIN_STEPS 1
-#endif
-	constexpr int kConstDepth = RIR_LOSSY_CONST_DEPTH; // slots of a thread's ring of frames: 3 in flight in the middle of a group (4: 1.49 M frames/s one stream, 6: 1.53, 8: 1.50 - vector issue, not what is in flight, bounds the kernel)
+	constexpr int kConstDepth = 4; // slots of a thread's ring of frames: 3 in flight in the middle of a group (4: 1.49 M frames/s one stream, 6: 1.53, 8: 1.50 - vector issue, not what is in flight, bounds the kernel)
 	// NP pairs of pixels per thread (4: one 16-byte access per thread, frame and array, as the resident kernel; 2; 1).  Nobody waits for anybody
 	// here, so a stream may be cut as finely as pays: with 8 pixels per thread a 640x512 stream is 640 waves on the chip's 1 024 SIMDs - each
 	// working through its ~300 vector instructions per frame alone - with 2 pixels it is 2 560 waves that hide each other's latencies.
@@ -1783,12 +1683,9 @@ namespace rir
 		else
 			__builtin_amdgcn_raw_buffer_store_b32(x.d[0], r, off, soff, AUX);
 	}
-#ifndef RIR_SPEC_OUT_STORE_AUX
-#define RIR_SPEC_OUT_STORE_AUX 2 /* nt: the speculative instance's output frames are read once more, by the sums kernel, from HBM either way (+3 % on the call) */
-#endif
-#ifndef RIR_CONST_OUT_STORE_AUX
-#define RIR_CONST_OUT_STORE_AUX 0 /* cache policy of the streaming kernel's output frames (2: nt) */
-#endif
+	// nt: the speculative instance's output frames are read once more, by the sums kernel, from HBM either way (+3 % on the call)
+	constexpr int kSpecOutStoreAux = 2;
+	constexpr int kConstOutStoreAux = 0; // cache policy of the streaming kernel's output frames (2: nt)
 
 	// lossy_pixel_pair without its wave-uniform branches (compile-time: a running average or none, the addLoss variant or not; run time, as
 	// masks: whether the ring is full).  Same values, bit for bit.
@@ -2140,7 +2037,7 @@ namespace rir
 			if constexpr (SPEC)
 				plane_store(dd, fg, (uint32_t)k * (uint32_t)s);
 			last = v;
-			buf_stn<NP, (SPEC ? RIR_SPEC_OUT_STORE_AUX : RIR_CONST_OUT_STORE_AUX)>(ov, lossy_rsrc((const void *)out_p, full_bytes), off_in);
+			buf_stn<NP, (SPEC ? kSpecOutStoreAux : kConstOutStoreAux)>(ov, lossy_rsrc((const void *)out_p, full_bytes), off_in);
 			out_p += frame_bytes;
 			if (RA_ON)
 			{
@@ -2245,7 +2142,7 @@ namespace rir
 					const_pixel_pair<RA_ON, ADD_LOSS, true, SPEC>(pc, v.d[p], old.d[p], before.d[p], ref.d[p], sum[2 * p], sum[2 * p + 1], cc.d[p], cv.d[p], t.d[p], o.d[p], &dd[p], &fg[p]);
 					ov.d[p] = lossy_bfi(lossy_mask, o.d[p], v.d[p]);
 				}
-				buf_stn<NP, (SPEC ? RIR_SPEC_OUT_STORE_AUX : RIR_CONST_OUT_STORE_AUX)>(ov, rs_out, off_in, so);
+				buf_stn<NP, (SPEC ? kSpecOutStoreAux : kConstOutStoreAux)>(ov, rs_out, off_in, so);
 				if constexpr (SPEC)
 				{
 					plane_store(dd, fg, so_d);
@@ -2267,11 +2164,9 @@ namespace rir
 					O[j] = buf_ldn<NP>(rs_old, off_o, so);
 				V[(j + D - 1) % D] = buf_ldn<NP>(rs_in, off_v, so - fb);
 				so += fb;
-#if RIR_LOSSY_CONST_PIN_STEPS
 				// a frame's instructions stay together: left alone, the scheduler gathers the loads of two or three frames at the end of the
 				// iteration, and its top then waits for loads issued 40 instructions ago
 				__builtin_amdgcn_sched_barrier(0);
-#endif
 			};
 			for (int k0 = mid0; k0 < mid1; k0 += D)
 			{
@@ -2514,9 +2409,8 @@ namespace rir
 	// split by input k > background k.  Per slab of kLossySpecSlab pixels four words, as lossy_const_run_kernel's partials; the LAST slab of
 	// a frame to arrive (a ticket per frame; rows written and read with agent-scope accesses, as lossy_last_arriver's callers do) adds them up and
 	// leaves the frame's statistic, stdDev's double arithmetic on the exact sums.
-#ifndef RIR_SPEC_STATS_AUX
-#define RIR_SPEC_STATS_AUX 2 /* cache policy of the sums kernel's loads: nt (every byte is read once; measured +4 % on the whole call against the default policy, sc1 no better) */
-#endif
+	// cache policy of the sums kernel's loads: nt (every byte is read once; measured +4 % on the whole call against the default policy, sc1 no better)
+	constexpr int kSpecStatsAux = 2;
 	// PLANE: the same sums from the byte plane the streaming kernel left (LossySpec::dplane: difference and class of every pixel in one byte - a
 	// quarter of the bytes of the two frames, four pixels to an instruction through v_dot4_u32_u8).  Both forms are queued behind every pass: the one
 	// from the plane does the work unless there is no plane or the pass met a difference of 128 or more (ctl[7]), then the one from the frames does.
@@ -2542,7 +2436,7 @@ namespace rir
 			for (int j = 0; j < kIter; ++j)
 			{
 				const uint32_t px = (uint32_t)i0 + (uint32_t)(j * 256 + tid) * 16u;
-				a[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, px, 0, RIR_SPEC_STATS_AUX);
+				a[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, px, 0, kSpecStatsAux);
 				valid += px < (uint32_t)i1 ? min(16u, (uint32_t)i1 - px) : 0u;
 			}
 			// (differences below 128, 64 pixels of a thread: sum d < 2^13, sum d^2 < 2^20)
@@ -2577,8 +2471,8 @@ namespace rir
 			for (int j = 0; j < kIter; ++j)
 			{ // (a lane past the end of the lossy rows: out of range - zeros against zeros: d = 0, counted nowhere but in `valid`)
 				const uint32_t off = (uint32_t)(i0 / 8 + j * 256 + tid) * 16u;
-				a[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, 0, RIR_SPEC_STATS_AUX);
-				p[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_pv, off, 0, RIR_SPEC_STATS_AUX);
+				a[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, off, 0, kSpecStatsAux);
+				p[j] = __builtin_amdgcn_raw_buffer_load_b128(rs_pv, off, 0, kSpecStatsAux);
 				valid += (i0 / 8 + j * 256 + tid) * 8 < i1 ? 8u : 0u;
 			}
 			// Two pixels to an instruction, the sums through v_dot2_u32_u16: d = max - min, the foreground mask as in const_pixel_pair, sum d and
@@ -3056,16 +2950,14 @@ namespace rir
 		return hipGetLastError();
 	}
 
-	// workgroups of lossy_run_kernel the current device holds at once (runtime.h: occupancy x CUs, less the margin; 0 = unknown)
-#ifndef RIR_LOSSY_RUN_MARGIN
-#define RIR_LOSSY_RUN_MARGIN 1 /* 0: every place of the device - 8 streams of 640x512 per launch instead of 7, 617 k frames/s instead of 577 k; not shipped: a launch
-                                  that fills the chip to the last place is called off whenever anything else is resident, and a loss run that is called off
-                                  goes on frame by frame - or, for queue-only calls, fails the stream */
-#endif
+	// workgroups of lossy_run_kernel the current device holds at once (runtime.h: occupancy x CUs, less the margin; 0 = unknown).  Without the
+	// margin - every place of the device - a launch takes 8 streams of 640x512 instead of 7, 617 k frames/s instead of 577 k; not shipped: a launch
+	// that fills the chip to the last place is called off whenever anything else is resident, and a loss run that is called off goes on frame by
+	// frame - or, for queue-only calls, fails the stream.
 	int lossy_run_capacity(bool parked)
 	{
 		return resident_capacity(parked ? reinterpret_cast<const void *>(lossy_run_parked_kernel) : reinterpret_cast<const void *>(lossy_run_kernel), kLossyRunThreads,
-								 0, RIR_LOSSY_RUN_MARGIN != 0);
+								 0, true);
 	}
 	hipError_t launch_lossy_run(const LossyRun *d_table, int nstreams, int full, unsigned int *d_ticket, unsigned int epoch, unsigned int arrivals_before, bool parked,
 								hipStream_t st, const unsigned int *d_ok)

@@ -116,9 +116,7 @@ namespace
 		}
 	};
 
-#ifndef RIR_ECC_FIRST_BATCH
-#define RIR_ECC_FIRST_BATCH 6 /* alignments of a tracked sequence settle within 4-6 iterations: one read-back of the state instead of two */
-#endif
+	constexpr int ECC_FIRST_BATCH = 6; // alignments of a tracked sequence settle within 4-6 iterations: one read-back of the state instead of two
 	// waits (polling the coherent view) until the alignment in flight reports done or `launched` iterations
 	bool wait_view(EccHostView *view, int launched, hipStream_t st)
 	{
@@ -210,16 +208,6 @@ namespace
 				view->iter = 0, view->done = 0;
 				state_is_reset = false;
 			}
-			static const bool diag = getenv("RIR_ECC_DIAG") != nullptr; // (-DRIR_ECC_DIAG builds: where an iteration's time goes)
-			if (diag && (sc.epoch % 64) == 0)
-			{
-				unsigned long long dg[16];
-				const size_t off = ecc_run_workspace_bytes(w, h) - 256 + 64;
-				if (hipMemcpy(dg, sc.partials.as<char>() + off, sizeof(dg), hipMemcpyDeviceToHost) == hipSuccess && dg[3])
-					std::fprintf(stderr, "ecc run, per iteration (us): workgroup 0: sums+publish %.2f  wait rows %.2f  add+solve+publish %.2f | last workgroup: sums+publish %.2f  wait %.2f  (%.1f iterations per frame) | workgroup 0: pixel loop %.2f  block reduce %.2f\n",
-								 dg[0] * 0.01 / dg[3], dg[1] * 0.01 / dg[3], dg[2] * 0.01 / dg[3], dg[8] * 0.01 / dg[11], dg[9] * 0.01 / dg[11], (double)dg[3] / sc.epoch,
-								 dg[4] * 0.01 / dg[3], dg[5] * 0.01 / dg[3]);
-			}
 		}
 		if (per_iteration || called_off)
 		{
@@ -236,7 +224,7 @@ namespace
 			int launched = 0;
 			while (true)
 			{
-				const int batch = std::min(launched == 0 ? RIR_ECC_FIRST_BATCH : 8, max_iter - launched);
+				const int batch = std::min(launched == 0 ? ECC_FIRST_BATCH : 8, max_iter - launched);
 				for (int i = 0; i < batch; ++i)
 					if (!hip_ok(launch_ecc_iterate(d_templ, d_image, d_gx, d_gy, d_mask, w, h, sc.partials.as<double>(), d_state, d_view, st), "ecc iterate"))
 						return -1;
@@ -607,7 +595,6 @@ RIR_EXPORT int rir_ecc_align_multi_overlapped_device(const float *const *d_ref_n
 		return -1;
 	const int V = ecc_rows(w, h);
 	static const bool env_per_iteration = getenv("RIR_ECC_LAUNCH_PER_ITERATION") != nullptr;
-	static const bool env_no_overlap = getenv("RIR_ECC_NO_OVERLAP") != nullptr; // (measurements: the jobs after the alignments, on the caller's stream)
 	const int cap = env_per_iteration ? 0 : ecc_run_multi_capacity();
 	// the jobs of `next`: once, on `on` (the side stream behind what the caller's stream held when the call came - its inputs are ready and
 	// the previous readers of its outputs are through - or the caller's stream itself)
@@ -632,7 +619,7 @@ RIR_EXPORT int rir_ecc_align_multi_overlapped_device(const float *const *d_ref_n
 				return false;
 		return true;
 	};
-	const bool overlap = nnext > 0 && !env_no_overlap && cap >= 1;
+	const bool overlap = nnext > 0 && cap >= 1;
 	if (overlap)
 	{
 		if (!sc.multi_go && !hip_ok(hipHostMalloc(reinterpret_cast<void **>(&sc.multi_go), 64, hipHostMallocCoherent | hipHostMallocMapped), "hipHostMalloc"))
@@ -706,11 +693,9 @@ RIR_EXPORT int rir_ecc_align_multi_overlapped_device(const float *const *d_ref_n
 	}
 	if (!hip_ok(hipMemcpyAsync(sc.multi_table.ptr, hs, (size_t)nseq * sizeof(EccSeq), hipMemcpyHostToDevice, st), "H2D"))
 		return -1;
-	// sequences per launch and workgroups per sequence: as many slices as the device holds for the sequences of the launch
-	// (RIR_ECC_MULTI_SLICES: a fixed number, for measurements).  Every launch first finds out whether it is fully resident
+	// sequences per launch and workgroups per sequence: as many slices as the device holds for the sequences of the launch.  Every launch first finds out whether it is fully resident
 	// (resident_device.h); one that is not has written nothing and is repeated with half the slices - any number of slices gives the
 	// same bits - and, from one slice per sequence, handed to the single-sequence path.
-	static const int env_slices = getenv("RIR_ECC_MULTI_SLICES") ? atoi(getenv("RIR_ECC_MULTI_SLICES")) : 0;
 	const bool debug_bail = test_hook("RIR_DEBUG_ECC_BAIL") != nullptr; // (tests: as if the first attempt of every launch had not become resident)
 	const bool fresh_ctl = sc.multi_ctl.cap == 0;
 	if (!sc.multi_ctl.reserve(256))
@@ -738,8 +723,6 @@ RIR_EXPORT int rir_ecc_align_multi_overlapped_device(const float *const *d_ref_n
 	{
 		const int nl = std::min(2 * plan.units_per_launch, nseq - q0), groups = (nl + 1) / 2;
 		int nslices = std::max(1, std::min(V, (cap - nl) / groups));
-		if (env_slices > 0)
-			nslices = std::max(1, std::min(nslices, env_slices));
 		for (int attempt = 0;; ++attempt)
 		{
 			// (a slice's time is that of its rows, one after the other: no more slices than give every slice the same largest number of rows)
@@ -788,14 +771,6 @@ RIR_EXPORT int rir_ecc_align_multi_overlapped_device(const float *const *d_ref_n
 	}
 	if (!back_fresh && (!read_back() || !hip_ok(wait_stream(st), "sync")))
 		return -1;
-	static const bool diag = getenv("RIR_ECC_DIAG") != nullptr; // (-DRIR_ECC_DIAG builds: where an iteration's time goes, sequence 0)
-	if (diag)
-	{
-		unsigned long long dg[16];
-		if (hipMemcpy(dg, sc.multi_rows.as<char>() + (size_t)V * 256 + 64, sizeof(dg), hipMemcpyDeviceToHost) == hipSuccess && dg[2] && dg[6] && dg[10])
-			std::fprintf(stderr, "ecc multi (us), sequence 0's service workgroup, per iteration: waiting for + adding the rows %.2f  solve + publish %.2f | group 0, per turn: slice 0: rows %.2f (pixel loop of the first row %.2f)  waiting for the decision %.2f | last slice: rows %.2f (%.2f)  waiting %.2f  (%llu iterations so far, %d sequences)\n",
-						 dg[0] * 0.01 / dg[2], dg[1] * 0.01 / dg[2], dg[4] * 0.01 / dg[6], dg[7] * 0.01 / dg[6], dg[5] * 0.01 / dg[6], dg[8] * 0.01 / dg[10], dg[11] * 0.01 / dg[10], dg[9] * 0.01 / dg[10], dg[2], nseq);
-	}
 	const EccSeq *back = reinterpret_cast<const EccSeq *>(hb);
 	const EccFrameResult *r = reinterpret_cast<const EccFrameResult *>(hb + (size_t)nseq * sizeof(EccSeq));
 	for (int q : solo)

@@ -14,9 +14,6 @@
 #include <mutex>
 #include <tuple>
 
-#ifndef RIR_SPIN_WAIT
-#define RIR_SPIN_WAIT 1
-#endif
 namespace rir
 {
 	namespace
@@ -117,7 +114,6 @@ namespace rir
 	// blocking wait adds its wake-up latency (20-50 us here) to every call.  Falls back to the blocking wait after 2 ms.
 	hipError_t wait_stream(hipStream_t st)
 	{
-#if RIR_SPIN_WAIT
 		const auto t0 = std::chrono::steady_clock::now();
 		for (long spins = 1;; ++spins)
 		{
@@ -128,13 +124,11 @@ namespace rir
 				break;
 			__builtin_ia32_pause();
 		}
-#endif
 		return hipStreamSynchronize(st);
 	}
 
 	hipError_t wait_event(hipEvent_t ev)
 	{
-#if RIR_SPIN_WAIT
 		const auto t0 = std::chrono::steady_clock::now();
 		for (long spins = 1;; ++spins)
 		{
@@ -145,7 +139,6 @@ namespace rir
 				break;
 			__builtin_ia32_pause();
 		}
-#endif
 		return hipEventSynchronize(ev);
 	}
 

@@ -547,11 +547,6 @@ namespace
 			bool have_run = false;
 		};
 		InFlight flying;
-#ifdef RIR_SAVER_DIAG
-		double dg_wait_ev = 0, dg_wait_writer = 0, dg_loss = 0, dg_submit = 0, dg_flush = 0;
-		int dg_n = 0;
-		static double dg_now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-#endif
 		PinnedBuffer h_errs; // [ERR_SLOTS][2] budgets of the chunk in flight, then the run kernel's error word and the poison word
 		hipEvent_t fly_ev = nullptr;
 		std::vector<IndexEntry> index;
@@ -968,19 +963,8 @@ namespace
 			rir_codec_layout L;
 			if (in_flight_mode && pending > 0)
 			{ // nothing is waited for but the chunk BEFORE this one: this chunk's loss step, its encode and its error budgets are queued
-#ifdef RIR_SAVER_DIAG
-				const double t0 = dg_now();
-				struct Fin { SaverObject *s; double t0; ~Fin() { s->dg_flush += dg_now() - t0; ++s->dg_n; } } fin{this, t0};
-				if (!usable() || !collect_flying())
-					return false;
-				const double t1 = dg_now();
-				if (!run_deferred_loss())
-					return false;
-				dg_loss += dg_now() - t1;
-#else
 				if (!usable() || !collect_flying() || !run_deferred_loss())
 					return false;
-#endif
 				if (rir_codec_layout_query(width, height, pending, chunk_gop, &L) != 0)
 					return false;
 				const bool staged_only = uploaded == 0; // every frame came through add_image and lies in the staging buffer
@@ -1045,13 +1029,7 @@ namespace
 				std::unique_lock<std::mutex> lk(wmu);
 				if (!writer.joinable())
 					writer = std::thread([this] { writer_loop(); });
-#ifdef RIR_SAVER_DIAG
-				const double tq = dg_now();
-#endif
 				wcv.wait(lk, [&] { return !job_ready && !writer_busy; }); // one job in flight: the previous chunk is on disk before this one is queued
-#ifdef RIR_SAVER_DIAG
-				dg_wait_writer += dg_now() - tq;
-#endif
 				if (write_failed)
 				{
 					log_error("h264 saver: write error on " + filename);
@@ -1136,14 +1114,8 @@ namespace
 			if (!flying.active)
 				return true;
 			flying.active = false;
-#ifdef RIR_SAVER_DIAG
-			const double tw = dg_now();
-#endif
 			if (!hip_ok(wait_event(fly_ev), "sync") || test_hook_is("RIR_DEBUG_SAVER_FAIL_FLYING", "wait"))
 				return abandon_from(flying.first_frame);
-#ifdef RIR_SAVER_DIAG
-			dg_wait_ev += dg_now() - tw;
-#endif
 			if (!flying.defs.empty())
 			{ // the chunk's bounded-loss frames: their budgets, and whether the run that stepped them gave up (resolve_errors)
 				const int *e = h_errs.as<int>();
@@ -1170,10 +1142,7 @@ namespace
 
 		// frames [uploaded, upto) of the chunk being assembled: page-locked staging -> device
 		static constexpr int kUploadGroup = 5;
-#ifndef RIR_RAW_UPLOAD_GROUP
-#define RIR_RAW_UPLOAD_GROUP 25
-#endif
-		static constexpr int kRawUploadGroup = RIR_RAW_UPLOAD_GROUP;
+		static constexpr int kRawUploadGroup = 25;
 		int uploaded = 0;
 		bool upload_staged(int upto)
 		{
@@ -1316,11 +1285,6 @@ namespace
 			if (!failed)
 				ok = collect_flying() && ok;
 			flying.active = false;
-#ifdef RIR_SAVER_DIAG
-			if (dg_n)
-				fprintf(stderr, "saver diag: %d chunk flushes, per flush: total %.0f us = wait for the chunk in flight %.0f + wait for the writer %.0f + loss step queued %.0f + the rest\n", dg_n,
-						dg_flush / dg_n, dg_wait_ev / dg_n, dg_wait_writer / dg_n, dg_loss / dg_n);
-#endif
 			stop_writer(); // every chunk is in the file from here on
 			ok = ok && !write_failed;
 			FileHeader hd;
@@ -1416,10 +1380,7 @@ namespace
 		// Sequential readers: while the images of chunk k are handed out from page-locked memory, helper threads ("lanes") read chunks
 		// k + 1 and k + 2 from the file and decode them, each on a stream and into a buffer set (`nx`) of its own, so that their images are
 		// in page-locked memory when the reader gets there; the lane's buffer set and the current one are then swapped.
-#ifndef RIR_LOADER_LANES
-#define RIR_LOADER_LANES 2
-#endif
-		static constexpr int kLanes = RIR_LOADER_LANES;
+		static constexpr int kLanes = 2;
 		ChunkCodec nx[kLanes];
 		struct Prefetch
 		{
@@ -2320,17 +2281,14 @@ namespace
 		// before it is decoded (one rirb1_decode_select launch a batch: only the selected frames are stored, MIN_T added on the way).
 		// Raw and ZFile images are read on the host and go up in batches.  With a read-back filter on, the batch is decoded into a
 		// scratch buffer and the batched filter kernels run on it before it goes to the output.
-#ifndef RIR_DIO_BATCH_CHUNKS
-#define RIR_DIO_BATCH_CHUNKS 8
-#endif
-		static constexpr int kDioBatchChunks = RIR_DIO_BATCH_CHUNKS;
+		static constexpr int kDioBatchChunks = 8;
 		static constexpr size_t kDioBatchBytes = (size_t)64 << 20; // page-locked bytes of a batch (compressed chunks, or raw images)
 		static constexpr size_t kDioScratchBytes = (size_t)256 << 20; // device scratch of a filtered batch
 		hipStream_t dio_st = nullptr;
 		hipEvent_t dio_ev[2] = {nullptr, nullptr}, dio_in_ev = nullptr;
 		bool dio_ev_set[2] = {false, false};
 		PinnedBuffer dio_h[2], dio_err_h;
-		DeviceBuffer dio_d[2], dio_scr, dio_shift, dio_err;
+		DeviceBuffer dio_scr, dio_shift, dio_err;
 
 		void dio_release()
 		{
@@ -2342,17 +2300,6 @@ namespace
 			for (hipEvent_t e : {dio_ev[0], dio_ev[1], dio_in_ev})
 				if (e)
 					(void)hipEventDestroy(e);
-		}
-
-		// Batches of RIRB chunks are decoded straight from page-locked memory (the kernel reads tables and payload over the link) or
-		// after an upload into device memory.  Default: the faster of the two on the MI355X; RIR_DIO_UPLOAD=0 / 1 forces one.
-		static bool dio_upload()
-		{
-			static const int v = [] {
-				const char *e = getenv("RIR_DIO_UPLOAD");
-				return e ? (std::atoi(e) != 0 ? 1 : 0) : 0;
-			}();
-			return v != 0;
 		}
 
 		// frames [k0, k0 + n) of the selection, uint16 in dio_scr, go to the output: read-back filters, then a copy or the conversion
@@ -2500,7 +2447,6 @@ namespace
 			}
 			const int ntiles = cc.L.ntiles, gop = (int)hd.gop;
 			const size_t hdr_per = (size_t)ntiles * gop * 8, toff_per = ((size_t)ntiles + 1) * 4;
-			const bool upload = dio_upload();
 			// the batches: chunks j0 .. j1 - 1, as many as kDioBatchChunks, kDioBatchBytes and (filtered) the scratch allow
 			struct Batch
 			{
@@ -2565,13 +2511,9 @@ namespace
 				}
 				coff[nb] = words;
 				reinterpret_cast<uint64_t *>(h + o_pay)[words] = 0;
+				// decoded straight from page-locked memory: the kernel reads tables and payload over the link, faster on the MI355X than
+				// an upload into device memory first
 				const char *src = h;
-				if (upload)
-				{
-					if (!dio_d[b].reserve(used) || !hip_ok(hipMemcpyAsync(dio_d[b].ptr, h, used, hipMemcpyHostToDevice, st), "H2D"))
-						return false;
-					src = dio_d[b].as<char>();
-				}
 				void *out = d_out;
 				int out_frames = count;
 				if (filtered)
@@ -3142,10 +3084,7 @@ RIR_EXPORT int rir_transcode_images(int cam, int file, int first, int count, con
 		if (c->kind != CameraObject::RIRB || c->width != s->width || c->height != s->height || filtered)
 			return -2;
 		const size_t npx = (size_t)c->width * c->height;
-		const bool diag = std::getenv("RIR_TRANSCODE_DIAG") != nullptr;
 		const std::vector<AttrMap> none(keep_attributes ? 0 : (size_t)std::max(1, (int)c->hd.gop)); // (a run never exceeds a chunk of the source)
-		double t_dec = 0, t_add = 0;
-		auto now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
 		int done = 0;
 		while (done < count)
 		{
@@ -3154,11 +3093,9 @@ RIR_EXPORT int rir_transcode_images(int cam, int file, int first, int count, con
 			if (ch < 0)
 				return -1;
 			const int run = std::min(count - done, (int)(c->index[ch].first_frame + c->index[ch].nframes) - pos);
-			const double t0 = diag ? now() : 0;
 			const unsigned short *d = c->device_frame(pos);
 			if (!d)
 				return -1;
-			const double t1 = diag ? now() : 0;
 			for (int k = 0; k < run;)
 			{
 				const int took = s->add_images_device(d + (size_t)k * npx, run - k, timestamps_ns + done + k,
@@ -3167,12 +3104,8 @@ RIR_EXPORT int rir_transcode_images(int cam, int file, int first, int count, con
 					return -1;
 				k += took;
 			}
-			if (diag)
-				t_dec += t1 - t0, t_add += now() - t1;
 			done += run;
 		}
-		if (diag)
-			fprintf(stderr, "rir_transcode_images: %d images, chunks into device memory %.0f us, into the saver %.0f us\n", count, t_dec, t_add);
 		if (count > 0)
 		{
 			c->last_pos = first + count - 1;
@@ -3830,12 +3763,10 @@ int lossy_step_streams(LossyObject *const *os, int nstreams, const unsigned shor
 			if (persistent)
 			{
 				// scratch of the run kernel: [ticket, error word | 256 B][streams][2][run_wgs][slot_words] exchange words (zeroed before every launch)
-				const char *stride_env = getenv("RIR_LOSSY_SLOT_WORDS");
-				const int slot_words = stride_env && atoi(stride_env) >= 4 ? atoi(stride_env) : 8;
+				constexpr int slot_words = 8;
 				const size_t exch_words = (size_t)2 * run_wgs * slot_words + 16, exch_bytes = (size_t)nstreams * exch_words * 8;
-				// workgroup 0 of a stream collects and decides (0: every workgroup does - measured slower at every stream count, kept for measurements)
-				const char *leader_env = getenv("RIR_LOSSY_LEADER");
-				const int leader = leader_env ? atoi(leader_env) : 1;
+				// workgroup 0 of a stream collects and decides (leader 0, every workgroup doing it, was measured slower at every stream count)
+				constexpr int leader = 1;
 				const size_t exch_cap = lead.run_exchange.cap;
 				if (!lead.run_exchange.reserve(256 + exch_bytes))
 					return -1;
@@ -4119,14 +4050,6 @@ int lossy_step_streams(LossyObject *const *os, int nstreams, const unsigned shor
 		}
 		if (!hip_ok(hipMemcpyAsync(e.data(), lead.batch_errs.ptr, e.size() * sizeof(int), hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(wait_stream(st), "sync"))
 			return -1;
-		if (getenv("RIR_LOSSY_DIAG") && lead.run_exchange.ptr)
-		{ // (-DRIR_LOSSY_DIAG builds) where the time of a frame goes, workgroup 0 of stream 0
-			unsigned long long dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-			if (hip_ok(hipMemcpy(dg, lead.run_exchange.as<char>() + 128, sizeof(dg), hipMemcpyDeviceToHost), "D2H") && dg[4])
-				std::fprintf(stderr, "lossy run, per frame (us): loads+pixel sums %.2f  reduce+publish %.2f (wave sums + barrier %.2f, merge + publish %.2f, window sum %.2f)  poll %.2f  budget %.2f  barrier+update %.2f  (%llu frames)\n",
-							 dg[5] * 0.01 / dg[4], dg[0] * 0.01 / dg[4], dg[6] * 0.01 / dg[4], dg[7] * 0.01 / dg[4], (dg[0] - dg[6] - dg[7]) * 0.01 / dg[4], dg[1] * 0.01 / dg[4],
-							 dg[2] * 0.01 / dg[4], dg[3] * 0.01 / dg[4], dg[4]);
-		}
 		if (lead.run_exchange.ptr)
 			lead.checked(gave_up, st);
 		bool any_failed = false;

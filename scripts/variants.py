@@ -1,5 +1,6 @@
-"""Development aid: build variants of the codec kernels with different -D switches and time them on
-the GPU box in one gpurun call.
+"""Development aid: build variants of the codec kernels from an older revision (--src=) or with -D switches
+and time them on the GPU in one session.  The library sources keep no compile-time switches of their
+own: a -D variant needs a switch added on a branch (02807a8 is the last revision with the old ones).
 
     python scripts/variants.py build  NAME="-DA=1 -DB=2" NAME2="..."     (here: cross-compile)
     python scripts/variants.py run                                        (on the GPU box)

@@ -2,8 +2,7 @@
     read:  IRMovie.to_tensor() against torch.from_numpy(mov.data).cuda(), uint16 and float32, read-back filters off and on
     write: IRSaver.add_images(t) against add_image(t.cpu().numpy()[i]) image by image
 images/s, and the compressed bytes per image over the wall time against the 55 GB/s link.
-    python tests/perf/device_io_time.py [--frames N] [--reps R] [--json out.json]
-RIR_DIO_UPLOAD=1 in the environment: RIRB batches are uploaded before they are decoded (default: decoded from page-locked memory)."""
+    python tests/perf/device_io_time.py [--frames N] [--reps R] [--json out.json]"""
 import argparse
 import json
 import os
@@ -43,7 +42,7 @@ def main():
     n, h, w = a.frames, 512, 640
     arr = inject_bad_pixels(s1_noisy_background(n, h, w), 50)
     ts = np.arange(n, dtype=np.int64) * 20000000
-    res = {"frames": n, "height": h, "width": w, "upload_first": os.environ.get("RIR_DIO_UPLOAD", "0") == "1"}
+    res = {"frames": n, "height": h, "width": w}
     with tempfile.TemporaryDirectory() as d:
         src = os.path.join(d, "s1.h264")
         with IRSaver(src, w, h, h) as s:

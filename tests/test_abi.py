@@ -76,6 +76,29 @@ def test_the_product_library_has_no_test_hooks():
     for name in (b"RIR_DEBUG_LOSSY_GIVE_UP", b"RIR_DEBUG_LOSSY_BAIL", b"RIR_DEBUG_ECC_BAIL", b"RIR_LOSSY_CONST_PAIRS"):
         assert name not in product, name
         assert name in hooks, name
+    # variables that only served measurements are read by neither build (what they found: DESIGN.md, profiles/, commit 02807a8)
+    for name in (b"RIR_ECC_DIAG", b"RIR_LOSSY_DIAG", b"RIR_TRANSCODE_DIAG", b"RIR_ECC_NO_OVERLAP", b"RIR_ECC_MULTI_SLICES", b"RIR_LOSSY_SLOT_WORDS",
+                 b"RIR_LOSSY_LEADER", b"RIR_ENC_LDS_WORDS", b"RIR_DIO_UPLOAD"):
+        assert name not in product, name
+        assert name not in hooks, name
+
+
+def test_library_sources_have_no_build_switches_and_document_every_variable():
+    """the only preprocessor switch of librir_amd/csrc/ is RIR_TEST_HOOKS, and every RIR_* variable it reads is in INTEGRATION.md §5"""
+    csrc = os.path.join(ROOT, "librir_amd", "csrc")
+    text = open(os.path.join(ROOT, "INTEGRATION.md"), encoding="utf-8").read()
+    section = text.split("\n## 5.", 1)[1].split("\n## ", 1)[0]
+    switches, undocumented = [], []
+    for f in sorted(os.listdir(csrc)):
+        src = open(os.path.join(csrc, f), encoding="utf-8").read()
+        for m in re.finditer(r"^[ \t]*#[ \t]*(if|ifdef|ifndef|elif|elifdef|elifndef)\b(.*(?:\\\n.*)*)", src, re.M):
+            if set(re.findall(r"\bRIR_\w+", m.group(2))) - {"RIR_TEST_HOOKS"}:
+                switches.append("%s: #%s%s" % (f, m.group(1), m.group(2)))
+        for name in re.findall(r"\b(?:getenv|test_hook|test_hook_is)\s*\(\s*\"(RIR_\w+)\"", src):
+            if not re.search(r"`%s[`=]" % name, section):
+                undocumented.append("%s: %s" % (f, name))
+    assert not switches, switches
+    assert not undocumented, undocumented
 
 
 def test_layout_query_is_pure_host(lib):
