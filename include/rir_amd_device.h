@@ -232,6 +232,15 @@ extern "C"
 	/* 3x3 median filter: reference Filters.h:71-129 (template without C export upstream). */
 	int rir_median_filter_device(const unsigned short *d_src, unsigned short *d_dst, int w, int h, int nframes, void *stream);
 
+	/* Temporal median of a uint16 stack d_src[nframes][h][w] (extension).  Output k < count is frame t = first + k * step: with
+	 * r = window / 2 (window odd, 1..63), S = frames max(0, t - r) .. min(nframes - 1, t + r) - truncated at the ends of THIS stack, never
+	 * padded - and m = sorted(S)[|S| / 2] (the upper median when |S| is even), d_dst[k] = m where |src[t] - m| > threshold (0..65535;
+	 * 0 gives the plain median), src[t] elsewhere; rows y >= `rows` (0..h) are copied unchanged.  A caller that passes a batch with r frames
+	 * of halo on either side gets the bits of one call over the whole sequence.  Asynchronous on `stream`; d_dst holds `count` frames and
+	 * may not overlap d_src.  count 0: nothing is done.  0 / -1 (invalid argument, overlap, no device). */
+	int rir_temporal_median_device(const unsigned short *d_src, unsigned short *d_dst, int w, int h, int nframes, int first, int count, int step,
+								   int window, int threshold, int rows, void *stream);
+
 	/* connected components: reference signal_processing.h:90-92 / Filters.h:365-540 (labelImage, keepLargestArea) on images in device memory,
 	 * [nframes][h][w], every image labelled on its own; five launches for the whole batch.  type: the reference's dtype character;
 	 * background: HOST pointer to one cell of that type.  d_dst int32 [nframes][h][w].

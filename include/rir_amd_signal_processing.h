@@ -60,6 +60,9 @@ extern "C"
 	 * rir_set_gaussian_reference_order(1) (rir_amd_device.h).  0 / -1. */
 	int rir_filter_chain(int bad_pixels_handle, unsigned short *in, unsigned short *out, int w, int h, float sigma, float dx, float dy,
 						 void *background, const char *strategy);
+	/* Temporal median of a host stack src[nframes][h][w] into dst (same shape): rir_temporal_median_device over the whole stack (first 0,
+	 * step 1), synchronous.  Large stacks go through the device in slabs with window / 2 frames of halo.  0 / -1. */
+	int rir_temporal_median(const unsigned short *src, unsigned short *dst, int w, int h, int nframes, int window, int threshold, int rows);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@
 #include "filter_kernels.h"
 #include "label_kernels.h"
 #include "runtime.h"
+#include "temporal_kernels.h"
 
 using namespace rir;
 
@@ -615,6 +616,31 @@ RIR_EXPORT int rir_median_filter_device(const unsigned short *d_src, unsigned sh
 	return hip_ok(launch_median3x3(d_src, d_dst, w, h, nframes, as_stream(stream)), "median_filter") ? 0 : -1;
 }
 
+// Temporal median (temporal_kernels.hip).  Every argument is checked here; the source and destination byte ranges may not overlap.
+RIR_EXPORT int rir_temporal_median_device(const unsigned short *d_src, unsigned short *d_dst, int w, int h, int nframes, int first, int count, int step,
+										  int window, int threshold, int rows, void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (w <= 0 || h <= 0 || nframes <= 0 || window < 1 || window > 63 || window % 2 == 0 || threshold < 0 || threshold > 65535 || rows < 0 || rows > h ||
+		step < 1 || count < 0 || first < 0 || first > nframes || (count > 0 && first + (long long)(count - 1) * step > nframes - 1))
+	{
+		log_error("rir_temporal_median_device: invalid argument (odd window 1..63, threshold 0..65535, 0 <= rows <= h, outputs inside the stack)");
+		return -1;
+	}
+	if (count == 0)
+		return 0;
+	const uintptr_t frame = (uintptr_t)w * h * 2, s = (uintptr_t)d_src, d = (uintptr_t)d_dst;
+	if (!d_src || !d_dst || (s < d + frame * count && d < s + frame * nframes))
+	{
+		log_error("rir_temporal_median_device: null pointer, or the source and destination overlap");
+		return -1;
+	}
+	return hip_ok(launch_temporal_median(d_src, d_dst, w, h, nframes, first, count, step, window, threshold, rows, as_stream(stream)), "temporal_median")
+			   ? 0
+			   : -1;
+}
+
 // =====================================================================================================
 // Reference entry points (host pointers, synchronous)
 // =====================================================================================================
@@ -797,6 +823,38 @@ RIR_EXPORT int rir_filter_chain(int bad_pixels_handle, unsigned short *in, unsig
 								background, strategy, st) != 0)
 		return -1;
 	return hand_out(s, out, dst, bytes, st) ? 0 : -1;
+}
+
+// Extension: the temporal median of a host stack, in slabs of at most TEMPORAL_SLAB_BYTES of output frames, each read with r frames of halo
+// on either side (the windows of a slab's outputs are then those of the whole stack).  Synchronous.  0 / -1.
+constexpr size_t TEMPORAL_SLAB_BYTES = (size_t)64 << 20;
+RIR_EXPORT int rir_temporal_median(const unsigned short *src, unsigned short *dst, int w, int h, int nframes, int window, int threshold, int rows)
+{
+	if (!device_ready())
+		return -1;
+	if (!src || !dst || w <= 0 || h <= 0 || nframes <= 0 || window < 1 || window > 63 || window % 2 == 0 || threshold < 0 || threshold > 65535 ||
+		rows < 0 || rows > h)
+	{
+		log_error("rir_temporal_median: invalid argument (odd window 1..63, threshold 0..65535, 0 <= rows <= h)");
+		return -1;
+	}
+	const int r = window / 2;
+	const size_t frame = (size_t)w * h * 2;
+	const int slab = (int)std::max<size_t>(1, std::min<size_t>(TEMPORAL_SLAB_BYTES / frame, (size_t)nframes));
+	DeviceBuffer in, out;
+	if (!in.reserve(frame * (size_t)std::min(nframes, slab + 2 * r)) || !out.reserve(frame * slab))
+		return -1;
+	hipStream_t st = default_stream();
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int count = std::min(slab, nframes - o), lo = std::max(0, o - r), hi = std::min(nframes, o + count + r);
+		if (!hip_ok(hipMemcpyAsync(in.ptr, src + (size_t)lo * w * h, frame * (hi - lo), hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
+			rir_temporal_median_device(in.as<unsigned short>(), out.as<unsigned short>(), w, h, hi - lo, o - lo, count, 1, window, threshold, rows, st) != 0 ||
+			!hip_ok(hipMemcpyAsync(dst + (size_t)o * w * h, out.ptr, frame * count, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+			!hip_ok(wait_stream(st), "temporal_median"))
+			return -1;
+	}
+	return 0;
 }
 
 RIR_EXPORT void bad_pixels_destroy(int handle)

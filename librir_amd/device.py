@@ -9,6 +9,7 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
+from .signal_processing.rir_signal_processing import _temporal_median_args
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -107,6 +108,7 @@ _lib.rir_bad_pixels_info.argtypes = [ct.c_int, _vp, _vp, ct.c_int]
 _lib.rir_remove_bad_pixels_device.argtypes = [ct.c_int, _vp, ct.c_int, ct.c_int, _vp]
 _lib.rir_remove_motion_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp, _vp]
 _lib.rir_median_filter_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, _vp]
+_lib.rir_temporal_median_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp]
 _lib.bad_pixels_destroy.argtypes = [ct.c_int]
 _lib.rir_label_workspace_bytes.argtypes = [ct.c_int, ct.c_int]
 _lib.rir_label_workspace_bytes.restype = ct.c_size_t
@@ -614,6 +616,89 @@ def median_filter(frames):
     out = torch.empty_like(fr)
     _check(_lib.rir_median_filter_device(fr.data_ptr(), out.data_ptr(), w, h, n, _stream()), "rir_median_filter_device")
     return out
+
+
+def temporal_median(frames, window, threshold=0, rows=None, first=0, count=None, step=1, out=None):
+    """Temporal median of a uint16 stack ``frames[n][h][w]`` (C ABI ``rir_temporal_median_device``), on the current stream: output k is
+    frame t = first + k * step, the upper median ``sorted(S)[len(S) // 2]`` of the frames t - r .. t + r (r = window // 2; the window is
+    truncated at the ends of ``frames``) where it differs from ``frames[t]`` by more than ``threshold``, ``frames[t]`` elsewhere; rows
+    ``>= rows`` are copied.  ``count=None``: every position from ``first`` to the end at ``step``.  Returns ``[count][h][w]`` uint16
+    (``out`` when given: a contiguous uint16 CUDA tensor of that shape that does not overlap ``frames``)."""
+    if frames.dim() == 2:
+        frames = frames.unsqueeze(0)
+    rows, count = _temporal_median_args(tuple(frames.shape), window, threshold, rows, first, count, step)
+    fr = _frames3(frames, torch.uint16)
+    n, h, w = fr.shape
+    if out is None:
+        out = torch.empty((count, h, w), dtype=torch.uint16, device=fr.device)
+    elif not out.is_cuda or out.dtype != torch.uint16 or tuple(out.shape) != (count, h, w) or not out.is_contiguous():
+        raise RuntimeError("temporal_median: out must be a contiguous uint16 CUDA tensor of shape %s" % ((count, h, w),))
+    if count:
+        _check(_lib.rir_temporal_median_device(fr.data_ptr(), out.data_ptr(), w, h, n, int(first), count, int(step), int(window), int(threshold), rows,
+                                               _stream()), "rir_temporal_median_device")
+    return out
+
+
+class TemporalMedian:
+    """``temporal_median`` over a sequence that arrives in batches.  ``push(frames)`` returns the outputs complete so far (they trail the
+    input by window // 2 frames, so a push may return none), ``finish()`` the last ones, over windows truncated at the sequence's end;
+    together they equal one ``temporal_median`` call over the concatenated input, bit for bit.  The object keeps at most window - 1 frames
+    of history (copied once per push) and is ready for a new sequence after ``finish()`` or ``reset()``."""
+
+    def __init__(self, window, threshold=0, rows=None):
+        _temporal_median_args((1, 1 if rows is None else int(rows), 1), window, threshold, rows)
+        self.window, self.threshold, self.rows = int(window), int(threshold), rows
+        self.reset()
+
+    def reset(self):
+        self._shape = None  # (h, w) of the sequence
+        self._hist = None  # input frames [base, seen) still needed
+        self._base = 0
+        self._seen = 0  # input frames pushed
+        self._done = 0  # outputs returned
+
+    def _range(self, batch, lo, hi):
+        """input frames [lo, hi) from the history and the batch that starts at self._seen"""
+        if lo >= self._seen:
+            return batch[lo - self._seen:hi - self._seen]
+        if hi <= self._seen:
+            return self._hist[lo - self._base:hi - self._base]
+        return torch.cat((self._hist[lo - self._base:], batch[:hi - self._seen]))
+
+    def _outputs(self, stack, lo, t0, t1, out):
+        """outputs [t0, t1) from `stack` = input frames lo .. into out"""
+        temporal_median(stack, self.window, self.threshold, self.rows, first=t0 - lo, count=t1 - t0, out=out)
+
+    def push(self, frames):
+        fr = _frames3(frames, torch.uint16)
+        if self._shape is None:
+            self._shape = tuple(fr.shape[1:])
+        elif tuple(fr.shape[1:]) != self._shape:
+            raise ValueError("TemporalMedian.push: frames of shape %s, the sequence's are %s" % (tuple(fr.shape[1:]), self._shape))
+        r = self.window // 2
+        n0, n = self._seen, self._seen + fr.shape[0]
+        t0, t1 = self._done, max(self._done, n - r)  # outputs whose window is complete
+        out = torch.empty((t1 - t0,) + self._shape, dtype=torch.uint16, device=fr.device)
+        split = min(max(t0, n0 + r if n0 else 0), t1)  # outputs from `split` on read the batch alone
+        if split > t0:
+            self._outputs(self._range(fr, max(0, t0 - r), split - 1 + r + 1), max(0, t0 - r), t0, split, out[:split - t0])
+        if t1 > split:
+            lo = max(0, split - r)
+            self._outputs(fr[lo - n0:t1 - 1 + r + 1 - n0], lo, split, t1, out[split - t0:])
+        keep = max(0, t1 - r)
+        self._hist = self._range(fr, keep, n).clone()
+        self._base, self._seen, self._done = keep, n, t1
+        return out
+
+    def finish(self):
+        h, w = self._shape if self._shape is not None else (0, 0)
+        t0, n = self._done, self._seen
+        device = self._hist.device if self._hist is not None else torch.device("cuda", torch.cuda.current_device())
+        out = torch.empty((n - t0, h, w), dtype=torch.uint16, device=device)
+        if n > t0:
+            self._outputs(self._hist, self._base, t0, n, out)
+        self.reset()
+        return out
 
 
 def _label_args(image, background):

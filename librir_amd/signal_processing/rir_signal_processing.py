@@ -156,6 +156,50 @@ def filter_chain(image, bad_pixels, sigma, dx, dy, strategy="nearest", backgroun
     return out
 
 
+# ---- extension: temporal median of a stack ------------------------------------------------------------------------------------
+_sp.rir_temporal_median.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int]
+
+
+def _temporal_median_args(shape, window, threshold, rows, first=0, count=None, step=1):
+    """the parameters of a temporal median over a stack of `shape`, checked without a device; -> (rows, count)"""
+    if len(shape) != 3:
+        raise ValueError("temporal_median: a stack [n][h][w] expected")
+    n, h, _ = shape
+    if int(window) != window or not 1 <= window <= 63 or window % 2 == 0:
+        raise ValueError("temporal_median: window must be odd, 1 to 63 (got %r)" % (window,))
+    if not 0 <= int(threshold) <= 65535:
+        raise ValueError("temporal_median: threshold must be in 0..65535")
+    rows = h if rows is None else int(rows)
+    if not 0 <= rows <= h:
+        raise ValueError("temporal_median: rows must be in 0..h")
+    step = int(step)
+    if step < 1:
+        raise ValueError("temporal_median: step must be >= 1")
+    first = int(first)
+    if not 0 <= first <= n:
+        raise ValueError("temporal_median: first must be in 0..%d" % n)
+    count = len(range(first, n, step)) if count is None else int(count)
+    if count < 0 or (count > 0 and first + (count - 1) * step > n - 1):
+        raise ValueError("temporal_median: outputs first + k * step (k < count) must lie in the stack")
+    return rows, count
+
+
+def temporal_median(images, window, threshold=0, rows=None):
+    """Extension: temporal median of a uint16 stack ``images[n][h][w]`` (``rir_temporal_median``): image t becomes the upper median of
+    images t - r .. t + r (r = window // 2, window odd 1..63, truncated at the ends of the stack) where it differs from image t by more
+    than ``threshold``; rows ``>= rows`` (default: all rows filtered) are left as they are.  ``ValueError`` on bad parameters,
+    ``RuntimeError`` when the library fails."""
+    img = np.ascontiguousarray(images)
+    if img.ndim != 3 or img.dtype != np.uint16:
+        raise RuntimeError("temporal_median: a 3-D uint16 stack expected")
+    rows, _ = _temporal_median_args(img.shape, window, threshold, rows)
+    out = np.empty_like(img)
+    if img.shape[0] and _sp.rir_temporal_median(img.ctypes.data, out.ctypes.data, img.shape[2], img.shape[1], img.shape[0], int(window), int(threshold),
+                                                rows) < 0:
+        raise RuntimeError("An error occured while calling 'temporal_median': " + (last_error() or ""))
+    return out
+
+
 # ---- time axes (host bookkeeping, csrc/time_series.cpp) -------------------------------------------------------------------------
 _sp.extract_times.argtypes = [ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p, ct.POINTER(ct.c_int)]
 _sp.resample_time_serie.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_void_p, ct.POINTER(ct.c_int)]

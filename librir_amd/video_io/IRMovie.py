@@ -265,15 +265,26 @@ class IRMovie(object):
         self._current = pos
         return image
 
-    def to_tensor(self, selection=slice(None), dtype=None, out=None):
+    def to_tensor(self, selection=slice(None), dtype=None, out=None, temporal_median=None, median_threshold=0):
         """Images of ``selection`` (an int, or a slice with a positive step; negative bounds as ``movie[...]`` takes them) as a CUDA
         tensor ``[n][h][w]`` of ``dtype`` (``torch.uint16``, the default, or ``torch.float32``) on the current CUDA device - the images
         ``movie[selection]`` gives, bit for bit, decoded on the device: only the compressed chunks of a recording of this library cross
         the link.  ``out``: a preallocated C-contiguous CUDA tensor of that shape and dtype.  The current image (``load_pos``) and its
-        attributes stay what they were."""
+        attributes stay what they were.
+
+        ``temporal_median=W`` (odd, 1..63): each selected image p becomes the temporal median of the images p - W//2 .. p + W//2 of the
+        recording as ``movie[...]`` gives them (read-back filters applied first; the window is truncated only at the recording's first and
+        last image), taken where it differs from image p by more than ``median_threshold`` - ``librir_amd.device.temporal_median``.  The
+        recording is read in pieces with W//2 images of halo on either side: the temporary device memory holds at most
+        max(64 MiB, W images) of uint16 input, plus as many uint16 output images for a float32 result, whatever the selection's length."""
         import torch
 
         dtype = torch.uint16 if dtype is None else dtype
+        if temporal_median is not None:
+            from ..device import _temporal_median_args
+
+            h, w = self.image_size
+            _temporal_median_args((1, h, w), temporal_median, median_threshold, None)
         if dtype not in (torch.uint16, torch.float32):
             raise ValueError("to_tensor: dtype torch.uint16 or torch.float32 expected, not %s" % (dtype,))
         if self._calibration_index != 0:
@@ -299,8 +310,33 @@ class IRMovie(object):
         if len(positions):
             if positions.start < 0 or positions[-1] >= total:
                 raise IndexError("to_tensor: images %s out of range (%d images)" % (positions, total))
-            _abi.load_images_device(self.handle, positions.start, len(positions), positions.step, out)
+            if temporal_median is None:
+                _abi.load_images_device(self.handle, positions.start, len(positions), positions.step, out)
+            else:
+                self._median_to_tensor(positions, int(temporal_median), int(median_threshold), out)
         return out
+
+    _MEDIAN_PIECE_BYTES = 64 << 20  # uint16 input images read at once by to_tensor(temporal_median=...)
+
+    def _median_to_tensor(self, positions, window, threshold, out):
+        import torch
+
+        from ..device import temporal_median
+
+        r, total, step = window // 2, self.images, positions.step
+        h, w = self.image_size
+        budget = max(window, self._MEDIAN_PIECE_BYTES // (2 * h * w))  # input images per piece
+        per_piece = max(1, (budget - 2 * r - 1) // step + 1)  # outputs per piece: their images, halo included, fit the budget
+        for k0 in range(0, len(positions), per_piece):
+            sel = positions[k0:k0 + per_piece]
+            lo, hi = max(0, sel[0] - r), min(total, sel[-1] + r + 1)
+            stack = torch.empty((hi - lo, h, w), dtype=torch.uint16, device=out.device)
+            _abi.load_images_device(self.handle, lo, hi - lo, 1, stack)
+            dst = out[k0:k0 + len(sel)]
+            if out.dtype == torch.uint16:
+                temporal_median(stack, window, threshold, first=sel[0] - lo, count=len(sel), step=step, out=dst)
+            else:
+                dst.copy_(temporal_median(stack, window, threshold, first=sel[0] - lo, count=len(sel), step=step))
 
     def load_secs(self, time, calibration=None):
         """The image whose time stamp is closest to ``time`` (seconds)."""
