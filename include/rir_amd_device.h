@@ -241,6 +241,19 @@ extern "C"
 	int rir_temporal_median_device(const unsigned short *d_src, unsigned short *d_dst, int w, int h, int nframes, int first, int count, int step,
 								   int window, int threshold, int rows, void *stream);
 
+	/* Per-region statistics of a uint16 stack d_frames[nframes][h][w] (extension).  d_labels: int32, one map [h][w] for every frame
+	 * (labels_per_frame 0) or one per frame [nframes][h][w] (1).  For frame f and region r < nregions (1..2^24), P = the flat indices
+	 * i = y * w + x whose label is r; labels outside [0, nregions) are ignored.  Outputs [nframes][nregions]: d_count = |P|, d_sum and
+	 * d_sumsq = the exact sums of the values and of their squares, d_min / d_max = the extremes over P, d_argmin / d_argmax = the lowest i
+	 * in P that holds them; an empty region has count, sums 0 and -1 for the other four.  Bitwise reproducible.  d_work: device memory,
+	 * 8-byte aligned, at least rir_region_stats_workspace_bytes(...) (0: arguments refused).  Asynchronous on `stream`; no output or
+	 * the workspace may overlap an input or another output.  nframes 0: nothing is done.  0 / -1 (invalid argument, null pointer,
+	 * overlap, workspace too small, no device). */
+	int rir_region_stats_device(const unsigned short *d_frames, const int *d_labels, int w, int h, int nframes, int labels_per_frame, int nregions,
+								int *d_count, long long *d_sum, long long *d_sumsq, int *d_min, int *d_max, int *d_argmin, int *d_argmax,
+								void *d_work, size_t work_bytes, void *stream);
+	size_t rir_region_stats_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions);
+
 	/* connected components: reference signal_processing.h:90-92 / Filters.h:365-540 (labelImage, keepLargestArea) on images in device memory,
 	 * [nframes][h][w], every image labelled on its own; five launches for the whole batch.  type: the reference's dtype character;
 	 * background: HOST pointer to one cell of that type.  d_dst int32 [nframes][h][w].

@@ -63,6 +63,11 @@ extern "C"
 	/* Temporal median of a host stack src[nframes][h][w] into dst (same shape): rir_temporal_median_device over the whole stack (first 0,
 	 * step 1), synchronous.  Large stacks go through the device in slabs with window / 2 frames of halo.  0 / -1. */
 	int rir_temporal_median(const unsigned short *src, unsigned short *dst, int w, int h, int nframes, int window, int threshold, int rows);
+	/* Per-region statistics of a host stack frames[nframes][h][w] with host label maps: rir_region_stats_device (rir_amd_device.h),
+	 * synchronous, host outputs [nframes][nregions].  The frames go through the device in slabs of at most 64 MiB; a shared map goes up
+	 * once.  0 / -1. */
+	int rir_region_stats(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
+						 int *count, long long *sum, long long *sumsq, int *min, int *max, int *argmin, int *argmax);
 
 #ifdef __cplusplus
 }

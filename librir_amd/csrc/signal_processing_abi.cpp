@@ -13,6 +13,7 @@
 
 #include "filter_kernels.h"
 #include "label_kernels.h"
+#include "region_kernels.h"
 #include "runtime.h"
 #include "temporal_kernels.h"
 
@@ -641,6 +642,76 @@ RIR_EXPORT int rir_temporal_median_device(const unsigned short *d_src, unsigned 
 			   : -1;
 }
 
+// Per-region statistics (region_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an input or
+// another output.
+namespace
+{
+	bool region_stats_args(int w, int h, int nframes, int labels_per_frame, int nregions)
+	{
+		return w > 0 && h > 0 && (long long)w * h < (1ll << 31) && nframes >= 0 && (labels_per_frame == 0 || labels_per_frame == 1) && nregions >= 1 &&
+			   nregions <= (1 << 24);
+	}
+} // namespace
+
+RIR_EXPORT size_t rir_region_stats_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions)
+{
+	if (!region_stats_args(w, h, nframes, labels_per_frame, nregions))
+		return 0;
+	return region_stats_workspace((int64_t)w * h, nframes, nregions);
+}
+
+RIR_EXPORT int rir_region_stats_device(const unsigned short *d_frames, const int *d_labels, int w, int h, int nframes, int labels_per_frame, int nregions,
+									   int *d_count, long long *d_sum, long long *d_sumsq, int *d_min, int *d_max, int *d_argmin, int *d_argmax,
+									   void *d_work, size_t work_bytes, void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (!region_stats_args(w, h, nframes, labels_per_frame, nregions))
+	{
+		log_error("rir_region_stats_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, "
+				  "1 <= nregions <= 2^24)");
+		return -1;
+	}
+	if (nframes == 0)
+		return 0;
+	const size_t npx = (size_t)w * h, cells = (size_t)nframes * nregions, need = region_stats_workspace((int64_t)npx, nframes, nregions);
+	if (!d_frames || !d_labels || !d_count || !d_sum || !d_sumsq || !d_min || !d_max || !d_argmin || !d_argmax || !d_work)
+	{
+		log_error("rir_region_stats_device: null pointer");
+		return -1;
+	}
+	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
+	{
+		log_error("rir_region_stats_device: the workspace must be 8-byte aligned and hold rir_region_stats_workspace_bytes() bytes");
+		return -1;
+	}
+	const struct
+	{
+		uintptr_t p;
+		size_t bytes;
+	} in[2] = {{(uintptr_t)d_frames, npx * nframes * 2}, {(uintptr_t)d_labels, npx * (labels_per_frame ? nframes : 1) * 4}},
+	  out[8] = {{(uintptr_t)d_count, cells * 4}, {(uintptr_t)d_sum, cells * 8}, {(uintptr_t)d_sumsq, cells * 8}, {(uintptr_t)d_min, cells * 4},
+				{(uintptr_t)d_max, cells * 4},	 {(uintptr_t)d_argmin, cells * 4}, {(uintptr_t)d_argmax, cells * 4}, {(uintptr_t)d_work, need}};
+	for (int i = 0; i < 8; ++i)
+	{
+		bool overlap = false;
+		for (const auto &a : in)
+			overlap |= out[i].p < a.p + a.bytes && a.p < out[i].p + out[i].bytes;
+		for (int j = 0; j < i; ++j)
+			overlap |= out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
+		if (overlap)
+		{
+			log_error("rir_region_stats_device: an output or the workspace overlaps an input or another output");
+			return -1;
+		}
+	}
+	return hip_ok(launch_region_stats(d_frames, d_labels, (int64_t)npx, nframes, labels_per_frame, nregions, d_count, (int64_t *)d_sum, (int64_t *)d_sumsq,
+									  d_min, d_max, d_argmin, d_argmax, d_work, as_stream(stream)),
+				  "region_stats")
+			   ? 0
+			   : -1;
+}
+
 // =====================================================================================================
 // Reference entry points (host pointers, synchronous)
 // =====================================================================================================
@@ -852,6 +923,56 @@ RIR_EXPORT int rir_temporal_median(const unsigned short *src, unsigned short *ds
 			rir_temporal_median_device(in.as<unsigned short>(), out.as<unsigned short>(), w, h, hi - lo, o - lo, count, 1, window, threshold, rows, st) != 0 ||
 			!hip_ok(hipMemcpyAsync(dst + (size_t)o * w * h, out.ptr, frame * count, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
 			!hip_ok(wait_stream(st), "temporal_median"))
+			return -1;
+	}
+	return 0;
+}
+
+// Extension: per-region statistics of a host stack, sent in slabs of at most REGION_SLAB_BYTES of frames (with their label maps when there
+// is one per frame; a shared map goes up once).  Synchronous.  0 / -1.
+constexpr size_t REGION_SLAB_BYTES = (size_t)64 << 20;
+RIR_EXPORT int rir_region_stats(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
+								int *count, long long *sum, long long *sumsq, int *min, int *max, int *argmin, int *argmax)
+{
+	if (!device_ready())
+		return -1;
+	if (!region_stats_args(w, h, nframes, labels_per_frame, nregions) || !frames || !labels || !count || !sum || !sumsq || !min || !max || !argmin ||
+		!argmax)
+	{
+		log_error("rir_region_stats: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, 1 <= nregions <= 2^24, "
+				  "no null pointer)");
+		return -1;
+	}
+	if (nframes == 0)
+		return 0;
+	const size_t npx = (size_t)w * h, frame = npx * 2, K = (size_t)nregions;
+	const size_t per_frame_out = K * (5 * 4 + 2 * 8 + 32); // outputs and workspace of one frame on the device
+	const int slab = (int)std::max<size_t>(1, std::min<size_t>({REGION_SLAB_BYTES / frame, REGION_SLAB_BYTES / per_frame_out, (size_t)nframes}));
+	const size_t cells = (size_t)slab * K, work = region_stats_workspace((int64_t)npx, slab, nregions);
+	DeviceBuffer fr, lab, o32, o64, ws;
+	if (!fr.reserve(frame * slab) || !lab.reserve(npx * 4 * (labels_per_frame ? slab : 1)) || !o32.reserve(cells * 4 * 5) || !o64.reserve(cells * 8 * 2) ||
+		!ws.reserve(work))
+		return -1;
+	hipStream_t st = default_stream();
+	if (!labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels, npx * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))
+		return -1;
+	int *d32 = o32.as<int>();
+	long long *d64 = o64.as<long long>();
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int c = std::min(slab, nframes - o);
+		const size_t n = (size_t)c * K, at = (size_t)o * K;
+		if (!hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, frame * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
+			(labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels + (size_t)o * npx, npx * 4 * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
+			rir_region_stats_device(fr.as<unsigned short>(), lab.as<int>(), w, h, c, labels_per_frame, nregions, d32, d64, d64 + cells, d32 + cells,
+									d32 + 2 * cells, d32 + 3 * cells, d32 + 4 * cells, ws.ptr, work, st) != 0)
+			return -1;
+		int *outs32[5] = {count + at, min + at, max + at, argmin + at, argmax + at};
+		for (int k = 0; k < 5; ++k)
+			if (!hip_ok(hipMemcpyAsync(outs32[k], d32 + (size_t)k * cells, n * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync"))
+				return -1;
+		if (!hip_ok(hipMemcpyAsync(sum + at, d64, n * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+			!hip_ok(hipMemcpyAsync(sumsq + at, d64 + cells, n * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") || !hip_ok(wait_stream(st), "region_stats"))
 			return -1;
 	}
 	return 0;

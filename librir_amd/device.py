@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
-from .signal_processing.rir_signal_processing import _temporal_median_args
+from .signal_processing.rir_signal_processing import RegionStats, _region_stats_args, _temporal_median_args  # noqa: F401 (RegionStats: API)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -109,6 +109,9 @@ _lib.rir_remove_bad_pixels_device.argtypes = [ct.c_int, _vp, ct.c_int, ct.c_int,
 _lib.rir_remove_motion_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp, _vp]
 _lib.rir_median_filter_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, _vp]
 _lib.rir_temporal_median_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp]
+_lib.rir_region_stats_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp] * 8 + [ct.c_size_t, _vp]
+_lib.rir_region_stats_workspace_bytes.argtypes = [ct.c_int] * 5
+_lib.rir_region_stats_workspace_bytes.restype = ct.c_size_t
 _lib.bad_pixels_destroy.argtypes = [ct.c_int]
 _lib.rir_label_workspace_bytes.argtypes = [ct.c_int, ct.c_int]
 _lib.rir_label_workspace_bytes.restype = ct.c_size_t
@@ -699,6 +702,47 @@ class TemporalMedian:
             self._outputs(self._hist, self._base, t0, n, out)
         self.reset()
         return out
+
+
+def _region_inputs(frames, labels, nregions):
+    """region_stats' checks, in the order that needs no device for the shapes, dtypes and nregions; -> (frames, labels, n, h, w, per_frame)"""
+    if frames.dtype != torch.uint16:
+        raise RuntimeError("region_stats: uint16 frames expected, not %s" % frames.dtype)
+    if labels.dtype != torch.int32:
+        raise RuntimeError("region_stats: int32 labels expected, not %s" % labels.dtype)
+    n, h, w, per_frame = _region_stats_args(tuple(frames.shape), tuple(labels.shape), nregions)
+    if not frames.is_cuda or not labels.is_cuda or frames.device != labels.device:
+        raise RuntimeError("region_stats: frames and labels on one CUDA device expected")
+    return _frames3(frames), labels.contiguous(), n, h, w, per_frame
+
+
+def _region_stats_into(fr, lab, per_frame, nregions, out):
+    """queue the statistics of fr [n][h][w] over lab into out (a RegionStats of contiguous [n][nregions] tensors)"""
+    n, h, w = fr.shape
+    need = _lib.rir_region_stats_workspace_bytes(w, h, n, per_frame, nregions)
+    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    _check(_lib.rir_region_stats_device(fr.data_ptr(), lab.data_ptr(), w, h, n, per_frame, nregions, *(t.data_ptr() for t in out), work.data_ptr(),
+                                        work.numel() * 8, _stream()), "rir_region_stats_device")
+
+
+def _region_stats_empty(n, nregions, device):
+    return RegionStats(*(torch.empty((n, nregions), dtype=dt, device=device)
+                         for dt in (torch.int32, torch.int64, torch.int64, torch.int32, torch.int32, torch.int32, torch.int32)))
+
+
+def region_stats(frames, labels, nregions=None):
+    """Statistics of a uint16 stack ``frames (n, h, w)`` (or one ``(h, w)`` image: a stack of one) over the regions of the int32 label map
+    ``labels`` (``(h, w)`` shared by every frame, or ``(n, h, w)``), on the current stream (C ABI ``rir_region_stats_device``): a
+    ``RegionStats`` of CUDA tensors ``[n][nregions]`` - count, exact sum and sum of squares, min, max and the lowest flat index y * w + x of
+    each.  Labels outside [0, nregions) are ignored; ``nregions=None`` takes ``labels.max() + 1`` (at least 1), which synchronises."""
+    fr, lab, n, h, w, per_frame = _region_inputs(frames, labels, nregions)
+    if nregions is None:
+        nregions = max(1, int(lab.max()) + 1)
+        _region_stats_args(tuple(frames.shape), tuple(labels.shape), nregions)
+    out = _region_stats_empty(n, int(nregions), fr.device)
+    if n:
+        _region_stats_into(fr, lab, per_frame, int(nregions), out)
+    return out
 
 
 def _label_args(image, background):

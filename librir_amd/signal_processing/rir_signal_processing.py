@@ -5,6 +5,7 @@ Same function names, argument meaning and error behaviour as the reference wrapp
 numpy arrays in, numpy arrays out, ``RuntimeError`` on bad dimensions / dtypes / library errors.
 """
 import ctypes as ct
+from collections import namedtuple
 
 import numpy as np
 
@@ -197,6 +198,80 @@ def temporal_median(images, window, threshold=0, rows=None):
     if img.shape[0] and _sp.rir_temporal_median(img.ctypes.data, out.ctypes.data, img.shape[2], img.shape[1], img.shape[0], int(window), int(threshold),
                                                 rows) < 0:
         raise RuntimeError("An error occured while calling 'temporal_median': " + (last_error() or ""))
+    return out
+
+
+# ---- extension: per-region statistics ------------------------------------------------------------------------------------------
+_sp.rir_region_stats.argtypes = [ct.c_void_p, ct.c_void_p] + [ct.c_int] * 5 + [ct.c_void_p] * 7
+
+MAX_REGIONS = 1 << 24
+
+
+class RegionStats(namedtuple("RegionStats", "count sum sumsq min max argmin argmax")):
+    """Statistics per (frame, region), each ``[n][nregions]``: count (int32), sum and sumsq (int64, exact), min and max (int32), argmin and
+    argmax (int32: the lowest flat index y * w + x that holds the extreme).  An empty region has count, sum and sumsq 0 and -1 elsewhere.
+    numpy arrays (``signal_processing.region_stats``) or CUDA tensors (``device.region_stats``)."""
+
+    __slots__ = ()
+
+    def mean(self):
+        """float64 mean from the exact sum; NaN where count == 0"""
+        if isinstance(self.sum, np.ndarray):
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return self.sum.astype(np.float64) / self.count
+        return self.sum.double() / self.count
+
+    def std(self):
+        """float64 population standard deviation from the exact sums; NaN where count == 0"""
+        if isinstance(self.sum, np.ndarray):
+            c = self.count.astype(np.float64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                m = self.sum / c
+                return np.sqrt(np.maximum((self.sumsq - self.sum * m) / c, 0.0))
+        c = self.count.double()
+        m = self.sum.double() / c
+        return ((self.sumsq.double() - self.sum.double() * m) / c).clamp_min(0.0).sqrt()
+
+
+def _region_stats_args(frames_shape, labels_shape, nregions):
+    """the shapes of a region_stats call, checked without a device; -> (n, h, w, labels_per_frame).  nregions None is left to the caller."""
+    if len(frames_shape) == 2:
+        frames_shape = (1,) + tuple(frames_shape)
+    if len(frames_shape) != 3:
+        raise ValueError("region_stats: frames (n, h, w) or (h, w) expected")
+    n, h, w = frames_shape
+    if h < 1 or w < 1 or h * w >= 1 << 31:
+        raise ValueError("region_stats: frames of at least 1x1 and fewer than 2^31 pixels expected")
+    if tuple(labels_shape) == (h, w):
+        per_frame = 0
+    elif tuple(labels_shape) == (n, h, w):
+        per_frame = 1
+    else:
+        raise ValueError("region_stats: labels of shape %s or %s expected, not %s" % ((h, w), (n, h, w), tuple(labels_shape)))
+    if nregions is not None and (int(nregions) != nregions or not 1 <= nregions <= MAX_REGIONS):
+        raise ValueError("region_stats: nregions must be in 1..2^24 (got %r)" % (nregions,))
+    return n, h, w, per_frame
+
+
+def region_stats(images, labels, nregions=None):
+    """Extension: statistics of a uint16 stack ``images[n][h][w]`` (or one ``(h, w)`` image) over the regions of the int32 label map
+    ``labels`` (``(h, w)`` shared by every image, or ``(n, h, w)``): a ``RegionStats`` of numpy arrays ``[n][nregions]``
+    (``rir_region_stats``).  Labels outside [0, nregions) are ignored; ``nregions=None`` takes labels.max() + 1 (at least 1).
+    ``ValueError`` on bad shapes or ``nregions``, ``RuntimeError`` on other dtypes and when the library fails."""
+    img = np.ascontiguousarray(images)
+    lab = np.ascontiguousarray(labels)
+    if img.dtype != np.uint16:
+        raise RuntimeError("region_stats: uint16 images expected, not %s" % img.dtype)
+    if lab.dtype != np.int32:
+        raise RuntimeError("region_stats: int32 labels expected, not %s" % lab.dtype)
+    n, h, w, per_frame = _region_stats_args(img.shape, lab.shape, nregions)
+    if nregions is None:
+        nregions = max(1, int(lab.max()) + 1 if lab.size else 1)
+        _region_stats_args(img.shape, lab.shape, nregions)
+    k = int(nregions)
+    out = RegionStats(*(np.empty((n, k), dt) for dt in (np.int32, np.int64, np.int64, np.int32, np.int32, np.int32, np.int32)))
+    if n and _sp.rir_region_stats(img.ctypes.data, lab.ctypes.data, w, h, n, per_frame, k, *(a.ctypes.data for a in out)) < 0:
+        raise RuntimeError("An error occured while calling 'region_stats': " + (last_error() or ""))
     return out
 
 

@@ -338,6 +338,52 @@ class IRMovie(object):
             else:
                 dst.copy_(temporal_median(stack, window, threshold, first=sel[0] - lo, count=len(sel), step=step))
 
+    _STATS_PIECE_BYTES = 64 << 20  # uint16 images read at once by region_stats
+
+    def region_stats(self, labels, selection=slice(None), nregions=None):
+        """Statistics of the images of ``selection`` (as ``to_tensor`` takes it) over the regions of one int32 label map ``labels`` (h, w),
+        numpy or CUDA, uploaded once - ``librir_amd.device.region_stats`` over the images ``movie[selection]`` gives (read-back filters
+        applied): a ``RegionStats`` of CUDA tensors ``[len(selection)][nregions]``.  ``nregions=None`` takes labels.max() + 1.  The
+        recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of images, so the device memory used does not grow with the selection."""
+        import torch
+
+        from ..device import _region_inputs, _region_stats_empty, _region_stats_into
+
+        h, w = self.image_size
+        if isinstance(labels, np.ndarray):
+            if labels.dtype != np.int32:
+                raise RuntimeError("region_stats: int32 labels expected, not %s" % labels.dtype)
+            labels = torch.from_numpy(np.ascontiguousarray(labels)).to(torch.device("cuda", torch.cuda.current_device()))
+        probe = torch.empty((0, h, w), dtype=torch.uint16, device=labels.device if labels.is_cuda else "cpu")
+        _, lab, _, _, _, _ = _region_inputs(probe, labels, nregions)
+        if nregions is None:
+            nregions = max(1, int(lab.max()) + 1)
+            _region_inputs(probe, labels, nregions)
+        positions = self._stats_positions(selection)
+        out = _region_stats_empty(len(positions), int(nregions), lab.device)
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=lab.device)
+        for k0 in range(0, len(positions), per_piece):
+            sel = positions[k0:k0 + per_piece]
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            _region_stats_into(fr, lab, 0, int(nregions), type(out)(*(t[k0:k0 + len(sel)] for t in out)))
+        return out
+
+    def _stats_positions(self, selection):
+        """the positions of an int or a slice with a positive step, as to_tensor takes them"""
+        total = self.images
+        if isinstance(selection, (int, np.integer)):
+            pos = int(selection) + (total if selection < 0 else 0)
+            if not 0 <= pos < total:
+                raise IndexError("image %d out of range (%d images)" % (int(selection), total))
+            return range(pos, pos + 1)
+        if isinstance(selection, slice):
+            if selection.step is not None and selection.step <= 0:
+                raise ValueError("region_stats: a slice with a positive step expected")
+            return self._positions(selection)[0]
+        raise TypeError("region_stats: an int or a slice expected")
+
     def load_secs(self, time, calibration=None):
         """The image whose time stamp is closest to ``time`` (seconds)."""
         if self.times is None:
