@@ -1719,30 +1719,22 @@ namespace rir
 		const int x = xy[2 * i], y = xy[2 * i + 1];
 		uint32_t v[9];
 		int c = 0;
-		const bool small = (w < 3 || rows < 3);
 		int dx_st = x - 1, dy_st = y - 1;
-		if (!small)
-		{
-			if (x == 0)
-				dx_st = 0;
-			else if (x == w - 1)
-				dx_st = w - 3;
-			if (y == 0)
-				dy_st = 0;
-			else if (y == rows - 1)
-				dy_st = rows - 3;
-		}
+		if (x == 0)
+			dx_st = 0;
+		else if (x == w - 1)
+			dx_st = w - 3;
+		if (y == 0)
+			dy_st = 0;
+		else if (y == rows - 1)
+			dy_st = rows - 3;
 #pragma unroll
 		for (int a = 0; a < 3; ++a)
 #pragma unroll
 			for (int b = 0; b < 3; ++b)
 			{
 				const int xx = dx_st + a, yy = dy_st + b;
-				bool ok;
-				if (small)
-					ok = xx >= 0 && yy >= 0 && xx < w && yy < rows;
-				else
-					ok = bitmap[xx + yy * w] == 0;
+				const bool ok = bitmap[xx + yy * w] == 0;
 				const uint32_t val = ok ? f[xx + (int64_t)yy * w] : 0u;
 #pragma unroll
 				for (int k = 0; k < 9; ++k)
@@ -1759,10 +1751,51 @@ namespace rir
 		f[x + (int64_t)y * w] = rank_select9(v, c);
 	}
 
+	// Frames under 3 columns or 3 rows (IRFileLoader.cpp:735-753): no bitmap - every in-bounds neighbour counts, flagged or not - so each
+	// repair reads the repairs before it in the list.  One lane per frame walks the list in its order (a frame this small has at most two
+	// rows or two columns: at most 2 * max(w, rows) pixels to repair).
+	__global__ __launch_bounds__(64) void remove_bad_pixels_small_kernel(uint16_t *__restrict__ img, int w, int h, int rows, int nframes,
+																		 const int *__restrict__ xy, int nbad)
+	{
+		const int n = blockIdx.x * blockDim.x + threadIdx.x;
+		if (n >= nframes)
+			return;
+		uint16_t *f = img + (int64_t)n * w * h;
+		for (int i = 0; i < nbad; ++i)
+		{
+			const int x = xy[2 * i], y = xy[2 * i + 1];
+			uint32_t v[9];
+			int c = 0;
+#pragma unroll
+			for (int a = -1; a <= 1; ++a)
+#pragma unroll
+				for (int b = -1; b <= 1; ++b)
+				{
+					const int xx = x + a, yy = y + b;
+					const bool ok = xx >= 0 && yy >= 0 && xx < w && yy < rows;
+					const uint32_t val = ok ? f[xx + (int64_t)yy * w] : 0u;
+#pragma unroll
+					for (int k = 0; k < 9; ++k)
+						if (ok && k == c)
+							v[k] = val;
+					c += ok;
+				}
+			if (c == 0)
+				continue; // (a listed pixel below `rows`: nothing in bounds)
+#pragma unroll
+			for (int k = 0; k < 9; ++k)
+				if (k >= c)
+					v[k] = 0xffffffffu;
+			f[x + (int64_t)y * w] = rank_select9(v, c);
+		}
+	}
+
 	hipError_t launch_remove_bad_pixels(uint16_t *img, int w, int h, int rows, int nframes, const int *d_xy, int nbad, const uint8_t *d_bitmap,
 										hipStream_t st)
 	{
-		if (nbad > 0)
+		if (nbad > 0 && (w < 3 || rows < 3))
+			hipLaunchKernelGGL(remove_bad_pixels_small_kernel, dim3((nframes + 63) / 64), dim3(64), 0, st, img, w, h, rows, nframes, d_xy, nbad);
+		else if (nbad > 0)
 			hipLaunchKernelGGL(remove_bad_pixels_kernel, dim3((nbad + 63) / 64, nframes), dim3(64), 0, st, img, w, h, rows, d_xy, nbad, d_bitmap);
 		return hipGetLastError();
 	}

@@ -8,6 +8,7 @@
 //     path, asynchronous on the caller's HIP stream) - what pipelines and bench.py use.
 // There is no CPU fallback: without a HIP device every entry point logs and returns its error code.
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <map>
 
@@ -235,6 +236,11 @@ namespace
 		int count() const { return (int)(xy.size() / 2); }
 	};
 
+	// double -> int as the reference's casts compile on x86-64 (cvttsd2si): truncation toward zero, and INT_MIN for NaN and for what is
+	// out of range.  The squares of deviations beyond 46340 wrap in 32 bits (Filters.h:151-153) and can make the sum negative, the
+	// deviation NaN: the casts below then meet NaN, which a plain C++ cast leaves undefined.
+	inline int32_t cvtt_i32(double v) { return (v > -2147483649.0 && v < 2147483648.0) ? (int32_t)v : INT32_MIN; }
+
 	// Detector on a device-resident frame.  rows = number of rows taken into account.
 	bool detect_bad_pixels(const uint16_t *d_img, int w, int rows, double std_factor, BadPixelsObject &bp, hipStream_t st)
 	{
@@ -256,9 +262,9 @@ namespace
 		double sum = (double)h_stats[1];
 		sum /= (double)(int)npx;
 		sum = std::sqrt(sum);
-		const uint16_t thr = (uint16_t)(int32_t)(sum * std_factor);
+		const uint16_t thr = (uint16_t)cvtt_i32(sum * std_factor);
 		bp.floor_detect = ((uint16_t)median > thr) ? (int)(uint16_t)((uint16_t)median - thr) : 0;
-		bp.floor_correct = median - (int)(sum * 2);
+		bp.floor_correct = (int)((uint32_t)median - (uint32_t)cvtt_i32(sum * 2)); // (int arithmetic: wraps like the reference's, NaN -> INT_MIN + median)
 
 		if (!hip_ok(launch_bad_pixels_detect(d_img, w, rows, std_factor, bp.floor_detect, flags.as<uint8_t>(), st), "bad_pixels_detect"))
 			return false;

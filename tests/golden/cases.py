@@ -201,3 +201,66 @@ def resample_cases():
         ts = np.sort(rng.integers(-10, 90, m) * 0.25 + (0.0 if k % 2 else rng.random(m) * 0.2))
         cases.append(("random_%d" % k, xs, ys, ts, int(rng.choice([0, 2, 4, 6])), float(np.round(rng.normal(), 3))))
     return cases
+
+
+# ---- full 16-bit range (frame-buffer filters) ----------------------------------------------------------------------------------------
+# What real frames hold and the 14-bit grids above never reach: integration-time bits above bit 13 (s2_uniform_dl_ti), saturated
+# pixels at the top of the range, deviations from the median beyond 46340 (the reference's 32-bit squares wrap; a negative sum makes the
+# deviation NaN and flags about half the frame), clamp floors above 32767.  The first seven kinds plus three flat frames.
+FULL_RANGE_KINDS = ["ti_bits", "saturated_blob", "checkerboard", "uniform", "high_dead", "flat_40000", "wide_normal", "flat_65535", "flat_40001"]
+FULL_RANGE_SHAPES = [(67, 83), (512, 640)]
+
+
+def _full_range_frame(kind, h, w, rng, later):
+    yy, xx = np.mgrid[0:h, 0:w]
+    if kind == "ti_bits":  # dl in the low 13 bits, ti (0..7, a band of columns each) above: values up to 61 000
+        dl = 1000 + (xx * 7 + yy * 3) % 2500 + rng.integers(0, 40, (h, w))
+        return (dl | ((xx * 8 // w) << 13)).astype(np.uint16)
+    if kind == "saturated_blob":  # cold scene (median ~128), a saturated ellipse: |v - median| > 46340, the NaN deviation
+        img = np.clip(128 + rng.normal(0, 12, (h, w)), 0, None).astype(np.uint16)
+        cy, cx = h * (0.45 + 0.05 * later), w * 0.4
+        img[((yy - cy) / (0.3 * h)) ** 2 + ((xx - cx) / (0.3 * w)) ** 2 < 1] = 65535
+        return img
+    if kind == "checkerboard":  # 0 / 65534: every square wraps
+        img = np.where((xx + yy) % 2 == 0, 0, 65534).astype(np.uint16)
+        k = max(1, h * w // 300)
+        img[rng.integers(0, h, k), rng.integers(0, w, k)] = rng.integers(0, 65535, k).astype(np.uint16)
+        return img
+    if kind == "uniform":
+        return rng.integers(0, 65536, (h, w)).astype(np.uint16)
+    if kind == "high_dead":  # a scene near 45 000 with dead (0) and hot (65535) pixels: no square wraps, clamp floor above 32767
+        img = (45000 + 300 * np.sin(xx / 7.0) + rng.normal(0, 150, (h, w))).astype(np.uint16)
+        k = max(2, h * w // 500)
+        img[rng.integers(0, h, k), rng.integers(0, w, k)] = 0
+        img[rng.integers(0, h, k), rng.integers(0, w, k)] = 65535
+        if later:  # a cooler band and scattered pixels below the clamp floor, odd and even columns alike
+            img[h // 3:h // 3 + max(2, h // 8)] = rng.integers(30000, 44000, (max(2, h // 8), w)).astype(np.uint16)
+            m = rng.random((h, w)) < 0.05
+            img[m] = rng.integers(0, 44000, int(m.sum())).astype(np.uint16)
+        return img
+    if kind in ("flat_40000", "flat_40001", "flat_65535"):
+        v = int(kind.split("_")[1])
+        if not later:
+            return np.full((h, w), v, np.uint16)
+        return np.clip(v + rng.normal(0, 2000, (h, w)), 0, 65535).astype(np.uint16)  # values on both sides of the clamp floor
+    if kind == "wide_normal":
+        return np.clip(rng.normal(24000, 14000, (h, w)), 0, 65535).astype(np.uint16)
+    raise ValueError(kind)
+
+
+def full_range_frames(kind, h, w, n_later=3):
+    """-> (first image, later frames (n_later, h, w)), uint16, seeded by kind and shape"""
+    rng = np.random.default_rng([FULL_RANGE_KINDS.index(kind), h, w])
+    first = _full_range_frame(kind, h, w, rng, 0)
+    later = np.stack([_full_range_frame(kind, h, w, rng, i + 1) for i in range(n_later)])
+    return first, later
+
+
+def without_top_value(img):
+    """The reference's find_median_pixel counts into 65 535 bins and writes past them for a pixel of 65535 (Filters.cpp:59, :81): inputs
+    it is asked about carry 65534 there instead."""
+    return np.minimum(img, 65534).astype(np.uint16)
+
+
+# quantiles of the full-range grid: MEDIAN_PERCENTS, and one answer in each quarter of the value range for the spread kinds
+FULL_RANGE_PERCENTS = MEDIAN_PERCENTS + [0.1, 0.3, 0.45, 0.6, 0.8, 0.97]

@@ -5,8 +5,9 @@ import hashlib
 
 import numpy as np
 import pytest
-from cases import (BADPIX_SHAPES, GAUSS_SHAPES, GAUSS_SIGMAS, MEDIAN_PERCENTS, TRANSLATE_DTYPES, TRANSLATE_OFFSETS, TRANSLATE_SHAPES,
-                   TRANSLATE_STRATEGIES, badpix_frames, gauss_input, median_input, translate_input)
+from cases import (BADPIX_SHAPES, FULL_RANGE_KINDS, FULL_RANGE_PERCENTS, FULL_RANGE_SHAPES, GAUSS_SHAPES, GAUSS_SIGMAS, MEDIAN_PERCENTS,
+                   TRANSLATE_DTYPES, TRANSLATE_OFFSETS, TRANSLATE_SHAPES, TRANSLATE_STRATEGIES, badpix_frames, full_range_frames, gauss_input,
+                   median_input, translate_input, without_top_value)
 
 
 def sha(a):
@@ -186,3 +187,85 @@ def test_byte_plane_split_merge_known_answer(oracle):
     Y, U, V = oracle.split_planes(img, linesize=4, it=it)
     back, it2 = oracle.merge_planes(Y, U, V, 3, with_it=True)
     assert np.array_equal(back, img) and np.array_equal(it2, it)
+
+
+# ---- the full 16-bit range: oracle vs the reference on FULL_RANGE_KINDS (cases.py) ----------------------------------------------------
+
+
+@pytest.mark.parametrize("shape", FULL_RANGE_SHAPES)
+@pytest.mark.parametrize("kind", FULL_RANGE_KINDS)
+def test_oracle_vs_ref_bad_pixels_full_range(oracle, ref_answers, kind, shape):
+    h, w = shape
+    first, later = full_range_frames(kind, h, w)
+    key = "full_range %s %dx%d " % (kind, h, w)
+    xy = oracle.bad_pixels_detect(first)
+    ref_answers.check(key + "bad_pixels_detect", xy, lambda ref: ref.bad_pixels_detect(first))
+    _, fc = oracle.bad_pixels_stats(first)
+    ref_answers.check(key + "bad_pixels_correct", [oracle.bad_pixels_correct(f, xy, fc) for f in later],
+                      lambda ref: [ref.bad_pixels_correct(first, f) for f in later])
+    ref_answers.check(key + "bad_pixels_floor", np.int64(max(fc, 0)), lambda ref: np.int64(ref.bad_pixels_floor(first)))
+
+
+@pytest.mark.parametrize("shape", FULL_RANGE_SHAPES)
+@pytest.mark.parametrize("kind", FULL_RANGE_KINDS)
+def test_oracle_vs_ref_find_median_pixel_full_range(oracle, ref_answers, kind, shape):
+    h, w = shape
+    first, later = full_range_frames(kind, h, w)
+    img = without_top_value(later[0] if kind.startswith("flat") else first)  # (the flat kinds: their noisy later frames)
+    mask = (np.random.default_rng(h + w).random((h, w)) < 0.4).astype(np.uint8)
+    key = "full_range %s %dx%d find_median_pixel" % (kind, h, w)
+    ref_answers.check(key, np.array([oracle.find_median_pixel(img, p) for p in FULL_RANGE_PERCENTS], np.int64),
+                      lambda ref: np.array([ref.find_median_pixel(img, p) for p in FULL_RANGE_PERCENTS], np.int64))
+    ref_answers.check(key + " mask", np.array([oracle.find_median_pixel(img, p, mask) for p in FULL_RANGE_PERCENTS], np.int64),
+                      lambda ref: np.array([ref.find_median_pixel(img, p, mask) for p in FULL_RANGE_PERCENTS], np.int64))
+
+
+@pytest.mark.parametrize("shape", FULL_RANGE_SHAPES)
+@pytest.mark.parametrize("kind", FULL_RANGE_KINDS)
+def test_oracle_vs_ref_median_translate_gaussian_full_range(oracle, ref_answers, kind, shape):
+    h, w = shape
+    first, later = full_range_frames(kind, h, w)
+    key = "full_range %s %dx%d " % (kind, h, w)
+    ref_answers.check(key + "median_filter", [oracle.median_filter(first), oracle.median_filter(later[0])],
+                      lambda ref: [ref.median_filter(first), ref.median_filter(later[0])])
+    f32 = later[0].astype(np.float32)
+    for strat in TRANSLATE_STRATEGIES:
+        for (dx, dy) in [(0.5, 0.25), (-1.25, 2.5), (3, -2)]:
+            for img in (later[0], f32):
+                ref_answers.check(key + "translate %s %s %r %r" % (img.dtype.str, strat or "none", dx, dy), oracle.translate(img, dx, dy, strat, background=65535),
+                                  lambda ref: ref.translate(img, dx, dy, strat, background=65535))
+    for s in [0.5, 0.75, 1.49, 2.0]:
+        ref_answers.check(key + "gaussian_filter %r" % s, oracle.gaussian_filter(f32, s), lambda ref: ref.gaussian_filter(f32, s))
+
+
+def test_full_range_grid_reaches_the_paths_it_is_for(oracle):
+    """The grid holds what it is there for: the NaN deviation (floor_correct near INT_MIN, about half of the frame flagged), a clamp floor
+    above 32767, a detector threshold that wraps in 16 bits, quantile answers in every quarter of the value range, 65534 as an answer and
+    a target only 65535 reaches (answer 0)."""
+    first, _ = full_range_frames("saturated_blob", 67, 83)
+    fd, fc = oracle.bad_pixels_stats(first)
+    assert fc < -(1 << 30) and fd == int(np.sort(first, axis=None)[first.size // 2])
+    assert len(oracle.bad_pixels_detect(first)) > first.size // 3
+    assert oracle.bad_pixels_stats(full_range_frames("high_dead", 67, 83)[0])[1] > 32767
+    assert oracle.bad_pixels_stats(full_range_frames("flat_65535", 512, 640)[0]) == (65535, 65535)
+    first, _ = full_range_frames("wide_normal", 67, 83)
+    fd, _ = oracle.bad_pixels_stats(first)
+    assert fd > np.sort(first, axis=None)[first.size // 2] - 5 * first.astype(np.float64).std()  # (uint16) of the threshold wrapped
+    uni = full_range_frames("uniform", 512, 640)[0]
+    quarters = {oracle.find_median_pixel(uni, p) >> 14 for p in FULL_RANGE_PERCENTS}
+    assert quarters == {0, 1, 2, 3}
+    chk = full_range_frames("checkerboard", 67, 83)[0]
+    assert oracle.find_median_pixel(chk, 0.99) == 65534
+    assert oracle.find_median_pixel(full_range_frames("saturated_blob", 67, 83)[0], 0.99) == 0
+
+
+def test_remove_bad_pixels_small_frame_repairs_in_list_order(oracle):
+    """IRFileLoader::removeBadPixels on a frame under 3 rows or columns (IRFileLoader.cpp:735-753): no bitmap, and each repair reads the
+    ones before it in the list.  Worked by hand on two rows; repairing both pixels from the unrepaired frame would give 18 at (2, 0)."""
+    img = np.array([[10, 900, 800, 10], [12, 14, 16, 18]], np.uint16)
+    # (1, 0): upper median of 10 12 900 14 800 16 -> 16;  (2, 0): of 16 14 800 16 10 18 -> 16  (from 900 instead of 16: 18)
+    out = oracle.remove_bad_pixels(img, [(1, 0), (2, 0)])
+    assert out.tolist() == [[10, 16, 16, 10], [12, 14, 16, 18]]
+    # one column: (0, 1): median of 0 1000 500 -> 500;  (0, 2): of 500 500 900 -> 500  (from 1000 instead of 500: 900)
+    col = np.array([[0], [1000], [500], [900], [9]], np.uint16)
+    assert oracle.remove_bad_pixels(col, [(0, 1), (0, 2)]).ravel().tolist() == [0, 500, 500, 900, 9]
