@@ -868,16 +868,22 @@ namespace rir
 		return off;
 	}
 
+	// DIR > 0: the wave walks its frames forwards and fills its region (and its extent) upwards from word 0.  DIR < 0: it walks them
+	// backwards and fills both DOWNWARDS from the top, so that what it leaves is still its records in frame order, contiguous, ending
+	// at the top: the indices of a record are taken relative to the record (pos = 0) and the wave-uniform first word of the record,
+	// top - words so far - words of this record, is added to them.
+	template <int DIR>
 	__device__ __forceinline__ uint64_t emit_staged(const Px8 &r, uint32_t mode, uint32_t base, Staging &sg, uint32_t pos, const LaneConsts &lc,
 													const TransposeConsts &tc, uint32_t *words)
 	{
 		const uint32_t any = (r.d[0] | r.d[1]) | (r.d[2] | r.d[3]);
 		RecordWords rw;
 		uint64_t h;
+		const uint32_t rel = DIR > 0 ? pos : 0u;
 		if (__ballot((any & 0xfff0fff0u) != 0) == 0)
-			h = emit_words_narrow(r, mode, base, rw, pos, lc, tc, words);
+			h = emit_words_narrow(r, mode, base, rw, rel, lc, tc, words);
 		else
-			h = emit_words_wide(r, mode, base, rw, pos, lc, tc, words);
+			h = emit_words_wide(r, mode, base, rw, rel, lc, tc, words);
 		if (!sg.spilling && pos + *words > sg.cap)
 		{
 			sg.spilling = true, sg.lds_used = pos;
@@ -895,13 +901,15 @@ namespace rir
 		}
 		if (!sg.spilling)
 		{ // LDS operations only inside this (wave-uniform) branch: the vector-memory stream below stays unconditional
+			uint64_t *rec = DIR > 0 ? sg.lds : sg.lds + (sg.cap - pos - *words); // (pos + words <= cap here)
 			if (rw.ia != RIR_NONE)
-				sg.lds[rw.ia] = ((uint64_t)rw.va.y << 32) | rw.va.x;
+				rec[rw.ia] = ((uint64_t)rw.va.y << 32) | rw.va.x;
 			if (rw.ib != RIR_NONE)
-				sg.lds[rw.ib] = ((uint64_t)rw.vb.y << 32) | rw.vb.x;
+				rec[rw.ib] = ((uint64_t)rw.vb.y << 32) | rw.vb.x;
 		}
-		// two stores per record whatever happens (counted waits, see RecordStores): out of range unless the wave spills
-		const uint32_t add = sg.spilling ? 0u - sg.lds_used * 8u : RIR_OOB;
+		// two stores per record whatever happens (counted waits, see RecordStores): out of range unless the wave spills.  A backward
+		// wave's extent ends with its first spilled record: need - words spilled so far - words of this record is where this one starts
+		const uint32_t add = !sg.spilling ? RIR_OOB : DIR > 0 ? 0u - sg.lds_used * 8u : (sg.need - (pos - sg.lds_used) - *words) * 8u;
 		const uint32_t oa = rw.ia != RIR_NONE ? rw.ia * 8u + add : RIR_OOB;
 		const uint32_t ob = rw.ib != RIR_NONE ? rw.ib * 8u + add : RIR_OOB;
 		__builtin_amdgcn_raw_buffer_store_b64(rw.va, sg.spill, oa, 0, SPARSE_STORE_AUX);
@@ -912,30 +920,36 @@ namespace rir
 	// One wave packs the records of frames [rec0, rec0 + nrec) of a chunk for one tile.  `first` points at the tile in the
 	// first frame the wave LOADS: the key frame when has_key, else the frame before its first record.  hdr_first: table
 	// entry of that loaded frame (headers of records go to hdr_first[1..] / hdr_first[0] for the key frame).
+	// DIR > 0: the wave walks its frames forwards.  DIR < 0: backwards - it loads its LAST frame first and its records come out
+	// last to first, the key record at the very end.  A record is frame f minus frame f - 1 either way, so every header and payload
+	// word is the same; only the order in which the wave produces them differs (and emit_staged<DIR> files them in frame order).
+	// The ring is indexed by the ORDER OF LOADING k (slot k % 4): step k packs what was loaded k-th against what was loaded (k-1)-th.
 	// Returns the number of payload words produced.
-	template <bool FAST>
+	template <bool FAST, int DIR>
 	__device__ __forceinline__ uint32_t encode_run(const uint16_t *__restrict__ frames, int64_t npx, int nload, int64_t frame_first, bool has_key,
 												   int tile, int lane, uint64_t *__restrict__ hdr_first, Staging &sg)
 	{
+		constexpr bool BACK = DIR < 0;
 		const int64_t p0 = (int64_t)tile * RIRB1_TILE_PX + lane * 8;
 		const TransposeConsts tc = make_transpose_consts(lane);
 		const LaneConsts lc = make_lane_consts(lane);
 		const uint32_t lane_off = (uint32_t)lane * 16u;
-		const uint16_t *next_ptr = frames + frame_first * npx + (int64_t)tile * RIRB1_TILE_PX;
+		const uint16_t *next_ptr = frames + (frame_first + (BACK ? nload - 1 : 0)) * npx + (int64_t)tile * RIRB1_TILE_PX;
 		int next_f = 0;
-		// frames are loaded strictly in order; a request past the wave's last frame is an out-of-range offset: the
-		// instruction is issued (the waits stay counted) and touches no memory
-		auto load = [&](int f, v4u32 &dst) {
+		// frames are loaded strictly in order (of time, or against it); a request past the wave's last frame is an out-of-range
+		// offset: the instruction is issued (the waits stay counted) and touches no memory
+		auto load = [&](int k, v4u32 &dst) {
 			if (FAST)
 			{
 				const Px8 p = buf_load8(next_ptr, next_f < nload ? lane_off : RIR_OOB);
 				dst.x = p.d[0], dst.y = p.d[1], dst.z = p.d[2], dst.w = p.d[3];
-				next_ptr += npx;
+				next_ptr = BACK ? next_ptr - npx : next_ptr + npx;
 				next_f += 1;
 			}
 			else
 			{
-				const Px8 p = load8(frames, frame_first + min(f, nload - 1), npx, p0, false);
+				const int i = min(k, nload - 1);
+				const Px8 p = load8(frames, frame_first + (BACK ? nload - 1 - i : i), npx, p0, false);
 				dst.x = p.d[0], dst.y = p.d[1], dst.z = p.d[2], dst.w = p.d[3];
 			}
 		};
@@ -946,14 +960,8 @@ namespace rir
 		};
 		uint32_t pos = 0;
 		uint64_t hdr_reg = 0;
-		v4u32 s0, s1, s2, s3;
-		load(0, s0);
-		load(1, s1);
-		load(2, s2);
-		load(3, s3);
-		if (has_key)
-		{ // key frame: RAW, or LEFT when its payload is strictly smaller
-			const Px8 cur = as_px8(s0);
+		// key frame: RAW, or LEFT when its payload is strictly smaller
+		auto key_record = [&](const Px8 &cur) {
 			const uint32_t base_raw = tile_base(cur, false);
 			const uint32_t b2 = base_raw | (base_raw << 16);
 			Px8 r_raw;
@@ -974,26 +982,35 @@ namespace rir
 				r_sel.d[k] = use_left ? r_left.d[k] : r_raw.d[k];
 			uint32_t words;
 			const uint32_t key_mode = use_left ? RIRB1_MODE_LEFT : RIRB1_MODE_RAW;
-			const uint64_t h = emit_staged(r_sel, key_mode, use_left ? base_left : base_raw, sg, pos, lc, tc, &words);
+			const uint64_t h = emit_staged<DIR>(r_sel, key_mode, use_left ? base_left : base_raw, sg, pos, lc, tc, &words);
 			if (lane == 0)
 				hdr_first[0] = h;
 			pos += words;
-		}
-#define RIR_ENC2_STEP(F, CUR, PREV)                                                            \
+		};
+		v4u32 s0, s1, s2, s3;
+		load(0, s0);
+		load(1, s1);
+		load(2, s2);
+		load(3, s3);
+		if (!BACK && has_key)
+			key_record(as_px8(s0));
+		// step K: NEW was loaded K-th, OLD (K-1)-th; forwards NEW is the record's frame and OLD the one before it, backwards OLD is
+		// the record's frame and NEW the one before it.  OLD's slot is free afterwards: the (K+3)-th load goes there.
+#define RIR_ENC2_STEP(K, NEW, OLD)                                                            \
 	{                                                                                          \
-		const int f = (F);                                                                     \
+		const int k_ = (K);                                                                    \
 		Px8 d;                                                                                 \
 		{                                                                                      \
-			const Px8 c_ = as_px8(CUR), p_ = as_px8(PREV);                                     \
+			const Px8 c_ = as_px8(BACK ? OLD : NEW), p_ = as_px8(BACK ? NEW : OLD);            \
 			_Pragma("unroll") for (int k = 0; k < 4; ++k) d.d[k] = pk_sub16(c_.d[k], p_.d[k]); \
 		}                                                                                      \
-		load(f + 3, PREV);                                                                     \
+		load(k_ + 3, OLD);                                                                     \
 		const uint32_t base = tile_base(d, true);                                              \
 		const uint32_t b2 = base | (base << 16);                                               \
 		_Pragma("unroll") for (int k = 0; k < 4; ++k) d.d[k] = pk_sub16(d.d[k], b2);          \
 		uint32_t words;                                                                        \
-		const uint64_t h = emit_staged(d, RIRB1_MODE_TEMPORAL, base, sg, pos, lc, tc, &words); \
-		if (lane == ((f - 1) & 63))                                                            \
+		const uint64_t h = emit_staged<DIR>(d, RIRB1_MODE_TEMPORAL, base, sg, pos, lc, tc, &words); \
+		if (lane == ((k_ - 1) & 63))                                                           \
 			hdr_reg = h;                                                                       \
 		pos += words;                                                                          \
 	}
@@ -1019,11 +1036,18 @@ namespace rir
 				}
 				fb = gend;
 			}
+			// lane l holds the header of step g0 + l: the record of frame g0 + l forwards, of frame nload - (g0 + l) backwards
 			if (g0 + lane < gend)
-				hdr_first[g0 + lane] = hdr_reg;
+				hdr_first[BACK ? nload - (g0 + lane) : g0 + lane] = hdr_reg;
 			hdr_reg = 0;
 		}
 #undef RIR_ENC2_STEP
+		if (BACK && has_key)
+		{ // the key frame was loaded last, (nload - 1)-th: it is in slot (nload - 1) % 4
+			const int ks = (nload - 1) & 3;
+			const v4u32 kv = ks == 0 ? s0 : ks == 1 ? s1 : ks == 2 ? s2 : s3;
+			key_record(as_px8(kv));
+		}
 		return pos;
 	}
 
@@ -1101,6 +1125,21 @@ namespace rir
 		return b < 1 ? (nf < 1 ? nf : 1) : (b > nf ? nf : b);
 	}
 
+	// The packed encoder's waves walk in mirrored pairs: an even wave walks its share backwards, the odd wave after it forwards, so both
+	// start on the frame where their shares meet and ask for it at the same moment, from the same CU - the frame crosses the fabric once.
+	__device__ __host__ __forceinline__ bool enc_walks_back(int w) { return (w & 1) == 0; }
+	// Its cuts: enc_split's, but with four waves the third cut gives waves 1 and 2 the same number of records.  They meet at the middle
+	// boundary from both sides at the END of their walks, and reach it in step only when they have equally far to go.
+	__device__ __host__ __forceinline__ int enc_split_mirrored(int w, int waves, int nf)
+	{
+		if (waves == 4 && w == 3)
+		{
+			const int c = 2 * enc_split(2, waves, nf) - enc_split(1, waves, nf);
+			return c > nf ? nf : c;
+		}
+		return enc_split(w, waves, nf);
+	}
+
 	// control block: 8 ticket heads on lines of their own, the error word, then P / group / gran
 	__device__ __host__ __forceinline__ int64_t enc_ctrl_words64(int nchunks, int ntiles)
 	{
@@ -1161,9 +1200,9 @@ namespace rir
 		{
 			const bool fast = ((npx & 7) == 0) && ((int64_t)(tile + 1) * RIRB1_TILE_PX <= npx) && ((((uintptr_t)frames) & 15) == 0);
 			if (fast)
-				pos = encode_run<true>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
+				pos = encode_run<true, 1>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
 			else
-				pos = encode_run<false>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
+				pos = encode_run<false, 1>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
 		}
 		for (int f = nf + (int)threadIdx.x; f < gop; f += WAVES * 64)
 			my_hdr[f] = 0; // short last chunk: the unused table entries are defined
@@ -1316,7 +1355,7 @@ namespace rir
 		const int nf = min(gop, nframes - f_begin);
 		uint64_t *my_hdr = hdr_table + seg * gop;
 
-		const int rec0 = enc_split(w, WAVES, nf), rec1 = enc_split(w + 1, WAVES, nf);
+		const int rec0 = enc_split_mirrored(w, WAVES, nf), rec1 = enc_split_mirrored(w + 1, WAVES, nf);
 		const int nrec = rec1 - rec0;
 		const bool has_key = w == 0;
 		const int first_load = has_key ? 0 : rec0 - 1;
@@ -1332,7 +1371,12 @@ namespace rir
 		sg.extent = ~0ull;
 		uint32_t pos = 0;
 		if (nrec > 0)
-			pos = encode_run<FAST>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
+		{
+			if (enc_walks_back(w))
+				pos = encode_run<FAST, -1>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
+			else
+				pos = encode_run<FAST, 1>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
+		}
 		for (int f = nf + (int)threadIdx.x; f < gop; f += WAVES * 64)
 			my_hdr[f] = 0; // short last chunk: the unused table entries are defined
 		if (lane == 0)
@@ -1386,24 +1430,31 @@ namespace rir
 			uint64_t *dst = stream + at;
 			for (int i = 0; i < WAVES; ++i)
 			{
-				const uint64_t *src = enc_lds + (size_t)i * cap;
-				const uint32_t n_all = sh_u32[i], n_lds = sh_u32[WAVES + i];
+				// A forward wave's words: its region from word 0, then (the later records) its extent from word 0.  A backward wave's: its
+				// extent (the EARLIER records, which it packed last) up to the extent's end, then its region up to the region's end.
+				const bool back = enc_walks_back(i);
+				const uint32_t n_all = sh_u32[i], n_lds = sh_u32[WAVES + i], n_ext = n_all - n_lds;
+				const uint64_t *src = enc_lds + (size_t)i * cap + (back ? (uint32_t)cap - n_lds : 0u);
+				uint64_t *dst_lds = dst + (back ? n_ext : 0u);
 				uint32_t j = (uint32_t)lane;
 				for (; j + 192 < n_lds; j += 256)
 				{
 					const uint64_t v0 = src[j], v1 = src[j + 64], v2 = src[j + 128], v3 = src[j + 192];
-					dst[j] = v0, dst[j + 64] = v1, dst[j + 128] = v2, dst[j + 192] = v3;
+					dst_lds[j] = v0, dst_lds[j + 64] = v1, dst_lds[j + 128] = v2, dst_lds[j + 192] = v3;
 				}
 				for (; j < n_lds; j += 64)
-					dst[j] = src[j];
-				if (n_all > n_lds)
+					dst_lds[j] = src[j];
+				if (n_ext > 0)
 				{ // what wave i spilled comes back from its extent (sc1 loads: from L2, where its stores went)
-					const int r0 = enc_split(i, WAVES, nf), r1 = enc_split(i + 1, WAVES, nf);
-					const __amdgpu_buffer_rsrc_t sp = make_rsrc(arena + sh_u64[1 + i], (uint32_t)(r1 - r0) * RIRB1_REC_MAX_WORDS * 8u);
-					for (uint32_t q = (uint32_t)lane; q < n_all - n_lds; q += 64)
+					const int r0 = enc_split_mirrored(i, WAVES, nf), r1 = enc_split_mirrored(i + 1, WAVES, nf);
+					const uint32_t need = (uint32_t)(r1 - r0) * RIRB1_REC_MAX_WORDS;
+					const __amdgpu_buffer_rsrc_t sp = make_rsrc(arena + sh_u64[1 + i], need * 8u);
+					const uint32_t first = back ? need - n_ext : 0u;
+					uint64_t *dst_ext = dst + (back ? 0u : n_lds);
+					for (uint32_t q = (uint32_t)lane; q < n_ext; q += 64)
 					{
-						const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(sp, q * 8u, 0, 16 /* sc1 */);
-						dst[n_lds + q] = ((uint64_t)v.y << 32) | v.x;
+						const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(sp, (first + q) * 8u, 0, 16 /* sc1 */);
+						dst_ext[q] = ((uint64_t)v.y << 32) | v.x;
 					}
 				}
 				dst += n_all;
