@@ -241,6 +241,7 @@ namespace rir
 	typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
 #define RIR_BUF_FLAGS 0x00020000 /* raw buffer, 32-bit data format (gfx942/gfx950 descriptor word 3) */
 #define RIR_OOB 0x40000000u		 /* beyond any num_records used here */
+#define RIR_NONE 0xffffffffu	 /* "no plane" as a word index */
 
 	__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *base, uint32_t bytes)
 	{
@@ -333,7 +334,7 @@ namespace rir
 		uint32_t n_hsh;	   // bit position of the slot's width inside its header dword
 		bool n_hhi;		   // the slot's width lives in the high header dword
 		bool n_first;	   // plane 0 of its slot
-		// narrow tier, packed-nibble order (see emit_record_narrow): nibble n of the packed dword holds slot
+		// narrow tier, packed-nibble order (see emit_words_narrow): nibble n of the packed dword holds slot
 		// NIB_SLOT[n] = {0,4,2,6,1,5,3,7}; lane (lane & 31) = 4n + b holds plane b of that slot
 		uint32_t p_before; // mask of the lanes whose plane words precede this lane's word in the stream
 		uint32_t p_hshw;   // header lane 16q+k: left shift that brings its bit of the width word W to bit 31
@@ -413,14 +414,17 @@ namespace rir
 	// bit length of a value < 2^31 without a zero test: bitlen(2f+1) = bitlen(f)+1
 	__device__ __forceinline__ uint32_t bitlen_nz(uint32_t f) { return 31u - (uint32_t)__builtin_clz((f << 1) | 1u); }
 
-	// The two 8-byte stores of a record (offsets are out of range for lanes without a plane).  They are issued
-	// by the caller, outside the wave-uniform tier branch: with every vector-memory operation of the frame loop
-	// unconditional the compiler keeps exact s_waitcnt vmcnt(N) counts (a store inside the branch made it fall
-	// back to vmcnt(0) on half of the steps).
-	struct RecordStores
+	// ---- the plane words of a record -----------------------------------------------------------------
+	// The two plane words of a lane and where they go.  A position is (index of the word in the wave's payload) * SCALE, or NONE for a
+	// lane without a plane: each target asks for the form it consumes as it is - the direct slot for byte offsets of buffer stores
+	// (SCALE 8, RIR_OOB), the staged target for word indices (SCALE 1, RIR_NONE) - so neither converts after the fact.
+	// The two 8-byte stores of a record are issued by the sink, outside the wave-uniform tier branch: with every vector-memory
+	// operation of the frame loop unconditional the compiler keeps exact s_waitcnt vmcnt(N) counts (a store inside the branch made
+	// it fall back to vmcnt(0) on half of the steps).
+	struct RecordWords
 	{
 		v2u32 va, vb;
-		uint32_t oa, ob;
+		uint32_t pa, pb;
 	};
 
 	// Narrow tier: every residual < 16.  The 8 nibbles of a lane are packed in one dword (3 shift-ors, nibble
@@ -430,8 +434,9 @@ namespace rir
 	// (non-zero mask smeared down inside each nibble), W = per-nibble popcount of M = the 8 widths.  A lane's
 	// word index is a popcount of M under a per-lane constant mask; the header is two ballots of per-lane
 	// bit tests of W and of (base | mode << 16).
-	__device__ __forceinline__ uint64_t emit_record_narrow(const Px8 &r, uint32_t mode, uint32_t base, RecordStores &rs, uint32_t pos,
-														   const LaneConsts &lc, const TransposeConsts &tc, uint32_t *words)
+	template <uint32_t SCALE, uint32_t NONE>
+	__device__ __forceinline__ uint64_t emit_words_narrow(const Px8 &r, uint32_t mode, uint32_t base, RecordWords &rw, uint32_t pos,
+														  const LaneConsts &lc, const TransposeConsts &tc, uint32_t *words)
 	{
 		uint32_t x = (r.d[0] | (r.d[1] << 8)) | ((r.d[2] | (r.d[3] << 8)) << 4);
 		x = transpose32(x, tc);
@@ -444,10 +449,10 @@ namespace rir
 		*words = (uint32_t)__builtin_popcount(M);
 		// lower-half lanes assemble the 64-bit plane word (their dword | the partner lane's dword << 32)
 		auto sw = __builtin_amdgcn_permlane32_swap(x, x, false, false); // sw[1] lower lanes = x of lane + 32
-		rs.va.x = x, rs.va.y = sw[1];
-		const uint32_t off = (pos + (uint32_t)__builtin_popcount(M & lc.p_before)) * 8u;
-		rs.oa = __builtin_amdgcn_inverse_ballot_w64((uint64_t)M) ? off : RIR_OOB; // lane l < 32 stores iff bit l of M
-		rs.vb = rs.va, rs.ob = RIR_OOB;
+		rw.va.x = x, rw.va.y = sw[1];
+		const uint32_t at = (pos + (uint32_t)__builtin_popcount(M & lc.p_before)) * SCALE;
+		rw.pa = __builtin_amdgcn_inverse_ballot_w64((uint64_t)M) ? at : NONE; // lane l < 32 has a word iff bit l of M
+		rw.vb = rw.va, rw.pb = NONE;
 		const uint32_t B = base | (mode << 16);
 		const uint64_t hw = __ballot((int32_t)(W << lc.p_hshw) < 0) & 0x00E700E700E700E7ull;
 		const uint64_t hb = __ballot((int32_t)(B << lc.p_hshb) < 0) & 0x3C003C003C00FC00ull;
@@ -455,8 +460,9 @@ namespace rir
 	}
 
 	// Wide tier (any width up to 16): two 64x64 transposes, lane 16q+k holds plane k of slots q and 4+q.
-	__device__ __forceinline__ uint64_t emit_record_wide(const Px8 &r, uint32_t mode, uint32_t base, RecordStores &rs, uint32_t pos,
-														 const LaneConsts &lc, const TransposeConsts &tc, uint32_t *words)
+	template <uint32_t SCALE, uint32_t NONE>
+	__device__ __forceinline__ uint64_t emit_words_wide(const Px8 &r, uint32_t mode, uint32_t base, RecordWords &rw, uint32_t pos,
+														const LaneConsts &lc, const TransposeConsts &tc, uint32_t *words)
 	{
 		uint32_t alo = r.d[0], ahi = r.d[1], blo = r.d[2], bhi = r.d[3];
 		transpose64x2(alo, ahi, blo, bhi, tc);
@@ -465,13 +471,10 @@ namespace rir
 		const uint32_t ia = rows_inclusive_sum(wa), ib = rows_inclusive_sum(wb);
 		const uint32_t tot_a = (uint32_t)__builtin_amdgcn_readlane((int)ia, 63);
 		const uint32_t tot_b = (uint32_t)__builtin_amdgcn_readlane((int)ib, 63);
-		// one unconditional 8-byte store per half; lanes without a plane point out of range
-		v2u32 va, vb;
-		va.x = alo, va.y = ahi, vb.x = blo, vb.y = bhi;
-		const uint32_t oa = lc.bit < wa ? (pos + ia - wa + lc.bit) * 8u : RIR_OOB;
-		const uint32_t ob = lc.bit < wb ? (pos + tot_a + ib - wb + lc.bit) * 8u : RIR_OOB;
-		rs.va = va, rs.oa = oa;
-		rs.vb = vb, rs.ob = ob;
+		// one word per half; lanes without a plane have none
+		rw.va.x = alo, rw.va.y = ahi, rw.vb.x = blo, rw.vb.y = bhi;
+		rw.pa = lc.bit < wa ? (pos + ia - wa + lc.bit) * SCALE : NONE;
+		rw.pb = lc.bit < wb ? (pos + tot_a + ib - wb + lc.bit) * SCALE : NONE;
 		*words = tot_a + tot_b;
 		// header = ballot of the row's 16-bit field (w_q | w_{4+q} << 5 | base nibble q << 10 | mode << 14)
 		const uint32_t nib = (base >> lc.sh4) & 15u;
@@ -479,57 +482,166 @@ namespace rir
 		return __ballot((field & lc.onehot) != 0);
 	}
 
-	// Emit the payload of one record: residuals r (packed pairs) -> plane words at out[pos..pos+words).
-	// Returns the header.  The tier is a property of
-	// the data (wave-uniform branch), the bitstream is the same either way.
-	__device__ __forceinline__ uint64_t emit_record(const Px8 &r, uint32_t mode, uint32_t base, __amdgpu_buffer_rsrc_t out, uint32_t pos,
-													const LaneConsts &lc, const TransposeConsts &tc, uint32_t *words)
+	// The payload of one record: residuals r (packed pairs) -> plane words at positions pos .. pos + words.  Returns the header.
+	// The tier is a property of the data (wave-uniform branch), the bitstream is the same either way.
+	template <uint32_t SCALE, uint32_t NONE>
+	__device__ __forceinline__ uint64_t emit_words(const Px8 &r, uint32_t mode, uint32_t base, RecordWords &rw, uint32_t pos, const LaneConsts &lc,
+												   const TransposeConsts &tc, uint32_t *words)
 	{
 		const uint32_t any = (r.d[0] | r.d[1]) | (r.d[2] | r.d[3]);
-		RecordStores rs;
-		uint64_t h;
 		if (__ballot((any & 0xfff0fff0u) != 0) == 0)
-			h = emit_record_narrow(r, mode, base, rs, pos, lc, tc, words);
-		else
-			h = emit_record_wide(r, mode, base, rs, pos, lc, tc, words);
-		__builtin_amdgcn_raw_buffer_store_b64(rs.va, out, rs.oa, 0, SPARSE_STORE_AUX);
-		__builtin_amdgcn_raw_buffer_store_b64(rs.vb, out, rs.ob, 0, SPARSE_STORE_AUX);
-		return h;
+			return emit_words_narrow<SCALE, NONE>(r, mode, base, rw, pos, lc, tc, words);
+		return emit_words_wide<SCALE, NONE>(r, mode, base, rw, pos, lc, tc, words);
 	}
 
-	// One wave = one tile over the frames of one chunk (see the kernel below).
-	template <bool FAST>
-	__device__ __forceinline__ void encode_tile(const uint16_t *__restrict__ frames, int64_t npx, int nf, int64_t frame0, int tile, int lane,
-												uint64_t *__restrict__ my_hdr, uint64_t *__restrict__ out_ptr, uint32_t out_bytes,
-												uint32_t *__restrict__ seg_words_slot, int gop)
+	// ---- where a record's words go: the two sinks of encode_run ------------------------------------------
+	// sink.emit<DIR>(residuals, mode, base, pos, ...) files the record that begins at word `pos` of what the wave has produced so far
+	// and returns its header.  Either sink issues exactly two unconditional buffer stores per record, out of range when unused.
+	//
+	// The direct sink: the segment's slot in the workspace (rirb1_encode_tiles), filled from word 0 in the order of production.
+	struct DirectSink
 	{
+		__amdgpu_buffer_rsrc_t out;
+		template <int DIR>
+		__device__ __forceinline__ uint64_t emit(const Px8 &r, uint32_t mode, uint32_t base, uint32_t pos, const LaneConsts &lc,
+												 const TransposeConsts &tc, uint32_t *words)
+		{
+			static_assert(DIR > 0, "a slot is filled in frame order from word 0: the direct sink only walks forwards");
+			RecordWords rw;
+			const uint64_t h = emit_words<8u, RIR_OOB>(r, mode, base, rw, pos, lc, tc, words);
+			__builtin_amdgcn_raw_buffer_store_b64(rw.va, out, rw.pa, 0, SPARSE_STORE_AUX);
+			__builtin_amdgcn_raw_buffer_store_b64(rw.vb, out, rw.pb, 0, SPARSE_STORE_AUX);
+			return h;
+		}
+	};
+
+	// first word of an extent of `need` words, ~0 when the arena is full (the launch is marked); wave-uniform
+	__device__ __noinline__ uint64_t staging_take_extent(unsigned long long *cursor, uint32_t need, uint64_t arena_words, uint32_t *error_word)
+	{
+		unsigned long long off = 0;
+		if ((threadIdx.x & 63u) == 0)
+			off = __hip_atomic_fetch_add(cursor, (unsigned long long)need, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)off);
+		const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(off >> 32));
+		off = ((unsigned long long)hi << 32) | lo;
+		if (off + need > arena_words)
+		{ // no room: the caller's descriptor stays empty (every store is dropped by the range check)
+			if ((threadIdx.x & 63u) == 0)
+				__hip_atomic_fetch_or(error_word, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+			return ~0ull;
+		}
+		return off;
+	}
+
+	// The staged sink (single-pass encoders): the first records go into the wave's LDS region, from the first record that does not fit
+	// (wave-uniform decision) everything into its spill area in the workspace.
+	// Two kinds of spill area.  STATIC (arena == nullptr): `spill` is the wave's own worst-case slot, there from the start
+	// (rirb1_encode_dense).  DYNAMIC (rirb1_encode_packed): nothing is reserved; the wave that starts to spill takes an extent
+	// of `need` words - the worst case of its share of the chunk - from a bump cursor in the workspace, once (a returning
+	// atomic inside the rare, wave-uniform branch), and an arena that is full raises bit 1 of the error word and leaves the
+	// descriptor empty: the stores go nowhere, the segment is reported unusable, nothing is written out of bounds.
+	// DIR > 0: the wave walks its frames forwards and fills its region (and its extent) upwards from word 0.  DIR < 0: it walks them
+	// backwards and fills both DOWNWARDS from the top, so that what it leaves is still its records in frame order, contiguous, ending
+	// at the top: the indices of a record are taken relative to the record (pos = 0) and the wave-uniform first word of the record,
+	// top - words so far - words of this record, is added to them.
+	struct Staging
+	{
+		uint64_t *lds;	   // this wave's region
+		uint32_t cap;	   // its capacity in words
+		uint32_t lds_used; // words in LDS once spilling has started
+		bool spilling;
+		__amdgpu_buffer_rsrc_t spill;
+		uint32_t need; // words of the spill area: the worst case of the wave's share of the chunk
+		// dynamic spill extents
+		uint64_t *arena;			// nullptr: static
+		unsigned long long *cursor; // words handed out so far
+		uint64_t arena_words;
+		uint64_t extent; // first word of its extent (valid once spilling and granted)
+		uint32_t *error_word;
+
+		// wave w's region of `cap` words, empty, and a static spill area (none yet: the caller sets `spill`, or the arena's fields)
+		__device__ __forceinline__ Staging(uint64_t *lds_all, int w, int cap_, int nrec)
+			: lds(lds_all + (size_t)w * cap_), cap((uint32_t)cap_), lds_used(0), spilling(false), need((uint32_t)(nrec > 0 ? nrec : 0) * RIRB1_REC_MAX_WORDS),
+			  arena(nullptr), cursor(nullptr), arena_words(0), extent(~0ull), error_word(nullptr)
+		{
+		}
+
+		template <int DIR>
+		__device__ __forceinline__ uint64_t emit(const Px8 &r, uint32_t mode, uint32_t base, uint32_t pos, const LaneConsts &lc, const TransposeConsts &tc,
+												 uint32_t *words)
+		{
+			RecordWords rw;
+			const uint64_t h = emit_words<1u, RIR_NONE>(r, mode, base, rw, DIR > 0 ? pos : 0u, lc, tc, words);
+			if (!spilling && pos + *words > cap)
+			{
+				spilling = true, lds_used = pos;
+				if (arena)
+				{
+					// (the extent comes back from a call: vector registers, "divergent" for the compiler - and with it the branch below and the
+					// descriptor it sets, which then lived in VGPRs and cost every record two waterfall loops, 12 vector + 12 scalar
+					// instructions, around its two stores.  It is wave-uniform: say so.)
+					const uint64_t ext = staging_take_extent(cursor, need, arena_words, error_word);
+					extent = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ext >> 32)) << 32) |
+							 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ext);
+					if (extent != ~0ull)
+						spill = make_rsrc(arena + extent, need * 8u);
+				}
+			}
+			if (!spilling)
+			{ // LDS operations only inside this (wave-uniform) branch: the vector-memory stream below stays unconditional
+				uint64_t *rec = DIR > 0 ? lds : lds + (cap - pos - *words); // (pos + words <= cap here)
+				if (rw.pa != RIR_NONE)
+					rec[rw.pa] = ((uint64_t)rw.va.y << 32) | rw.va.x;
+				if (rw.pb != RIR_NONE)
+					rec[rw.pb] = ((uint64_t)rw.vb.y << 32) | rw.vb.x;
+			}
+			// two stores per record whatever happens (counted waits, see RecordWords): out of range unless the wave spills.  A backward
+			// wave's extent ends with its first spilled record: need - words spilled so far - words of this record is where this one starts
+			const uint32_t add = !spilling ? RIR_OOB : DIR > 0 ? 0u - lds_used * 8u : (need - (pos - lds_used) - *words) * 8u;
+			const uint32_t oa = rw.pa != RIR_NONE ? rw.pa * 8u + add : RIR_OOB;
+			const uint32_t ob = rw.pb != RIR_NONE ? rw.pb * 8u + add : RIR_OOB;
+			__builtin_amdgcn_raw_buffer_store_b64(rw.va, spill, oa, 0, SPARSE_STORE_AUX);
+			__builtin_amdgcn_raw_buffer_store_b64(rw.vb, spill, ob, 0, SPARSE_STORE_AUX);
+			return h;
+		}
+	};
+
+	// ---- the frame walk -----------------------------------------------------------------------------------
+	// One wave packs the records of a run of frames of a chunk for one tile: every encoder kernel calls it.  `nload` frames are LOADED,
+	// from frame `frame_first` on: the key frame first when has_key, else the frame before the wave's first record.  hdr_first: table
+	// entry of that first loaded frame (headers of records go to hdr_first[1..] / hdr_first[0] for the key frame).
+	// DIR > 0: the wave walks its frames forwards.  DIR < 0: backwards - it loads its LAST frame first and its records come out
+	// last to first, the key record at the very end.  A record is frame f minus frame f - 1 either way, so every header and payload
+	// word is the same; only the order in which the wave produces them differs (and the staged sink files them in frame order).
+	// The ring is indexed by the ORDER OF LOADING k (slot k % 4): step k packs what was loaded k-th against what was loaded (k-1)-th.
+	// Returns the number of payload words produced.
+	template <bool FAST, int DIR, class Sink>
+	__device__ __forceinline__ uint32_t encode_run(const uint16_t *__restrict__ frames, int64_t npx, int nload, int64_t frame_first, bool has_key,
+												   int tile, int lane, uint64_t *__restrict__ hdr_first, Sink &sink)
+	{
+		constexpr bool BACK = DIR < 0;
 		const int64_t p0 = (int64_t)tile * RIRB1_TILE_PX + lane * 8;
 		const TransposeConsts tc = make_transpose_consts(lane);
 		const LaneConsts lc = make_lane_consts(lane);
-		const __amdgpu_buffer_rsrc_t out = make_rsrc(out_ptr, out_bytes);
 		const uint32_t lane_off = (uint32_t)lane * 16u;
-		const uint16_t *tile0 = frames + frame0 * npx + (int64_t)tile * RIRB1_TILE_PX; // tile of the chunk's first frame
-		// FAST: whole tile inside the frame and 16-byte aligned rows -> raw-buffer loads, unconditional;
-		// past the end of the chunk the prefetch re-reads the last frame (an L2 hit, no HBM traffic).
-		// Frame loads are compiler-visible builtins: the waits are the compiler's own counted s_waitcnt, which
-		// stay exact because no vector-memory operation of the frame loop sits inside a branch.
-		// Frames are loaded strictly in order (0,1,2,3 up front, then frame f+3 at step f), so the address is a
-		// running wave-uniform pointer (2 scalar adds per load instead of a 64-bit multiply chain); past the end
-		// of the chunk it stays on the last frame.
-		const uint16_t *next_ptr = tile0;
-		int next_f = 0;
-		auto load = [&](int f, v4u32 &dst) {
+		// FAST: whole tile inside the frame and 16-byte aligned rows -> raw-buffer loads, unconditional.  They are compiler-visible
+		// builtins: the waits are the compiler's own counted s_waitcnt, which stay exact because no vector-memory operation of the
+		// frame loop sits inside a branch.  Frames are loaded strictly in order (of time, or against it: 0,1,2,3 up front, then the
+		// (k+3)-th at step k), so the address is a running wave-uniform pointer (2 scalar adds per load instead of a 64-bit multiply
+		// chain); a request past the wave's last frame is an out-of-range offset: the instruction is issued (the waits stay counted)
+		// and touches no memory.
+		const uint16_t *next_ptr = frames + (frame_first + (BACK ? nload - 1 : 0)) * npx + (int64_t)tile * RIRB1_TILE_PX;
+		auto load = [&](int k, v4u32 &dst) { // the k-th load of the wave
 			if (FAST)
 			{
-				const Px8 p = buf_load8(next_ptr, lane_off);
+				const Px8 p = buf_load8(next_ptr, k < nload ? lane_off : RIR_OOB);
 				dst.x = p.d[0], dst.y = p.d[1], dst.z = p.d[2], dst.w = p.d[3];
-				const bool more = next_f < nf - 1;
-				next_ptr += more ? npx : 0;
-				next_f += more ? 1 : 0;
+				next_ptr = BACK ? next_ptr - npx : next_ptr + npx;
 			}
 			else
 			{
-				const Px8 p = load8(frames, frame0 + min(f, nf - 1), npx, p0, false);
+				const int i = min(k, nload - 1);
+				const Px8 p = load8(frames, frame_first + (BACK ? nload - 1 - i : i), npx, p0, false);
 				dst.x = p.d[0], dst.y = p.d[1], dst.z = p.d[2], dst.w = p.d[3];
 			}
 		};
@@ -538,22 +650,10 @@ namespace rir
 			p.d[0] = v.x, p.d[1] = v.y, p.d[2] = v.z, p.d[3] = v.w;
 			return p;
 		};
-
 		uint32_t pos = 0;
-		uint64_t hdr_reg = 0; // lane (f & 63) keeps the header of frame f until the 64-frame flush
-
-		// Ring of 4 frame slots: frame f lives in slot f % 4, three frames are in flight ahead of the
-		// one being packed.  The loop is unrolled by 4 so that slots are fixed registers (a register
-		// copy of a loaded value would force an early wait on the load).
-		v4u32 s0, s1, s2, s3;
-		load(0, s0);
-		load(1, s1);
-		load(2, s2);
-		load(3, s3);
-
-		// ---- key frame: RAW, or LEFT when its payload is strictly smaller ----
-		{
-			const Px8 cur = as_px8(s0);
+		uint64_t hdr_reg = 0; // lane (k - 1) & 63 keeps the header of step k until the 64-step flush
+		// key frame: RAW, or LEFT when its payload is strictly smaller
+		auto key_record = [&](const Px8 &cur) {
 			const uint32_t base_raw = tile_base(cur, false);
 			const uint32_t b2 = base_raw | (base_raw << 16);
 			Px8 r_raw;
@@ -574,39 +674,48 @@ namespace rir
 				r_sel.d[k] = use_left ? r_left.d[k] : r_raw.d[k];
 			uint32_t words;
 			const uint32_t key_mode = use_left ? RIRB1_MODE_LEFT : RIRB1_MODE_RAW;
-			const uint64_t h = emit_record(r_sel, key_mode, use_left ? base_left : base_raw, out, pos, lc, tc, &words);
+			const uint64_t h = sink.template emit<DIR>(r_sel, key_mode, use_left ? base_left : base_raw, pos, lc, tc, &words);
 			if (lane == 0)
-				my_hdr[0] = h;
+				hdr_first[0] = h;
 			pos += words;
-		}
-
-		// ---- temporal frames ----
-		// Steps come in groups of 64 (one header per lane of hdr_reg, flushed with one coalesced store per
-		// group) and the steady-state loop runs whole iterations of 4 steps with NO condition around any
-		// vector-memory operation: that is what lets the compiler keep counted waits, i.e. keeps the loads
-		// of the next frames in flight across the packing of the current one.
-#define RIR_ENC_STEP(F, CUR, PREV)                                                             \
+		};
+		// Ring of 4 frame slots: what was loaded k-th lives in slot k % 4, three frames are in flight ahead of the one being packed.
+		// The loop is unrolled by 4 so that slots are fixed registers (a register copy of a loaded value would force an early wait
+		// on the load).
+		v4u32 s0, s1, s2, s3;
+		load(0, s0);
+		load(1, s1);
+		load(2, s2);
+		load(3, s3);
+		if (!BACK && has_key)
+			key_record(as_px8(s0));
+		// step K: NEW was loaded K-th, OLD (K-1)-th; forwards NEW is the record's frame and OLD the one before it, backwards OLD is
+		// the record's frame and NEW the one before it.  OLD's slot is free afterwards: the (K+3)-th load goes there.
+#define RIR_ENC_STEP(K, NEW, OLD)                                                             \
 	{                                                                                          \
-		const int f = (F);                                                                     \
+		const int k_ = (K);                                                                    \
 		Px8 d;                                                                                 \
 		{                                                                                      \
-			const Px8 c_ = as_px8(CUR), p_ = as_px8(PREV);                                     \
+			const Px8 c_ = as_px8(BACK ? OLD : NEW), p_ = as_px8(BACK ? NEW : OLD);            \
 			_Pragma("unroll") for (int k = 0; k < 4; ++k) d.d[k] = pk_sub16(c_.d[k], p_.d[k]); \
 		}                                                                                      \
-		load(f + 3, PREV); /* the slot of frame f-1 is free: prefetch frame f+3 into it */     \
+		load(k_ + 3, OLD);                                                                     \
 		const uint32_t base = tile_base(d, true);                                              \
 		const uint32_t b2 = base | (base << 16);                                               \
 		_Pragma("unroll") for (int k = 0; k < 4; ++k) d.d[k] = pk_sub16(d.d[k], b2);          \
 		uint32_t words;                                                                        \
-		const uint64_t h = emit_record(d, RIRB1_MODE_TEMPORAL, base, out, pos, lc, tc, &words);      \
-		if (lane == ((f - 1) & 63))                                                            \
+		const uint64_t h = sink.template emit<DIR>(d, RIRB1_MODE_TEMPORAL, base, pos, lc, tc, &words); \
+		if (lane == ((k_ - 1) & 63))                                                           \
 			hdr_reg = h;                                                                       \
 		pos += words;                                                                          \
 	}
+		// Steps come in groups of 64 (one header per lane of hdr_reg, flushed with one coalesced store per group) and the steady-state
+		// loop runs whole iterations of 4 steps with NO condition around any vector-memory operation: that is what lets the compiler
+		// keep counted waits, i.e. keeps the loads of the next frames in flight across the packing of the current one.
 		int fb = 1;
-		while (fb < nf)
+		while (fb < nload)
 		{
-			const int g0 = fb, gend = min(fb + 64, nf); // this group: frames [g0, gend), header of frame f in lane f - g0
+			const int g0 = fb, gend = min(fb + 64, nload); // this group: steps [g0, gend), header of step k in lane k - g0
 			for (; fb + 3 < gend; fb += 4)
 			{
 				RIR_ENC_STEP(fb, s1, s0)
@@ -615,7 +724,7 @@ namespace rir
 				RIR_ENC_STEP(fb + 3, s0, s3)
 			}
 			if (fb < gend)
-			{ // up to three left-over steps of the chunk's last group (64 % 4 == 0: the slot rotation stays aligned)
+			{ // up to three left-over steps of the run's last group (64 % 4 == 0: the slot rotation stays aligned)
 				RIR_ENC_STEP(fb, s1, s0)
 				if (fb + 1 < gend)
 				{
@@ -625,15 +734,19 @@ namespace rir
 				}
 				fb = gend;
 			}
+			// lane l holds the header of step g0 + l: the record of frame g0 + l forwards, of frame nload - (g0 + l) backwards
 			if (g0 + lane < gend)
-				my_hdr[g0 + lane] = hdr_reg;
+				hdr_first[BACK ? nload - (g0 + lane) : g0 + lane] = hdr_reg;
 			hdr_reg = 0;
 		}
 #undef RIR_ENC_STEP
-		for (int f = nf + lane; f < gop; f += 64)
-			my_hdr[f] = 0; // short last chunk: the unused table entries are defined
-		if (lane == 0)
-			*seg_words_slot = pos;
+		if (BACK && has_key)
+		{ // the key frame was loaded last, (nload - 1)-th: it is in slot (nload - 1) % 4
+			const int ks = (nload - 1) & 3;
+			const v4u32 kv = ks == 0 ? s0 : ks == 1 ? s1 : ks == 2 ? s2 : s3;
+			key_record(as_px8(kv));
+		}
+		return pos;
 	}
 
 	// ---- encode -----------------------------------------------------------------------------
@@ -642,6 +755,7 @@ namespace rir
 	// hdr       [nchunks][ntiles][gop]      u64  record headers
 	// seg_words [nchunks][ntiles]           u32  segment length (sum over the chunk's frames)
 	// sparse    [nchunks][ntiles][gop*128]  u64, only the first seg_words words of a slot are written
+	// One wave = one tile over all the frames of one chunk: the walk with the key frame, forwards, into the segment's slot.
 	// Two kernels: FAST for tiles that lie whole inside 16-byte aligned frames (every tile but the last one of a frame whose
 	// size is not a multiple of 512 pixels) - unconditional raw-buffer loads, 64 registers, no scratch - and the ragged form
 	// (element-wise loads with bounds tests) for the rest; as one kernel the ragged instantiation's spills cost the fast path
@@ -664,9 +778,12 @@ namespace rir
 		const int nf = min(gop, nframes - f_begin);
 		const int64_t slot = (int64_t)chunk * ntiles + tile;
 		uint64_t *my_hdr = hdr_table + slot * gop;
-		uint64_t *out = sparse + slot * RIRB1_SLOT_WORDS(gop);
-		const uint32_t out_bytes = (uint32_t)gop * RIRB1_REC_MAX_WORDS * 8u;
-		encode_tile<FAST>(frames, npx, nf, f_begin, tile, lane, my_hdr, out, out_bytes, seg_words + slot, gop);
+		DirectSink sink{make_rsrc(sparse + slot * RIRB1_SLOT_WORDS(gop), (uint32_t)gop * RIRB1_REC_MAX_WORDS * 8u)};
+		const uint32_t words = encode_run<FAST, 1>(frames, npx, nf, f_begin, true, tile, lane, my_hdr, sink);
+		for (int f = nf + lane; f < gop; f += 64)
+			my_hdr[f] = 0; // short last chunk: the unused table entries are defined
+		if (lane == 0)
+			seg_words[slot] = words;
 	}
 
 	// ---- offsets ------------------------------------------------------------------------------
@@ -778,278 +895,6 @@ namespace rir
 #define RIR_LB_TAG (1ull << 63)
 #define RIR_LB_TIMEOUT_TICKS 200000000ull /* s_memrealtime runs at 100 MHz: 2 s */
 	constexpr int LB_SLEEP = 8; // s_sleep between two polls of a look-back
-#define RIR_NONE 0xffffffffu
-
-	struct RecordWords
-	{
-		v2u32 va, vb;
-		uint32_t ia, ib; // word index inside the wave's payload, RIR_NONE for a lane without a plane
-	};
-
-	__device__ __forceinline__ uint64_t emit_words_narrow(const Px8 &r, uint32_t mode, uint32_t base, RecordWords &rw, uint32_t pos, const LaneConsts &lc,
-														  const TransposeConsts &tc, uint32_t *words)
-	{
-		uint32_t x = (r.d[0] | (r.d[1] << 8)) | ((r.d[2] | (r.d[3] << 8)) << 4);
-		x = transpose32(x, tc);
-		const uint64_t nz64 = __ballot(x != 0);
-		const uint32_t nz = (uint32_t)nz64 | (uint32_t)(nz64 >> 32);
-		uint32_t M = nz | ((nz >> 1) & 0x77777777u);
-		M |= (M >> 2) & 0x33333333u;
-		uint32_t W = M - ((M >> 1) & 0x55555555u);
-		W = (W & 0x33333333u) + ((W >> 2) & 0x33333333u);
-		*words = (uint32_t)__builtin_popcount(M);
-		auto sw = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-		rw.va.x = x, rw.va.y = sw[1];
-		rw.ia = __builtin_amdgcn_inverse_ballot_w64((uint64_t)M) ? pos + (uint32_t)__builtin_popcount(M & lc.p_before) : RIR_NONE;
-		rw.vb = rw.va, rw.ib = RIR_NONE;
-		const uint32_t B = base | (mode << 16);
-		const uint64_t hw = __ballot((int32_t)(W << lc.p_hshw) < 0) & 0x00E700E700E700E7ull;
-		const uint64_t hb = __ballot((int32_t)(B << lc.p_hshb) < 0) & 0x3C003C003C00FC00ull;
-		return hw | hb;
-	}
-
-	__device__ __forceinline__ uint64_t emit_words_wide(const Px8 &r, uint32_t mode, uint32_t base, RecordWords &rw, uint32_t pos, const LaneConsts &lc,
-														const TransposeConsts &tc, uint32_t *words)
-	{
-		uint32_t alo = r.d[0], ahi = r.d[1], blo = r.d[2], bhi = r.d[3];
-		transpose64x2(alo, ahi, blo, bhi, tc);
-		const uint32_t wa = row_allmax((alo | ahi) != 0 ? lc.bitp1 : 0u);
-		const uint32_t wb = row_allmax((blo | bhi) != 0 ? lc.bitp1 : 0u);
-		const uint32_t ia = rows_inclusive_sum(wa), ib = rows_inclusive_sum(wb);
-		const uint32_t tot_a = (uint32_t)__builtin_amdgcn_readlane((int)ia, 63);
-		const uint32_t tot_b = (uint32_t)__builtin_amdgcn_readlane((int)ib, 63);
-		rw.va.x = alo, rw.va.y = ahi, rw.vb.x = blo, rw.vb.y = bhi;
-		rw.ia = lc.bit < wa ? pos + ia - wa + lc.bit : RIR_NONE;
-		rw.ib = lc.bit < wb ? pos + tot_a + ib - wb + lc.bit : RIR_NONE;
-		*words = tot_a + tot_b;
-		const uint32_t nib = (base >> lc.sh4) & 15u;
-		const uint32_t field = ((nib << 10) | (lc.row0 ? mode << 14 : 0u)) | ((wb << 5) | wa);
-		return __ballot((field & lc.onehot) != 0);
-	}
-
-	// Where a wave's payload goes: the first records into its LDS region, from the first record that does not fit
-	// (wave-uniform decision) everything into its spill area in the workspace.
-	// Two kinds of spill area.  STATIC (arena == nullptr): `spill` is the wave's own worst-case slot, there from the start
-	// (rirb1_encode_dense).  DYNAMIC (rirb1_encode_packed): nothing is reserved; the wave that starts to spill takes an extent
-	// of `need` words - the worst case of its share of the chunk - from a bump cursor in the workspace, once (a returning
-	// atomic inside the rare, wave-uniform branch), and an arena that is full raises bit 1 of the error word and leaves the
-	// descriptor empty: the stores go nowhere, the segment is reported unusable, nothing is written out of bounds.
-	struct Staging
-	{
-		uint64_t *lds;	   // this wave's region
-		uint32_t cap;	   // its capacity in words
-		uint32_t lds_used; // words in LDS once spilling has started
-		bool spilling;
-		__amdgpu_buffer_rsrc_t spill;
-		// dynamic spill extents
-		uint64_t *arena;			 // nullptr: static
-		unsigned long long *cursor;	 // words handed out so far
-		uint64_t arena_words;
-		uint32_t need;				 // words this wave asks for when it starts to spill
-		uint64_t extent;			 // first word of its extent (valid once spilling and granted)
-		uint32_t *error_word;
-	};
-
-	// first word of an extent of `need` words, ~0 when the arena is full (the launch is marked); wave-uniform
-	__device__ __noinline__ uint64_t staging_take_extent(unsigned long long *cursor, uint32_t need, uint64_t arena_words, uint32_t *error_word)
-	{
-		unsigned long long off = 0;
-		if ((threadIdx.x & 63u) == 0)
-			off = __hip_atomic_fetch_add(cursor, (unsigned long long)need, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)off);
-		const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(off >> 32));
-		off = ((unsigned long long)hi << 32) | lo;
-		if (off + need > arena_words)
-		{ // no room: the caller's descriptor stays empty (every store is dropped by the range check)
-			if ((threadIdx.x & 63u) == 0)
-				__hip_atomic_fetch_or(error_word, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			return ~0ull;
-		}
-		return off;
-	}
-
-	// DIR > 0: the wave walks its frames forwards and fills its region (and its extent) upwards from word 0.  DIR < 0: it walks them
-	// backwards and fills both DOWNWARDS from the top, so that what it leaves is still its records in frame order, contiguous, ending
-	// at the top: the indices of a record are taken relative to the record (pos = 0) and the wave-uniform first word of the record,
-	// top - words so far - words of this record, is added to them.
-	template <int DIR>
-	__device__ __forceinline__ uint64_t emit_staged(const Px8 &r, uint32_t mode, uint32_t base, Staging &sg, uint32_t pos, const LaneConsts &lc,
-													const TransposeConsts &tc, uint32_t *words)
-	{
-		const uint32_t any = (r.d[0] | r.d[1]) | (r.d[2] | r.d[3]);
-		RecordWords rw;
-		uint64_t h;
-		const uint32_t rel = DIR > 0 ? pos : 0u;
-		if (__ballot((any & 0xfff0fff0u) != 0) == 0)
-			h = emit_words_narrow(r, mode, base, rw, rel, lc, tc, words);
-		else
-			h = emit_words_wide(r, mode, base, rw, rel, lc, tc, words);
-		if (!sg.spilling && pos + *words > sg.cap)
-		{
-			sg.spilling = true, sg.lds_used = pos;
-			if (sg.arena)
-			{
-				// (the extent comes back from a call: vector registers, "divergent" for the compiler - and with it the branch below and the
-				// descriptor it sets, which then lived in VGPRs and cost every record two waterfall loops, 12 vector + 12 scalar
-				// instructions, around its two stores.  It is wave-uniform: say so.)
-				const uint64_t ext = staging_take_extent(sg.cursor, sg.need, sg.arena_words, sg.error_word);
-				sg.extent = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ext >> 32)) << 32) |
-							(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ext);
-				if (sg.extent != ~0ull)
-					sg.spill = make_rsrc(sg.arena + sg.extent, sg.need * 8u);
-			}
-		}
-		if (!sg.spilling)
-		{ // LDS operations only inside this (wave-uniform) branch: the vector-memory stream below stays unconditional
-			uint64_t *rec = DIR > 0 ? sg.lds : sg.lds + (sg.cap - pos - *words); // (pos + words <= cap here)
-			if (rw.ia != RIR_NONE)
-				rec[rw.ia] = ((uint64_t)rw.va.y << 32) | rw.va.x;
-			if (rw.ib != RIR_NONE)
-				rec[rw.ib] = ((uint64_t)rw.vb.y << 32) | rw.vb.x;
-		}
-		// two stores per record whatever happens (counted waits, see RecordStores): out of range unless the wave spills.  A backward
-		// wave's extent ends with its first spilled record: need - words spilled so far - words of this record is where this one starts
-		const uint32_t add = !sg.spilling ? RIR_OOB : DIR > 0 ? 0u - sg.lds_used * 8u : (sg.need - (pos - sg.lds_used) - *words) * 8u;
-		const uint32_t oa = rw.ia != RIR_NONE ? rw.ia * 8u + add : RIR_OOB;
-		const uint32_t ob = rw.ib != RIR_NONE ? rw.ib * 8u + add : RIR_OOB;
-		__builtin_amdgcn_raw_buffer_store_b64(rw.va, sg.spill, oa, 0, SPARSE_STORE_AUX);
-		__builtin_amdgcn_raw_buffer_store_b64(rw.vb, sg.spill, ob, 0, SPARSE_STORE_AUX);
-		return h;
-	}
-
-	// One wave packs the records of frames [rec0, rec0 + nrec) of a chunk for one tile.  `first` points at the tile in the
-	// first frame the wave LOADS: the key frame when has_key, else the frame before its first record.  hdr_first: table
-	// entry of that loaded frame (headers of records go to hdr_first[1..] / hdr_first[0] for the key frame).
-	// DIR > 0: the wave walks its frames forwards.  DIR < 0: backwards - it loads its LAST frame first and its records come out
-	// last to first, the key record at the very end.  A record is frame f minus frame f - 1 either way, so every header and payload
-	// word is the same; only the order in which the wave produces them differs (and emit_staged<DIR> files them in frame order).
-	// The ring is indexed by the ORDER OF LOADING k (slot k % 4): step k packs what was loaded k-th against what was loaded (k-1)-th.
-	// Returns the number of payload words produced.
-	template <bool FAST, int DIR>
-	__device__ __forceinline__ uint32_t encode_run(const uint16_t *__restrict__ frames, int64_t npx, int nload, int64_t frame_first, bool has_key,
-												   int tile, int lane, uint64_t *__restrict__ hdr_first, Staging &sg)
-	{
-		constexpr bool BACK = DIR < 0;
-		const int64_t p0 = (int64_t)tile * RIRB1_TILE_PX + lane * 8;
-		const TransposeConsts tc = make_transpose_consts(lane);
-		const LaneConsts lc = make_lane_consts(lane);
-		const uint32_t lane_off = (uint32_t)lane * 16u;
-		const uint16_t *next_ptr = frames + (frame_first + (BACK ? nload - 1 : 0)) * npx + (int64_t)tile * RIRB1_TILE_PX;
-		int next_f = 0;
-		// frames are loaded strictly in order (of time, or against it); a request past the wave's last frame is an out-of-range
-		// offset: the instruction is issued (the waits stay counted) and touches no memory
-		auto load = [&](int k, v4u32 &dst) {
-			if (FAST)
-			{
-				const Px8 p = buf_load8(next_ptr, next_f < nload ? lane_off : RIR_OOB);
-				dst.x = p.d[0], dst.y = p.d[1], dst.z = p.d[2], dst.w = p.d[3];
-				next_ptr = BACK ? next_ptr - npx : next_ptr + npx;
-				next_f += 1;
-			}
-			else
-			{
-				const int i = min(k, nload - 1);
-				const Px8 p = load8(frames, frame_first + (BACK ? nload - 1 - i : i), npx, p0, false);
-				dst.x = p.d[0], dst.y = p.d[1], dst.z = p.d[2], dst.w = p.d[3];
-			}
-		};
-		auto as_px8 = [](const v4u32 &v) {
-			Px8 p;
-			p.d[0] = v.x, p.d[1] = v.y, p.d[2] = v.z, p.d[3] = v.w;
-			return p;
-		};
-		uint32_t pos = 0;
-		uint64_t hdr_reg = 0;
-		// key frame: RAW, or LEFT when its payload is strictly smaller
-		auto key_record = [&](const Px8 &cur) {
-			const uint32_t base_raw = tile_base(cur, false);
-			const uint32_t b2 = base_raw | (base_raw << 16);
-			Px8 r_raw;
-#pragma unroll
-			for (int k = 0; k < 4; ++k)
-				r_raw.d[k] = pk_sub16(cur.d[k], b2);
-			const Px8 dl = left_delta(cur, lane);
-			const uint32_t base_left = tile_base(dl, true);
-			const uint32_t bl2 = base_left | (base_left << 16);
-			Px8 r_left;
-#pragma unroll
-			for (int k = 0; k < 4; ++k)
-				r_left.d[k] = pk_sub16(dl.d[k], bl2);
-			const bool use_left = payload_words(r_left) < payload_words(r_raw);
-			Px8 r_sel;
-#pragma unroll
-			for (int k = 0; k < 4; ++k)
-				r_sel.d[k] = use_left ? r_left.d[k] : r_raw.d[k];
-			uint32_t words;
-			const uint32_t key_mode = use_left ? RIRB1_MODE_LEFT : RIRB1_MODE_RAW;
-			const uint64_t h = emit_staged<DIR>(r_sel, key_mode, use_left ? base_left : base_raw, sg, pos, lc, tc, &words);
-			if (lane == 0)
-				hdr_first[0] = h;
-			pos += words;
-		};
-		v4u32 s0, s1, s2, s3;
-		load(0, s0);
-		load(1, s1);
-		load(2, s2);
-		load(3, s3);
-		if (!BACK && has_key)
-			key_record(as_px8(s0));
-		// step K: NEW was loaded K-th, OLD (K-1)-th; forwards NEW is the record's frame and OLD the one before it, backwards OLD is
-		// the record's frame and NEW the one before it.  OLD's slot is free afterwards: the (K+3)-th load goes there.
-#define RIR_ENC2_STEP(K, NEW, OLD)                                                            \
-	{                                                                                          \
-		const int k_ = (K);                                                                    \
-		Px8 d;                                                                                 \
-		{                                                                                      \
-			const Px8 c_ = as_px8(BACK ? OLD : NEW), p_ = as_px8(BACK ? NEW : OLD);            \
-			_Pragma("unroll") for (int k = 0; k < 4; ++k) d.d[k] = pk_sub16(c_.d[k], p_.d[k]); \
-		}                                                                                      \
-		load(k_ + 3, OLD);                                                                     \
-		const uint32_t base = tile_base(d, true);                                              \
-		const uint32_t b2 = base | (base << 16);                                               \
-		_Pragma("unroll") for (int k = 0; k < 4; ++k) d.d[k] = pk_sub16(d.d[k], b2);          \
-		uint32_t words;                                                                        \
-		const uint64_t h = emit_staged<DIR>(d, RIRB1_MODE_TEMPORAL, base, sg, pos, lc, tc, &words); \
-		if (lane == ((k_ - 1) & 63))                                                           \
-			hdr_reg = h;                                                                       \
-		pos += words;                                                                          \
-	}
-		int fb = 1;
-		while (fb < nload)
-		{
-			const int g0 = fb, gend = min(fb + 64, nload);
-			for (; fb + 3 < gend; fb += 4)
-			{
-				RIR_ENC2_STEP(fb, s1, s0)
-				RIR_ENC2_STEP(fb + 1, s2, s1)
-				RIR_ENC2_STEP(fb + 2, s3, s2)
-				RIR_ENC2_STEP(fb + 3, s0, s3)
-			}
-			if (fb < gend)
-			{
-				RIR_ENC2_STEP(fb, s1, s0)
-				if (fb + 1 < gend)
-				{
-					RIR_ENC2_STEP(fb + 1, s2, s1)
-					if (fb + 2 < gend)
-						RIR_ENC2_STEP(fb + 2, s3, s2)
-				}
-				fb = gend;
-			}
-			// lane l holds the header of step g0 + l: the record of frame g0 + l forwards, of frame nload - (g0 + l) backwards
-			if (g0 + lane < gend)
-				hdr_first[BACK ? nload - (g0 + lane) : g0 + lane] = hdr_reg;
-			hdr_reg = 0;
-		}
-#undef RIR_ENC2_STEP
-		if (BACK && has_key)
-		{ // the key frame was loaded last, (nload - 1)-th: it is in slot (nload - 1) % 4
-			const int ks = (nload - 1) & 3;
-			const v4u32 kv = ks == 0 ? s0 : ks == 1 ? s1 : ks == 2 ? s2 : s3;
-			key_record(as_px8(kv));
-		}
-		return pos;
-	}
 
 	__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v)
 	{
@@ -1060,10 +905,9 @@ namespace rir
 	}
 
 	// Look-back of workgroup (c, t), run by ONE wave.  A = sum of the lengths of tiles < t of chunk c, Pc = first word of
-	// chunk c.  false: gave up (clock or error word); the error word is raised.  The last argument is unused (the diagnostic
-	// build of 02807a8 wrote its timings there); dropping it would rename the device function.
+	// chunk c.  false: gave up (clock or error word); the error word is raised.
 	__device__ __noinline__ bool encode_lookback(const uint64_t *P, const uint64_t *gtotal, const uint64_t *gran, uint32_t *error_word, int c, int t,
-												 int ntiles, int ngroups, int lane, uint64_t *A_out, uint64_t *P_out, uint64_t * /* unused */)
+												 int ntiles, int ngroups, int lane, uint64_t *A_out, uint64_t *P_out)
 	{
 		const int g = t >> 6, e1 = t & 63, E = e1 + g + (c > 0 ? 1 : 0);
 		uint64_t accA = 0, accP = 0;
@@ -1148,6 +992,77 @@ namespace rir
 			   (int64_t)nchunks * ngroups + nchunks + 16;
 	}
 
+	// ---- what the two staged encoders share ---------------------------------------------------------------------
+	// Wave w's share of a chunk of nf frames under the cuts CUT (enc_split or enc_split_mirrored): records [rec0, rec0 + nrec).  It loads
+	// nload frames from frame first_load of the chunk on: the key frame first (wave 0), else the frame before its first record.
+	struct WaveShare
+	{
+		int rec0, nrec, first_load, nload;
+		bool has_key;
+	};
+	template <int (*CUT)(int, int, int)>
+	__device__ __forceinline__ WaveShare wave_share(int w, int waves, int nf)
+	{
+		WaveShare s;
+		const int rec1 = CUT(w + 1, waves, nf);
+		s.rec0 = CUT(w, waves, nf);
+		s.nrec = rec1 - s.rec0;
+		s.has_key = w == 0;
+		s.first_load = s.has_key ? 0 : s.rec0 - 1;
+		s.nload = s.nrec > 0 ? rec1 - s.first_load : 0;
+		return s;
+	}
+
+	// The end of a wave's walk, before the barrier: the workgroup defines the table entries a short last chunk leaves unused, the wave
+	// publishes its words and how many of them are in LDS, and what it spilled has left it before another wave reads it.
+	template <int WAVES>
+	__device__ __forceinline__ void staged_publish(uint64_t *__restrict__ my_hdr, int nf, int gop, const Staging &sg, uint32_t pos, int w, int lane,
+												   uint32_t *sh_words, uint32_t *sh_lds_words)
+	{
+		for (int f = nf + (int)threadIdx.x; f < gop; f += WAVES * 64)
+			my_hdr[f] = 0;
+		if (lane == 0)
+		{
+			sh_words[w] = pos;
+			sh_lds_words[w] = sg.spilling ? sg.lds_used : pos;
+		}
+		if (sg.spilling)
+			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+	}
+
+	// Copies one wave's n_all words to dst in frame order: n_lds of them are in its LDS region (`cap` words), the rest in its spill area,
+	// which spill_area(need) describes (its size in words goes to `need`) and which is asked for only when there is a rest.  A forward
+	// wave's words: its region from word 0, then (the later records) its area from word 0.  A backward wave's: its area (the EARLIER
+	// records, which it packed last) up to the area's end, then its region up to the region's end.
+	template <class SpillArea>
+	__device__ __forceinline__ void copy_wave_words(uint64_t *__restrict__ dst, const uint64_t *region, uint32_t cap, uint32_t n_all, uint32_t n_lds, bool back,
+													int lane, SpillArea spill_area)
+	{
+		const uint32_t n_ext = n_all - n_lds;
+		const uint64_t *src = region + (back ? cap - n_lds : 0u);
+		uint64_t *dst_lds = dst + (back ? n_ext : 0u);
+		uint32_t j = (uint32_t)lane;
+		for (; j + 192 < n_lds; j += 256)
+		{
+			const uint64_t v0 = src[j], v1 = src[j + 64], v2 = src[j + 128], v3 = src[j + 192];
+			dst_lds[j] = v0, dst_lds[j + 64] = v1, dst_lds[j + 128] = v2, dst_lds[j + 192] = v3;
+		}
+		for (; j < n_lds; j += 64)
+			dst_lds[j] = src[j];
+		if (n_ext > 0)
+		{ // what the wave spilled comes back from the workspace (sc1 loads: from L2, where its stores went)
+			uint32_t need;
+			const __amdgpu_buffer_rsrc_t sp = spill_area(need);
+			const uint32_t first = back ? need - n_ext : 0u;
+			uint64_t *dst_ext = dst + (back ? 0u : n_lds);
+			for (uint32_t q = (uint32_t)lane; q < n_ext; q += 64)
+			{
+				const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(sp, (first + q) * 8u, 0, 16 /* sc1 */);
+				dst_ext[q] = ((uint64_t)v.y << 32) | v.x;
+			}
+		}
+	}
+
 	template <int WAVES>
 	__attribute__((amdgpu_waves_per_eu(8, 8))) __global__ __launch_bounds__(WAVES * 64) void rirb1_encode_dense(
 		const uint16_t *__restrict__ frames, int64_t npx, int ntiles, int nframes, int gop, int nchunks, uint64_t *__restrict__ hdr_table,
@@ -1181,38 +1096,24 @@ namespace rir
 		const int nf = min(gop, nframes - f_begin);
 		uint64_t *my_hdr = hdr_table + (int64_t)seg * gop;
 
-		// this wave's share of the chunk
-		const int rec0 = enc_split(w, WAVES, nf), rec1 = enc_split(w + 1, WAVES, nf);
-		const int nrec = rec1 - rec0;
-		const bool has_key = w == 0;
-		const int first_load = has_key ? 0 : rec0 - 1;
-		const int nload = nrec > 0 ? rec1 - first_load : 0;
-		Staging sg;
-		sg.lds = enc_lds + (size_t)w * cap;
-		sg.cap = (uint32_t)cap;
-		sg.lds_used = 0;
-		sg.spilling = false;
-		sg.arena = nullptr, sg.cursor = nullptr, sg.arena_words = 0, sg.need = 0, sg.extent = 0, sg.error_word = nullptr;
-		uint64_t *my_spill = spill + (int64_t)seg * RIRB1_SLOT_WORDS(gop) + (int64_t)rec0 * RIRB1_REC_MAX_WORDS;
-		sg.spill = make_rsrc(my_spill, (uint32_t)(nrec > 0 ? nrec : 0) * RIRB1_REC_MAX_WORDS * 8u);
+		// a wave's spill area: its share of the segment's worst-case slot
+		auto spill_area = [&](const WaveShare &s, uint32_t &need) {
+			need = (uint32_t)s.nrec * RIRB1_REC_MAX_WORDS;
+			return make_rsrc(spill + (int64_t)seg * RIRB1_SLOT_WORDS(gop) + (int64_t)s.rec0 * RIRB1_REC_MAX_WORDS, need * 8u);
+		};
+		const WaveShare sh = wave_share<enc_split>(w, WAVES, nf);
+		Staging sg(enc_lds, w, cap, sh.nrec);
+		sg.spill = spill_area(sh, sg.need);
 		uint32_t pos = 0;
-		if (nrec > 0)
+		if (sh.nrec > 0)
 		{
 			const bool fast = ((npx & 7) == 0) && ((int64_t)(tile + 1) * RIRB1_TILE_PX <= npx) && ((((uintptr_t)frames) & 15) == 0);
 			if (fast)
-				pos = encode_run<true, 1>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
+				pos = encode_run<true, 1>(frames, npx, sh.nload, (int64_t)f_begin + sh.first_load, sh.has_key, tile, lane, my_hdr + sh.first_load, sg);
 			else
-				pos = encode_run<false, 1>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
+				pos = encode_run<false, 1>(frames, npx, sh.nload, (int64_t)f_begin + sh.first_load, sh.has_key, tile, lane, my_hdr + sh.first_load, sg);
 		}
-		for (int f = nf + (int)threadIdx.x; f < gop; f += WAVES * 64)
-			my_hdr[f] = 0; // short last chunk: the unused table entries are defined
-		if (lane == 0)
-		{
-			sh_u32[w] = pos;
-			sh_u32[WAVES + 2 + w] = sg.spilling ? sg.lds_used : pos; // words of this wave that are in LDS
-		}
-		if (sg.spilling)
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the spilled words have left this wave before wave 0 is told of them
+		staged_publish<WAVES>(my_hdr, nf, gop, sg, pos, w, lane, sh_u32, sh_u32 + WAVES + 2);
 		__syncthreads();
 		// Only wave 0 goes on: the segment is complete in LDS (+ spill), what is left is to wait for its place in the stream and
 		// to copy it there.  The other waves END here - a workgroup that waits holds one wave slot, not four, so the CU can
@@ -1241,7 +1142,7 @@ namespace rir
 			}
 		}
 		uint64_t A = 0, Pc = 0;
-		const bool ok = encode_lookback(P, gtotal, gran, error_word, chunk, tile, ntiles, ngroups, lane, &A, &Pc, nullptr);
+		const bool ok = encode_lookback(P, gtotal, gran, error_word, chunk, tile, ntiles, ngroups, lane, &A, &Pc);
 		if (!ok)
 			return; // the look-back gave up: the error word is raised, nothing is copied
 		if (lane == 0)
@@ -1259,27 +1160,9 @@ namespace rir
 		uint64_t *dst = stream + (Pc + A);
 		for (int i = 0; i < WAVES; ++i)
 		{
-			const uint64_t *src = enc_lds + (size_t)i * cap;
-			const uint32_t n_all = sh_u32[i], n_lds = sh_u32[WAVES + 2 + i];
-			uint32_t j = (uint32_t)lane;
-			for (; j + 192 < n_lds; j += 256)
-			{
-				const uint64_t v0 = src[j], v1 = src[j + 64], v2 = src[j + 128], v3 = src[j + 192];
-				dst[j] = v0, dst[j + 64] = v1, dst[j + 128] = v2, dst[j + 192] = v3;
-			}
-			for (; j < n_lds; j += 64)
-				dst[j] = src[j];
-			if (n_all > n_lds)
-			{ // what wave i spilled comes back from its area of the workspace (sc1 loads: from L2, where its stores went)
-				const int r0 = enc_split(i, WAVES, nf), r1 = enc_split(i + 1, WAVES, nf);
-				const __amdgpu_buffer_rsrc_t sp =
-					make_rsrc(spill + (int64_t)seg * RIRB1_SLOT_WORDS(gop) + (int64_t)r0 * RIRB1_REC_MAX_WORDS, (uint32_t)(r1 - r0) * RIRB1_REC_MAX_WORDS * 8u);
-				for (uint32_t q = (uint32_t)lane; q < n_all - n_lds; q += 64)
-				{
-					const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(sp, q * 8u, 0, 16 /* sc1 */);
-					dst[n_lds + q] = ((uint64_t)v.y << 32) | v.x;
-				}
-			}
+			const uint32_t n_all = sh_u32[i];
+			copy_wave_words(dst, enc_lds + (size_t)i * cap, (uint32_t)cap, n_all, sh_u32[WAVES + 2 + i], false, lane,
+							[&](uint32_t &need) { return spill_area(wave_share<enc_split>(i, WAVES, nf), need); });
 			dst += n_all;
 		}
 	}
@@ -1337,7 +1220,7 @@ namespace rir
 	__attribute__((amdgpu_waves_per_eu(8, 8))) __global__ __launch_bounds__(WAVES * 64) void rirb1_encode_packed(
 		const uint16_t *__restrict__ frames, int64_t npx, int ntiles, int tile_first, int nframes, int gop, uint64_t *__restrict__ hdr_table,
 		uint64_t *__restrict__ seg_pos, uint32_t *__restrict__ seg_words, uint64_t *__restrict__ stream, uint64_t capacity_words,
-		uint64_t *__restrict__ ctrl, uint64_t *__restrict__ arena, uint64_t arena_words, int cap, int diag)
+		uint64_t *__restrict__ ctrl, uint64_t *__restrict__ arena, uint64_t arena_words, int cap)
 	{
 		extern __shared__ __attribute__((aligned(16))) uint64_t enc_lds[];
 		uint64_t *sh_u64 = enc_lds + (size_t)WAVES * cap;			  // [0] segment's first word in the stream, [1 + w] wave w's spill extent
@@ -1345,7 +1228,7 @@ namespace rir
 		const int lane = threadIdx.x & 63;
 		const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 		const int chunk = blockIdx.y, tile = tile_first + blockIdx.x;
-		const bool downwards = ((tile + chunk) & 1) != 0 && diag != 1; // (diag 1: one cursor)
+		const bool downwards = ((tile + chunk) & 1) != 0;
 		unsigned long long *cursor = reinterpret_cast<unsigned long long *>(ctrl) + (downwards ? 16 : 0);
 		unsigned long long *spill_cursor = reinterpret_cast<unsigned long long *>(ctrl + 32);
 		uint32_t *error_word = reinterpret_cast<uint32_t *>(ctrl + 48);
@@ -1355,38 +1238,21 @@ namespace rir
 		const int nf = min(gop, nframes - f_begin);
 		uint64_t *my_hdr = hdr_table + seg * gop;
 
-		const int rec0 = enc_split_mirrored(w, WAVES, nf), rec1 = enc_split_mirrored(w + 1, WAVES, nf);
-		const int nrec = rec1 - rec0;
-		const bool has_key = w == 0;
-		const int first_load = has_key ? 0 : rec0 - 1;
-		const int nload = nrec > 0 ? rec1 - first_load : 0;
-		Staging sg;
-		sg.lds = enc_lds + (size_t)w * cap;
-		sg.cap = (uint32_t)cap;
-		sg.lds_used = 0;
-		sg.spilling = false;
+		const WaveShare sh = wave_share<enc_split_mirrored>(w, WAVES, nf);
+		Staging sg(enc_lds, w, cap, sh.nrec);
 		sg.spill = make_rsrc(arena, 0); // empty until the wave takes an extent
 		sg.arena = arena, sg.cursor = spill_cursor, sg.arena_words = arena_words, sg.error_word = error_word;
-		sg.need = (uint32_t)(nrec > 0 ? nrec : 0) * RIRB1_REC_MAX_WORDS;
-		sg.extent = ~0ull;
 		uint32_t pos = 0;
-		if (nrec > 0)
+		if (sh.nrec > 0)
 		{
 			if (enc_walks_back(w))
-				pos = encode_run<FAST, -1>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
+				pos = encode_run<FAST, -1>(frames, npx, sh.nload, (int64_t)f_begin + sh.first_load, sh.has_key, tile, lane, my_hdr + sh.first_load, sg);
 			else
-				pos = encode_run<FAST, 1>(frames, npx, nload, (int64_t)f_begin + first_load, has_key, tile, lane, my_hdr + first_load, sg);
+				pos = encode_run<FAST, 1>(frames, npx, sh.nload, (int64_t)f_begin + sh.first_load, sh.has_key, tile, lane, my_hdr + sh.first_load, sg);
 		}
-		for (int f = nf + (int)threadIdx.x; f < gop; f += WAVES * 64)
-			my_hdr[f] = 0; // short last chunk: the unused table entries are defined
 		if (lane == 0)
-		{
-			sh_u32[w] = pos;
-			sh_u32[WAVES + w] = sg.spilling ? sg.lds_used : pos;
 			sh_u64[1 + w] = sg.extent;
-		}
-		if (sg.spilling)
-			asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the spilled words have left this wave before another wave reads them
+		staged_publish<WAVES>(my_hdr, nf, gop, sg, pos, w, lane, sh_u32, sh_u32 + WAVES);
 		__syncthreads();
 		// the segment is complete in LDS (+ extents): one wave places and copies it, the others make room (the alternative, every
 		// wave copying its own words after one more barrier, is RIR_PACKED_COPY_ALL_WAVES in 02807a8)
@@ -1401,64 +1267,38 @@ namespace rir
 			total += n;
 			lost |= n > sh_u32[WAVES + i] && sh_u64[1 + i] == ~0ull;
 		}
-		if (w == 0)
+		unsigned long long at = 0;
+		if (lane == 0)
+			at = __hip_atomic_fetch_add(cursor, (unsigned long long)total | (1ull << RIR_PACKED_COUNT_SHIFT), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)at);
+		const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(at >> 32));
+		// segments placed on this side before this one: the last of them all leaves the control block clean
+		const uint32_t arrived = hi >> (RIR_PACKED_COUNT_SHIFT - 32);
+		const uint64_t nseg = (uint64_t)gridDim.y * (uint32_t)ntiles; // (both launches: every segment of the batch)
+		const uint64_t on_side = downwards ? nseg / 2 : (nseg + 1) / 2; // (tile + chunk) odd / even
+		if ((uint64_t)arrived + 1 == on_side)
+			packed_finish(ctrl, capacity_words, nseg < 2 ? 1u : 2u);
+		at = ((unsigned long long)hi << 32 | lo) & RIR_PACKED_WORDS_MASK;
+		const bool fits = at + total <= capacity_words; // (a segment that does not fit leaves its cursor beyond the capacity)
+		if (downwards)
+			at = capacity_words - at - total; // (unused when it does not fit)
+		if (lane == 0)
 		{
-			unsigned long long at = 0;
-			if (lane == 0)
-				at = __hip_atomic_fetch_add(cursor, (unsigned long long)total | (1ull << RIR_PACKED_COUNT_SHIFT), __ATOMIC_RELAXED,
-											__HIP_MEMORY_SCOPE_AGENT);
-			const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)at);
-			const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(at >> 32));
-			// segments placed on this side before this one: the last of them all leaves the control block clean
-			const uint32_t arrived = hi >> (RIR_PACKED_COUNT_SHIFT - 32);
-			const uint64_t nseg = (uint64_t)gridDim.y * (uint32_t)ntiles; // (both launches: every segment of the batch)
-			const uint64_t on_side = diag == 1 ? nseg : downwards ? nseg / 2 : (nseg + 1) / 2; // (tile + chunk) odd / even
-			if ((uint64_t)arrived + 1 == on_side)
-				packed_finish(ctrl, capacity_words, diag == 1 || nseg < 2 ? 1u : 2u);
-			at = ((unsigned long long)hi << 32 | lo) & RIR_PACKED_WORDS_MASK;
-			const bool fits = at + total <= capacity_words; // (a segment that does not fit leaves its cursor beyond the capacity)
-			if (downwards)
-				at = capacity_words - at - total; // (unused when it does not fit)
-			if (lane == 0)
-			{
-				seg_pos[seg] = at;
-				seg_words[seg] = total;
-				sh_u64[0] = (fits && !lost) ? at : ~0ull;
-			}
-			if (!fits || lost)
-				return;
-			uint64_t *dst = stream + at;
-			for (int i = 0; i < WAVES; ++i)
-			{
-				// A forward wave's words: its region from word 0, then (the later records) its extent from word 0.  A backward wave's: its
-				// extent (the EARLIER records, which it packed last) up to the extent's end, then its region up to the region's end.
-				const bool back = enc_walks_back(i);
-				const uint32_t n_all = sh_u32[i], n_lds = sh_u32[WAVES + i], n_ext = n_all - n_lds;
-				const uint64_t *src = enc_lds + (size_t)i * cap + (back ? (uint32_t)cap - n_lds : 0u);
-				uint64_t *dst_lds = dst + (back ? n_ext : 0u);
-				uint32_t j = (uint32_t)lane;
-				for (; j + 192 < n_lds; j += 256)
-				{
-					const uint64_t v0 = src[j], v1 = src[j + 64], v2 = src[j + 128], v3 = src[j + 192];
-					dst_lds[j] = v0, dst_lds[j + 64] = v1, dst_lds[j + 128] = v2, dst_lds[j + 192] = v3;
-				}
-				for (; j < n_lds; j += 64)
-					dst_lds[j] = src[j];
-				if (n_ext > 0)
-				{ // what wave i spilled comes back from its extent (sc1 loads: from L2, where its stores went)
-					const int r0 = enc_split_mirrored(i, WAVES, nf), r1 = enc_split_mirrored(i + 1, WAVES, nf);
-					const uint32_t need = (uint32_t)(r1 - r0) * RIRB1_REC_MAX_WORDS;
-					const __amdgpu_buffer_rsrc_t sp = make_rsrc(arena + sh_u64[1 + i], need * 8u);
-					const uint32_t first = back ? need - n_ext : 0u;
-					uint64_t *dst_ext = dst + (back ? 0u : n_lds);
-					for (uint32_t q = (uint32_t)lane; q < n_ext; q += 64)
-					{
-						const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(sp, (first + q) * 8u, 0, 16 /* sc1 */);
-						dst_ext[q] = ((uint64_t)v.y << 32) | v.x;
-					}
-				}
-				dst += n_all;
-			}
+			seg_pos[seg] = at;
+			seg_words[seg] = total;
+			sh_u64[0] = (fits && !lost) ? at : ~0ull;
+		}
+		if (!fits || lost)
+			return;
+		uint64_t *dst = stream + at;
+		for (int i = 0; i < WAVES; ++i)
+		{
+			const uint32_t n_all = sh_u32[i];
+			copy_wave_words(dst, enc_lds + (size_t)i * cap, (uint32_t)cap, n_all, sh_u32[WAVES + i], enc_walks_back(i), lane, [&](uint32_t &need) {
+				need = (uint32_t)wave_share<enc_split_mirrored>(i, WAVES, nf).nrec * RIRB1_REC_MAX_WORDS;
+				return make_rsrc(arena + sh_u64[1 + i], need * 8u); // its extent
+			});
+			dst += n_all;
 		}
 	}
 
@@ -1903,20 +1743,37 @@ namespace rir
 
 	// ---- host launchers --------------------------------------------------------------------------------
 
+	// The FAST-then-ragged pair of every kernel that has the two forms: launch(fast, t0, t1) for the tiles [0, nfast) that lie whole
+	// inside 16-byte aligned frames at `frames`, launch(ragged, t0, t1) for the rest (no launch for an empty range).
+	template <class KFast, class KRagged, class Launch>
+	static void launch_fast_then_ragged(const void *frames, int64_t npx, int ntiles, KFast fast, KRagged ragged, Launch launch)
+	{
+		const bool aligned = ((npx & 7) == 0) && ((((uintptr_t)frames) & 15) == 0);
+		const int nfast = aligned ? (int)std::min<int64_t>(ntiles, npx / RIRB1_TILE_PX) : 0;
+		if (nfast > 0)
+			launch(fast, 0, nfast);
+		if (ntiles > nfast)
+			launch(ragged, nfast, ntiles);
+	}
+
+	// LDS words per wave of a staged encoder whose `waves` waves pack one segment: 14.4 KB per workgroup - 11 workgroups per CU, in the
+	// dense encoder 7 packing (28 waves) while 4 wait for their offsets (1 wave each); the reference's recipe needs 290-355 words per
+	// wave of four - and never more than the worst case of the wave's share of the chunk
+	static int staged_lds_words(int gop, int waves)
+	{
+		const int share = (gop + 1 + waves - 1) / waves + 1;
+		return std::min(448 * 4 / waves, share * RIRB1_REC_MAX_WORDS);
+	}
+
 	// stage 1: one pass over the raw frames -> headers, per-tile segment lengths, sparse payload
 	hipError_t launch_encode_tiles(const uint16_t *d_frames, int64_t npx, int ntiles, int nframes, int gop, uint64_t *d_hdr,
 								   uint32_t *d_seg_words, uint64_t *d_sparse, hipStream_t st)
 	{
 		const int nchunks = (nframes + gop - 1) / gop;
-		const bool aligned = ((npx & 7) == 0) && ((((uintptr_t)d_frames) & 15) == 0);
-		const int nfast = aligned ? (int)(npx / RIRB1_TILE_PX) : 0; // tiles that lie whole inside the frame
-		dim3 block(256);
-		if (nfast > 0)
-			hipLaunchKernelGGL(rirb1_encode_tiles<true>, dim3((nfast + 3) / 4, nchunks), block, 0, st, d_frames, npx, ntiles, 0, nfast, nframes, gop, d_hdr,
-							   d_seg_words, d_sparse);
-		if (ntiles > nfast)
-			hipLaunchKernelGGL(rirb1_encode_tiles<false>, dim3((ntiles - nfast + 3) / 4, nchunks), block, 0, st, d_frames, npx, ntiles, nfast, ntiles - nfast,
-							   nframes, gop, d_hdr, d_seg_words, d_sparse);
+		launch_fast_then_ragged(d_frames, npx, ntiles, rirb1_encode_tiles<true>, rirb1_encode_tiles<false>, [&](auto kernel, int t0, int t1) {
+			hipLaunchKernelGGL(kernel, dim3((t1 - t0 + 3) / 4, nchunks), dim3(256), 0, st, d_frames, npx, ntiles, t0, t1 - t0, nframes, gop, d_hdr, d_seg_words,
+							   d_sparse);
+		});
 		return hipGetLastError();
 	}
 
@@ -1944,12 +1801,7 @@ namespace rir
 		if (e != hipSuccess)
 			return e;
 		constexpr int WAVES = 4;
-		// LDS words per wave: what 8 workgroups per CU leave (160 KiB / 8 = 20 KiB per workgroup), never more than the
-		// worst case of the wave's share of the chunk
-		const int share = (gop + 1 + WAVES - 1) / WAVES + 1;
-		int cap = 448; // 14.4 KB per workgroup: 11 workgroups per CU, 7 packing (28 waves) while 4 wait for their offsets (1 wave each)
-		if (cap > share * RIRB1_REC_MAX_WORDS)
-			cap = share * RIRB1_REC_MAX_WORDS;
+		const int cap = staged_lds_words(gop, WAVES);
 		const size_t lds = (size_t)WAVES * cap * 8 + 8 + (2 * WAVES + 2) * 4;
 		const int64_t total = (int64_t)nchunks * ntiles;
 		// its workgroups wait for the segments in front of them (dealt by tickets, so any grid size makes progress on its own - but
@@ -1987,15 +1839,6 @@ namespace rir
 	// the packed form.  d_ctrl: RIRB1_PACKED_CTRL_BYTES at the start of the workspace (zeroed here when `reset`; the kernel leaves it
 	// zero), d_arena: the rest of it.
 	constexpr int PACKED_WAVES = 4; // waves that pack one segment between them
-	int packed_lds_words(int gop)
-	{
-		constexpr int WAVES = PACKED_WAVES;
-		const int share = (gop + 1 + WAVES - 1) / WAVES + 1;
-		int cap = 448 * 4 / WAVES; // 14.4 KB per workgroup, as the dense kernel: the reference's recipe needs 290-355 words per wave of four
-		if (cap > share * RIRB1_REC_MAX_WORDS)
-			cap = share * RIRB1_REC_MAX_WORDS;
-		return cap;
-	}
 	hipError_t launch_encode_packed(const uint16_t *d_frames, int64_t npx, int ntiles, int nframes, int gop, uint64_t *d_hdr, uint64_t *d_seg_pos,
 									uint32_t *d_seg_words, uint64_t *d_stream, uint64_t capacity_words, uint64_t *d_ctrl, uint64_t *d_arena,
 									uint64_t arena_words, bool reset, hipStream_t st)
@@ -2008,37 +1851,26 @@ namespace rir
 				return e;
 		}
 		constexpr int WAVES = PACKED_WAVES;
-		const int cap = packed_lds_words(gop);
-		// two stream cursors: diag 1 sends every segment through the low one, 207 us a launch against 162-165 with two
-		constexpr int diag = 0;
+		const int cap = staged_lds_words(gop, WAVES);
 		const size_t lds = (size_t)WAVES * cap * 8 + (1 + WAVES) * 8 + 2 * WAVES * 4;
-		const bool aligned = ((npx & 7) == 0) && ((((uintptr_t)d_frames) & 15) == 0);
-		const int nfast = aligned ? (int)(npx / RIRB1_TILE_PX) : 0; // tiles that lie whole inside the frame
-		if (nfast > 0)
-			hipLaunchKernelGGL((rirb1_encode_packed<WAVES, true>), dim3(nfast, nchunks), dim3(WAVES * 64), lds, st, d_frames, npx, ntiles, 0, nframes, gop, d_hdr,
-							   d_seg_pos, d_seg_words, d_stream, capacity_words, d_ctrl, d_arena, arena_words, cap, diag);
-		if (ntiles > nfast)
-			hipLaunchKernelGGL((rirb1_encode_packed<WAVES, false>), dim3(ntiles - nfast, nchunks), dim3(WAVES * 64), lds, st, d_frames, npx, ntiles, nfast,
-							   nframes, gop, d_hdr, d_seg_pos, d_seg_words, d_stream, capacity_words, d_ctrl, d_arena, arena_words, cap, diag);
+		launch_fast_then_ragged(d_frames, npx, ntiles, rirb1_encode_packed<WAVES, true>, rirb1_encode_packed<WAVES, false>, [&](auto kernel, int t0, int t1) {
+			hipLaunchKernelGGL(kernel, dim3(t1 - t0, nchunks), dim3(WAVES * 64), lds, st, d_frames, npx, ntiles, t0, nframes, gop, d_hdr, d_seg_pos, d_seg_words,
+							   d_stream, capacity_words, d_ctrl, d_arena, arena_words, cap);
+		});
 		return hipGetLastError();
 	}
 	hipError_t launch_decode_packed(const uint64_t *d_hdr, const uint64_t *d_seg_pos, const uint32_t *d_seg_words, const uint64_t *d_stream,
 									uint64_t stream_words, int64_t npx, int ntiles, int nframes, int gop, uint16_t *d_frames, int *d_error, hipStream_t st)
 	{
 		const int nchunks = (nframes + gop - 1) / gop;
-		const bool aligned = ((npx & 7) == 0) && ((((uintptr_t)d_frames) & 15) == 0);
-		const int nfast = aligned ? (int)std::min<int64_t>(ntiles, npx / RIRB1_TILE_PX) : 0; // tiles that lie whole inside the frame
 		// The kernel uses no LDS and its registers admit 8 workgroups per CU, but the decoder is bound by the HBM writes of the frames,
 		// not by latency: with more of its waves writing at once the step is slower (DESIGN.md §3, 8 / 7 / 6 / 5 / 4 / 3 / 2 workgroups
 		// per CU measured).  The launch reserves LDS it does not use so that 5 share a CU: 160 KiB / 32 KiB.
 		constexpr unsigned lds_reserve = 32768;
-		auto go = [&](auto kernel, int t0, int t1) {
-			if (t1 > t0)
-				hipLaunchKernelGGL(kernel, dim3((t1 - t0 + 3) / 4, nchunks), dim3(256), lds_reserve, st, d_hdr, d_seg_pos, d_seg_words, d_stream, stream_words, npx,
-								   ntiles, t0, t1, nframes, gop, d_frames, d_error);
-		};
-		go(rirb1_decode_packed<true>, 0, nfast);
-		go(rirb1_decode_packed<false>, nfast, ntiles);
+		launch_fast_then_ragged(d_frames, npx, ntiles, rirb1_decode_packed<true>, rirb1_decode_packed<false>, [&](auto kernel, int t0, int t1) {
+			hipLaunchKernelGGL(kernel, dim3((t1 - t0 + 3) / 4, nchunks), dim3(256), lds_reserve, st, d_hdr, d_seg_pos, d_seg_words, d_stream, stream_words, npx,
+							   ntiles, t0, t1, nframes, gop, d_frames, d_error);
+		});
 		return hipGetLastError();
 	}
 
@@ -2048,17 +1880,14 @@ namespace rir
 	{
 		if (entries <= 0)
 			return hipSuccess;
-		const bool aligned = ((npx & 7) == 0) && ((((uintptr_t)out) & 15) == 0);
-		const int nfast = aligned ? (int)std::min<int64_t>(ntiles, npx / RIRB1_TILE_PX) : 0; // tiles that lie whole inside the frame
 		auto go = [&](auto kernel, int t0, int t1) {
-			if (t1 > t0)
-				hipLaunchKernelGGL(kernel, dim3((t1 - t0 + 3) / 4, entries), dim3(256), 0, st, hdr, tile_off, chunk_off, stream, stream_words, npx, ntiles, t0, t1,
-								   gop, nchunks, table, out_frames, out, min_px, min_t, d_error);
+			hipLaunchKernelGGL(kernel, dim3((t1 - t0 + 3) / 4, entries), dim3(256), 0, st, hdr, tile_off, chunk_off, stream, stream_words, npx, ntiles, t0, t1,
+							   gop, nchunks, table, out_frames, out, min_px, min_t, d_error);
 		};
 		if (f32)
-			go(rirb1_decode_select<true, true>, 0, nfast), go(rirb1_decode_select<true, false>, nfast, ntiles);
+			launch_fast_then_ragged(out, npx, ntiles, rirb1_decode_select<true, true>, rirb1_decode_select<true, false>, go);
 		else
-			go(rirb1_decode_select<false, true>, 0, nfast), go(rirb1_decode_select<false, false>, nfast, ntiles);
+			launch_fast_then_ragged(out, npx, ntiles, rirb1_decode_select<false, true>, rirb1_decode_select<false, false>, go);
 		return hipGetLastError();
 	}
 } // namespace rir

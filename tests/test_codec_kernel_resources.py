@@ -1,4 +1,4 @@
-"""CPU: the codec kernels of the bench step are admitted at 8 workgroups of 256 threads per CU.
+"""CPU: the codec kernels of the bench step and of the saver are admitted at 8 workgroups of 256 threads per CU.
 
 codec_kernels.hip is compiled device-only for gfx950 with the build's flags, and the resources each kernel records in its code object
 metadata are read back.  The admission rule for 256-thread workgroups is min(8, floor(800 / (ceil(sgpr / 16) * 16 + 16))); the
@@ -19,6 +19,7 @@ pytestmark = pytest.mark.skipif(not HIPCC_FOUND, reason="hipcc not found")
 STEP_KERNELS = {
     "rirb1_decode_packed<true>": "_ZN3rir19rirb1_decode_packedILb1E",
     "rirb1_encode_packed<4,true>": "_ZN3rir19rirb1_encode_packedILi4ELb1E",
+    "rirb1_encode_tiles<true>": "_ZN3rir18rirb1_encode_tilesILb1E",  # the saver's encoder (two-pass, stage 1)
 }
 
 

@@ -520,3 +520,92 @@ def test_packed_identity_and_footprint_at_baseline_size(dev):
     enc = ctx.encode(fr)
     assert enc.total_words() == batch.words
     assert torch.equal(ctx.hdr, batch.hdr)
+
+
+# ---- the two-pass and the single-pass encoder over the packed encoder's grid -------------------------------------------------
+# All three encoders run one frame walk (encode_run in codec_kernels.hip), so the two that write the dense stream get the cases
+# of tests/test_gpu_packed_mirrored.py: every GOP that changes which waves have records with every kind of short last chunk,
+# the ragged instantiation (frame sizes that are no multiple of 512 pixels, a frame pointer off the 16-byte grid), and scenes
+# whose waves leave part of their words in LDS and part in their spill slot (single-pass).  Every header, table entry and stream
+# word is compared with the oracle, then the batch is decoded back to the input.
+from test_gpu_packed_mirrored import GOP_CASES, _scene  # noqa: E402
+
+_GRID_ORACLE = {}  # case key -> (frames, [(headers, tile offsets, stream) per chunk]): one oracle pass serves both encoders
+
+
+def _grid_reference(oracle, key, make, gop):
+    if key not in _GRID_ORACLE:
+        fr = make()
+        fr.setflags(write=False)
+        chunks = [oracle.codec_encode_chunk(fr[f0:f0 + gop]) for f0 in range(0, fr.shape[0], gop)]
+        _GRID_ORACLE[key] = (fr, chunks)
+    return _GRID_ORACLE[key]
+
+
+def _encode_and_compare_dense(dev, fr, chunks, gop, single_pass, offset=0):
+    """`offset`: the frames start that many uint16 elements past a 16-byte boundary"""
+    import torch
+
+    n, h, w = fr.shape
+    ctx = dev.CodecContext(w, h, n, gop)
+    flat = torch.zeros((fr.size + 8,), dtype=torch.uint16, device="cuda")
+    t = flat[offset:offset + fr.size].view(n, h, w)
+    t.copy_(torch.from_numpy(fr).cuda())
+    assert t.data_ptr() % 16 == 2 * offset and t.is_contiguous()
+    enc = ctx.encode(t, single_pass=single_pass)
+    torch.cuda.synchronize()
+    if single_pass:
+        assert ctx.encode_status() == 0
+    hdr, toff, coff, st = to_np(enc)
+    assert coff[0] == 0 and len(chunks) == ctx.layout.nchunks
+    for c, (h_o, o_o, st_o) in enumerate(chunks):
+        nf = min(gop, n - c * gop)
+        assert np.array_equal(hdr[c][:, :nf], h_o), ("headers", c)
+        assert not hdr[c][:, nf:].any(), ("headers past a short chunk", c)
+        assert np.array_equal(toff[c], o_o), ("tile offsets", c)
+        assert coff[c + 1] - coff[c] == st_o.size, ("chunk offsets", c)
+        assert np.array_equal(st[coff[c]:coff[c + 1]], st_o), ("stream words", c)
+    assert np.array_equal(ctx.decode(enc).cpu().numpy(), fr), "decode differs from the input"
+
+
+ENCODERS = pytest.mark.parametrize("single_pass", [False, True], ids=["two_pass", "single_pass"])
+
+
+@ENCODERS
+@pytest.mark.parametrize("gop,last", GOP_CASES, ids=["gop%d_last%d" % c for c in GOP_CASES])
+def test_grid_every_gop_and_short_last_chunk(dev, oracle, gop, last, single_pass):
+    """two full chunks and a last chunk of `last` frames (GOP 1 has no short chunk: three chunks), 3 tiles of 512 pixels: waves with
+    0, 1 and 2 records, the header flush past 64 records of one wave, the header tail of a short chunk"""
+    n = 2 * gop + last if gop > 1 else 3
+    fr, chunks = _grid_reference(oracle, ("gop", gop, last), lambda: s1_noisy_background(n, 24, 64, seed=100 + gop), gop)
+    _encode_and_compare_dense(dev, fr, chunks, gop, single_pass)
+
+
+@ENCODERS
+@pytest.mark.parametrize("gop", [3, 50, 130])
+@pytest.mark.parametrize("shape,offset", [((5, 103), 0), ((3, 1025), 0), ((32, 64), 1), ((32, 64), 3)],
+                         ids=["515px", "3075px", "off_2_bytes", "off_6_bytes"])
+@pytest.mark.parametrize("scene", ["s1", "quiet_then_loud"])
+def test_grid_ragged_frames(dev, oracle, scene, shape, offset, gop, single_pass):
+    """515 and 3075 pixels (no 16-byte rows) and whole tiles behind a frame pointer off the 16-byte grid: the ragged instantiation
+    of each encoder takes every tile"""
+    h, w = shape
+    n = 2 * gop + min(2, gop - 1)
+    fr, chunks = _grid_reference(oracle, ("ragged", scene, h, w, gop), lambda: _scene(scene, n, h, w, gop), gop)
+    _encode_and_compare_dense(dev, fr, chunks, gop, single_pass, offset=offset)
+
+
+@ENCODERS
+@pytest.mark.parametrize("scene", ["loud", "quiet_then_loud", "loud_then_quiet"])
+def test_grid_dense_spill_boundary(dev, oracle, scene, single_pass):
+    """10 bits of noise (80-odd words per record: a wave's LDS region holds a few of them) and half-quiet, half-loud chunks at
+    GOP 50: waves of the single-pass encoder leave part of their words in LDS and part in their spill slot"""
+    n, h, w, gop = 2 * 50 + 7, 32, 64, 50
+
+    def make():
+        if scene == "loud":
+            return np.random.default_rng(41).integers(20000, 21024, (n, h, w)).astype(np.uint16)
+        return _scene(scene, n, h, w, gop)
+
+    fr, chunks = _grid_reference(oracle, ("spill", scene), make, gop)
+    _encode_and_compare_dense(dev, fr, chunks, gop, single_pass)
