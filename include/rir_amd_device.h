@@ -254,6 +254,24 @@ extern "C"
 								void *d_work, size_t work_bytes, void *stream);
 	size_t rir_region_stats_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions);
 
+	/* Per-pixel statistics over time of a uint16 stack d_frames[nframes][h][w] (extension).  For pixel i = y * w + x, with v_f = d_frames[f][i],
+	 * f = 0 .. nframes - 1, and a time origin t0 >= 0, the outputs [h][w] are: d_sum[i] = the exact sum of the v_f, d_sumsq[i] = the exact sum
+	 * of their squares (int64), d_min[i] / d_max[i] = the extremes over f, d_argmin[i] / d_argmax[i] = t0 + f for the LOWEST f that holds the
+	 * extreme (int32).  Two groups: the sums (d_sum, d_sumsq) and the extremes (d_min, d_max, d_argmin, d_argmax); the pointers of a group are
+	 * all given or all null, and at least one group is given.  accumulate 0: the outputs are written from this stack alone.  accumulate 1: they
+	 * are merged with what they hold, which must be the result of earlier calls over other time indices or the empty state (sums 0, -1 in
+	 * the other four): sums add; the smaller minimum wins and, of equal minima, the lower time index; likewise for the maximum.  So any
+	 * split of a sequence into batches, pushed in any order with the right t0, gives the bits of one call over the whole sequence.
+	 * Bounds: w, h >= 1, w * h < 2^31, t0 + nframes <= 2^31 - 1; under them the int64 sums cannot overflow (65535^2 * 2^31 < 2^63).  No
+	 * floating point is used on the device: the result is bitwise reproducible and independent of the order the workgroups run in.
+	 * d_work: device memory, 8-byte aligned, at least rir_pixel_stats_workspace_bytes(w, h, nframes) bytes (0 only for refused arguments).
+	 * Asynchronous on `stream`; no output or the workspace may overlap the input or another output.  nframes 0: 0, nothing is done.
+	 * 0 / -1 (invalid argument, null or half-given group, overlap, workspace too small, no device). */
+	int rir_pixel_stats_device(const unsigned short *d_frames, int w, int h, int nframes, int t0, int accumulate,
+							   long long *d_sum, long long *d_sumsq, int *d_min, int *d_max, int *d_argmin, int *d_argmax,
+							   void *d_work, size_t work_bytes, void *stream);
+	size_t rir_pixel_stats_workspace_bytes(int w, int h, int nframes);
+
 	/* connected components: reference signal_processing.h:90-92 / Filters.h:365-540 (labelImage, keepLargestArea) on images in device memory,
 	 * [nframes][h][w], every image labelled on its own; five launches for the whole batch.  type: the reference's dtype character;
 	 * background: HOST pointer to one cell of that type.  d_dst int32 [nframes][h][w].

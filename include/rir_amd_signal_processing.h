@@ -68,6 +68,11 @@ extern "C"
 	 * once.  0 / -1. */
 	int rir_region_stats(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
 						 int *count, long long *sum, long long *sumsq, int *min, int *max, int *argmin, int *argmax);
+	/* Per-pixel statistics over time of a host stack frames[nframes][h][w]: rir_pixel_stats_device (rir_amd_device.h) with t0 = 0,
+	 * synchronous, host outputs [h][w]; a group (sum, sumsq / min, max, argmin, argmax) may be null, not both.  The frames go through the
+	 * device in slabs of at most 64 MiB that accumulate there; the outputs come back once.  nframes 0: nothing is done.  0 / -1. */
+	int rir_pixel_stats(const unsigned short *frames, int w, int h, int nframes, long long *sum, long long *sumsq, int *min, int *max,
+						int *argmin, int *argmax);
 
 #ifdef __cplusplus
 }

@@ -14,6 +14,7 @@
 
 #include "filter_kernels.h"
 #include "label_kernels.h"
+#include "pixel_kernels.h"
 #include "region_kernels.h"
 #include "runtime.h"
 #include "temporal_kernels.h"
@@ -718,6 +719,78 @@ RIR_EXPORT int rir_region_stats_device(const unsigned short *d_frames, const int
 			   : -1;
 }
 
+// Per-pixel statistics over time (pixel_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap the input
+// or another output.
+namespace
+{
+	bool pixel_stats_args(int w, int h, int nframes) { return w > 0 && h > 0 && (long long)w * h < (1ll << 31) && nframes >= 0; }
+} // namespace
+
+RIR_EXPORT size_t rir_pixel_stats_workspace_bytes(int w, int h, int nframes)
+{
+	if (!pixel_stats_args(w, h, nframes))
+		return 0;
+	return pixel_stats_workspace((int64_t)w * h, nframes);
+}
+
+RIR_EXPORT int rir_pixel_stats_device(const unsigned short *d_frames, int w, int h, int nframes, int t0, int accumulate, long long *d_sum,
+									  long long *d_sumsq, int *d_min, int *d_max, int *d_argmin, int *d_argmax, void *d_work, size_t work_bytes,
+									  void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (!pixel_stats_args(w, h, nframes) || t0 < 0 || (long long)t0 + nframes > 2147483647ll || (accumulate != 0 && accumulate != 1))
+	{
+		log_error("rir_pixel_stats_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, t0 >= 0 with t0 + nframes <= 2^31 - 1, "
+				  "accumulate 0 or 1)");
+		return -1;
+	}
+	if (nframes == 0)
+		return 0;
+	const bool sums = d_sum || d_sumsq, extremes = d_min || d_max || d_argmin || d_argmax;
+	if ((sums && (!d_sum || !d_sumsq)) || (extremes && (!d_min || !d_max || !d_argmin || !d_argmax)) || (!sums && !extremes))
+	{
+		log_error("rir_pixel_stats_device: a group of outputs (sum, sumsq / min, max, argmin, argmax) is all given or all null, and one is given");
+		return -1;
+	}
+	if (!d_frames || !d_work)
+	{
+		log_error("rir_pixel_stats_device: null pointer");
+		return -1;
+	}
+	const size_t npx = (size_t)w * h, need = pixel_stats_workspace((int64_t)npx, nframes);
+	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
+	{
+		log_error("rir_pixel_stats_device: the workspace must be 8-byte aligned and hold rir_pixel_stats_workspace_bytes() bytes");
+		return -1;
+	}
+	const struct
+	{
+		uintptr_t p;
+		size_t bytes;
+	} in = {(uintptr_t)d_frames, npx * nframes * 2}, out[7] = {{(uintptr_t)d_sum, npx * 8},	  {(uintptr_t)d_sumsq, npx * 8}, {(uintptr_t)d_min, npx * 4},
+															   {(uintptr_t)d_max, npx * 4},	  {(uintptr_t)d_argmin, npx * 4}, {(uintptr_t)d_argmax, npx * 4},
+															   {(uintptr_t)d_work, need}};
+	for (int i = 0; i < 7; ++i)
+	{
+		if (!out[i].p)
+			continue;
+		bool overlap = out[i].p < in.p + in.bytes && in.p < out[i].p + out[i].bytes;
+		for (int j = 0; j < i; ++j)
+			overlap |= out[j].p && out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
+		if (overlap)
+		{
+			log_error("rir_pixel_stats_device: an output or the workspace overlaps the input or another output");
+			return -1;
+		}
+	}
+	return hip_ok(launch_pixel_stats(d_frames, (int64_t)npx, nframes, t0, accumulate, (int64_t *)d_sum, (int64_t *)d_sumsq, d_min, d_max, d_argmin,
+									 d_argmax, d_work, as_stream(stream)),
+				  "pixel_stats")
+			   ? 0
+			   : -1;
+}
+
 // =====================================================================================================
 // Reference entry points (host pointers, synchronous)
 // =====================================================================================================
@@ -982,6 +1055,50 @@ RIR_EXPORT int rir_region_stats(const unsigned short *frames, const int *labels,
 			return -1;
 	}
 	return 0;
+}
+
+// Extension: per-pixel statistics over time of a host stack, sent in slabs of at most REGION_SLAB_BYTES of frames that accumulate on the
+// device; the outputs come back once.  A group (sum, sumsq / min, max, argmin, argmax) may be null.  Synchronous.  0 / -1.
+RIR_EXPORT int rir_pixel_stats(const unsigned short *frames, int w, int h, int nframes, long long *sum, long long *sumsq, int *min, int *max,
+							   int *argmin, int *argmax)
+{
+	if (!device_ready())
+		return -1;
+	const bool sums = sum || sumsq, extremes = min || max || argmin || argmax;
+	if (!pixel_stats_args(w, h, nframes) || !frames || (sums && (!sum || !sumsq)) || (extremes && (!min || !max || !argmin || !argmax)) ||
+		(!sums && !extremes))
+	{
+		log_error("rir_pixel_stats: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, frames given, each group of outputs all given "
+				  "or all null and one given)");
+		return -1;
+	}
+	if (nframes == 0)
+		return 0;
+	const size_t npx = (size_t)w * h, frame = npx * 2;
+	const int slab = (int)std::max<size_t>(1, std::min<size_t>(REGION_SLAB_BYTES / frame, (size_t)nframes));
+	const size_t work = pixel_stats_workspace((int64_t)npx, slab);
+	DeviceBuffer fr, o32, o64, ws;
+	if (!fr.reserve(frame * slab) || !ws.reserve(work) || (sums && !o64.reserve(npx * 8 * 2)) || (extremes && !o32.reserve(npx * 4 * 4)))
+		return -1;
+	hipStream_t st = default_stream();
+	long long *d64 = sums ? o64.as<long long>() : nullptr;
+	int *d32 = extremes ? o32.as<int>() : nullptr;
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int c = std::min(slab, nframes - o);
+		if (!hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, frame * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
+			rir_pixel_stats_device(fr.as<unsigned short>(), w, h, c, o, o != 0, d64, sums ? d64 + npx : nullptr, d32, extremes ? d32 + npx : nullptr,
+								   extremes ? d32 + 2 * npx : nullptr, extremes ? d32 + 3 * npx : nullptr, ws.ptr, work, st) != 0)
+			return -1;
+	}
+	if (sums && (!hip_ok(hipMemcpyAsync(sum, d64, npx * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+				 !hip_ok(hipMemcpyAsync(sumsq, d64 + npx, npx * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync")))
+		return -1;
+	int *outs32[4] = {min, max, argmin, argmax};
+	for (int k = 0; extremes && k < 4; ++k)
+		if (!hip_ok(hipMemcpyAsync(outs32[k], d32 + (size_t)k * npx, npx * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync"))
+			return -1;
+	return hip_ok(wait_stream(st), "pixel_stats") ? 0 : -1;
 }
 
 RIR_EXPORT void bad_pixels_destroy(int handle)

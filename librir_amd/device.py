@@ -9,7 +9,8 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
-from .signal_processing.rir_signal_processing import RegionStats, _region_stats_args, _temporal_median_args  # noqa: F401 (RegionStats: API)
+from .signal_processing.rir_signal_processing import (PixelStats, RegionStats, _pixel_stats_args, _region_stats_args,  # noqa: F401 (API)
+                                                      _temporal_median_args)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -112,6 +113,9 @@ _lib.rir_temporal_median_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_i
 _lib.rir_region_stats_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp] * 8 + [ct.c_size_t, _vp]
 _lib.rir_region_stats_workspace_bytes.argtypes = [ct.c_int] * 5
 _lib.rir_region_stats_workspace_bytes.restype = ct.c_size_t
+_lib.rir_pixel_stats_device.argtypes = [_vp] + [ct.c_int] * 5 + [_vp] * 7 + [ct.c_size_t, _vp]
+_lib.rir_pixel_stats_workspace_bytes.argtypes = [ct.c_int] * 3
+_lib.rir_pixel_stats_workspace_bytes.restype = ct.c_size_t
 _lib.bad_pixels_destroy.argtypes = [ct.c_int]
 _lib.rir_label_workspace_bytes.argtypes = [ct.c_int, ct.c_int]
 _lib.rir_label_workspace_bytes.restype = ct.c_size_t
@@ -743,6 +747,114 @@ def region_stats(frames, labels, nregions=None):
     if n:
         _region_stats_into(fr, lab, per_frame, int(nregions), out)
     return out
+
+
+def _pixel_inputs(frames, sums, extremes, t0):
+    """pixel_stats' checks, those that need no device first; -> (frames, n, h, w)"""
+    if frames.dtype != torch.uint16:
+        raise RuntimeError("pixel_stats: uint16 frames expected, not %s" % frames.dtype)
+    n, h, w = _pixel_stats_args(tuple(frames.shape), sums, extremes, t0)
+    if not frames.is_cuda:
+        raise RuntimeError("pixel_stats: frames on a CUDA device expected")
+    return _frames3(frames), n, h, w
+
+
+def _pixel_stats_state(h, w, device, sums, extremes, empty):
+    """the six outputs [h][w] (None for a group that is off); empty: in the empty state (sums 0, -1 elsewhere), else uninitialised"""
+    def make(dtype, fill):
+        return torch.full((h, w), fill, dtype=dtype, device=device) if empty else torch.empty((h, w), dtype=dtype, device=device)
+
+    return [make(torch.int64, 0) if sums else None for _ in range(2)] + [make(torch.int32, -1) if extremes else None for _ in range(4)]
+
+
+def _pixel_stats_into(fr, t0, accumulate, out):
+    """queue the statistics of fr [n][h][w], n >= 1, into out (six contiguous [h][w] tensors or None), written or merged"""
+    n, h, w = fr.shape
+    need = _lib.rir_pixel_stats_workspace_bytes(w, h, n)
+    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    _check(_lib.rir_pixel_stats_device(fr.data_ptr(), w, h, n, int(t0), int(accumulate), *(None if t is None else t.data_ptr() for t in out),
+                                       work.data_ptr(), work.numel() * 8, _stream()), "rir_pixel_stats_device")
+
+
+def pixel_stats(frames, sums=True, extremes=True, t0=0):
+    """Statistics over time of a uint16 stack ``frames (n, h, w)`` (or one ``(h, w)`` image: a stack of one), on the current stream (C ABI
+    ``rir_pixel_stats_device``): a ``PixelStats`` of CUDA tensors ``[h][w]`` - per pixel the exact sum and sum of squares (``sums``), the
+    min, the max and ``t0`` + the lowest frame index that holds each (``extremes``).  A group that is off is ``None`` and costs nothing."""
+    fr, n, h, w = _pixel_inputs(frames, sums, extremes, t0)
+    out = _pixel_stats_state(h, w, fr.device, sums, extremes, empty=n == 0)
+    if n:
+        _pixel_stats_into(fr, t0, 0, out)
+    return PixelStats(*out, count=n)
+
+
+class PixelStatsAccumulator:
+    """``pixel_stats`` over a sequence that arrives in batches, in any order.  ``push(frames, t0)`` merges a batch whose first frame has time
+    index ``t0`` into the state in place (``t0=None``: right after the highest index pushed so far); ``result()`` is the ``PixelStats`` so
+    far, bit for bit that of one call over the frames pushed; ``merge(stats)`` takes in a result computed elsewhere (another device's shard,
+    say) over other time indices.  The frame size is that of the first batch, or ``shape=(h, w)`` when given; before any frame arrives
+    ``result()`` is the empty state - sums 0, -1 elsewhere, ``count`` 0 - of that size, or of size ``(0, 0)`` when none is known."""
+
+    def __init__(self, sums=True, extremes=True, shape=None, device=None):
+        _pixel_stats_args((0, 1, 1) if shape is None else (0,) + tuple(shape), sums, extremes)
+        self.sums, self.extremes = bool(sums), bool(extremes)
+        self._shape0 = None if shape is None else (int(shape[0]), int(shape[1]))
+        self._device0 = device
+        self.reset()
+
+    def reset(self):
+        self.count = 0  # frames behind the state
+        self._next = 0  # one past the highest time index pushed
+        self._out = None
+        if self._shape0 is not None:
+            dev = torch.device("cuda", torch.cuda.current_device()) if self._device0 is None else torch.device(self._device0)
+            self._out = _pixel_stats_state(*self._shape0, dev, self.sums, self.extremes, empty=True)
+
+    def _state(self, h, w, device):
+        if self._out is None:
+            self._out = _pixel_stats_state(h, w, device, self.sums, self.extremes, empty=True)
+        ref = next(t for t in self._out if t is not None)
+        if tuple(ref.shape) != (h, w) or ref.device != device:
+            raise RuntimeError("PixelStatsAccumulator: frames of %s on %s expected, not %s on %s" % (tuple(ref.shape), ref.device, (h, w), device))
+        return self._out
+
+    def push(self, frames, t0=None):
+        t = self._next if t0 is None else t0
+        fr, n, h, w = _pixel_inputs(frames, self.sums, self.extremes, t)
+        out = self._state(h, w, fr.device)
+        if n:
+            _pixel_stats_into(fr, t, 1, out)
+            self.count += n
+            self._next = max(self._next, int(t) + n)
+
+    def merge(self, other):
+        """take in ``other``, a ``PixelStats`` over time indices that were not pushed here: sums add; the smaller minimum wins and, of equal
+        minima, the lower time index; likewise for the maximum.  ``other`` must hold the groups this accumulator keeps."""
+        ref = next((t for t in other if t is not None), None)
+        if ref is None or (self.sums and other.sum is None) or (self.extremes and other.min is None):
+            raise ValueError("PixelStatsAccumulator.merge: the other result lacks a group that this one keeps")
+        if not other.count:
+            return
+        h, w = ref.shape
+        cur = self._out[0 if self.sums else 2].device if self._out is not None else None
+        dev = cur if cur is not None else (ref.device if hasattr(ref, "is_cuda") and ref.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        out = self._state(int(h), int(w), dev)
+        o = [None if t is None else torch.as_tensor(t).to(dev) for t in other]
+        if self.sums:
+            out[0] += o[0]
+            out[1] += o[1]
+        if self.extremes:
+            for val, arg, better in ((2, 4, torch.lt), (3, 5, torch.gt)):
+                mine, theirs = out[val], o[val]
+                take = (theirs >= 0) & ((mine < 0) | better(theirs, mine) | ((theirs == mine) & (o[arg] < out[arg])))
+                out[arg].copy_(torch.where(take, o[arg], out[arg]))
+                out[val].copy_(torch.where(take, theirs, mine))
+        self.count += other.count
+
+    def result(self):
+        if self._out is None:
+            dev = torch.device("cuda", torch.cuda.current_device()) if self._device0 is None else torch.device(self._device0)
+            return PixelStats(*_pixel_stats_state(0, 0, dev, self.sums, self.extremes, empty=True), count=0)
+        return PixelStats(*(None if t is None else t.clone() for t in self._out), count=self.count)
 
 
 def _label_args(image, background):

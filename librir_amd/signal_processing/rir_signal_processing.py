@@ -275,6 +275,78 @@ def region_stats(images, labels, nregions=None):
     return out
 
 
+# ---- extension: per-pixel statistics over time ----------------------------------------------------------------------------------
+_sp.rir_pixel_stats.argtypes = [ct.c_void_p] + [ct.c_int] * 3 + [ct.c_void_p] * 6
+
+_PIXEL_DTYPES = ("int64", "int64", "int32", "int32", "int32", "int32")  # of sum sumsq min max argmin argmax
+
+
+class PixelStats(namedtuple("PixelStats", "sum sumsq min max argmin argmax")):
+    """Statistics per pixel over time, each ``[h][w]``: sum and sumsq (int64, exact), min and max (int32), argmin and argmax (int32: the
+    lowest time index that holds the extreme).  A group that was not asked for (sum, sumsq / min, max, argmin, argmax) is ``None``.
+    ``count`` is the number of frames behind them; with none the sums are 0 and the other four -1.  numpy arrays
+    (``signal_processing.pixel_stats``) or CUDA tensors (``device.pixel_stats``)."""
+
+    count = 0
+
+    def __new__(cls, sum, sumsq, min, max, argmin, argmax, count=0):
+        self = super().__new__(cls, sum, sumsq, min, max, argmin, argmax)
+        self.count = int(count)
+        return self
+
+    def mean(self):
+        """float64 mean from the exact sum; NaN where count == 0"""
+        if isinstance(self.sum, np.ndarray):
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return self.sum.astype(np.float64) / np.float64(self.count)
+        return self.sum.double() / float(self.count) if self.count else self.sum.double() * float("nan")
+
+    def std(self):
+        """float64 population standard deviation from the exact sums; NaN where count == 0"""
+        if isinstance(self.sum, np.ndarray):
+            c = np.float64(self.count)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                m = self.sum / c
+                return np.sqrt(np.maximum((self.sumsq - self.sum * m) / c, 0.0))
+        if not self.count:
+            return self.sum.double() * float("nan")
+        c = float(self.count)
+        m = self.sum.double() / c
+        return ((self.sumsq.double() - self.sum.double() * m) / c).clamp_min(0.0).sqrt()
+
+
+def _pixel_stats_args(frames_shape, sums=True, extremes=True, t0=0):
+    """the arguments of a pixel_stats call, checked without a device; -> (n, h, w)"""
+    if len(frames_shape) == 2:
+        frames_shape = (1,) + tuple(frames_shape)
+    if len(frames_shape) != 3:
+        raise ValueError("pixel_stats: frames (n, h, w) or (h, w) expected")
+    n, h, w = frames_shape
+    if h < 1 or w < 1 or h * w >= 1 << 31:
+        raise ValueError("pixel_stats: frames of at least 1x1 and fewer than 2^31 pixels expected")
+    if not sums and not extremes:
+        raise ValueError("pixel_stats: at least one of sums and extremes expected")
+    if int(t0) != t0 or t0 < 0 or t0 + n > (1 << 31) - 1:
+        raise ValueError("pixel_stats: t0 >= 0 with t0 + n <= 2^31 - 1 expected (got t0 = %r, n = %d)" % (t0, n))
+    return n, h, w
+
+
+def pixel_stats(images, sums=True, extremes=True):
+    """Extension: statistics over time of a uint16 stack ``images[n][h][w]`` (or one ``(h, w)`` image): a ``PixelStats`` of numpy arrays
+    ``[h][w]`` (``rir_pixel_stats``) - per pixel the exact sum and sum of squares (``sums``), the min, the max and the lowest image index of
+    each (``extremes``).  ``ValueError`` on bad shapes or when neither group is asked for, ``RuntimeError`` on other dtypes and when the
+    library fails."""
+    img = np.ascontiguousarray(images)
+    if img.dtype != np.uint16:
+        raise RuntimeError("pixel_stats: uint16 images expected, not %s" % img.dtype)
+    n, h, w = _pixel_stats_args(img.shape, sums, extremes)
+    on = (sums, sums, extremes, extremes, extremes, extremes)
+    out = [np.full((h, w), 0 if k < 2 else -1, dt) if g else None for k, (g, dt) in enumerate(zip(on, _PIXEL_DTYPES))]
+    if n and _sp.rir_pixel_stats(img.ctypes.data, w, h, n, *(a.ctypes.data if a is not None else None for a in out)) < 0:
+        raise RuntimeError("An error occured while calling 'pixel_stats': " + (last_error() or ""))
+    return PixelStats(*out, count=n)
+
+
 # ---- time axes (host bookkeeping, csrc/time_series.cpp) -------------------------------------------------------------------------
 _sp.extract_times.argtypes = [ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p, ct.POINTER(ct.c_int)]
 _sp.resample_time_serie.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_void_p, ct.POINTER(ct.c_int)]

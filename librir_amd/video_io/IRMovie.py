@@ -370,7 +370,30 @@ class IRMovie(object):
             _region_stats_into(fr, lab, 0, int(nregions), type(out)(*(t[k0:k0 + len(sel)] for t in out)))
         return out
 
-    def _stats_positions(self, selection):
+    def pixel_stats(self, selection=slice(None), sums=True, extremes=True):
+        """Statistics over time of the images of ``selection`` (as ``region_stats`` takes it) - ``librir_amd.device.pixel_stats`` over the
+        images ``movie[selection]`` gives (read-back filters applied): a ``PixelStats`` of CUDA tensors ``[h][w]``, per pixel the exact sum
+        and sum of squares (``sums``), the min, the max and where each first occurs (``extremes``).  ``argmin`` / ``argmax`` index into the
+        selection: k means image ``movie[selection][k]``.  The recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of images
+        into one accumulator, so the device memory used does not grow with the selection."""
+        import torch
+
+        from ..device import PixelStatsAccumulator
+
+        h, w = self.image_size
+        positions = self._stats_positions(selection, "pixel_stats")
+        device = torch.device("cuda", torch.cuda.current_device())
+        acc = PixelStatsAccumulator(sums, extremes, shape=(h, w), device=device)
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=device)
+        for k0 in range(0, len(positions), per_piece):
+            sel = positions[k0:k0 + per_piece]
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            acc.push(fr, k0)
+        return acc.result()
+
+    def _stats_positions(self, selection, what="region_stats"):
         """the positions of an int or a slice with a positive step, as to_tensor takes them"""
         total = self.images
         if isinstance(selection, (int, np.integer)):
@@ -380,9 +403,9 @@ class IRMovie(object):
             return range(pos, pos + 1)
         if isinstance(selection, slice):
             if selection.step is not None and selection.step <= 0:
-                raise ValueError("region_stats: a slice with a positive step expected")
+                raise ValueError("%s: a slice with a positive step expected" % what)
             return self._positions(selection)[0]
-        raise TypeError("region_stats: an int or a slice expected")
+        raise TypeError("%s: an int or a slice expected" % what)
 
     def load_secs(self, time, calibration=None):
         """The image whose time stamp is closest to ``time`` (seconds)."""
