@@ -58,14 +58,7 @@ namespace rir
 	{
 		if (!TABLE)
 			return one;
-		static_assert(sizeof(LossyStep) % 8 == 0, "LossyStep is copied in 8-byte words");
-		LossyStep p;
-		RIR_GLOBAL(const unsigned long long) *src = (RIR_GLOBAL(const unsigned long long) *)(table + blockIdx.y); // (wave-uniform: scalar loads)
-		unsigned long long *dst = reinterpret_cast<unsigned long long *>(&p);
-#pragma unroll
-		for (size_t k = 0; k < sizeof(LossyStep) / 8; ++k)
-			dst[k] = src[k];
-		return p;
+		return lossy_load_struct(table + blockIdx.y);
 	}
 	// Sum of a 64-bit integer over the wave, the same value in every lane: four DPP steps inside each row of 16 lanes (xor 1, xor 2,
 	// mirror of 8, mirror of 16 - integer sums do not care about the pairing), then the four rows through readlane.  A butterfly
@@ -602,49 +595,42 @@ namespace rir
 		return d;
 	}
 
-	// L2: sums of |t - prev| and of its (32-bit wrapped) square, split by img > background.
-	// stats[1..6] = {fg sum d, fg sum d2, fg count, bg sum d, bg sum d2, bg count}; the last workgroup to arrive turns
-	// them into the frame's error budget (lossy_budget) and clears them for the next frame.
-	template <bool TABLE>
-	__global__ __launch_bounds__(256) void lossy_sums_budget_kernel(LossyStep one, const LossyStep *__restrict__ table)
+	// L2 of ONE pixel (stdDev, h264.cpp:1993-2036): d = |t - prev|, t = the pixel less the optional minimum, prev = the previous output; its
+	// square wraps at 32 bits and is added as a SIGNED number; foreground or background by iv > background (iv: the pixel as it came).
+	// S: what the sums of d and the counts are kept in - 32 bits where a thread, or a wave, has few pixels.
+	template <class S>
+	struct LossySums
 	{
-		const LossyStep sp = lossy_step_of<TABLE>(one, table);
-		RIR_GLOBAL(const uint16_t) *prevT = as_global((const uint16_t *)sp.st.prevT), *tmp = as_global(sp.tmp), *img = as_global(sp.img);
-		RIR_GLOBAL(long long) *stats = as_global(sp.stats);
-		const int s = sp.s, subtract_min = sp.st.subtract_min;
-		const uint32_t mn = sp.st.min;
-		const uint32_t background = (uint32_t)stats[0];
-		long long a[6] = {0, 0, 0, 0, 0, 0};
-		auto pixel = [&](uint32_t tv, uint32_t pv, uint32_t iv) {
-			const uint32_t t = subtract_min ? sub_min(tv, mn) : tv;
-			const int32_t d = abs((int32_t)t - (int32_t)pv);
+		S fd = 0, fn = 0, bd = 0, bn = 0;
+		long long f2 = 0, b2 = 0;
+		// counted: false for a lane's pixels outside the lossy rows (they are on the background side with d = 0, and counted nowhere)
+		__device__ __forceinline__ void add(uint32_t v, uint32_t prev, uint32_t iv, uint32_t background, int subtract_min, uint32_t mn, bool counted = true)
+		{
+			const uint32_t t = subtract_min ? sub_min(v, mn) : v;
+			const int32_t d = counted ? abs((int32_t)t - (int32_t)prev) : 0;
 			const int32_t d2 = (int32_t)((uint32_t)d * (uint32_t)d);
-			const int o = iv > background ? 0 : 3;
-			a[o] += d;
-			a[o + 1] += d2;
-			a[o + 2] += 1;
-		};
-		if ((s & 7) == 0)
-		{ // 8 pixels per 16-byte load
-			for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s / 8; i += gridDim.x * blockDim.x)
-			{
-				const lossy_v4u tv = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(tmp + (size_t)i * 8);
-				const lossy_v4u pv = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(prevT + (size_t)i * 8);
-				const lossy_v4u iv = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(img + (size_t)i * 8);
-#pragma unroll
-				for (int k = 0; k < 4; ++k)
-				{
-					pixel(tv[k] & 0xffffu, pv[k] & 0xffffu, iv[k] & 0xffffu);
-					pixel(tv[k] >> 16, pv[k] >> 16, iv[k] >> 16);
-				}
-			}
+			const int one = counted ? 1 : 0;
+			// (on a copy: the two sides storing through `this` become one store to a selected address, and the sums live in scratch)
+			LossySums a = *this;
+			if (iv > background)
+				a.fd += d, a.f2 += d2, a.fn += one;
+			else
+				a.bd += d, a.b2 += d2, a.bn += one;
+			*this = a;
 		}
-		else
-			for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s; i += gridDim.x * blockDim.x)
-				pixel(tmp[i], prevT[i], img[i]);
+		// stats[1..6] = {fg sum d, fg sum d2, fg count, bg sum d, bg sum d2, bg count}
+		__device__ __forceinline__ void words(long long *a) const { a[0] = fd, a[1] = f2, a[2] = fn, a[3] = bd, a[4] = b2, a[5] = bn; }
+	};
+	// The sums of a frame over the launch and, in the last workgroup to arrive, its budget (lossy_budget): stats[1..6] are added to with
+	// atomics and cleared for the next frame by the last arriver.  a[6]: this thread's share (64 bits each: a thread may stride over the whole
+	// frame); every thread of the workgroup calls.
+	__device__ __forceinline__ void lossy_sums_tail(const LossyStep &sp, const long long *a, long long background, int *errors_out)
+	{
+		RIR_GLOBAL(long long) *stats = as_global(sp.stats);
 		// wave reduction, then the four waves of the block through LDS: one atomic per block and sum (a few hundred
 		// in total - one per wave made 24 000 contended 64-bit atomics and cost 0.29 ms per frame)
 		__shared__ long long red[4][6];
+		__shared__ LossyBudget bl;
 #pragma unroll
 		for (int k = 0; k < 6; ++k)
 		{
@@ -668,7 +654,6 @@ namespace rir
 			stats[1 + threadIdx.x] = 0; // the sums are accumulated with atomics: cleared for the next frame
 		}
 		// the budget state comes to LDS in one coalesced load, is worked on there by one thread, and goes back the same way
-		__shared__ LossyBudget bl;
 		static_assert(sizeof(LossyBudget) % 8 == 0 && sizeof(LossyBudget) / 8 <= 256, "LossyBudget is moved by one 8-byte word per thread");
 		RIR_GLOBAL(unsigned long long) *gb = (RIR_GLOBAL(unsigned long long) *)as_global(sp.budget);
 		unsigned long long *lb = reinterpret_cast<unsigned long long *>(&bl);
@@ -678,117 +663,99 @@ namespace rir
 		if (threadIdx.x == 0)
 		{
 			long long st[7];
-			st[0] = stats[0];
+			st[0] = background;
 			for (int i = 1; i < 7; ++i)
 				st[i] = red[1][i - 1];
-			lossy_budget(sp, st, bl, sp.errors_out);
+			lossy_budget(sp, st, bl, errors_out);
 		}
 		__syncthreads();
 		if (threadIdx.x < sizeof(LossyBudget) / 8)
 			gb[threadIdx.x] = lb[threadIdx.x];
 	}
 
-	// L3 + L4: running average update and decision loop, one thread per pixel of the whole frame.
+	// L2: sums of |t - prev| and of its (32-bit wrapped) square, split by img > background.
+	// stats[1..6] = {fg sum d, fg sum d2, fg count, bg sum d, bg sum d2, bg count}; the last workgroup to arrive turns
+	// them into the frame's error budget (lossy_budget) and clears them for the next frame.
 	template <bool TABLE>
-	__global__ __launch_bounds__(256) void lossy_update_kernel(LossyStep one, const LossyStep *__restrict__ table)
+	__global__ __launch_bounds__(256) void lossy_sums_budget_kernel(LossyStep one, const LossyStep *__restrict__ table)
 	{
 		const LossyStep sp = lossy_step_of<TABLE>(one, table);
-		RIR_GLOBAL(const uint16_t) *tmp = as_global(sp.tmp);
-		RIR_GLOBAL(uint16_t) *out = as_global(sp.out);
-		const LossyDeviceState st_ = sp.st;
-		struct
-		{ // the state's arrays through global pointers; the scalars as they are
-			RIR_GLOBAL(uint16_t) * refT, *prevT, *lastDL, *ra_const_value, *ra_images;
-			RIR_GLOBAL(uint32_t) * ra_sums;
-			RIR_GLOBAL(int16_t) * ra_const_count;
-			int ra_count, ra_head, running_average, subtract_min;
-			uint32_t min;
-		} st = {as_global(st_.refT), as_global(st_.prevT), as_global(st_.lastDL), as_global(st_.ra_const_value), as_global(st_.ra_images),
-				as_global(st_.ra_sums), as_global(st_.ra_const_count), st_.ra_count, st_.ra_head, st_.running_average, st_.subtract_min, st_.min};
-		RIR_GLOBAL(const LossyDecision) *decision = as_global((const LossyDecision *)sp.decision);
-		const int s = sp.s, full = sp.full, add_loss = sp.add_loss;
-		const int i = blockIdx.x * blockDim.x + threadIdx.x;
-		if (i >= full)
-			return;
-		const uint32_t background = decision->background;
-		const int low_error = decision->low_error, high_error = decision->high_error;
-		const uint32_t v = tmp[i];
-		if (i >= s)
-		{ // rows past lossy_height: stored as they are
-			out[i] = (uint16_t)v;
-			st.lastDL[i] = (uint16_t)v;
-			return;
-		}
-		uint32_t t = st.subtract_min ? sub_min(v, st.min) : v;
-		const int ra = st.running_average;
-		uint32_t sum = 0;
-		if (ra > 0)
-		{ // RunningAverage2::addImage
-			sum = st.ra_sums[i] + t;
-			if (st.ra_count == ra)
+		RIR_GLOBAL(const uint16_t) *prevT = as_global((const uint16_t *)sp.st.prevT), *tmp = as_global(sp.tmp), *img = as_global(sp.img);
+		const int s = sp.s, subtract_min = sp.st.subtract_min;
+		const uint32_t mn = sp.st.min;
+		const long long stats0 = as_global(sp.stats)[0];
+		const uint32_t background = (uint32_t)stats0;
+		LossySums<long long> sm;
+		if ((s & 7) == 0)
+		{ // 8 pixels per 16-byte load
+			for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s / 8; i += gridDim.x * blockDim.x)
 			{
-				const int16_t cc = st.ra_const_count[i];
-				if (cc)
+				const lossy_v4u tv = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(tmp + (size_t)i * 8);
+				const lossy_v4u pv = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(prevT + (size_t)i * 8);
+				const lossy_v4u iv = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(img + (size_t)i * 8);
+#pragma unroll
+				for (int k = 0; k < 4; ++k)
 				{
-					st.ra_const_count[i] = (int16_t)(cc - 1);
-					sum -= st.ra_const_value[i];
+					sm.add(tv[k] & 0xffffu, pv[k] & 0xffffu, iv[k] & 0xffffu, background, subtract_min, mn);
+					sm.add(tv[k] >> 16, pv[k] >> 16, iv[k] >> 16, background, subtract_min, mn);
 				}
-				else
-					sum -= st.ra_images[(size_t)st.ra_head * s + i];
 			}
-			// the new image takes the free slot (ring not full) or replaces the oldest one
-			const int slot = (st.ra_count == ra) ? st.ra_head : (st.ra_head + st.ra_count) % ra;
-			st.ra_images[(size_t)slot * s + i] = (uint16_t)t;
 		}
-		const int n_after = ra > 0 ? (st.ra_count == ra ? ra : st.ra_count + 1) : 0; // images.size() after addImage
-		const uint32_t ref = st.refT[i];
-		const int diff = abs((int)t - (int)ref);
-		const int max_error = v > background ? high_error : low_error;
-		bool keep = diff <= max_error;
-		if (!add_loss)
-			keep = keep && ((st.lastDL[i] >> 13) == (v >> 13));
-		if (keep)
-			t = ra > 0 ? sum / (uint32_t)n_after : ref;
 		else
-		{
-			st.refT[i] = (uint16_t)t;
-			if (ra > 0)
-			{
-				st.ra_const_value[i] = (uint16_t)t;
-				st.ra_const_count[i] = (int16_t)n_after;
-				sum = t * (uint32_t)n_after;
-			}
-		}
-		if (ra > 0)
-			st.ra_sums[i] = sum;
-		out[i] = (uint16_t)t;
-		st.prevT[i] = (uint16_t)t;
-		st.lastDL[i] = (uint16_t)v;
+			for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < s; i += gridDim.x * blockDim.x)
+				sm.add(tmp[i], prevT[i], img[i], background, subtract_min, mn);
+		long long a[6];
+		sm.words(a);
+		lossy_sums_tail(sp, a, stats0, sp.errors_out);
 	}
 
-	// The same update, 8 consecutive pixels per thread through 16-byte loads and stores (used when the lossy region and the frame
-	// are whole multiples of 8 pixels: every group is wholly inside or wholly past lossy_height).  One pixel per thread moves 2
-	// bytes per lane and instruction: with 32 streams per launch that kernel ran at a third of the bandwidth this one reaches.
-	struct U16x8
+	// 2 NP consecutive pixels of a thread, two to a word (NP = 4: one 16-byte access per thread and array).  One pixel per thread moves 2
+	// bytes per lane and instruction: with 32 streams per launch the per-pixel update ran at a third of the bandwidth the 8-pixel one reaches.
+	typedef unsigned int lossy_v2u __attribute__((ext_vector_type(2)));
+	template <int NP>
+	struct PxN
 	{
-		uint32_t d[4];
+		uint32_t d[NP];
 		__device__ __forceinline__ uint32_t get(int k) const { return (k & 1) ? d[k >> 1] >> 16 : d[k >> 1] & 0xffffu; }
 		__device__ __forceinline__ void set(int k, uint32_t v) { d[k >> 1] = (k & 1) ? (d[k >> 1] & 0x0000ffffu) | (v << 16) : (d[k >> 1] & 0xffff0000u) | (v & 0xffffu); }
 	};
-	template <class P>
-	__device__ __forceinline__ U16x8 ld8(P p, int i8)
+	typedef PxN<4> U16x8;
+	// group i of 2 NP pixels of the array p
+	template <int NP, class P>
+	__device__ __forceinline__ PxN<NP> ldn(P p, size_t i)
 	{
-		const lossy_v4u v = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(p + (size_t)i8 * 8);
-		U16x8 r;
-		r.d[0] = v.x, r.d[1] = v.y, r.d[2] = v.z, r.d[3] = v.w;
+		PxN<NP> r;
+		if constexpr (NP == 4)
+		{
+			const lossy_v4u v = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(p + i * 8);
+			r.d[0] = v.x, r.d[1] = v.y, r.d[2] = v.z, r.d[3] = v.w;
+		}
+		else if constexpr (NP == 2)
+		{
+			const lossy_v2u v = *reinterpret_cast<RIR_GLOBAL(const lossy_v2u) *>(p + i * 4);
+			r.d[0] = v.x, r.d[1] = v.y;
+		}
+		else
+			r.d[0] = *reinterpret_cast<RIR_GLOBAL(const uint32_t) *>(p + i * 2);
 		return r;
 	}
-	template <class P>
-	__device__ __forceinline__ void st8(P p, int i8, const U16x8 &r)
+	template <int NP, class P>
+	__device__ __forceinline__ void stn(P p, size_t i, const PxN<NP> &r)
 	{
-		lossy_v4u v;
-		v.x = r.d[0], v.y = r.d[1], v.z = r.d[2], v.w = r.d[3];
-		*reinterpret_cast<RIR_GLOBAL(lossy_v4u) *>(p + (size_t)i8 * 8) = v;
+		if constexpr (NP == 4)
+		{
+			lossy_v4u v;
+			v.x = r.d[0], v.y = r.d[1], v.z = r.d[2], v.w = r.d[3];
+			*reinterpret_cast<RIR_GLOBAL(lossy_v4u) *>(p + i * 8) = v;
+		}
+		else if constexpr (NP == 2)
+		{
+			lossy_v2u v;
+			v.x = r.d[0], v.y = r.d[1];
+			*reinterpret_cast<RIR_GLOBAL(lossy_v2u) *>(p + i * 4) = v;
+		}
+		else
+			*reinterpret_cast<RIR_GLOBAL(uint32_t) *>(p + i * 2) = r.d[0];
 	}
 	// L3 + L4 of ONE pixel (RunningAverage2::addImage h264.cpp:1526-1615, decision loop :2397-2413 / :2574-2590), on values in
 	// registers: v = the frame's pixel, old = the ring's oldest image at this pixel (read only when the ring is full and the pixel
@@ -803,6 +770,16 @@ namespace rir
 	// floor(2^32 / n) + 1, is exact as long as sum * (M - 2^32 / n) / 2^32 < 1 / n, and sum / 2^32 < 2^-10 < 1 / 64.
 	__device__ __forceinline__ uint32_t lossy_div_magic(int n) { return n > 1 ? (uint32_t)(0x100000000ull / (uint32_t)n) + 1u : 0u; }
 	__device__ __forceinline__ uint32_t lossy_div(uint32_t sum, uint32_t magic) { return magic ? __umulhi(sum, magic) : sum; }
+	// the constants of a frame from the state and the frame's decision
+	__device__ __forceinline__ LossyFrameConsts lossy_frame_consts(const LossyDeviceState &st, RIR_GLOBAL(const LossyDecision) * decision, int add_loss)
+	{
+		const int ra = st.running_average;
+		const bool full_ring = ra > 0 && st.ra_count == ra;
+		const int n_after = ra > 0 ? (full_ring ? ra : st.ra_count + 1) : 0; // images.size() after addImage
+		const uint32_t background = decision->background;
+		const int low_error = decision->low_error, high_error = decision->high_error;
+		return {st.min, background, st.subtract_min, ra, full_ring ? 1 : 0, n_after, add_loss, low_error, high_error, lossy_div_magic(n_after)};
+	}
 	__device__ __forceinline__ uint32_t lossy_pixel(const LossyFrameConsts &c, uint32_t v, uint32_t old, uint32_t last, uint32_t &ref, uint32_t &sum, uint32_t &cc,
 												   uint32_t &cv, uint32_t *t_in, bool &ref_changed, bool &cc_changed)
 	{
@@ -846,6 +823,56 @@ namespace rir
 		sum = sm;
 		return t;
 	}
+	// the ring slot the frame's image goes to: the free slot (ring not full) or the oldest image's
+	__device__ __forceinline__ int lossy_ring_slot(const LossyDeviceState &st) { return st.ra_count == st.running_average ? st.ra_head : (st.ra_head + st.ra_count) % st.running_average; }
+
+	// L3 + L4: running average update and decision loop, one thread per pixel of the whole frame (frames whose lossy part or whose size is
+	// no multiple of 8 pixels).  The state arrays are written only where the pixel changed them.
+	template <bool TABLE>
+	__global__ __launch_bounds__(256) void lossy_update_kernel(LossyStep one, const LossyStep *__restrict__ table)
+	{
+		const LossyStep sp = lossy_step_of<TABLE>(one, table);
+		RIR_GLOBAL(const uint16_t) *tmp = as_global(sp.tmp);
+		RIR_GLOBAL(uint16_t) *out = as_global(sp.out);
+		const LossyDeviceState st = sp.st;
+		RIR_GLOBAL(uint16_t) *refT = as_global(st.refT), *lastDL = as_global(st.lastDL), *cval = as_global(st.ra_const_value), *ring = as_global(st.ra_images);
+		RIR_GLOBAL(uint16_t) *ccnt = (RIR_GLOBAL(uint16_t) *)as_global(st.ra_const_count);
+		RIR_GLOBAL(uint32_t) *sums = as_global(st.ra_sums);
+		const int s = sp.s, i = blockIdx.x * blockDim.x + threadIdx.x;
+		if (i >= sp.full)
+			return;
+		const uint32_t v = tmp[i];
+		if (i >= s)
+		{ // rows past lossy_height: stored as they are
+			out[i] = (uint16_t)v;
+			lastDL[i] = (uint16_t)v;
+			return;
+		}
+		const LossyFrameConsts fc = lossy_frame_consts(st, as_global((const LossyDecision *)sp.decision), sp.add_loss);
+		uint32_t ref = refT[i], sum = 0, cc = 0, cv = 0, old = 0, t_in;
+		if (fc.ra > 0)
+		{
+			sum = sums[i], cc = ccnt[i], cv = cval[i];
+			if (fc.full_ring)
+				old = ring[(size_t)st.ra_head * s + i];
+		}
+		bool ref_changed = false, cc_changed = false;
+		const uint32_t t = lossy_pixel(fc, v, old, sp.add_loss ? 0u : (uint32_t)lastDL[i], ref, sum, cc, cv, &t_in, ref_changed, cc_changed);
+		if (fc.ra > 0)
+		{
+			ring[(size_t)lossy_ring_slot(st) * s + i] = (uint16_t)t_in;
+			sums[i] = sum;
+			if (cc_changed)
+				ccnt[i] = (uint16_t)cc;
+			if (ref_changed) // (a pixel that is not kept begins a constant stretch at its value)
+				cval[i] = (uint16_t)cv;
+		}
+		if (ref_changed)
+			refT[i] = (uint16_t)ref;
+		out[i] = (uint16_t)t;
+		as_global(st.prevT)[i] = (uint16_t)t;
+		lastDL[i] = (uint16_t)v;
+	}
 
 	// L3 + L4 for the 8 pixels of group i8 (inside the lossy rows), v8 = the frame's pixels: state arrays updated, the lossy pixels
 	// stored to `out` (and to prevT when store_prev) and returned.
@@ -864,18 +891,18 @@ namespace rir
 		const int ra = st.running_average;
 		const bool full_ring = ra > 0 && st.ra_count == ra;
 		const int n_after = ra > 0 ? (full_ring ? ra : st.ra_count + 1) : 0; // images.size() after addImage
-		U16x8 ref8 = ld8(refT, i8), last8, cc8, cv8, old8, t8, o8;
+		U16x8 ref8 = ldn<4>(refT, i8), last8, cc8, cv8, old8, t8, o8;
 		uint32_t sum[8];
 		if (!add_loss)
-			last8 = ld8(lastDL, i8);
+			last8 = ldn<4>(lastDL, i8);
 		if (ra > 0)
 		{
 			const lossy_v4u s0 = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(sums + (size_t)i8 * 8), s1 = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(sums + (size_t)i8 * 8 + 4);
 			sum[0] = s0.x, sum[1] = s0.y, sum[2] = s0.z, sum[3] = s0.w, sum[4] = s1.x, sum[5] = s1.y, sum[6] = s1.z, sum[7] = s1.w;
-			cc8 = ld8(ccnt, i8);
-			cv8 = ld8(cval, i8);
+			cc8 = ldn<4>(ccnt, i8);
+			cv8 = ldn<4>(cval, i8);
 			if (full_ring)
-				old8 = ld8(ring + (size_t)st.ra_head * s, i8);
+				old8 = ldn<4>(ring + (size_t)st.ra_head * s, i8);
 		}
 		bool ref_changed = false, cc_changed = false; // (per group of 8: the arrays are written back only where a pixel changed them)
 		const LossyFrameConsts fc = {st.min, background, st.subtract_min, ra, full_ring ? 1 : 0, n_after, add_loss, low_error, high_error, lossy_div_magic(n_after)};
@@ -895,26 +922,28 @@ namespace rir
 		{
 			// the new image takes the free slot (ring not full) or replaces the oldest one
 			const int slot = full_ring ? st.ra_head : (st.ra_head + st.ra_count) % ra;
-			st8(ring + (size_t)slot * s, i8, t8);
+			stn<4>(ring + (size_t)slot * s, i8, t8);
 			lossy_v4u s0, s1;
 			s0.x = sum[0], s0.y = sum[1], s0.z = sum[2], s0.w = sum[3], s1.x = sum[4], s1.y = sum[5], s1.z = sum[6], s1.w = sum[7];
 			*reinterpret_cast<RIR_GLOBAL(lossy_v4u) *>(sums + (size_t)i8 * 8) = s0;
 			*reinterpret_cast<RIR_GLOBAL(lossy_v4u) *>(sums + (size_t)i8 * 8 + 4) = s1;
 			if (cc_changed)
 			{
-				st8(ccnt, i8, cc8);
-				st8(cval, i8, cv8);
+				stn<4>(ccnt, i8, cc8);
+				stn<4>(cval, i8, cv8);
 			}
 		}
 		if (ref_changed)
-			st8(refT, i8, ref8);
-		st8(out, i8, o8);
+			stn<4>(refT, i8, ref8);
+		stn<4>(out, i8, o8);
 		if (store_prev)
-			st8(prevT, i8, o8);
-		st8(lastDL, i8, v8);
+			stn<4>(prevT, i8, o8);
+		stn<4>(lastDL, i8, v8);
 		return o8;
 	}
 
+	// The same update, 8 consecutive pixels per thread through 16-byte loads and stores (used when the lossy region and the frame
+	// are whole multiples of 8 pixels: every group is wholly inside or wholly past lossy_height).
 	template <bool TABLE>
 	__global__ __launch_bounds__(256) void lossy_update_vec_kernel(LossyStep one, const LossyStep *__restrict__ table)
 	{
@@ -922,60 +951,14 @@ namespace rir
 		const int i8 = blockIdx.x * blockDim.x + threadIdx.x; // group of 8 pixels
 		if (i8 * 8 >= sp.full)
 			return;
-		const U16x8 v8 = ld8(as_global(sp.tmp), i8);
+		const U16x8 v8 = ldn<4>(as_global(sp.tmp), i8);
 		if (i8 * 8 >= sp.s)
 		{ // rows past lossy_height: stored as they are
-			st8(as_global(sp.out), i8, v8);
-			st8(as_global(sp.st.lastDL), i8, v8);
+			stn<4>(as_global(sp.out), i8, v8);
+			stn<4>(as_global(sp.st.lastDL), i8, v8);
 			return;
 		}
 		(void)lossy_update8(sp, i8, v8, true);
-	}
-
-	// The sums of a frame and, in the last workgroup to arrive, its budget: tail shared by lossy_sums_budget_kernel's form for
-	// runs.  a[6]: this thread's share; every thread of the workgroup calls.
-	__device__ __forceinline__ void lossy_sums_tail(const LossyStep &sp, const long long *a, long long background, int *errors_out)
-	{
-		RIR_GLOBAL(long long) *stats = as_global(sp.stats);
-		__shared__ long long red[4][6];
-		__shared__ LossyBudget bl;
-#pragma unroll
-		for (int k = 0; k < 6; ++k)
-		{
-			const long long v = lossy_wave_sum(a[k]);
-			if ((threadIdx.x & 63) == 0)
-				red[threadIdx.x >> 6][k] = v;
-		}
-		__syncthreads();
-		if (threadIdx.x < 6)
-		{
-			const long long v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-			if (v)
-				__hip_atomic_fetch_add((RIR_GLOBAL(unsigned long long) *)&stats[1 + threadIdx.x], (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		}
-		if (!lossy_last_arriver(sp.tickets + 1, gridDim.x, reinterpret_cast<unsigned int *>(&red[0][0])))
-			return;
-		if (threadIdx.x < 6)
-		{
-			red[1][threadIdx.x] = (long long)__hip_atomic_load((RIR_GLOBAL(unsigned long long) *)&stats[1 + threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-			stats[1 + threadIdx.x] = 0; // the sums are accumulated with atomics: cleared for the next frame
-		}
-		RIR_GLOBAL(unsigned long long) *gb = (RIR_GLOBAL(unsigned long long) *)as_global(sp.budget);
-		unsigned long long *lb = reinterpret_cast<unsigned long long *>(&bl);
-		if (threadIdx.x < sizeof(LossyBudget) / 8)
-			lb[threadIdx.x] = gb[threadIdx.x];
-		__syncthreads();
-		if (threadIdx.x == 0)
-		{
-			long long st[7];
-			st[0] = background;
-			for (int i = 1; i < 7; ++i)
-				st[i] = red[1][i - 1];
-			lossy_budget(sp, st, bl, errors_out);
-		}
-		__syncthreads();
-		if (threadIdx.x < sizeof(LossyBudget) / 8)
-			gb[threadIdx.x] = lb[threadIdx.x];
 	}
 
 	// One launch per frame of a run (lossy_kernels.h, LossyStep::next_*): L3 + L4 of frame f, and L2 of frame f + 1 taken while
@@ -995,42 +978,31 @@ namespace rir
 		{
 			if (inside)
 			{
-				const U16x8 v8 = ld8(as_global(sp.tmp), i8);
+				const U16x8 v8 = ldn<4>(as_global(sp.tmp), i8);
 				if (lossy)
 					o8 = lossy_update8(sp, i8, v8, !next);
 				else
 				{ // rows past lossy_height: stored as they are
-					st8(as_global(sp.out), i8, v8);
-					st8(as_global(sp.st.lastDL), i8, v8);
+					stn<4>(as_global(sp.out), i8, v8);
+					stn<4>(as_global(sp.st.lastDL), i8, v8);
 				}
 			}
 		}
 		else if (lossy)
-			o8 = ld8(as_global((const uint16_t *)sp.st.prevT), i8);
+			o8 = ldn<4>(as_global((const uint16_t *)sp.st.prevT), i8);
 		if (!next)
 			return; // (the whole grid)
 		long long a[6] = {0, 0, 0, 0, 0, 0};
 		const long long background = *as_global(sp.next_background);
 		if (lossy)
 		{
-			const int subtract_min = sp.st.subtract_min;
-			const uint32_t mn = sp.st.min, bg = (uint32_t)background;
-			const U16x8 tv = ld8(as_global(sp.next_tmp), i8);
-			const U16x8 iv = sp.next_img == sp.next_tmp ? tv : ld8(as_global(sp.next_img), i8);
-			int32_t fd = 0, fn = 0, bd = 0; // (8 pixels: |d| < 65 536; the wrapped squares are summed in 64 bits)
-			long long f2 = 0, b2 = 0;
+			const U16x8 tv = ldn<4>(as_global(sp.next_tmp), i8);
+			const U16x8 iv = sp.next_img == sp.next_tmp ? tv : ldn<4>(as_global(sp.next_img), i8);
+			LossySums<int32_t> sm; // (8 pixels: |d| < 65 536; the wrapped squares are summed in 64 bits)
 #pragma unroll
 			for (int k = 0; k < 8; ++k)
-			{
-				const uint32_t t = subtract_min ? sub_min(tv.get(k), mn) : tv.get(k);
-				const int32_t d = abs((int32_t)t - (int32_t)o8.get(k));
-				const int32_t d2 = (int32_t)((uint32_t)d * (uint32_t)d);
-				if (iv.get(k) > bg)
-					fd += d, f2 += d2, fn += 1;
-				else
-					bd += d, b2 += d2;
-			}
-			a[0] = fd, a[1] = f2, a[2] = fn, a[3] = bd, a[4] = b2, a[5] = 8 - fn;
+				sm.add(tv.get(k), o8.get(k), iv.get(k), (uint32_t)background, sp.st.subtract_min, sp.st.min);
+			sm.words(a);
 		}
 		lossy_sums_tail(sp, a, background, sp.next_errors_out);
 	}
@@ -1133,7 +1105,7 @@ namespace rir
 	// the kernel be built for 6 waves per SIMD (80 VGPRs, nothing spilled; 25.6 KB of LDS: six workgroups to a CU) instead of 5: NINE
 	// streams of 640x512 per launch instead of seven.  Seven streams run about as fast either way (568 against 580 k frames/s), nine at
 	// once are faster than seven (636 k): the host takes this form when it saves a launch (lossy_run_parked_kernel; same arithmetic,
-	// same results; scripts/lossy_forms.sh).
+	// same results; scripts/lossy_forms.sh in f3cec6e).
 	template <bool PARKED>
 	__device__ __forceinline__ void lossy_run_body(const LossyRun *__restrict__ table, unsigned int *__restrict__ ticket_, int nb, int nstreams, unsigned int epoch, unsigned int arrivals_before,
 												   const unsigned int *__restrict__ ok_word)
@@ -1207,17 +1179,17 @@ namespace rir
 		int count = st.ra_count, head = st.ra_head;
 		if (lossy)
 		{
-			ref8 = ld8(refT, i8);
-			last8 = ld8(lastDL, i8);
-			o8 = ld8(prevT, i8);
+			ref8 = ldn<4>(refT, i8);
+			last8 = ldn<4>(lastDL, i8);
+			o8 = ldn<4>(prevT, i8);
 			if (ra > 0)
 			{
 				const lossy_v4u s0 = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(sums + (size_t)i8 * 8), s1 = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(sums + (size_t)i8 * 8 + 4);
 				sum[0] = s0.x, sum[1] = s0.y, sum[2] = s0.z, sum[3] = s0.w, sum[4] = s1.x, sum[5] = s1.y, sum[6] = s1.z, sum[7] = s1.w;
-				cc8 = ld8(ccnt, i8);
-				cv8 = ld8(cval, i8);
+				cc8 = ldn<4>(ccnt, i8);
+				cv8 = ldn<4>(cval, i8);
 				if (count == ra)
-					old8 = ld8(ring + (size_t)head * s, i8);
+					old8 = ldn<4>(ring + (size_t)head * s, i8);
 			}
 		}
 		if constexpr (PARKED)
@@ -1231,7 +1203,7 @@ namespace rir
 		}
 		U16x8 v8{};
 		if (inside)
-			v8 = ld8(in, i8);
+			v8 = ldn<4>(in, i8);
 		const unsigned long long t_limit = 200000000ull; // 2 s of the 100 MHz clock
 		bool gave_up = false;
 		for (int k = 0; k < rp.nsteps; ++k)
@@ -1239,11 +1211,11 @@ namespace rir
 			// the next frame's pixels are requested now: they arrive while this frame's sums go round
 			U16x8 vn{};
 			if (inside && k + 1 < rp.nsteps)
-				vn = ld8(in + (size_t)(k + 1) * rp.frame_px, i8);
+				vn = ldn<4>(in + (size_t)(k + 1) * rp.frame_px, i8);
 			const long long background = as_global(rp.bg)[(size_t)k * rp.bg_stride];
 			// 1. this workgroup's share of the frame's sums (a packed form of the sums, four reductions instead of six, gave the same values,
-			// but its extra live registers cost more than its instructions save: 7 streams 509 k frames/s against 593 k; scripts/lossy_ab.sh,
-			// RIR_LOSSY_PACKED_SUMS in 02807a8)
+			// but its extra live registers cost more than its instructions save: 7 streams 509 k frames/s against 593 k; scripts/lossy_ab.sh
+			// in 3fb7530, RIR_LOSSY_PACKED_SUMS in 02807a8)
 			int32_t fd = 0, fn = 0, bd = 0, bn = 0;
 			long long f2 = 0, b2 = 0;
 			if (lossy)
@@ -1441,15 +1413,15 @@ namespace rir
 				}
 				if constexpr (!PARKED)
 					last8 = v8;
-				st8(out + (size_t)k * rp.frame_px, i8, o8);
+				stn<4>(out + (size_t)k * rp.frame_px, i8, o8);
 				if (ra > 0)
 				{
 					const int slot = full_ring ? head : (head + count) % ra;
-					st8(ring + (size_t)slot * s, i8, t8);
+					stn<4>(ring + (size_t)slot * s, i8, t8);
 				}
 			}
 			else if (inside)
-				st8(out + (size_t)k * rp.frame_px, i8, v8); // rows past lossy_height: stored as they are
+				stn<4>(out + (size_t)k * rp.frame_px, i8, v8); // rows past lossy_height: stored as they are
 			if (ra > 0)
 			{
 				if (count == ra)
@@ -1458,7 +1430,7 @@ namespace rir
 					++count;
 				// the oldest image for the next frame: written at least one frame ago (by this thread) unless the ring holds one image
 				if (lossy && count == ra && k + 1 < rp.nsteps)
-					old8 = ra == 1 ? t8 : ld8(ring + (size_t)head * s, i8);
+					old8 = ra == 1 ? t8 : ldn<4>(ring + (size_t)head * s, i8);
 			}
 			if (k + 1 < rp.nsteps)
 				v8 = vn;
@@ -1476,21 +1448,21 @@ namespace rir
 		}
 		if (lossy)
 		{
-			st8(refT, i8, ref8);
-			st8(lastDL, i8, last8);
-			st8(prevT, i8, o8);
+			stn<4>(refT, i8, ref8);
+			stn<4>(lastDL, i8, last8);
+			stn<4>(prevT, i8, o8);
 			if (ra > 0)
 			{
 				lossy_v4u s0, s1;
 				s0.x = sum[0], s0.y = sum[1], s0.z = sum[2], s0.w = sum[3], s1.x = sum[4], s1.y = sum[5], s1.z = sum[6], s1.w = sum[7];
 				*reinterpret_cast<RIR_GLOBAL(lossy_v4u) *>(sums + (size_t)i8 * 8) = s0;
 				*reinterpret_cast<RIR_GLOBAL(lossy_v4u) *>(sums + (size_t)i8 * 8 + 4) = s1;
-				st8(ccnt, i8, cc8);
-				st8(cval, i8, cv8);
+				stn<4>(ccnt, i8, cc8);
+				stn<4>(cval, i8, cv8);
 			}
 		}
 		else if (inside)
-			st8(lastDL, i8, v8);
+			stn<4>(lastDL, i8, v8);
 		if (b == 0)
 		{
 			__syncthreads();
@@ -1581,50 +1553,8 @@ namespace rir
 	// NP pairs of pixels per thread (4: one 16-byte access per thread, frame and array, as the resident kernel; 2; 1).  Nobody waits for anybody
 	// here, so a stream may be cut as finely as pays: with 8 pixels per thread a 640x512 stream is 640 waves on the chip's 1 024 SIMDs - each
 	// working through its ~300 vector instructions per frame alone - with 2 pixels it is 2 560 waves that hide each other's latencies.
-	typedef unsigned int lossy_v2u __attribute__((ext_vector_type(2)));
-	template <int NP>
-	struct PxN
-	{
-		uint32_t d[NP];
-		__device__ __forceinline__ uint32_t get(int k) const { return (k & 1) ? d[k >> 1] >> 16 : d[k >> 1] & 0xffffu; }
-	};
-	template <int NP, class P>
-	__device__ __forceinline__ PxN<NP> ldn(P p, size_t i)
-	{
-		PxN<NP> r;
-		if constexpr (NP == 4)
-		{
-			const lossy_v4u v = *reinterpret_cast<RIR_GLOBAL(const lossy_v4u) *>(p + i * 8);
-			r.d[0] = v.x, r.d[1] = v.y, r.d[2] = v.z, r.d[3] = v.w;
-		}
-		else if constexpr (NP == 2)
-		{
-			const lossy_v2u v = *reinterpret_cast<RIR_GLOBAL(const lossy_v2u) *>(p + i * 4);
-			r.d[0] = v.x, r.d[1] = v.y;
-		}
-		else
-			r.d[0] = *reinterpret_cast<RIR_GLOBAL(const uint32_t) *>(p + i * 2);
-		return r;
-	}
-	template <int NP, class P>
-	__device__ __forceinline__ void stn(P p, size_t i, const PxN<NP> &r)
-	{
-		if constexpr (NP == 4)
-		{
-			lossy_v4u v;
-			v.x = r.d[0], v.y = r.d[1], v.z = r.d[2], v.w = r.d[3];
-			*reinterpret_cast<RIR_GLOBAL(lossy_v4u) *>(p + i * 8) = v;
-		}
-		else if constexpr (NP == 2)
-		{
-			lossy_v2u v;
-			v.x = r.d[0], v.y = r.d[1];
-			*reinterpret_cast<RIR_GLOBAL(lossy_v2u) *>(p + i * 4) = v;
-		}
-		else
-			*reinterpret_cast<RIR_GLOBAL(uint32_t) *>(p + i * 2) = r.d[0];
-	}
-
+	// (PxN, ldn, stn: with the one-frame kernels above.)
+	//
 	// Every vector-memory operation of the frame loop is an UNCONDITIONAL raw-buffer access - a lane without a pixel, a frame past the end
 	// of the group, a ring that is not read or written this frame: an out-of-range offset or an empty descriptor, which the hardware turns
 	// into "no access" - in straight-line code: only then does the compiler keep counted waits (s_waitcnt vmcnt(N)) and the loads of the
@@ -2505,6 +2435,7 @@ namespace rir
 				}
 				else
 				{
+					LossySums<uint32_t> one_by_one;
 #pragma unroll
 					for (int j = 0; j < kIter; ++j)
 					{
@@ -2514,16 +2445,10 @@ namespace rir
 						{
 							const uint32_t aw = a[j][q >> 1], pw = p[j][q >> 1];
 							const uint32_t v = (q & 1) ? aw >> 16 : aw & 0xffffu, o = (q & 1) ? pw >> 16 : pw & 0xffffu;
-							const uint32_t t = subtract_min ? sub_min(v, mn) : v;
-							const int32_t d = in ? abs((int32_t)t - (int32_t)o) : 0;
-							const int32_t d2 = (int32_t)((uint32_t)d * (uint32_t)d);
-							const uint32_t one = in ? 1u : 0u;
-							if (v > background)
-								fd += (uint32_t)d, f2 += d2, fn += one;
-							else
-								bd += (uint32_t)d, b2 += d2, bn += one;
+							one_by_one.add(v, o, v, background, subtract_min, mn, in);
 						}
 					}
+					fd = one_by_one.fd, bd = one_by_one.bd, fn = one_by_one.fn, bn = one_by_one.bn, f2 = one_by_one.f2, b2 = one_by_one.b2;
 				}
 			}
 		}
@@ -2991,30 +2916,40 @@ namespace rir
 		return 1;
 	}
 	int lossy_const_workgroups(int full, int nstreams) { return (full / (2 * lossy_const_pairs(full, nstreams)) + 255) / 256; }
+	// The streaming kernel's instantiation for a launch: pairs per thread, and the variant - a running average or none, addLoss or not - which
+	// is the launch's: streams of a call share add_loss, and a call whose streams differ in having a running average goes through the
+	// instantiation with one, which reads each stream's own length.  SPEC: the speculative instance (no ok word, no poison; the streams' LossySpec).
+	template <bool SPEC, int NP>
+	static void lossy_const_launch_np(bool any_ra, bool add_loss, dim3 grid, hipStream_t st, const LossyRun *d_table, int nstreams, unsigned int *d_ok, const unsigned int *d_poison,
+									  const LossySpec *d_spec)
+	{
+#define RIR_CONST_LAUNCH(RA, ADD) hipLaunchKernelGGL((lossy_const_run_kernel<NP, RA, ADD, SPEC>), grid, dim3(256), 0, st, d_table, nstreams, d_ok, d_poison, d_spec)
+		if (any_ra && add_loss)
+			RIR_CONST_LAUNCH(true, true);
+		else if (any_ra)
+			RIR_CONST_LAUNCH(true, false);
+		else if (add_loss)
+			RIR_CONST_LAUNCH(false, true);
+		else
+			RIR_CONST_LAUNCH(false, false);
+#undef RIR_CONST_LAUNCH
+	}
+	template <bool SPEC>
+	static void lossy_const_launch(int np, bool any_ra, bool add_loss, dim3 grid, hipStream_t st, const LossyRun *d_table, int nstreams, unsigned int *d_ok, const unsigned int *d_poison,
+								   const LossySpec *d_spec)
+	{
+		if (np == 4)
+			lossy_const_launch_np<SPEC, 4>(any_ra, add_loss, grid, st, d_table, nstreams, d_ok, d_poison, d_spec);
+		else if (np == 2)
+			lossy_const_launch_np<SPEC, 2>(any_ra, add_loss, grid, st, d_table, nstreams, d_ok, d_poison, d_spec);
+		else
+			lossy_const_launch_np<SPEC, 1>(any_ra, add_loss, grid, st, d_table, nstreams, d_ok, d_poison, d_spec);
+	}
 	hipError_t launch_lossy_const(const LossyRun *d_table, int nstreams, int full, bool any_ra, bool add_loss, unsigned int *d_ok, const unsigned int *d_poison, hipStream_t st)
 	{
 		const int np = lossy_const_pairs(full, nstreams), nb = lossy_const_workgroups(full, nstreams);
 		const dim3 grid((unsigned)nb, (unsigned)nstreams);
-		// (the variant - a running average or none, addLoss or not - is the launch's: streams of a call share add_loss, and a call whose streams
-		// differ in having a running average goes through the instantiation with one, which reads each stream's own length)
-#define RIR_CONST_LAUNCH(NPV)                                                                                                                  \
-	{                                                                                                                                          \
-		if (any_ra && add_loss)                                                                                                                \
-			hipLaunchKernelGGL((lossy_const_run_kernel<NPV, true, true>), grid, dim3(256), 0, st, d_table, nstreams, d_ok, d_poison, (const LossySpec *)nullptr);          \
-		else if (any_ra)                                                                                                                       \
-			hipLaunchKernelGGL((lossy_const_run_kernel<NPV, true, false>), grid, dim3(256), 0, st, d_table, nstreams, d_ok, d_poison, (const LossySpec *)nullptr);         \
-		else if (add_loss)                                                                                                                     \
-			hipLaunchKernelGGL((lossy_const_run_kernel<NPV, false, true>), grid, dim3(256), 0, st, d_table, nstreams, d_ok, d_poison, (const LossySpec *)nullptr);         \
-		else                                                                                                                                   \
-			hipLaunchKernelGGL((lossy_const_run_kernel<NPV, false, false>), grid, dim3(256), 0, st, d_table, nstreams, d_ok, d_poison, (const LossySpec *)nullptr);        \
-	}
-		if (np == 4)
-			RIR_CONST_LAUNCH(4)
-		else if (np == 2)
-			RIR_CONST_LAUNCH(2)
-		else
-			RIR_CONST_LAUNCH(1)
-#undef RIR_CONST_LAUNCH
+		lossy_const_launch<false>(np, any_ra, add_loss, grid, st, d_table, nstreams, d_ok, d_poison, nullptr);
 		hipLaunchKernelGGL(lossy_const_finish_kernel, dim3((unsigned)nstreams), dim3(1024), 0, st, d_table, nb, (const unsigned int *)d_ok);
 		return hipGetLastError();
 	}
@@ -3028,24 +2963,7 @@ namespace rir
 	{
 		const int np = lossy_const_pairs(full, nstreams), nb = lossy_const_workgroups(full, nstreams);
 		const dim3 grid((unsigned)nb, (unsigned)nstreams);
-#define RIR_SPEC_LAUNCH(NPV)                                                                                                                                      \
-	{                                                                                                                                                             \
-		if (any_ra && add_loss)                                                                                                                                   \
-			hipLaunchKernelGGL((lossy_const_run_kernel<NPV, true, true, true>), grid, dim3(256), 0, st, d_table, nstreams, (unsigned int *)nullptr, (const unsigned int *)nullptr, d_spec);   \
-		else if (any_ra)                                                                                                                                          \
-			hipLaunchKernelGGL((lossy_const_run_kernel<NPV, true, false, true>), grid, dim3(256), 0, st, d_table, nstreams, (unsigned int *)nullptr, (const unsigned int *)nullptr, d_spec);  \
-		else if (add_loss)                                                                                                                                        \
-			hipLaunchKernelGGL((lossy_const_run_kernel<NPV, false, true, true>), grid, dim3(256), 0, st, d_table, nstreams, (unsigned int *)nullptr, (const unsigned int *)nullptr, d_spec);  \
-		else                                                                                                                                                      \
-			hipLaunchKernelGGL((lossy_const_run_kernel<NPV, false, false, true>), grid, dim3(256), 0, st, d_table, nstreams, (unsigned int *)nullptr, (const unsigned int *)nullptr, d_spec); \
-	}
-		if (np == 4)
-			RIR_SPEC_LAUNCH(4)
-		else if (np == 2)
-			RIR_SPEC_LAUNCH(2)
-		else
-			RIR_SPEC_LAUNCH(1)
-#undef RIR_SPEC_LAUNCH
+		lossy_const_launch<true>(np, any_ra, add_loss, grid, st, d_table, nstreams, nullptr, nullptr, d_spec);
 		const int nslabs = lossy_spec_stat_workgroups(s);
 		// (the sums from the byte plane; from the frames where there is no plane or it does not hold the pass's differences: one of the two returns at once)
 		hipLaunchKernelGGL(lossy_spec_stats_kernel<true>, dim3((unsigned)nslabs, (unsigned)((max_frames + kLossySpecStatFrames - 1) / kLossySpecStatFrames), (unsigned)nstreams), dim3(256), 0, st, d_table, d_spec);

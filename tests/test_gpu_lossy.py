@@ -69,6 +69,73 @@ def test_add_image_lossy_matches_oracle(tmp_path, oracle, name):
     assert np.array_equal(got[:, c["hl"]:], arr[:, c["hl"]:])
 
 
+def _jumping_scene(n, h, w, hl, seed):
+    """s1_noisy_background plus a few pixels of the lossy rows that jump by more than any budget every fifth frame"""
+    arr = s1_noisy_background(n, h, w, seed=seed)
+    ys, xs = np.array([0, hl // 2, hl - 1, hl - 1]), np.array([0, w // 3, w - 2, w - 1])
+    arr[::5, ys, xs] += np.uint16(40)
+    return arr
+
+
+# Frames whose lossy part is no multiple of 8 pixels go one pixel per thread (lossy_update_kernel): here WITH a running average -
+# rings that fill, turn over, and whose constant stretches begin and run out.
+_FLAT = {"lowValueError": 3, "highValueError": 3, "stdFactor": 0}
+ODD_RING_CASES = {
+    f"{h}x{w}_ring{ra}{'_min' if mn else ''}{'' if flat else '_defaults'}": dict(h=h, w=w, hl=hl, n=70 if ra == 64 else 12,
+                                                                               p=dict(_FLAT if flat else {}, runningAverage=ra, **({"subtractMin": 1} if mn else {})))
+    for (h, w, hl) in [(35, 83, 32), (9, 13, 6)]
+    for ra, flat in [(1, True), (3, True), (64, True), (3, False)]
+    for mn in (0, 1)
+}
+ODD_RING_CASES["35x83_ring3_add_loss_from_6"] = dict(h=35, w=83, hl=32, n=12, p=dict(_FLAT, runningAverage=3), add_loss_from=6)
+
+
+@pytest.mark.parametrize("name", list(ODD_RING_CASES))
+def test_odd_sized_frames_with_a_running_average_match_oracle(tmp_path, oracle, name):
+    c = ODD_RING_CASES[name]
+    n, h, w, hl, p, mid = c["n"], c["h"], c["w"], c["hl"], c["p"], c.get("add_loss_from")
+    ra = p["runningAverage"]
+    assert (w * hl) % 8 != 0 or (w * h) % 8 != 0
+    arr = _jumping_scene(n, h, w, hl, seed=29)
+    L = OracleLossy(oracle, w, h, hl, low_err=int(p.get("lowValueError", 6)), high_err=int(p.get("highValueError", 2)),
+                    std_factor=float(p.get("stdFactor", 5.0)), running_average=ra, subtract_min=bool(p.get("subtractMin", 0)))
+    # the oracle alone: both sides of the decision are taken while the ring is full.  keep (h264.cpp:2397-2413) restated from the
+    # oracle's own budgets and background: |t - ref| <= error of the pixel's class, and the integration time unchanged
+    mn = int(arr[0, :hl].min()) if p.get("subtractMin") else 0
+    less_min = lambda f: np.maximum(f[:hl].astype(np.int32) - mn, 0)
+    exp, elow, ehigh, both = [], [], [], 0
+    ref = less_min(arr[0])
+    for i in range(n):
+        add = mid is not None and i >= mid
+        exp.append(L.step(arr[i], add_loss=add))
+        lo, hi, bg = L.last_errors()
+        elow.append(lo)
+        ehigh.append(hi)
+        if i == 0:
+            continue
+        v, t = arr[i, :hl].astype(np.int32), less_min(arr[i])
+        keep = np.abs(t - ref) <= np.where(v > bg, hi, lo)
+        if not add:
+            keep &= (arr[i - 1, :hl] >> 13) == (arr[i, :hl] >> 13)
+        ref = np.where(keep, ref, t)
+        assert np.array_equal(exp[i][:hl][~keep], t[~keep])
+        if i > ra and keep.any() and not keep.all():  # (i > ra: the ring was full when this frame came)
+            both += 1
+    assert both > 0
+    exp = np.stack(exp)
+    dst = tmp_path / "odd.h264"
+    low, high, losses = run_saver(dst, arr, hl, p, add_loss_from=mid)
+    assert low.tolist() == elow and high.tolist() == ehigh
+    nfile = n if mid is None else mid
+    for j, f in enumerate(losses):
+        assert np.array_equal(f, exp[mid + j]), mid + j
+    if p.get("subtractMin"):  # the loader adds MIN_T back on the first MIN_T_HEIGHT rows (IRFileLoader.cpp:1173-1179)
+        exp = exp.copy()
+        exp[:, :hl] += np.uint16(mn)
+    with IRMovie.from_filename(dst) as mov:
+        assert mov.images == nfile and np.array_equal(mov.data, exp[:nfile])
+
+
 def test_add_loss_matches_oracle_and_leaves_the_file_alone(tmp_path, oracle):
     n, h, w, hl = 50, 40, 72, 37
     arr = s1_noisy_background(n, h, w, seed=13)
