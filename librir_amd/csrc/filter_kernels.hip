@@ -43,6 +43,180 @@ namespace rir
 		return id < per * 8u ? (id % 8u) * per + id / 8u : id;
 	}
 
+	// ---- the wave-tile scheme -------------------------------------------------------------------
+	// translate, the two gaussians, the fused chain and the 3x3 median work the same way: a WAVE owns a tile of 64 columns x
+	// TY rows, a lane one column - its pixels in registers, fetched with one raw-buffer load per row - and the neighbouring
+	// columns come from the neighbouring lanes through DPP wave shifts: no LDS, no barrier.  The parts of the scheme are
+	// written once, here.
+
+	// The tile of a workgroup (its four waves take four consecutive row bands of it): XCD-major order, then (frame, ...) with
+	// either index fastest.  Row band fastest: vertically adjacent tiles, which share their halo rows, run on the same XCD
+	// back to back.  Column fastest, for tiles whose rows are not line-aligned (63- and 60-pixel rows): neighbours along x
+	// split cache lines of the same rows - on one XCD, one after the other, the second half of a line is an L2 hit and the
+	// two halves of a written line merge before they leave for HBM.
+	struct TileId
+	{
+		int bx, by, n;
+	};
+	template <bool COLUMN_FASTEST>
+	__device__ __forceinline__ TileId tile_decode()
+	{
+		const unsigned gx = gridDim.x, gy = gridDim.y;
+		const unsigned id = xcd_major(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
+		if constexpr (COLUMN_FASTEST)
+			return {(int)(id % gx), (int)((id / gx) % gy), (int)(id / (gx * gy))};
+		else
+			return {(int)((id / gy) % gx), (int)(id % gy), (int)(id / (gy * gx))};
+	}
+
+	// lane i <- lane i + 1 (0 into lane 63) / lane i <- lane i - 1 (0 into lane 0), for 4- and 8-byte values
+	template <int CTRL, class T>
+	__device__ __forceinline__ T wave_shift1(T v)
+	{
+		static_assert(sizeof(T) == 4 || sizeof(T) == 8, "one or two dwords");
+		if constexpr (sizeof(T) == 4)
+			return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+		else
+		{
+			const uint64_t b = __builtin_bit_cast(uint64_t, v);
+			const uint32_t lo = wave_shift1<CTRL>((uint32_t)b), hi = wave_shift1<CTRL>((uint32_t)(b >> 32));
+			return __builtin_bit_cast(T, (uint64_t)lo | ((uint64_t)hi << 32));
+		}
+	}
+	template <class T>
+	__device__ __forceinline__ T wave_shl1(T v) { return wave_shift1<0x130>(v); }
+	template <class T>
+	__device__ __forceinline__ T wave_shr1(T v) { return wave_shift1<0x138>(v); }
+
+	// Raw-buffer descriptor over `bytes` bytes at p (wave-uniform; made scalar here).  An access whose byte offset lies outside
+	// [0, bytes) reads as 0 and stores nothing - the range check the kernels below lean on; it covers the per-lane offset only,
+	// the scalar offset is NOT checked.  A descriptor holds 32 bits of size: a frame of BUFFER_FRAME_LIMIT bytes or more
+	// takes plain loads and stores instead.
+	constexpr int64_t BUFFER_FRAME_LIMIT = (int64_t)1 << 31; // 2 GiB
+	template <class T>
+	__device__ __forceinline__ bool frame_fits_buffer(int w, int h)
+	{
+		return (int64_t)w * h * (int64_t)sizeof(T) < BUFFER_FRAME_LIMIT;
+	}
+	__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void *p, int bytes)
+	{
+		const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)p);
+		const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)p >> 32));
+		return __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, bytes, 0x00020000);
+	}
+	template <class T>
+	__device__ __forceinline__ T buffer_load_px(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff)
+	{
+		if constexpr (sizeof(T) == 1)
+			return __builtin_bit_cast(T, (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)voff, (int)soff, 0));
+		else if constexpr (sizeof(T) == 2)
+			return __builtin_bit_cast(T, (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)voff, (int)soff, 0));
+		else if constexpr (sizeof(T) == 4)
+			return __builtin_bit_cast(T, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, (int)soff, 0));
+		else
+			return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)voff, (int)soff, 0));
+	}
+
+	// A lane's column: rows ytop .. ytop + NR - 1 of column x0 + lane of frame s, as raw values (a uint16 pixel as a uint32).
+	// Returns whether the whole 64 x NR block lies inside the image (wave-uniform).  A pixel outside the image reads as 0 - what
+	// such a pixel adds to a sum; without ZERO_OUTSIDE, for callers that never use it or drop it themselves, it is left
+	// unspecified (frames of 2 GiB and more then give the nearest pixel of the frame, with no select behind the load).
+	// Raw-buffer loads over the frame: a pixel outside the image has a byte offset outside the buffer (rows above: negative =
+	// huge unsigned; rows below: past the end; columns outside: forced there) and the hardware returns 0 for it.  No branch,
+	// no select, one add per row, and all NR loads are in flight together (a load under a condition becomes a branch with its
+	// own wait: that many serial latencies).  INSIDE_BRANCH: a block inside the image gets a branch of its own with one lane
+	// offset and the row steps on the scalar side.
+	template <class T>
+	using raw_px_t = typename std::conditional<sizeof(T) == 2, uint32_t, T>::type;
+	template <int NR, class T, bool INSIDE_BRANCH, bool ZERO_OUTSIDE>
+	__device__ __forceinline__ bool load_column(const T *__restrict__ s, int w, int h, int x0, int lane, int ytop, raw_px_t<T> (&v)[NR])
+	{
+		const int x = x0 + lane;
+		const bool xin = x >= 0 && x < w;
+		if (frame_fits_buffer<T>(w, h))
+		{
+			const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(s, w * h * (int)sizeof(T));
+			const uint32_t step = (uint32_t)w * (uint32_t)sizeof(T);
+			if (INSIDE_BRANCH && x0 >= 0 && x0 + 63 < w && ytop >= 0 && ytop + NR <= h)
+			{
+				const uint32_t off = (uint32_t)((ytop * w + x) * (int)sizeof(T));
+#pragma unroll
+				for (int i = 0; i < NR; ++i)
+					v[i] = buffer_load_px<T>(rs, off, (uint32_t)i * step);
+				return true;
+			}
+			uint32_t off = xin ? (uint32_t)((ytop * w + x) * (int)sizeof(T)) : 0x80000000u;
+#pragma unroll
+			for (int i = 0; i < NR; ++i)
+			{
+				v[i] = buffer_load_px<T>(rs, off, 0);
+				off += step;
+			}
+			return false;
+		}
+		// frames of 2 GiB and more: plain loads at addresses clamped into the frame
+		const T *col = s + min(max(x, 0), w - 1);
+#pragma unroll
+		for (int i = 0; i < NR; ++i)
+		{
+			const int gy = ytop + i;
+			const T val = col[(int64_t)min(max(gy, 0), h - 1) * w];
+			v[i] = (!ZERO_OUTSIDE || (xin && gy >= 0 && gy < h)) ? val : T(0);
+		}
+		return false;
+	}
+
+	// The separable gaussian's 1-D factor a[d], d = -R .. R (uploaded behind the 2-D table), and the weight of the taps of an
+	// output at `pos` that fall inside [0, size): border pixels are renormalised by it, Sx(x) * Sy(y), as the reference does
+	// with its 2-D sum.  The stand-alone kernel and the fused chain, which is specified to give the same bits, both take their
+	// weights from here: d from -R to R, float adds.  full_weight: every tap inside (not exactly 1).
+	template <int R>
+	__device__ __forceinline__ void load_factors(const float *__restrict__ kern, float (&a)[2 * R + 1])
+	{
+		constexpr int KW = 2 * R + 1;
+#pragma unroll
+		for (int d = 0; d < KW; ++d)
+			a[d] = kern[KW * KW + d];
+	}
+	template <int R>
+	__device__ __forceinline__ float axis_weight(const float (&a)[2 * R + 1], int pos, int size)
+	{
+		float s = 0.f;
+#pragma unroll
+		for (int d = -R; d <= R; ++d)
+			if (pos + d >= 0 && pos + d < size)
+				s += a[d + R];
+		return s;
+	}
+	template <int R>
+	__device__ __forceinline__ float full_weight(const float (&a)[2 * R + 1])
+	{
+		return axis_weight<R>(a, R, 2 * R + 1);
+	}
+
+	// The runtime radius 1..4 as a compile-time constant: f(std::integral_constant<int, R>).  false: another radius, f not called.
+	template <class F>
+	static bool with_radius(int radius, F &&f)
+	{
+		switch (radius)
+		{
+		case 1:
+			f(std::integral_constant<int, 1>());
+			return true;
+		case 2:
+			f(std::integral_constant<int, 2>());
+			return true;
+		case 3:
+			f(std::integral_constant<int, 3>());
+			return true;
+		case 4:
+			f(std::integral_constant<int, 4>());
+			return true;
+		default:
+			return false;
+		}
+	}
+
 
 	// ---- translate ------------------------------------------------------------------------------
 
@@ -199,25 +373,6 @@ namespace rir
 	// "noborder" are handled in place.  Every other tile (rows above / below the source, "wrap", ...) runs
 	// translate_px pixel by pixel.  Bit-identical to the reference.  (0.135 -> 0.097 ms per 256 frames 640x512 uint16; the XCD-major order is a quarter of that.)
 	constexpr int TR_TY = 16; // output rows per wave tile
-	template <class T>
-	__device__ __forceinline__ T buffer_load_px(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff)
-	{
-		if constexpr (sizeof(T) == 1)
-			return __builtin_bit_cast(T, (uint8_t)__builtin_amdgcn_raw_buffer_load_b8(rs, (int)voff, (int)soff, 0));
-		else if constexpr (sizeof(T) == 2)
-			return __builtin_bit_cast(T, (uint16_t)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)voff, (int)soff, 0));
-		else if constexpr (sizeof(T) == 4)
-			return __builtin_bit_cast(T, (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs, (int)voff, (int)soff, 0));
-		else
-			return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(rs, (int)voff, (int)soff, 0));
-	}
-	__device__ __forceinline__ double wave_shl1_f64(double v) // lane i <- lane i + 1
-	{
-		const uint64_t b = __builtin_bit_cast(uint64_t, v);
-		const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)b, 0x130, 0xf, 0xf, true);
-		const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(b >> 32), 0x130, 0xf, 0xf, true);
-		return __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
-	}
 
 	// rows: rows of the image the translation applies to (h_ for translate; h_ - 3 for the read-back motion removal, whose
 	// last rows are copied: copy_tail).  sign: -1 for the motion removal (it shifts by -x, -y).
@@ -229,18 +384,8 @@ namespace rir
 		constexpr int OW = 63, OH = TR_TY;
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-		// XCD-major tile order with the column index fastest: tiles that are neighbours along x split cache lines of the
-		// same rows (63-pixel rows are not line-aligned) - on one XCD, one after the other, the second half of a line is
-		// an L2 hit and the two halves of a written line merge before they leave for HBM
-		int bx, by, n;
-		{
-			const unsigned gx = gridDim.x, gy = gridDim.y;
-			const unsigned id2 = xcd_major(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
-			bx = (int)(id2 % gx);
-			by = (int)((id2 / gx) % gy);
-			n = (int)(id2 / (gx * gy));
-		}
-		const int x0 = bx * OW, y0 = (by * 4 + wv) * OH;
+		const TileId id = tile_decode<true>(); // (63-pixel rows are not line-aligned)
+		const int n = id.n, x0 = id.bx * OW, y0 = (id.by * 4 + wv) * OH;
 		if (y0 >= h_)
 			return;
 		const int64_t fbase = (int64_t)n * w * h_;
@@ -253,7 +398,7 @@ namespace rir
 		const bool act_x = lane < OW && x < w;
 		const int nrows = min(OH, rows - y0); // translated rows of this tile (<= 0: only copied rows)
 
-		if (small && nrows > 0 && (int64_t)w * h_ * (int64_t)sizeof(T) < ((int64_t)1 << 31))
+		if (small && nrows > 0 && frame_fits_buffer<T>(w, h_))
 		{
 			// columns (this lane), with the reference's expressions
 			const float px = (float)x - dx;
@@ -297,10 +442,7 @@ namespace rir
 			if (inside != 0 && in_rows != 0 && __ballot(!(col_ok && row_ok)) == 0 && ((outs == 0 && out_rows == 0) || x_border_ok) && one_side && rows_fit &&
 				l0 > -64 && t0 > -64 && ((last_rows >> frow) & 1) == 0)
 			{
-				const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)s);
-				const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)s >> 32));
-				const __amdgpu_buffer_rsrc_t rs =
-					__builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, w * h_ * (int)sizeof(T), 0x00020000);
+				const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(s, w * h_ * (int)sizeof(T));
 				const int col = l0 + lane;
 				// (columns outside [0, w) would alias pixels of the neighbouring rows: they are sent out of range -> 0)
 				const uint32_t voff = (col >= 0 && col < w) ? (uint32_t)((t0 * w + col) * (int)sizeof(T)) : 0x80000000u;
@@ -335,7 +477,7 @@ namespace rir
 					for (int j = 0; j < OH; ++j)
 					{
 						const double cl = dl[j + 1] * v1 + dl[j] * vv;
-						const double cs = wave_shl1_f64(cl);
+						const double cs = wave_shl1(cl);
 						const double cr = r_is_l ? cl : cs;
 						const U res = CastTo<U>::from(cl * u1 + cr * u);
 						if (act_x && j < nrows)
@@ -362,7 +504,7 @@ namespace rir
 					{
 						const bool last = j == jl; // wave-uniform
 						const double cl = (last ? dl[j] : dl[j + 1]) * (last ? v1l : v1) + dl[j] * (last ? vvl : vv);
-						const double cs = wave_shl1_f64(cl);
+						const double cs = wave_shl1(cl);
 						const double cr = r_is_l ? cl : cs;
 						U res = CastTo<U>::from(cl * u1 + cr * u);
 						bool wr = act_x && j < nrows;
@@ -549,23 +691,13 @@ namespace rir
 	// agree to a few 1e-7 relative (the parity bar for float32 filters is 1e-5, BASELINE.json); border pixels
 	// are renormalised by the in-image weight, Sx(x) * Sy(y), as the reference does with its 2-D sum.
 	// Each WAVE works alone on a tile of 64 columns (the outer R on each side are halo) x TY rows: every lane
-	// owns one column, fetches its TY + 2R values with back-to-back independent raw-buffer loads (row-coalesced
-	// across the lanes; pixels outside the image read as 0 through the buffer's range check) and does the COLUMN
-	// pass in registers with packed FMAs; the ROW pass takes the 2R neighbouring column sums from the neighbouring
-	// lanes with DPP wave shifts.  No LDS, no barrier.  (History: the tile-staging version took 0.25 ms per 256
-	// frames whatever the radius, set by its load / barrier / compute phases; the version with a wave-private LDS
-	// strip for the row pass and loads under conditions 0.136 ms.)
+	// owns one column, fetches its TY + 2R values (load_column) and does the COLUMN pass in registers with packed
+	// FMAs; the ROW pass takes the 2R neighbouring column sums from the neighbouring lanes with DPP wave shifts.
+	// (History: the tile-staging version took 0.25 ms per 256 frames whatever the radius, set by its load / barrier /
+	// compute phases; the version with a wave-private LDS strip for the row pass and loads under conditions 0.136 ms.)
 	constexpr int GAUSS_TY = 16; // output rows per wave tile
 	// TIN = float, or uint16_t (the integer -> float conversion of a u16 frame folded into the load).
 	typedef float v2f __attribute__((ext_vector_type(2)));
-	__device__ __forceinline__ float wave_shl1(float f) // lane i <- lane i + 1 (0 into lane 63)
-	{
-		return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0x130, 0xf, 0xf, true));
-	}
-	__device__ __forceinline__ float wave_shr1(float f) // lane i <- lane i - 1 (0 into lane 0)
-	{
-		return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0x138, 0xf, 0xf, true));
-	}
 
 	template <int R, class TIN>
 	__global__ __launch_bounds__(256) void gaussian_sep_kernel(const TIN *__restrict__ src, float *__restrict__ dst, int w, int h,
@@ -575,77 +707,21 @@ namespace rir
 		static_assert(TY % 2 == 0, "rows are processed in pairs (packed FMAs)");
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-		// XCD-aware tile order (xcd_major), then (frame, column strip, row band) with the row band fastest:
-		// vertically adjacent tiles, which share 2R halo rows, run on the same XCD back to back.
-		int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-		{
-			const unsigned gx = gridDim.x, gy = gridDim.y;
-			const unsigned id2 = xcd_major(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
-			by = (int)(id2 % gy);
-			bx = (int)((id2 / gy) % gx);
-			bz = (int)(id2 / (gy * gx));
-		}
-		const int x0 = bx * OUTW - R;
+		const TileId id = tile_decode<false>(); // (vertically adjacent tiles share 2R halo rows)
+		const int x0 = id.bx * OUTW - R;
 		const int x = x0 + lane;				 // this lane's column (halo lanes may fall outside the image)
-		const int y0 = (by * 4 + wv) * TY;		 // first output row of this wave
+		const int y0 = (id.by * 4 + wv) * TY;	 // first output row of this wave
 		if (y0 >= h)
 			return;
-		const int64_t fbase = (int64_t)bz * w * h;
-		const TIN *s = src + fbase;
+		const int64_t fbase = (int64_t)id.n * w * h;
 		float a[KW];
-#pragma unroll
-		for (int d = 0; d < KW; ++d)
-			a[d] = kern[KW * KW + d];
-		const bool xin = x >= 0 && x < w;
+		load_factors<R>(kern, a);
+		raw_px_t<TIN> raw[NR];
+		load_column<NR, TIN, true, true>(src + fbase, w, h, x0, lane, y0 - R, raw);
 		float v[NR];
-		if ((int64_t)w * h * (int64_t)sizeof(TIN) < (int64_t)1 << 31)
-		{
-			// Raw-buffer loads over the frame: a pixel outside the image has a byte offset outside the buffer (rows above:
-			// negative = huge unsigned; rows below: past the end; columns outside: forced there) and reads as 0 - exactly
-			// what such a pixel adds to the sums.  No branch, no select, and all TY + 2R loads are in flight together
-			// (a load under a condition becomes a branch with its own wait: that many serial latencies).
-			const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)s);
-			const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)s >> 32));
-			const __amdgpu_buffer_rsrc_t rs =
-				__builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, w * h * (int)sizeof(TIN), 0x00020000);
-			const uint32_t step = (uint32_t)w * (uint32_t)sizeof(TIN);
-			if (x0 >= 0 && x0 + 63 < w && y0 - R >= 0 && y0 - R + NR <= h)
-			{ // block inside the image: one lane offset, the row steps on the scalar side
-				const uint32_t off = (uint32_t)(((y0 - R) * w + x) * (int)sizeof(TIN));
 #pragma unroll
-				for (int i = 0; i < NR; ++i)
-				{
-					if constexpr (sizeof(TIN) == 2)
-						v[i] = (float)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, (int)((uint32_t)i * step), 0);
-					else
-						v[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, (int)((uint32_t)i * step), 0));
-				}
-			}
-			else
-			{
-				uint32_t off = xin ? (uint32_t)(((y0 - R) * w + x) * (int)sizeof(TIN)) : 0x80000000u;
-#pragma unroll
-				for (int i = 0; i < NR; ++i)
-				{
-					if constexpr (sizeof(TIN) == 2)
-						v[i] = (float)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, 0, 0);
-					else
-						v[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, 0, 0));
-					off += step;
-				}
-			}
-		}
-		else
-		{ // frames of 2 GiB and more: plain loads at addresses clamped into the frame, values outside dropped afterwards
-			const TIN *col = s + min(max(x, 0), w - 1);
-#pragma unroll
-			for (int i = 0; i < NR; ++i)
-			{
-				const int gy = y0 - R + i;
-				const float val = (float)col[(int64_t)min(max(gy, 0), h - 1) * w];
-				v[i] = (xin && gy >= 0 && gy < h) ? val : 0.f; // zeros outside the image add nothing
-			}
-		}
+		for (int i = 0; i < NR; ++i)
+			v[i] = (float)raw[i];
 		// column pass, in registers: rows j and j + TY/2 side by side in packed FMAs (two IEEE fmas per instruction)
 		float cs[TY];
 #pragma unroll
@@ -681,21 +757,9 @@ namespace rir
 		}
 		if (lane < R || lane >= 64 - R || x >= w)
 			return; // halo lanes, and columns past the right edge, have no output
-		// in-image weight of the row taps of this column, and the full 1-D sum (not exactly 1)
-		float full = 0.f;
-#pragma unroll
-		for (int d = 0; d < KW; ++d)
-			full += a[d];
+		const float full = full_weight<R>(a);
 		const bool xb = x < R || x >= w - R;
-		float sx = full;
-		if (xb)
-		{
-			sx = 0.f;
-#pragma unroll
-			for (int d = -R; d <= R; ++d)
-				if (x + d >= 0 && x + d < w)
-					sx += a[d + R];
-		}
+		const float sx = xb ? axis_weight<R>(a, x, w) : full;
 		float *o = dst + fbase + x + (int64_t)y0 * w;
 #pragma unroll
 		for (int j = 0; j < TY; ++j)
@@ -705,19 +769,8 @@ namespace rir
 				break;
 			float acc = g[j];
 			const bool yb = y < R || y >= h - R;
-			if (xb || yb)
-			{ // border pixels are renormalised by the weight of the taps that fall inside the image
-				float sy = full;
-				if (yb)
-				{
-					sy = 0.f;
-#pragma unroll
-					for (int d = -R; d <= R; ++d)
-						if (y + d >= 0 && y + d < h)
-							sy += a[d + R];
-				}
-				acc = acc / (sx * sy);
-			}
+			if (xb || yb) // border pixels are renormalised by the weight of the taps that fall inside the image
+				acc = acc / (sx * (yb ? axis_weight<R>(a, y, h) : full));
 			o[(int64_t)j * w] = acc;
 		}
 	}
@@ -734,52 +787,20 @@ namespace rir
 		constexpr int TY = GAUSS_TY, KW = 2 * R + 1, OUTW = 64 - 2 * R, NR = TY + 2 * R;
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-		int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-		{
-			const unsigned gx = gridDim.x, gy = gridDim.y;
-			const unsigned id2 = xcd_major(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
-			by = (int)(id2 % gy);
-			bx = (int)((id2 / gy) % gx);
-			bz = (int)(id2 / (gy * gx));
-		}
-		const int x0 = bx * OUTW - R;
+		const TileId id = tile_decode<false>();
+		const int x0 = id.bx * OUTW - R;
 		const int x = x0 + lane;
-		const int y0 = (by * 4 + wv) * TY;
+		const int y0 = (id.by * 4 + wv) * TY;
 		if (y0 >= h)
 			return;
-		const int64_t fbase = (int64_t)bz * w * h;
-		const TIN *s = src + fbase;
+		const int64_t fbase = (int64_t)id.n * w * h;
 		const bool xin = x >= 0 && x < w;
+		raw_px_t<TIN> raw[NR];
+		load_column<NR, TIN, false, true>(src + fbase, w, h, x0, lane, y0 - R, raw);
 		float v[NR];
-		if ((int64_t)w * h * (int64_t)sizeof(TIN) < (int64_t)1 << 31)
-		{ // raw-buffer loads: a pixel outside the image has an offset outside the buffer and reads as 0 (gaussian_sep_kernel)
-			const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)s);
-			const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)s >> 32));
-			const __amdgpu_buffer_rsrc_t rs =
-				__builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, w * h * (int)sizeof(TIN), 0x00020000);
-			const uint32_t step = (uint32_t)w * (uint32_t)sizeof(TIN);
-			uint32_t off = xin ? (uint32_t)(((y0 - R) * w + x) * (int)sizeof(TIN)) : 0x80000000u;
 #pragma unroll
-			for (int i = 0; i < NR; ++i)
-			{
-				if constexpr (sizeof(TIN) == 2)
-					v[i] = (float)__builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, 0, 0);
-				else
-					v[i] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)off, 0, 0));
-				off += step;
-			}
-		}
-		else
-		{
-			const TIN *col = s + min(max(x, 0), w - 1);
-#pragma unroll
-			for (int i = 0; i < NR; ++i)
-			{
-				const int gy = y0 - R + i;
-				const float val = (float)col[(int64_t)min(max(gy, 0), h - 1) * w];
-				v[i] = (xin && gy >= 0 && gy < h) ? val : 0.f;
-			}
-		}
+		for (int i = 0; i < NR; ++i)
+			v[i] = (float)raw[i];
 		// every output pixel of the tile an interior pixel of the image?  (wave-uniform: then no weight sums are needed)
 		const bool interior = x0 >= 0 && x0 + 63 - R < w - R && y0 >= R && y0 + TY - 1 < h - R;
 		float res[TY], sum[TY];
@@ -862,58 +883,23 @@ namespace rir
 		}
 	}
 
+	// radius 1..4 (false otherwise): the separable form, or - exact - the reference's order
 	template <class TIN>
-	static bool launch_gaussian_sep(const TIN *src, float *dst, int w, int h, int nframes, const float *d_kernel, int radius, hipStream_t st)
+	static bool launch_gaussian_tiles(bool exact, const TIN *src, float *dst, int w, int h, int nframes, const float *d_kernel, int radius, hipStream_t st)
 	{
-		if (radius < 1 || radius > 4)
-			return false;
-		const int outw = 64 - 2 * radius;
-		dim3 block(256), tgrid((w + outw - 1) / outw, (h + 4 * GAUSS_TY - 1) / (4 * GAUSS_TY), nframes);
-		switch (radius)
-		{
-		case 1:
-			hipLaunchKernelGGL((gaussian_sep_kernel<1, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
-			return true;
-		case 2:
-			hipLaunchKernelGGL((gaussian_sep_kernel<2, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
-			return true;
-		case 3:
-			hipLaunchKernelGGL((gaussian_sep_kernel<3, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
-			return true;
-		default:
-			hipLaunchKernelGGL((gaussian_sep_kernel<4, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
-			return true;
-		}
-	}
-
-	template <class TIN>
-	static bool launch_gaussian_exact(const TIN *src, float *dst, int w, int h, int nframes, const float *d_kernel, int radius, hipStream_t st)
-	{
-		if (radius < 1 || radius > 4)
-			return false;
-		const int outw = 64 - 2 * radius;
-		dim3 block(256), tgrid((w + outw - 1) / outw, (h + 4 * GAUSS_TY - 1) / (4 * GAUSS_TY), nframes);
-		switch (radius)
-		{
-		case 1:
-			hipLaunchKernelGGL((gaussian_exact_kernel<1, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
-			return true;
-		case 2:
-			hipLaunchKernelGGL((gaussian_exact_kernel<2, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
-			return true;
-		case 3:
-			hipLaunchKernelGGL((gaussian_exact_kernel<3, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
-			return true;
-		default:
-			hipLaunchKernelGGL((gaussian_exact_kernel<4, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
-			return true;
-		}
+		return with_radius(radius, [&](auto r) {
+			constexpr int R = decltype(r)::value, OUTW = 64 - 2 * R;
+			dim3 block(256), tgrid((w + OUTW - 1) / OUTW, (h + 4 * GAUSS_TY - 1) / (4 * GAUSS_TY), nframes);
+			if (exact)
+				hipLaunchKernelGGL((gaussian_exact_kernel<R, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
+			else
+				hipLaunchKernelGGL((gaussian_sep_kernel<R, TIN>), tgrid, block, 0, st, src, dst, w, h, d_kernel);
+		});
 	}
 
 	hipError_t launch_gaussian(const float *src, float *dst, int w, int h, int nframes, const float *d_kernel, int radius, hipStream_t st)
 	{
-		if (gaussian_reference_order() ? !launch_gaussian_exact<float>(src, dst, w, h, nframes, d_kernel, radius, st)
-									   : !launch_gaussian_sep<float>(src, dst, w, h, nframes, d_kernel, radius, st))
+		if (!launch_gaussian_tiles<float>(gaussian_reference_order(), src, dst, w, h, nframes, d_kernel, radius, st))
 		{ // radius > 4: the direct 2-D form, one thread per pixel (the reference's order too)
 			dim3 block(256), grid((w + 255) / 256, h, nframes);
 			hipLaunchKernelGGL(gaussian_kernel<float>, grid, block, 0, st, src, dst, w, h, d_kernel, radius);
@@ -924,12 +910,8 @@ namespace rir
 	// uint16 frames in, float out (radius <= 4 only: hipErrorInvalidValue otherwise)
 	hipError_t launch_gaussian_u16(const uint16_t *src, float *dst, int w, int h, int nframes, const float *d_kernel, int radius, hipStream_t st)
 	{
-		if (radius < 1 || radius > 4)
+		if (!launch_gaussian_tiles<uint16_t>(gaussian_reference_order(), src, dst, w, h, nframes, d_kernel, radius, st))
 			return hipErrorInvalidValue;
-		if (gaussian_reference_order())
-			launch_gaussian_exact<uint16_t>(src, dst, w, h, nframes, d_kernel, radius, st);
-		else
-			launch_gaussian_sep<uint16_t>(src, dst, w, h, nframes, d_kernel, radius, st);
 		return hipGetLastError();
 	}
 
@@ -1080,9 +1062,7 @@ namespace rir
 		if (c < 0 || c >= w || r < 0 || r >= h)
 			return 0.f;
 		float a[KW];
-#pragma unroll
-		for (int d = 0; d < KW; ++d)
-			a[d] = kern[KW * KW + d];
+		load_factors<R>(kern, a);
 		float cs[KW];
 #pragma unroll
 		for (int dc = 0; dc < KW; ++dc)
@@ -1111,31 +1091,11 @@ namespace rir
 #pragma unroll
 		for (int d = 0; d < KW; ++d)
 			acc = fmaf(a[d], cs[d], acc);
-		float full = 0.f;
-#pragma unroll
-		for (int d = 0; d < KW; ++d)
-			full += a[d];
 		const bool xb = c < R || c >= w - R, yb = r < R || r >= h - R;
 		if (xb || yb)
 		{
-			float sx = full, sy = full;
-			if (xb)
-			{
-				sx = 0.f;
-#pragma unroll
-				for (int d = -R; d <= R; ++d)
-					if (c + d >= 0 && c + d < w)
-						sx += a[d + R];
-			}
-			if (yb)
-			{
-				sy = 0.f;
-#pragma unroll
-				for (int d = -R; d <= R; ++d)
-					if (r + d >= 0 && r + d < h)
-						sy += a[d + R];
-			}
-			acc = acc / (sx * sy);
+			const float full = full_weight<R>(a);
+			acc = acc / ((xb ? axis_weight<R>(a, c, w) : full) * (yb ? axis_weight<R>(a, r, h) : full));
 		}
 		return acc;
 	}
@@ -1149,7 +1109,7 @@ namespace rir
 
 	// One wave's tile of the chain: output pixels [x0, x0 + OW) x [y0, y0 + OH) of frame n, x0 = bx * OW, y0 = byw * OH.
 	// MODE 0: both paths below in one kernel (radius 2..4).  Radius 1 - the configuration the chain is used with, sigma 0.75 -
-	// is two kernels: MODE 1, the REGULAR tiles only, entirely in registers (39 VGPRs: 8 waves per SIMD, no scratch); a tile that
+	// is two kernels: MODE 1, the REGULAR tiles only, entirely in registers (within the 64 VGPRs of 8 waves per SIMD, no scratch); a tile that
 	// is not regular (first / last row bands of the image, float rounding of px + 1, ...) is put on a list instead (one 64-bit
 	// entry, n << 32 | byw << 16 | bx) and MODE 2, the general path, works the list off.  As one kernel the general path's
 	// registers (10 spilled at the regular path's occupancy) cost every wave its scratch set-up and the regular path a wave
@@ -1183,10 +1143,7 @@ namespace rir
 		const int64_t fix_base = (int64_t)n * bp.nbad;
 
 		float a[KW];
-#pragma unroll
-		for (int d = 0; d < KW; ++d)
-			a[d] = kern[KW * KW + d];
-		// raw pixels of the column, clamped like BadPixels::correct does (Filters.cpp:7-50)
+		load_factors<R>(kern, a);
 		// The run of the flagged-pixel list that lies under the block's rows (the list is in raster order): its bounds, and
 		// its first 64 entries - one per lane, position and repaired value - are fetched here, ahead of the pixels, so
 		// that their latency overlaps the pixel loads instead of following them.  Buffer loads: with no flagged pixels
@@ -1195,9 +1152,9 @@ namespace rir
 		int2 lf;
 		uint32_t lfix;
 		{
-			const __amdgpu_buffer_rsrc_t r_rows = __builtin_amdgcn_make_buffer_rsrc((void *)bp.row_start, 0, bp.nbad > 0 ? (h + 1) * 4 : 0, 0x00020000);
-			const __amdgpu_buffer_rsrc_t r_xy = __builtin_amdgcn_make_buffer_rsrc((void *)bp.xy, 0, bp.nbad * 8, 0x00020000);
-			const __amdgpu_buffer_rsrc_t r_fix = __builtin_amdgcn_make_buffer_rsrc((void *)(bp.fix + fix_base), 0, bp.nbad * 4, 0x00020000);
+			const __amdgpu_buffer_rsrc_t r_rows = buffer_rsrc(bp.row_start, bp.nbad > 0 ? (h + 1) * 4 : 0);
+			const __amdgpu_buffer_rsrc_t r_xy = buffer_rsrc(bp.xy, bp.nbad * 8);
+			const __amdgpu_buffer_rsrc_t r_fix = buffer_rsrc(bp.fix + fix_base, bp.nbad * 4);
 			const int ra = max(gy0 - R, 0), rb = min(gy0 - R + NR, h);
 			li0 = __builtin_amdgcn_readfirstlane((int)__builtin_amdgcn_raw_buffer_load_b32(r_rows, ra * 4, 0, 0));
 			li1 = __builtin_amdgcn_readfirstlane((int)__builtin_amdgcn_raw_buffer_load_b32(r_rows, rb * 4, 0, 0));
@@ -1207,53 +1164,54 @@ namespace rir
 			lf = i < li1 ? make_int2((int)e.x, (int)e.y) : make_int2(-(1 << 30), 0);
 			lfix = __builtin_amdgcn_raw_buffer_load_b32(r_fix, (int)(eo * 4u), 0, 0);
 		}
+		// raw pixels of the column, clamped like BadPixels::correct does (Filters.cpp:7-50)
 		float v[NR];
-		if ((int64_t)w * h < (1 << 30))
 		{
-			// Raw-buffer loads over the frame: the byte offset of a pixel outside the image is out of the buffer's range
-			// (rows above: negative, i.e. >= 2^31 unsigned; rows below: past the end; columns outside: forced there) and
-			// the hardware returns 0 for it - the value such a pixel contributes.  One add per row, no branch, no select.
-			const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)s);
-			const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)s >> 32));
-			const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, w * h * 2, 0x00020000);
-			const uint32_t step = (uint32_t)w * 2u;
-			uint32_t raw[NR];
-			if (gx0 - R >= 0 && gx0 - R + 63 < w && gy0 - R >= 0 && gy0 - R + NR <= h)
-			{ // the usual case, every pixel under the block is in the image: one lane offset, the row steps on the scalar side
-				const uint32_t off = (uint32_t)(((gy0 - R) * w + cx) * 2);
+			// (load_column's three branches in the chain's own text, the clamp floor and the conversion inside each: through the
+			// shared loader the radius-4 kernel lost 0.6 - 0.9 % of its rate on 640 x 512 frames, with the same instructions in
+			// another schedule - profiles/filters_refactor_time.txt)
+			if (frame_fits_buffer<uint16_t>(w, h))
+			{
+				const __amdgpu_buffer_rsrc_t rs = buffer_rsrc(s, w * h * 2);
+				const uint32_t step = (uint32_t)w * 2u;
+				uint32_t raw[NR];
+				if (gx0 - R >= 0 && gx0 - R + 63 < w && gy0 - R >= 0 && gy0 - R + NR <= h)
+				{ // the usual case, every pixel under the block is in the image: one lane offset, the row steps on the scalar side
+					const uint32_t off = (uint32_t)(((gy0 - R) * w + cx) * 2);
 #pragma unroll
-				for (int i = 0; i < NR; ++i)
-					raw[i] = __builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, (int)((uint32_t)i * step), 0);
+					for (int i = 0; i < NR; ++i)
+						raw[i] = buffer_load_px<uint16_t>(rs, off, (uint32_t)i * step);
 #pragma unroll
-				for (int i = 0; i < NR; ++i)
-					v[i] = (float)max(raw[i], bp.floor_v);
+					for (int i = 0; i < NR; ++i)
+						v[i] = (float)max(raw[i], bp.floor_v);
+				}
+				else
+				{
+					uint32_t off = xin ? (uint32_t)(((gy0 - R) * w + cx) * 2) : 0x80000000u;
+#pragma unroll
+					for (int i = 0; i < NR; ++i)
+					{
+						raw[i] = buffer_load_px<uint16_t>(rs, off, 0);
+						off += step;
+					}
+#pragma unroll
+					for (int i = 0; i < NR; ++i)
+					{ // (the clamp floor must not lift the zeros of pixels outside the image)
+						const int gy = gy0 - R + i;
+						v[i] = (float)((xin && gy >= 0 && gy < h) ? max(raw[i], bp.floor_v) : 0u);
+					}
+				}
 			}
 			else
-			{
-				uint32_t off = xin ? (uint32_t)(((gy0 - R) * w + cx) * 2) : 0x80000000u;
+			{ // frames of 2 GiB and more: plain loads at addresses clamped into the frame, values outside dropped afterwards
+				const uint16_t *col = s + min(max(cx, 0), w - 1);
 #pragma unroll
 				for (int i = 0; i < NR; ++i)
 				{
-					raw[i] = __builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, 0, 0);
-					off += step;
-				}
-#pragma unroll
-				for (int i = 0; i < NR; ++i)
-				{ // (the clamp floor must not lift the zeros of pixels outside the image)
 					const int gy = gy0 - R + i;
-					v[i] = (float)((xin && gy >= 0 && gy < h) ? max(raw[i], bp.floor_v) : 0u);
+					const float val = (float)max((uint32_t)col[(int64_t)min(max(gy, 0), h - 1) * w], bp.floor_v);
+					v[i] = (xin && gy >= 0 && gy < h) ? val : 0.f;
 				}
-			}
-		}
-		else
-		{ // frames of 2 GiB and more: plain loads at addresses clamped into the frame, values outside dropped afterwards
-			const uint16_t *col = s + min(max(cx, 0), w - 1);
-#pragma unroll
-			for (int i = 0; i < NR; ++i)
-			{
-				const int gy = gy0 - R + i;
-				const float val = (float)max((uint32_t)col[(int64_t)min(max(gy, 0), h - 1) * w], bp.floor_v);
-				v[i] = (xin && gy >= 0 && gy < h) ? val : 0.f;
 			}
 		}
 		// flagged pixels under the block take their repaired value (first 64 entries of the run: fetched above)
@@ -1336,29 +1294,14 @@ namespace rir
 			// (frames of 2 GiB and more do not fit a buffer descriptor: they take the general path)
 			// rows: the block must not touch the first / last R rows (their renormalisation depends on the row); columns may -
 			// the renormalisation of the first / last R columns is a per-lane factor, applied below where a tile needs it
-			const bool rows_interior = gy0 >= R && gy0 + TY - 1 < h - R && (int64_t)w * h < (1 << 30);
+			const bool rows_interior = gy0 >= R && gy0 + TY - 1 < h - R && frame_fits_buffer<uint16_t>(w, h);
 			const bool xb = xin && (cx < R || cx >= w - R);
 			const bool needs_norm = __ballot(xb) != 0;
 			if (rows_interior && one_side && __ballot(!(row_ok && col_ok)) == 0)
 			{
-				auto shl1 = [](float f) -> float
-				{ return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0x130, 0xf, 0xf, true)); }; // lane i <- i + 1
-				auto shr1 = [](float f) -> float
-				{ return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, f), 0x138, 0xf, 0xf, true)); }; // lane i <- i - 1
 				float norm_den = 1.f;
-				if (needs_norm)
-				{ // sx * sy of the general path with sy = the full 1-D sum (no row of the block is a border row)
-					float full = 0.f;
-#pragma unroll
-					for (int d = 0; d < KW; ++d)
-						full += a[d];
-					float sx = 0.f;
-#pragma unroll
-					for (int d = -R; d <= R; ++d)
-						if (cx + d >= 0 && cx + d < w)
-							sx += a[d + R];
-					norm_den = sx * full;
-				}
+				if (needs_norm) // sx * sy of the general path with sy = the full 1-D sum (no row of the block is a border row)
+					norm_den = axis_weight<R>(a, cx, w) * full_weight<R>(a);
 				const double u1 = 1 - u;
 				const double vv = (double)vv0, v1 = 1 - vv;
 				// Results leave through raw-buffer stores (written once, not read again here).
@@ -1366,10 +1309,7 @@ namespace rir
 				// two-byte stores per tile were a quarter of the kernel's time: when rows are 8-byte aligned (w % 4 == 0)
 				// the tile is turned through the wave's LDS strip so that a lane writes 4 neighbouring pixels at once -
 				// 15 pieces per row, OH rows, 4 store instructions instead of OH.
-				const uint64_t db = (uint64_t)(dst + fbase);
-				const uint32_t dlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)db);
-				const uint32_t dhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(db >> 32));
-				const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)dhi << 32) | dlo), 0, w * h * 2, 0x00020000);
+				const __amdgpu_buffer_rsrc_t rd = buffer_rsrc(dst + fbase, w * h * 2);
 				const uint32_t dstep = (uint32_t)w * 2u;
 				const bool wide = (w & 3) == 0;
 				uint16_t *ot = reinterpret_cast<uint16_t *>(&tile_w[0][0]); // [OH][64] uint16
@@ -1378,10 +1318,7 @@ namespace rir
 				// (rows past the end of the image are computed and not stored: no early exit, the loop unrolls)
 				auto blend_row = [&](double top, double bottom) -> uint16_t {
 					const double cl = bottom * v1 + top * vv;
-					const uint64_t clb = __builtin_bit_cast(uint64_t, cl);
-					const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)clb, 0x130, 0xf, 0xf, true);
-					const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(clb >> 32), 0x130, 0xf, 0xf, true);
-					const double cs1 = __builtin_bit_cast(double, (uint64_t)lo | ((uint64_t)hi << 32));
+					const double cs1 = wave_shl1(cl); // (every lane takes part in the shift: not under the condition below)
 					const double cr = r_is_l ? cl : cs1;
 					uint16_t out = CastTo<u16_via_f32>::from(cl * u1 + cr * u).v;
 					if (outs != 0)
@@ -1399,16 +1336,16 @@ namespace rir
 				for (int p = 0; p < HY; ++p)
 				{
 					const v2f cs = column_pair(2 * p, 2 * p + 1); // column sums of rows 2p, 2p + 1
-					v2f acc = __builtin_elementwise_fma((v2f){a[0], a[0]}, (v2f){shr1(cs.x), shr1(cs.y)}, (v2f){0.f, 0.f});
+					v2f acc = __builtin_elementwise_fma((v2f){a[0], a[0]}, (v2f){wave_shr1(cs.x), wave_shr1(cs.y)}, (v2f){0.f, 0.f});
 					acc = __builtin_elementwise_fma((v2f){a[1], a[1]}, cs, acc);
-					acc = __builtin_elementwise_fma((v2f){a[2], a[2]}, (v2f){shl1(cs.x), shl1(cs.y)}, acc);
+					acc = __builtin_elementwise_fma((v2f){a[2], a[2]}, (v2f){wave_shl1(cs.x), wave_shl1(cs.y)}, acc);
 					if (needs_norm)
 					{ // (wave-uniform) first / last R columns of the image: renormalised by the weight of the taps inside it
 						acc.x = xb ? acc.x / norm_den : acc.x;
 						acc.y = xb ? acc.y / norm_den : acc.y;
 					}
 					// lane i owns column gx0 - 1 + i: column gx0 + i, this lane's left tap column, is one lane up
-					const double d0 = (double)shl1(acc.x), d1 = (double)shl1(acc.y);
+					const double d0 = (double)wave_shl1(acc.x), d1 = (double)wave_shl1(acc.y);
 					if (p > 0)
 						res[2 * p - 1] = blend_row(carry, d0);
 					if (2 * p < OH)
@@ -1468,20 +1405,9 @@ namespace rir
 		__builtin_amdgcn_wave_barrier();
 		__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 		{
-			float full = 0.f;
-#pragma unroll
-			for (int d = 0; d < KW; ++d)
-				full += a[d];
+			const float full = full_weight<R>(a);
 			const bool xb = cx < R || cx >= w - R;
-			float sx = full;
-			if (xb)
-			{
-				sx = 0.f;
-#pragma unroll
-				for (int d = -R; d <= R; ++d)
-					if (cx + d >= 0 && cx + d < w)
-						sx += a[d + R];
-			}
+			const float sx = xb ? axis_weight<R>(a, cx, w) : full;
 			const bool owner = lane >= R && lane < 64 - R && xin;
 #pragma unroll
 			for (int j = 0; j < TY; ++j)
@@ -1495,18 +1421,7 @@ namespace rir
 					acc = fmaf(a[d], tile_w[j][(lane - R + d) & 63], acc);
 				const bool yb = gy < R || gy >= h - R;
 				if (xb || yb)
-				{
-					float sy = full;
-					if (yb)
-					{
-						sy = 0.f;
-#pragma unroll
-						for (int d = -R; d <= R; ++d)
-							if (gy + d >= 0 && gy + d < h)
-								sy += a[d + R];
-					}
-					acc = acc / (sx * sy);
-				}
+					acc = acc / (sx * (yb ? axis_weight<R>(a, gy, h) : full));
 				if (owner)
 					tile_w[j][lane] = acc; // every lane has read row j before any lane writes it (one wave, in order)
 			}
@@ -1556,20 +1471,28 @@ namespace rir
 
 	// register budget of the one-kernel form (radius 2: 6 waves per SIMD - at 7 it spilled 2 VGPRs; wider: the compiler's choice)
 #define RIR_CHAIN_OCC __attribute__((amdgpu_waves_per_eu(R == 1 ? 7 : R == 2 ? 5 : 1, R == 1 ? 7 : R == 2 ? 5 : 8)))
-	// grid = (tiles along x, groups of 4 tile rows, frames), block = 256 (4 independent waves, one tile each)
+	// What the three kernels of the chain start with: the wave's lane and number, and its LDS strip [TY][64]
+	struct ChainWave
+	{
+		int lane, wv;
+		float (*strip)[64];
+	};
+	__device__ __forceinline__ ChainWave chain_wave(float (*tile)[CHAIN_TY][64])
+	{
+		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+		return {(int)(threadIdx.x & 63), wv, tile[wv]};
+	}
+	// grid = (tiles along x, groups of 4 tile rows, frames), block = 256 (4 independent waves, one tile each; row bands fastest)
 	template <int R>
 	RIR_CHAIN_OCC __global__ __launch_bounds__(256) void filter_chain_kernel(const uint16_t *__restrict__ src, uint16_t *__restrict__ dst, int w, int h,
 															   ChainBadPixels bp, const float *__restrict__ kern, const float *__restrict__ offsets,
 															   int per_frame_offsets, int strategy, uint32_t background)
 	{
 		__shared__ float tile[4][CHAIN_TY][64];
-		const int lane = threadIdx.x & 63;
-		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-		// XCD-major tile order, row bands fastest (see gaussian_sep_kernel)
-		const unsigned gx = gridDim.x, gy = gridDim.y;
-		const unsigned id2 = xcd_major(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
-		const int by = (int)(id2 % gy), bx = (int)((id2 / gy) % gx), bz = (int)(id2 / (gy * gx));
-		chain_tile<R, 0>(src, dst, w, h, bp, kern, offsets, per_frame_offsets, strategy, background, bx, by * 4 + wv, bz, lane, tile[wv], nullptr, nullptr);
+		const ChainWave cw = chain_wave(tile);
+		const TileId id = tile_decode<false>();
+		chain_tile<R, 0>(src, dst, w, h, bp, kern, offsets, per_frame_offsets, strategy, background, id.bx, id.by * 4 + cw.wv, id.n, cw.lane, cw.strip, nullptr,
+						 nullptr);
 	}
 	// radius 1, the regular tiles (same grid): 8 waves per SIMD, no scratch; what it cannot take goes on the list
 	__attribute__((amdgpu_waves_per_eu(8, 8))) __global__ __launch_bounds__(256) void filter_chain_regular_kernel(
@@ -1578,12 +1501,10 @@ namespace rir
 		unsigned int *__restrict__ work_count)
 	{
 		__shared__ float tile[4][CHAIN_TY][64];
-		const int lane = threadIdx.x & 63;
-		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-		const unsigned gx = gridDim.x, gy = gridDim.y;
-		const unsigned id2 = xcd_major(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
-		const int by = (int)(id2 % gy), bx = (int)((id2 / gy) % gx), bz = (int)(id2 / (gy * gx));
-		chain_tile<1, 1>(src, dst, w, h, bp, kern, offsets, per_frame_offsets, strategy, background, bx, by * 4 + wv, bz, lane, tile[wv], worklist, work_count);
+		const ChainWave cw = chain_wave(tile);
+		const TileId id = tile_decode<false>();
+		chain_tile<1, 1>(src, dst, w, h, bp, kern, offsets, per_frame_offsets, strategy, background, id.bx, id.by * 4 + cw.wv, id.n, cw.lane, cw.strip, worklist,
+						 work_count);
 	}
 	// radius 1, the listed tiles through the general path: grid = any, block = 256; wave (block, wv) takes entries block * 4 + wv,
 	// + 4 * gridDim.x, ... of the list
@@ -1594,14 +1515,13 @@ namespace rir
 																	  unsigned int *__restrict__ other_count)
 	{
 		__shared__ float tile[4][CHAIN_TY][64];
-		const int lane = threadIdx.x & 63;
-		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+		const ChainWave cw = chain_wave(tile);
 		const unsigned int count = __hip_atomic_load(work_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		for (unsigned int e = blockIdx.x * 4u + (unsigned int)wv; e < count; e += gridDim.x * 4u)
+		for (unsigned int e = blockIdx.x * 4u + (unsigned int)cw.wv; e < count; e += gridDim.x * 4u)
 		{
 			const unsigned long long id = worklist[e];
 			chain_tile<1, 2>(src, dst, w, h, bp, kern, offsets, per_frame_offsets, strategy, background, (int)(id & 0xffffu), (int)((id >> 16) & 0xffffu),
-							 (int)(id >> 32), lane, tile[wv], nullptr, nullptr);
+							 (int)(id >> 32), cw.lane, cw.strip, nullptr, nullptr);
 			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); // (the strip is reused by the wave's next tile)
 			__builtin_amdgcn_wave_barrier();
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1661,7 +1581,7 @@ namespace rir
 								   int strategy, uint16_t background, hipStream_t st)
 	{
 		if (radius < 1 || radius > 4 || (strategy != TRANSLATE_CONSTANT && strategy != TRANSLATE_NEAREST))
-			return hipErrorInvalidValue;
+			return hipErrorInvalidValue; // (before the repair launch; with_radius below refuses the same radii)
 		const uint32_t fl = floor_v > 0 ? (uint32_t)(uint16_t)floor_v : 0u;
 		if (nbad > 0)
 			hipLaunchKernelGGL(bad_pixels_fix_kernel, dim3((nbad + 63) / 64, nframes), dim3(64), 0, st, src, (uint16_t *)nullptr, w, h, d_xy, nbad, fl,
@@ -1669,40 +1589,38 @@ namespace rir
 		ChainBadPixels bp{d_xy, d_row_start, d_fix, nbad, fl};
 		const int ow = 64 - 2 * radius - 2, oh = CHAIN_TY - 2;
 		dim3 block(256), grid((w + ow - 1) / ow, (h + 4 * oh - 1) / (4 * oh), nframes);
-		switch (radius)
-		{
-		case 1:
-		{
-			// regular tiles in registers; the rest through a list (stream-ordered scratch: [count | pad to 8 bytes][one entry per tile]).
-			// (Round 2's form, both paths in one kernel at 7 waves per SIMD, is RIR_CHAIN_ONE_KERNEL in 02807a8.)
-			const size_t ntile = (size_t)grid.x * grid.y * 4 * grid.z;
-			int par = 0;
-			unsigned int *counters = chain_list_of(st, ntile, &par);
-			if (!counters)
-				return hipErrorOutOfMemory;
-			unsigned long long *entries = reinterpret_cast<unsigned long long *>(counters + 2);
-			unsigned int *count = counters + par;
-			// (8 waves per SIMD; with its workgroups per CU capped by unused LDS - 7, 6, 5, 4 waves per SIMD - the kernel is no faster: 0.152-0.159,
-			// 0.154-0.156, 0.152-0.157, 0.164, 0.163 ms per 256 frames against 0.153-0.159)
-			hipLaunchKernelGGL(filter_chain_regular_kernel, grid, block, 0, st, src, dst, w, h, bp, d_kernel, d_offsets, per_frame, strategy,
-							   (uint32_t)background, entries, count);
-			// (the list is short - the first / last row bands of every frame: enough workgroups for it, not for every tile)
-			const unsigned int lb = (unsigned int)std::min<size_t>((ntile / 8 + 3) / 4 + 1, 2048);
-			hipLaunchKernelGGL(filter_chain_listed_kernel, dim3(lb), block, 0, st, src, dst, w, h, bp, d_kernel, d_offsets, per_frame, strategy,
-							   (uint32_t)background, entries, count, counters + (par ^ 1));
-			break;
-		}
-		case 2:
-			hipLaunchKernelGGL((filter_chain_kernel<2>), grid, block, 0, st, src, dst, w, h, bp, d_kernel, d_offsets, per_frame, strategy, (uint32_t)background);
-			break;
-		case 3:
-			hipLaunchKernelGGL((filter_chain_kernel<3>), grid, block, 0, st, src, dst, w, h, bp, d_kernel, d_offsets, per_frame, strategy, (uint32_t)background);
-			break;
-		default:
-			hipLaunchKernelGGL((filter_chain_kernel<4>), grid, block, 0, st, src, dst, w, h, bp, d_kernel, d_offsets, per_frame, strategy, (uint32_t)background);
-			break;
-		}
-		return hipGetLastError();
+		hipError_t err = hipSuccess;
+		const bool launched = with_radius(radius, [&](auto r) {
+			constexpr int R = decltype(r)::value;
+			if constexpr (R == 1)
+			{
+				// regular tiles in registers; the rest through a list (stream-ordered scratch: [count | pad to 8 bytes][one entry per tile]).
+				// (Round 2's form, both paths in one kernel at 7 waves per SIMD, is RIR_CHAIN_ONE_KERNEL in 02807a8.)
+				const size_t ntile = (size_t)grid.x * grid.y * 4 * grid.z;
+				int par = 0;
+				unsigned int *counters = chain_list_of(st, ntile, &par);
+				if (!counters)
+				{
+					err = hipErrorOutOfMemory;
+					return;
+				}
+				unsigned long long *entries = reinterpret_cast<unsigned long long *>(counters + 2);
+				unsigned int *count = counters + par;
+				// (8 waves per SIMD; with its workgroups per CU capped by unused LDS - 7, 6, 5, 4 waves per SIMD - the kernel is no faster: 0.152-0.159,
+				// 0.154-0.156, 0.152-0.157, 0.164, 0.163 ms per 256 frames against 0.153-0.159)
+				hipLaunchKernelGGL(filter_chain_regular_kernel, grid, block, 0, st, src, dst, w, h, bp, d_kernel, d_offsets, per_frame, strategy,
+								   (uint32_t)background, entries, count);
+				// (the list is short - the first / last row bands of every frame: enough workgroups for it, not for every tile)
+				const unsigned int lb = (unsigned int)std::min<size_t>((ntile / 8 + 3) / 4 + 1, 2048);
+				hipLaunchKernelGGL(filter_chain_listed_kernel, dim3(lb), block, 0, st, src, dst, w, h, bp, d_kernel, d_offsets, per_frame, strategy,
+								   (uint32_t)background, entries, count, counters + (par ^ 1));
+			}
+			else
+				hipLaunchKernelGGL((filter_chain_kernel<R>), grid, block, 0, st, src, dst, w, h, bp, d_kernel, d_offsets, per_frame, strategy, (uint32_t)background);
+		});
+		if (!launched)
+			return hipErrorInvalidValue;
+		return err != hipSuccess ? err : hipGetLastError();
 	}
 
 	// ---- read-back repair (IRFileLoader::removeBadPixels) ---------------------------------------
@@ -2167,12 +2085,10 @@ namespace rir
 	// (min / median / max of 3) and takes the sorted triples of the two neighbouring columns from lanes i - 1 and i + 1 by
 	// DPP wave shifts: median of 9 = med3(max of the column minima, median of the column medians, min of the column
 	// maxima) - 11 vector instructions per pixel.  Pixels on the image border (median of 3 along the edge, min of 2 in the
-	// corners) take median3x3_px.  XCD-major tile order with x fastest (60-pixel rows are not line-aligned).
+	// corners) take median3x3_px.  Tile order: x fastest.
 	// (The first version - 8 consecutive outputs per thread, 3 x 10 windows fetched with dword loads - was bound by its
 	// instruction count at 0.134 ms per 256 frames 640x512.)
 	constexpr int MEDIAN_TY = 16; // output rows per wave tile
-	__device__ __forceinline__ uint32_t wave_shl1_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true); }
-	__device__ __forceinline__ uint32_t wave_shr1_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true); }
 
 	__global__ __launch_bounds__(256) void median3x3_kernel(const uint16_t *__restrict__ src, uint16_t *__restrict__ dst, int w, int h)
 	{
@@ -2180,57 +2096,19 @@ namespace rir
 		__shared__ uint16_t strip[4][TY][64];
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-		int bx, by, n;
-		{
-			const unsigned gx = gridDim.x, gy = gridDim.y;
-			const unsigned id2 = xcd_major(blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z), gx * gy * gridDim.z);
-			bx = (int)(id2 % gx);
-			by = (int)((id2 / gx) % gy);
-			n = (int)(id2 / (gx * gy));
-		}
-		const int x0 = bx * OW, y0 = (by * 4 + wv) * TY;
+		const TileId id = tile_decode<true>(); // (60-pixel rows are not line-aligned)
+		const int x0 = id.bx * OW, y0 = (id.by * 4 + wv) * TY;
 		if (y0 >= h)
 			return;
-		const int64_t fbase = (int64_t)n * w * h;
+		const int64_t fbase = (int64_t)id.n * w * h;
 		const uint16_t *s = src + fbase;
 		uint16_t *d = dst + fbase;
 		const int x = x0 - 1 + lane; // this lane's column
-		const bool xin = x >= 0 && x < w;
-		uint32_t v[TY + 2];
-		if ((int64_t)w * h < (1 << 30))
-		{ // pixels outside the image read as 0 through the buffer's range check (they are never used by an interior output)
-			const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uint64_t)s);
-			const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)s >> 32));
-			const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)hi << 32) | lo), 0, w * h * 2, 0x00020000);
-			const uint32_t step = (uint32_t)w * 2u;
-			if (x0 - 1 >= 0 && x0 + 62 < w && y0 - 1 >= 0 && y0 + TY < h)
-			{ // block inside the image: the row steps on the scalar side (the scalar offset is not range-checked)
-				const uint32_t off = (uint32_t)(((y0 - 1) * w + x) * 2);
-#pragma unroll
-				for (int i = 0; i < TY + 2; ++i)
-					v[i] = __builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, (int)((uint32_t)i * step), 0);
-			}
-			else
-			{
-				uint32_t off = xin ? (uint32_t)(((y0 - 1) * w + x) * 2) : 0x80000000u;
-#pragma unroll
-				for (int i = 0; i < TY + 2; ++i)
-				{
-					v[i] = __builtin_amdgcn_raw_buffer_load_b16(rs, (int)off, 0, 0);
-					off += step;
-				}
-			}
-		}
-		else
-		{
-			const uint16_t *col = s + min(max(x, 0), w - 1);
-#pragma unroll
-			for (int i = 0; i < TY + 2; ++i)
-				v[i] = col[(int64_t)min(max(y0 - 1 + i, 0), h - 1) * w];
-		}
+		uint32_t v[TY + 2]; // (what stands for the pixels outside the image is never used by an interior output)
+		load_column<TY + 2, uint16_t, true, false>(s, w, h, x0 - 1, lane, y0 - 1, v);
 		const bool out_lane = lane >= 1 && lane <= OW && x < w;
 		const bool x_interior = x >= 1 && x < w - 1;
-		const bool wide = (w & 3) == 0 && (int64_t)w * h < (1 << 30);
+		const bool wide = (w & 3) == 0 && frame_fits_buffer<uint16_t>(w, h);
 #pragma unroll
 		for (int j = 0; j < TY; ++j)
 		{
@@ -2238,9 +2116,9 @@ namespace rir
 			// (all 64 lanes take part in the shifts; rows past the image are computed and not stored)
 			const uint32_t a = v[j], b = v[j + 1], c = v[j + 2];
 			const uint32_t lo = min(min(a, b), c), hi = max(max(a, b), c), mi = med3(a, b, c);
-			const uint32_t m_lo = max(max(lo, wave_shr1_u32(lo)), wave_shl1_u32(lo));
-			const uint32_t m_hi = min(min(hi, wave_shr1_u32(hi)), wave_shl1_u32(hi));
-			const uint32_t m_mi = med3(wave_shr1_u32(mi), mi, wave_shl1_u32(mi));
+			const uint32_t m_lo = max(max(lo, wave_shr1(lo)), wave_shl1(lo));
+			const uint32_t m_hi = min(min(hi, wave_shr1(hi)), wave_shl1(hi));
+			const uint32_t m_mi = med3(wave_shr1(mi), mi, wave_shl1(mi));
 			uint32_t res = med3(m_lo, m_mi, m_hi);
 			if (out_lane && y < h && !(x_interior && y >= 1 && y < h - 1))
 				res = median3x3_px(s, w, h, x, y);
@@ -2255,10 +2133,7 @@ namespace rir
 			__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
 			__builtin_amdgcn_wave_barrier();
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-			const uint64_t db = (uint64_t)d;
-			const uint32_t dlo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)db);
-			const uint32_t dhi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(db >> 32));
-			const __amdgpu_buffer_rsrc_t rd = __builtin_amdgcn_make_buffer_rsrc((void *)(((uint64_t)dhi << 32) | dlo), 0, w * h * 2, 0x00020000);
+			const __amdgpu_buffer_rsrc_t rd = buffer_rsrc(d, w * h * 2);
 			constexpr int PPR = OW / 4;
 #pragma unroll
 			for (int q = 0; q < (PPR * TY + 63) / 64; ++q)

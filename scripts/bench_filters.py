@@ -48,4 +48,16 @@ rec("filter_chain (3 filters fused)", timeit(lambda: D.filter_chain(t16, bp, 0.7
 rec("filter_chain + encode", timeit(lambda: ctx.encode(D.filter_chain(t16, bp, 0.75, offs, "nearest")), 5), 2 * WH)
 for s in (0.75, 1.0, 2.0):
     rec("gaussian u16 in, sigma=%g" % s, timeit(lambda: D.gaussian_filter(t16, s)), 6 * WH)
+# the remaining instances of the tiled kernels: radius 3 (sigma 1.7), the fused chain beyond radius 1, gaussian_filter in the reference's order
+rec("gaussian sigma=1.7", timeit(lambda: D.gaussian_filter(f32, 1.7)), 8 * WH)
+rec("gaussian u16 in, sigma=1.7", timeit(lambda: D.gaussian_filter(t16, 1.7)), 6 * WH)
+for s in (1.0, 1.7, 2.0):
+    rec("filter_chain sigma=%g" % s, timeit(lambda: D.filter_chain(t16, bp, s, offs, "nearest")), 4 * WH)
+D._lib.rir_set_gaussian_reference_order(1)
+try:
+    for s in (0.75, 1.0, 1.7, 2.0):
+        rec("gaussian reference order, sigma=%g" % s, timeit(lambda: D.gaussian_filter(f32, s)), 8 * WH)
+        rec("gaussian reference order, u16 in, sigma=%g" % s, timeit(lambda: D.gaussian_filter(t16, s)), 6 * WH)
+finally:
+    D._lib.rir_set_gaussian_reference_order(0)
 print(json.dumps(res))
