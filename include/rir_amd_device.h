@@ -272,6 +272,27 @@ extern "C"
 							   void *d_work, size_t work_bytes, void *stream);
 	size_t rir_pixel_stats_workspace_bytes(int w, int h, int nframes);
 
+	/* Connected components tracked through time (extension).  d_labels: int32 label maps [nframes][h][w] as rir_label_images_device writes
+	 * them; d_counts: int[nframes], components + 1 per frame as it returns them, or null; nlabels = K >= 1.  Component k of frame t exists
+	 * when 1 <= k < min(K, d_counts[t]) (1 <= k < K without d_counts); every other label value is background.  Components (t, a) and
+	 * (t + 1, b) are linked when a pixel p has d_labels[t][p] == a and d_labels[t + 1][p] == b; a track is a connected set of components
+	 * under these links; the node of (t, k) has index t * K + k, and tracks are numbered 1, 2, ... in the order of their lowest node
+	 * (track 0 = background).  For a boolean stack labelled frame by frame this is the 3-D labelling with 4-connectivity inside a frame and
+	 * the same pixel in adjacent frames, numbered in raster order of each component's first voxel.
+	 * Outputs: d_track_of int[nframes][K], the track of each component, 0 where it does not exist; d_info int[2] = {tracks + 1, frames with
+	 * d_counts[t] > K, whose components >= K were dropped}; tables of `table_entries` ints per track: d_first_frame, d_last_frame,
+	 * d_first_label (the label of the lowest node, in frame first_frame) and d_components (nodes of the track) - entry 0 is -1, -1, 0, 0,
+	 * entries from d_info[0] on are 0, tracks >= table_entries are not written; d_dst (or null) int32 [nframes][h][w], the track map
+	 * d_track_of[t][d_labels[t][p]], 0 on the background, which may be d_labels itself.  Integer work, bitwise reproducible.  nframes 0:
+	 * d_info = {1, 0} and the empty tables.  Bounds: w * h <= 0x7FFF0000, nframes * K <= 0x7FFF0000, table_entries >= 1.
+	 * d_work: device memory, 8-byte aligned, at least rir_track_components_workspace_bytes(...) (0: arguments refused).  Asynchronous on
+	 * `stream`; no output or the workspace may overlap an input or another output, except d_dst == d_labels.  0 / -1 (invalid argument,
+	 * null pointer, overlap, workspace too small, no device). */
+	int rir_track_components_device(const int *d_labels, const int *d_counts, int w, int h, int nframes, int nlabels, int *d_track_of, int *d_info,
+									int *d_first_frame, int *d_last_frame, int *d_first_label, int *d_components, int table_entries, int *d_dst,
+									void *d_work, size_t work_bytes, void *stream);
+	size_t rir_track_components_workspace_bytes(int w, int h, int nframes, int nlabels);
+
 	/* connected components: reference signal_processing.h:90-92 / Filters.h:365-540 (labelImage, keepLargestArea) on images in device memory,
 	 * [nframes][h][w], every image labelled on its own; five launches for the whole batch.  type: the reference's dtype character;
 	 * background: HOST pointer to one cell of that type.  d_dst int32 [nframes][h][w].

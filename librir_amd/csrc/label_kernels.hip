@@ -24,6 +24,7 @@
 #include <stdint.h>
 
 #include "label_kernels.h"
+#include "union_find.h"
 
 namespace rir
 {
@@ -38,63 +39,7 @@ namespace rir
 		constexpr int kTileW = 64, kTileH = 32, kTileThreads = 1024, kRowsPerWave = kTileH / (kTileThreads / 64);
 		static_assert(kRowsPerWave * (kTileThreads / 64) == kTileH && kRowsPerWave >= 1, "tile rows divide over the wavefronts");
 
-		// The forests are read and written by many waves at once: a link is loaded and stored as one 32-bit access at the scope that
-		// shares it (never a stale copy from the CU's vector cache, never torn).
-		template <int SCOPE>
-		__device__ __forceinline__ int link_load(const int *p)
-		{
-			return __hip_atomic_load(p, __ATOMIC_RELAXED, SCOPE);
-		}
-		template <int SCOPE>
-		__device__ __forceinline__ void link_store(int *p, int v)
-		{
-			__hip_atomic_store(p, v, __ATOMIC_RELAXED, SCOPE);
-		}
-
-		// Root of i's tree; on the way every visited node is re-pointed at its grandparent (path splitting).  A link only ever moves to an
-		// ancestor, so a reader that sees the older value still climbs the same tree.  Racing with unite(): a node that unite() found to
-		// be a root (atomicMin returned the node itself) was a root until that instant, so no splitting store - which only touches nodes
-		// read as non-roots - can overwrite the link unite() just made; when the atomicMin lands on a node that had stopped being a root,
-		// unite() carries on with the parent it displaced, and whatever a splitting store does to that node stays inside one tree.
-		template <int SCOPE>
-		__device__ __forceinline__ int find_root(int *L, int i)
-		{
-			int p = link_load<SCOPE>(&L[i]);
-			while (p != i)
-			{
-				const int g = link_load<SCOPE>(&L[p]);
-				if (g != p)
-					link_store<SCOPE>(&L[i], g);
-				i = p;
-				p = g;
-			}
-			return i;
-		}
-
-		// Joins the trees of a and b: the higher root is hung under the lower one, so a root is always the lowest index of its tree.
-		// Every failed round lowers max(a, b) (the displaced parent is below the node it was read from), so the loop ends for every wave
-		// whatever the others do.
-		template <int SCOPE>
-		__device__ __forceinline__ void unite(int *L, int a, int b)
-		{
-			for (;;)
-			{
-				a = find_root<SCOPE>(L, a);
-				b = find_root<SCOPE>(L, b);
-				if (a == b)
-					return;
-				if (a > b)
-				{
-					const int t = a;
-					a = b;
-					b = t;
-				}
-				const int old = atomicMin(&L[b], a);
-				if (old == b)
-					return;
-				b = old;
-			}
-		}
+		// (link_load, link_store, find_root and unite - the forest with lowest-index roots - are in union_find.h)
 		constexpr int kTile = __HIP_MEMORY_SCOPE_WORKGROUP, kImage = __HIP_MEMORY_SCOPE_AGENT;
 
 		// A launch works on a batch of images [frames][h][w] (blockIdx.y = the image): where the next image's part of every array begins.

@@ -18,6 +18,7 @@
 #include "region_kernels.h"
 #include "runtime.h"
 #include "temporal_kernels.h"
+#include "track_kernels.h"
 
 using namespace rir;
 
@@ -787,6 +788,63 @@ RIR_EXPORT int rir_pixel_stats_device(const unsigned short *d_frames, int w, int
 	return hip_ok(launch_pixel_stats(d_frames, (int64_t)npx, nframes, t0, accumulate, (int64_t *)d_sum, (int64_t *)d_sumsq, d_min, d_max, d_argmin,
 									 d_argmax, d_work, as_stream(stream)),
 				  "pixel_stats")
+			   ? 0
+			   : -1;
+}
+
+// Components tracked through time (track_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an
+// input or another output, except d_dst == d_labels (relabelling in place).
+RIR_EXPORT size_t rir_track_components_workspace_bytes(int w, int h, int nframes, int nlabels) { return track_workspace_bytes(w, h, nframes, nlabels); }
+
+RIR_EXPORT int rir_track_components_device(const int *d_labels, const int *d_counts, int w, int h, int nframes, int nlabels, int *d_track_of, int *d_info,
+										   int *d_first_frame, int *d_last_frame, int *d_first_label, int *d_components, int table_entries, int *d_dst,
+										   void *d_work, size_t work_bytes, void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (!track_geometry_ok(w, h, nframes, nlabels) || table_entries < 1)
+	{
+		log_error("rir_track_components_device: invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, nframes >= 0, nlabels >= 1 with "
+				  "nframes * nlabels <= 0x7FFF0000, table_entries >= 1)");
+		return -1;
+	}
+	if (!d_info || !d_first_frame || !d_last_frame || !d_first_label || !d_components || !d_work || (nframes > 0 && (!d_labels || !d_track_of)))
+	{
+		log_error("rir_track_components_device: null pointer");
+		return -1;
+	}
+	const size_t npx = (size_t)w * h, nodes = (size_t)nframes * nlabels, need = track_workspace_bytes(w, h, nframes, nlabels);
+	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
+	{
+		log_error("rir_track_components_device: the workspace must be 8-byte aligned and hold rir_track_components_workspace_bytes() bytes");
+		return -1;
+	}
+	const size_t stack = npx * nframes * 4, table = (size_t)table_entries * 4;
+	const struct
+	{
+		uintptr_t p;
+		size_t bytes;
+	} in[2] = {{(uintptr_t)d_labels, stack}, {(uintptr_t)d_counts, d_counts ? (size_t)nframes * 4 : 0}},
+	  out[8] = {{(uintptr_t)d_track_of, nodes * 4},	  {(uintptr_t)d_info, 8},			   {(uintptr_t)d_first_frame, table}, {(uintptr_t)d_last_frame, table},
+				{(uintptr_t)d_first_label, table}, {(uintptr_t)d_components, table}, {(uintptr_t)d_work, need},		  {(uintptr_t)d_dst, d_dst ? stack : 0}};
+	for (int i = 0; i < 8; ++i)
+	{
+		if (out[i].bytes == 0)
+			continue;
+		bool overlap = false;
+		for (int j = 0; j < 2; ++j)
+			overlap |= in[j].bytes != 0 && !(i == 7 && j == 0 && d_dst == d_labels) && out[i].p < in[j].p + in[j].bytes && in[j].p < out[i].p + out[i].bytes;
+		for (int j = 0; j < i; ++j)
+			overlap |= out[j].bytes != 0 && out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
+		if (overlap)
+		{
+			log_error("rir_track_components_device: an output or the workspace overlaps an input or another output (only d_dst == d_labels may)");
+			return -1;
+		}
+	}
+	return hip_ok(launch_track_components(d_labels, d_counts, w, h, nframes, nlabels, d_track_of, d_info, d_first_frame, d_last_frame, d_first_label,
+										  d_components, table_entries, d_dst, d_work, as_stream(stream)),
+				  "track_components")
 			   ? 0
 			   : -1;
 }

@@ -4,6 +4,7 @@ Inputs and outputs are ``torch`` CUDA(HIP) tensors; torch is plumbing only (devi
 streams) - every operation is one call into ``librir_amd.so`` on torch's current HIP stream.
 """
 import ctypes as ct
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -116,6 +117,9 @@ _lib.rir_region_stats_workspace_bytes.restype = ct.c_size_t
 _lib.rir_pixel_stats_device.argtypes = [_vp] + [ct.c_int] * 5 + [_vp] * 7 + [ct.c_size_t, _vp]
 _lib.rir_pixel_stats_workspace_bytes.argtypes = [ct.c_int] * 3
 _lib.rir_pixel_stats_workspace_bytes.restype = ct.c_size_t
+_lib.rir_track_components_device.argtypes = [_vp, _vp] + [ct.c_int] * 4 + [_vp] * 6 + [ct.c_int, _vp, _vp, ct.c_size_t, _vp]
+_lib.rir_track_components_workspace_bytes.argtypes = [ct.c_int] * 4
+_lib.rir_track_components_workspace_bytes.restype = ct.c_size_t
 _lib.bad_pixels_destroy.argtypes = [ct.c_int]
 _lib.rir_label_workspace_bytes.argtypes = [ct.c_int, ct.c_int]
 _lib.rir_label_workspace_bytes.restype = ct.c_size_t
@@ -914,19 +918,107 @@ def _label_batch_args(frames, background):
     return fr, ch, n, h, w, work, back
 
 
+def _label_images_into(frames, background, dst, xy, area, count):
+    """queue the labelling of a batch into dst int32 (n, h, w), xy float64 (n, cap, 2), area int32 (n, cap) and count int32 (n,), all contiguous"""
+    fr, ch, n, h, w, work, back = _label_batch_args(frames, background)
+    _check(_lib.rir_label_images_device(ord(ch), fr.data_ptr(), dst.data_ptr(), w, h, n, back.ctypes.data, xy.data_ptr(), area.data_ptr(),
+                                        area.shape[1], count.data_ptr(), work.data_ptr(), work.numel() * 8, _stream()), "rir_label_images_device")
+
+
 def label_images(frames, background=0, table_entries=None):
     """Connected components of every image of a batch (n, h, w) in device memory, five launches for the whole batch: (labels int32 (n, h, w),
     areas (n, table_entries), first-pixel table (n, table_entries, 2), counts (n,)), on the device.  counts[i] = components of image i + 1;
     a table with fewer entries than that holds the first ``table_entries`` of them (default: 1 024 entries, or h*w + 1 if that is less)."""
-    fr, ch, n, h, w, work, back = _label_batch_args(frames, background)
+    fr = _frames3(frames)
+    n, h, w = fr.shape
     cap = min(1024, h * w + 1) if table_entries is None else int(table_entries)
     dst = torch.empty((n, h, w), dtype=torch.int32, device=fr.device)
     xy = torch.zeros((n, cap, 2), dtype=torch.float64, device=fr.device)
     area = torch.zeros((n, cap), dtype=torch.int32, device=fr.device)
     count = torch.zeros(n, dtype=torch.int32, device=fr.device)
-    _check(_lib.rir_label_images_device(ord(ch), fr.data_ptr(), dst.data_ptr(), w, h, n, back.ctypes.data, xy.data_ptr(), area.data_ptr(), cap,
-                                        count.data_ptr(), work.data_ptr(), work.numel() * 8, _stream()), "rir_label_images_device")
+    _label_images_into(fr, background, dst, xy, area, count)
     return dst, area, xy, count
+
+
+TRACK_MAX_INDEX = 0x7FFF0000  # pixels of a frame, and frames x nlabels, of one track_components call
+
+
+class ComponentTracks(namedtuple("ComponentTracks", "tracks track_of ntracks truncated first_frame last_frame first_label components")):
+    """The result of ``track_components``, CUDA tensors: ``tracks`` int32 (n, h, w), the track of every pixel (0: background), or None;
+    ``track_of`` int32 (n, nlabels), the track of each component (0 where it does not exist); ``ntracks`` (0-d) = tracks + 1 and
+    ``truncated`` (0-d) = frames whose components >= nlabels were dropped; per track, ``table_entries`` entries each: ``first_frame``,
+    ``last_frame``, ``first_label`` (the label of the track's lowest node, in frame first_frame) and ``components`` (its nodes).  Entry 0
+    is the background's (-1, -1, 0, 0); entries from ntracks on are 0."""
+
+    __slots__ = ()
+
+
+def _track_args(labels_shape, counts_shape, nlabels, table_entries):
+    """the shapes and ranges of a track_components call, checked without a device; -> (n, h, w).  nlabels / table_entries None: left to the caller"""
+    if len(labels_shape) != 3:
+        raise ValueError("track_components: labels (n, h, w) expected")
+    n, h, w = labels_shape
+    if h < 1 or w < 1 or h * w > TRACK_MAX_INDEX:
+        raise ValueError("track_components: frames of at least 1x1 and at most 0x7FFF0000 pixels expected")
+    if counts_shape is not None and tuple(counts_shape) != (n,):
+        raise ValueError("track_components: counts of shape %s expected, not %s" % ((n,), tuple(counts_shape)))
+    if nlabels is not None and (int(nlabels) != nlabels or nlabels < 1 or n * nlabels > TRACK_MAX_INDEX):
+        raise ValueError("track_components: nlabels must be at least 1 with n * nlabels <= 0x7FFF0000 (got %r)" % (nlabels,))
+    if table_entries is not None and (int(table_entries) != table_entries or not 1 <= table_entries <= 0x7FFFFFFF):
+        raise ValueError("track_components: table_entries must be in 1..2^31 - 1 (got %r)" % (table_entries,))
+    return n, h, w
+
+
+def _track_inputs(labels, counts, nlabels, table_entries, relabel, out):
+    """track_components' checks, those that need no device first; -> (n, h, w)"""
+    if labels.dtype != torch.int32:
+        raise RuntimeError("track_components: int32 labels expected, not %s" % labels.dtype)
+    if counts is not None and counts.dtype != torch.int32:
+        raise RuntimeError("track_components: int32 counts expected, not %s" % counts.dtype)
+    n, h, w = _track_args(tuple(labels.shape), None if counts is None else tuple(counts.shape), nlabels, table_entries)
+    if out is not None:
+        if not relabel:
+            raise ValueError("track_components: 'out' given with relabel=False")
+        if out.dtype != torch.int32 or tuple(out.shape) != (n, h, w) or not out.is_contiguous():
+            raise RuntimeError("track_components: 'out' must be a C-contiguous int32 tensor of shape %s" % ((n, h, w),))
+    if not labels.is_cuda or (counts is not None and counts.device != labels.device) or (out is not None and out.device != labels.device):
+        raise RuntimeError("track_components: labels, counts and out on one CUDA device expected")
+    return n, h, w
+
+
+def track_components(labels, counts=None, nlabels=None, table_entries=None, relabel=True, out=None):
+    """Tracks of the components of a stack of per-frame label maps ``labels`` int32 (n, h, w), as ``label_images`` writes them, on the
+    current stream (C ABI ``rir_track_components_device``): a ``ComponentTracks``.  Component k of frame t exists when
+    1 <= k < min(nlabels, counts[t]) (``counts``: int32 (n,) as ``label_images`` returns it; without it 1 <= k < nlabels); components of
+    adjacent frames that share a pixel are linked, a track is a connected set of components, and tracks are numbered 1, 2, ... in the
+    order of their lowest (frame, label).  ``relabel``: also the track map ``tracks``, written into ``out`` when given - ``out=labels``
+    relabels in place.  ``nlabels=None`` takes ``int(counts.max())`` (``labels.max() + 1`` without counts, at least 1), which synchronises;
+    ``table_entries`` defaults to min(n * (nlabels - 1) + 1, 65 536).  ``region_stats(frames, tracks, int(ntracks))`` is then the time
+    trace of every track: its ``count`` is the track's area in each frame."""
+    n, h, w = _track_inputs(labels, counts, nlabels, table_entries, relabel, out)
+    in_place = out is not None and out.data_ptr() == labels.data_ptr() and labels.is_contiguous()
+    lab = labels.contiguous()
+    cnt = None if counts is None else counts.contiguous()
+    if nlabels is None:
+        nlabels = max(1, (int(cnt.max()) if cnt is not None else int(lab.max()) + 1) if n else 1)
+        _track_args(tuple(labels.shape), None, nlabels, None)
+    K = int(nlabels)
+    T = min(n * (K - 1) + 1, 65536) if table_entries is None else int(table_entries)
+    dev = lab.device
+    track_of = torch.empty((n, K), dtype=torch.int32, device=dev)
+    info = torch.empty(2, dtype=torch.int32, device=dev)
+    tables = [torch.empty(T, dtype=torch.int32, device=dev) for _ in range(4)]
+    dst = None
+    if relabel:
+        dst = lab if in_place else out if out is not None else torch.empty((n, h, w), dtype=torch.int32, device=dev)
+    need = _lib.rir_track_components_workspace_bytes(w, h, n, K)
+    if need == 0:
+        raise RuntimeError("track_components: geometry refused")
+    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    _check(_lib.rir_track_components_device(lab.data_ptr(), None if cnt is None else cnt.data_ptr(), w, h, n, K, track_of.data_ptr(), info.data_ptr(),
+                                            *(t.data_ptr() for t in tables), T, None if dst is None else dst.data_ptr(), work.data_ptr(),
+                                            work.numel() * 8, _stream()), "rir_track_components_device")
+    return ComponentTracks(out if in_place else dst, track_of, info[0], info[1], *tables)
 
 
 def keep_largest_areas(frames, background=0, foreground=1):

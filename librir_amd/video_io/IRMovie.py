@@ -393,6 +393,62 @@ class IRMovie(object):
             acc.push(fr, k0)
         return acc.result()
 
+    def track_hot_spots(self, threshold, selection=slice(None), table_entries=None, stats=True):
+        """The hot spots of the images of ``selection`` (as ``region_stats`` takes it) as tracks through time: every image ``movie[selection]``
+        gives (read-back filters applied) is thresholded - ``image > threshold``, an int or an ``(h, w)`` array or tensor for a per-pixel
+        threshold, e.g. from ``pixel_stats`` - and labelled (``librir_amd.device.label_images``), and the components of adjacent images of
+        the selection that share a pixel are joined into tracks (``librir_amd.device.track_components``).  -> ``(ComponentTracks,
+        RegionStats or None)``: the tracks, with ``tracks`` the int32 track map ``[len(selection)][h][w]``, and with ``stats`` the
+        ``region_stats`` of every image over its track map, ``[len(selection)][ntracks]`` - the time trace of every hot spot (``count`` is
+        its area in each image).  The recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of images (twice with ``stats``), but
+        the label stack of the whole selection stays on the device: 4 bytes a pixel and image."""
+        import torch
+
+        from ..device import _label_images_into, _region_stats_empty, _region_stats_into, _track_args, track_components
+
+        h, w = self.image_size
+        positions = self._stats_positions(selection, "track_hot_spots")
+        n = len(positions)
+        _track_args((n, h, w), None, None, table_entries)
+        device = torch.device("cuda", torch.cuda.current_device())
+        if isinstance(threshold, (int, np.integer)):
+            cut = int(threshold)
+        else:
+            cut = threshold if isinstance(threshold, torch.Tensor) else np.asarray(threshold)
+            if tuple(cut.shape) != (h, w):
+                raise ValueError("track_hot_spots: an int or an (h, w) threshold expected, not shape %s" % (tuple(cut.shape),))
+            if isinstance(cut, np.ndarray):
+                cut = torch.from_numpy(np.ascontiguousarray(cut, np.float64 if cut.dtype.kind == "f" else np.int64))
+            cut = cut.to(device)
+            if not cut.is_floating_point():
+                cut = cut.to(torch.int32) if cut.dtype in (torch.uint16, torch.int16, torch.uint8, torch.int8) else cut
+        stack = torch.empty((n, h, w), dtype=torch.int32, device=device)
+        counts = torch.zeros(n, dtype=torch.int32, device=device)
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, n), h, w), dtype=torch.uint16, device=device)
+        xy = torch.zeros((piece.shape[0], 1, 2), dtype=torch.float64, device=device)
+        area = torch.zeros((piece.shape[0], 1), dtype=torch.int32, device=device)
+
+        def pieces():
+            for k0 in range(0, n, per_piece):
+                sel = positions[k0:k0 + per_piece]
+                fr = piece[:len(sel)]
+                self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+                yield k0, k0 + len(sel), fr
+
+        for k0, k1, fr in pieces():
+            hot = (fr.view(torch.int16).to(torch.int32) & 0xFFFF) > cut
+            _label_images_into(hot, 0, stack[k0:k1], xy[:k1 - k0], area[:k1 - k0], counts[k0:k1])
+        nlabels = max(1, int(counts.max())) if n else 1
+        tracks = track_components(stack, counts, nlabels, table_entries, out=stack)
+        if not stats:
+            return tracks, None
+        ntracks = int(tracks.ntracks)
+        out = _region_stats_empty(n, ntracks, device)
+        for k0, k1, fr in pieces():
+            _region_stats_into(fr, stack[k0:k1], 1, ntracks, type(out)(*(t[k0:k1] for t in out)))
+        return tracks, out
+
     def _stats_positions(self, selection, what="region_stats"):
         """the positions of an int or a slice with a positive step, as to_tensor takes them"""
         total = self.images
