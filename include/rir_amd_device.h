@@ -293,6 +293,33 @@ extern "C"
 									void *d_work, size_t work_bytes, void *stream);
 	size_t rir_track_components_workspace_bytes(int w, int h, int nframes, int nlabels);
 
+	/* Polygon regions of interest rasterised into int32 label maps d_dst[nmaps][h][w], as rir_region_stats_device takes them (extension).
+	 * d_xy: double [nsets][npoly][max_pts][2], the (x, y) vertices; d_npts: int [nsets][npoly], the vertices of each polygon (0..max_pts;
+	 * any other count draws nothing); nsets = 1 (sets_per_map 0: one set for every map) or nmaps (1: set m for map m); d_values: int
+	 * [npoly], or null for the values 0 .. npoly - 1; d_shifts: null, or double [nmaps][2], (dx, dy) of map m.  Map m is filled with
+	 * `background`, then polygons 0 .. npoly - 1 are painted in that order with their values, later ones over earlier ones - bit for bit
+	 * the reference's draw_polygon (geometry.cpp:81-152, DrawPolygon.h:180-398) on an int32 image, called once per polygon:
+	 * vertices X = round(x + dx), Y = round(y + dy) in double (one addition, halves away from zero); 1 vertex: that pixel; 2 vertices:
+	 * the reference's line (vertical, horizontal, x-major y = round(x * a + b), y-major x = round((y - b) / a), from the first point up
+	 * to the second, which is drawn on its own); 3 or more: with B the vertices' bounding box [xmin, xmax + 1) x [ymin, ymax + 1), nothing
+	 * when B misses the image, else every row Y0 of B clipped to the image: edge (i, j = i - 1) with Y_i != Y_j crosses where
+	 * (Y_i < Y0 && Y_j >= Y0) || (Y_j < Y0 && Y_i >= Y0) - with <= for < on the clipped box's first row - at the node
+	 * round(X_i + ((double)(Y0 - Y_i) / (Y_j - Y_i)) * (X_j - X_i)), every operation rounded on its own; the sorted nodes are filled in pairs
+	 * (a, b): stop at the first a >= xmax, skip b < xmin, else max(a, xmin) .. min(b, xmax - 1).  On the first row equal neighbours are
+	 * dropped first, in place in a buffer of npts + 1 zeros: the count is then at least 1 and an odd count pairs its last node with the
+	 * entry after it (the sorted list's leftover, or 0) - so an apex draws its pixel, a polygon that is one horizontal run draws pixel
+	 * (0, y) if it reaches column 0 and nothing otherwise, and identical vertices draw nothing.
+	 * Deviation: the reference leaves huge and non-finite coordinates undefined; here a polygon draws nothing in a map where one of its
+	 * shifted coordinates is not finite or exceeds 2^24 in magnitude.
+	 * Every pixel of every map is written exactly once (no pre-fill needed), without atomics: bitwise reproducible.  npoly 0: background
+	 * maps (d_xy, d_npts may be null).  nmaps 0: nothing is done.  Bounds: w, h >= 1, w * h <= 0x7FFF0000, 0 <= npoly <= 65536,
+	 * 1 <= max_pts <= 1024.  d_work: device memory, 8-byte aligned, at least rir_polygon_map_workspace_bytes(...) (0: arguments refused).
+	 * Asynchronous on `stream`; the maps and the workspace may not overlap an input or each other.  0 / -1 (invalid argument, null
+	 * pointer, overlap, workspace too small, no device). */
+	int rir_polygon_map_device(const double *d_xy, const int *d_npts, const int *d_values, int npoly, int max_pts, int nmaps, int sets_per_map,
+							   const double *d_shifts, int w, int h, int background, int *d_dst, void *d_work, size_t work_bytes, void *stream);
+	size_t rir_polygon_map_workspace_bytes(int w, int h, int nmaps, int npoly, int max_pts);
+
 	/* connected components: reference signal_processing.h:90-92 / Filters.h:365-540 (labelImage, keepLargestArea) on images in device memory,
 	 * [nframes][h][w], every image labelled on its own; five launches for the whole batch.  type: the reference's dtype character;
 	 * background: HOST pointer to one cell of that type.  d_dst int32 [nframes][h][w].

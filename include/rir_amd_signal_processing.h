@@ -73,6 +73,11 @@ extern "C"
 	 * device in slabs of at most 64 MiB that accumulate there; the outputs come back once.  nframes 0: nothing is done.  0 / -1. */
 	int rir_pixel_stats(const unsigned short *frames, int w, int h, int nframes, long long *sum, long long *sumsq, int *min, int *max,
 						int *argmin, int *argmax);
+	/* Polygon label maps into host memory dst[nmaps][h][w] from host polygons: rir_polygon_map_device (rir_amd_device.h, where the fill is
+	 * defined), synchronous.  The polygons, values and shifts go up once; the maps come back in slabs of at most 64 MiB.  values and shifts
+	 * may be null.  nmaps 0: nothing is done.  0 / -1. */
+	int rir_polygon_map(const double *xy, const int *npts, const int *values, int npoly, int max_pts, int nmaps, int sets_per_map,
+						const double *shifts, int w, int h, int background, int *dst);
 
 #ifdef __cplusplus
 }

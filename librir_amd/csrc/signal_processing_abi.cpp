@@ -15,6 +15,7 @@
 #include "filter_kernels.h"
 #include "label_kernels.h"
 #include "pixel_kernels.h"
+#include "polygon_kernels.h"
 #include "region_kernels.h"
 #include "runtime.h"
 #include "temporal_kernels.h"
@@ -849,6 +850,62 @@ RIR_EXPORT int rir_track_components_device(const int *d_labels, const int *d_cou
 			   : -1;
 }
 
+// Polygon label maps (polygon_kernels.hip).  Every argument is checked here; the maps and the workspace may not overlap an input or each other.
+RIR_EXPORT size_t rir_polygon_map_workspace_bytes(int w, int h, int nmaps, int npoly, int max_pts)
+{
+	return polygon_map_workspace(w, h, nmaps, npoly, max_pts);
+}
+
+RIR_EXPORT int rir_polygon_map_device(const double *d_xy, const int *d_npts, const int *d_values, int npoly, int max_pts, int nmaps, int sets_per_map,
+									  const double *d_shifts, int w, int h, int background, int *d_dst, void *d_work, size_t work_bytes, void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (!polygon_geometry_ok(w, h, nmaps, npoly, max_pts) || (sets_per_map != 0 && sets_per_map != 1))
+	{
+		log_error("rir_polygon_map_device: invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, nmaps >= 0, 0 <= npoly <= 65536, 1 <= max_pts <= 1024, "
+				  "sets_per_map 0 or 1)");
+		return -1;
+	}
+	if (nmaps == 0)
+		return 0;
+	if (!d_dst || !d_work || (npoly > 0 && (!d_xy || !d_npts)))
+	{
+		log_error("rir_polygon_map_device: null pointer");
+		return -1;
+	}
+	const size_t need = polygon_map_workspace(w, h, nmaps, npoly, max_pts);
+	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
+	{
+		log_error("rir_polygon_map_device: the workspace must be 8-byte aligned and hold rir_polygon_map_workspace_bytes() bytes");
+		return -1;
+	}
+	const size_t polys = (size_t)npoly * (sets_per_map ? nmaps : 1);
+	const struct
+	{
+		uintptr_t p;
+		size_t bytes;
+	} in[4] = {{(uintptr_t)d_xy, polys * max_pts * 16},
+			   {(uintptr_t)d_npts, polys * 4},
+			   {(uintptr_t)d_values, d_values ? (size_t)npoly * 4 : 0},
+			   {(uintptr_t)d_shifts, d_shifts ? (size_t)nmaps * 16 : 0}},
+	  out[2] = {{(uintptr_t)d_dst, (size_t)w * h * nmaps * 4}, {(uintptr_t)d_work, need}};
+	bool overlap = out[0].p < out[1].p + out[1].bytes && out[1].p < out[0].p + out[0].bytes;
+	for (const auto &o : out)
+		for (const auto &a : in)
+			overlap |= a.bytes != 0 && o.p < a.p + a.bytes && a.p < o.p + o.bytes;
+	if (overlap)
+	{
+		log_error("rir_polygon_map_device: the maps or the workspace overlap an input or each other");
+		return -1;
+	}
+	return hip_ok(launch_polygon_map(d_xy, d_npts, d_values, npoly, max_pts, nmaps, sets_per_map, d_shifts, w, h, background, d_dst, d_work,
+									 as_stream(stream)),
+				  "polygon_map")
+			   ? 0
+			   : -1;
+}
+
 // =====================================================================================================
 // Reference entry points (host pointers, synchronous)
 // =====================================================================================================
@@ -1157,6 +1214,50 @@ RIR_EXPORT int rir_pixel_stats(const unsigned short *frames, int w, int h, int n
 		if (!hip_ok(hipMemcpyAsync(outs32[k], d32 + (size_t)k * npx, npx * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync"))
 			return -1;
 	return hip_ok(wait_stream(st), "pixel_stats") ? 0 : -1;
+}
+
+// Extension: polygon label maps into host memory.  The polygons, values and shifts go up once; the maps are made on the device in slabs of at
+// most REGION_SLAB_BYTES and come back slab by slab.  Synchronous.  0 / -1.
+RIR_EXPORT int rir_polygon_map(const double *xy, const int *npts, const int *values, int npoly, int max_pts, int nmaps, int sets_per_map,
+							   const double *shifts, int w, int h, int background, int *dst)
+{
+	if (!device_ready())
+		return -1;
+	if (!polygon_geometry_ok(w, h, nmaps, npoly, max_pts) || (sets_per_map != 0 && sets_per_map != 1) || (nmaps > 0 && !dst) ||
+		(nmaps > 0 && npoly > 0 && (!xy || !npts)))
+	{
+		log_error("rir_polygon_map: invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, nmaps >= 0, 0 <= npoly <= 65536, 1 <= max_pts <= 1024, "
+				  "sets_per_map 0 or 1, no null pointer)");
+		return -1;
+	}
+	if (nmaps == 0)
+		return 0;
+	const size_t npx = (size_t)w * h, polys = (size_t)npoly * (sets_per_map ? nmaps : 1), set_doubles = (size_t)npoly * max_pts * 2;
+	const int slab = (int)std::max<size_t>(1, std::min<size_t>(REGION_SLAB_BYTES / (npx * 4), (size_t)nmaps));
+	const size_t work = polygon_map_workspace(w, h, slab, npoly, max_pts);
+	DeviceBuffer dxy, dn, dv, ds, maps, ws;
+	hipStream_t st = default_stream();
+	const bool with_values = npoly > 0 && values;
+	if (!maps.reserve(npx * 4 * slab) || !ws.reserve(work) || (npoly > 0 && (!dxy.reserve(polys * max_pts * 16) || !dn.reserve(polys * 4))) ||
+		(with_values && !dv.reserve((size_t)npoly * 4)) || (shifts && !ds.reserve((size_t)nmaps * 16)))
+		return -1; // nothing is queued yet
+	bool ok = (npoly == 0 || (hip_ok(hipMemcpyAsync(dxy.ptr, xy, polys * max_pts * 16, hipMemcpyHostToDevice, st), "hipMemcpyAsync") &&
+							  hip_ok(hipMemcpyAsync(dn.ptr, npts, polys * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))) &&
+			  (!with_values || hip_ok(hipMemcpyAsync(dv.ptr, values, (size_t)npoly * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) &&
+			  (!shifts || hip_ok(hipMemcpyAsync(ds.ptr, shifts, (size_t)nmaps * 16, hipMemcpyHostToDevice, st), "hipMemcpyAsync"));
+	for (int o = 0; ok && o < nmaps; o += slab)
+	{
+		const int c = std::min(slab, nmaps - o);
+		const size_t set = sets_per_map ? (size_t)o : 0;
+		ok = rir_polygon_map_device(npoly > 0 ? dxy.as<double>() + set * set_doubles : nullptr, npoly > 0 ? dn.as<int>() + set * npoly : nullptr,
+									with_values ? dv.as<int>() : nullptr, npoly, max_pts, c, sets_per_map, shifts ? ds.as<double>() + (size_t)o * 2 : nullptr, w,
+									h, background, maps.as<int>(), ws.ptr, work, st) == 0 &&
+			 hip_ok(hipMemcpyAsync(dst + (size_t)o * npx, maps.ptr, npx * 4 * c, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") &&
+			 hip_ok(wait_stream(st), "polygon_map");
+	}
+	if (!ok)
+		(void)wait_stream(st); // what was queued is done before the buffers go
+	return ok ? 0 : -1;
 }
 
 RIR_EXPORT void bad_pixels_destroy(int handle)

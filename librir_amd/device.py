@@ -10,8 +10,8 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
-from .signal_processing.rir_signal_processing import (PixelStats, RegionStats, _pixel_stats_args, _region_stats_args,  # noqa: F401 (API)
-                                                      _temporal_median_args)
+from .signal_processing.rir_signal_processing import (PixelStats, RegionStats, _pixel_stats_args, _polygon_map_args,  # noqa: F401 (API)
+                                                      _region_stats_args, _temporal_median_args)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -120,6 +120,9 @@ _lib.rir_pixel_stats_workspace_bytes.restype = ct.c_size_t
 _lib.rir_track_components_device.argtypes = [_vp, _vp] + [ct.c_int] * 4 + [_vp] * 6 + [ct.c_int, _vp, _vp, ct.c_size_t, _vp]
 _lib.rir_track_components_workspace_bytes.argtypes = [ct.c_int] * 4
 _lib.rir_track_components_workspace_bytes.restype = ct.c_size_t
+_lib.rir_polygon_map_device.argtypes = [_vp] * 3 + [ct.c_int] * 4 + [_vp] + [ct.c_int] * 3 + [_vp, _vp, ct.c_size_t, _vp]
+_lib.rir_polygon_map_workspace_bytes.argtypes = [ct.c_int] * 5
+_lib.rir_polygon_map_workspace_bytes.restype = ct.c_size_t
 _lib.bad_pixels_destroy.argtypes = [ct.c_int]
 _lib.rir_label_workspace_bytes.argtypes = [ct.c_int, ct.c_int]
 _lib.rir_label_workspace_bytes.restype = ct.c_size_t
@@ -750,6 +753,59 @@ def region_stats(frames, labels, nregions=None):
     out = _region_stats_empty(n, int(nregions), fr.device)
     if n:
         _region_stats_into(fr, lab, per_frame, int(nregions), out)
+    return out
+
+
+def _polygon_inputs(a, device):
+    """the packed polygons, values and shifts of a PolygonMapArgs as contiguous tensors on `device` (None where there is none)"""
+    def up(t, dtype):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor):
+            t = torch.from_numpy(np.ascontiguousarray(t))
+        return t.to(device=device, dtype=dtype).contiguous()
+
+    return up(a.xy, torch.float64), up(a.npts, torch.int32), up(a.values, torch.int32), up(a.shifts, torch.float64)
+
+
+def _polygon_map_into(xy, npts, values, shifts, per_map, background, out):
+    """queue the maps out [n][h][w] (contiguous int32) of the packed polygons xy [(n)][npoly][max_pts][2], npts [(n)][npoly]"""
+    n, h, w = out.shape
+    npoly, max_pts = xy.shape[-3], xy.shape[-2]
+    need = _lib.rir_polygon_map_workspace_bytes(w, h, n, npoly, max_pts)
+    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=out.device)
+    _check(_lib.rir_polygon_map_device(xy.data_ptr() if npoly else None, npts.data_ptr() if npoly else None,
+                                       values.data_ptr() if values is not None and npoly else None, npoly, max_pts, n, per_map,
+                                       shifts.data_ptr() if shifts is not None else None, w, h, int(background), out.data_ptr(), work.data_ptr(),
+                                       work.numel() * 8, _stream()), "rir_polygon_map_device")
+
+
+def polygon_map(polygons, shape, values=None, background=-1, shifts=None, out=None):
+    """Polygon regions of interest rasterised into int32 label maps of ``shape`` (h, w) on the current stream (C ABI
+    ``rir_polygon_map_device``), as ``region_stats`` takes them: the map is filled with ``background`` (-1: what region_stats ignores) and
+    the polygons are painted in order with ``values`` (default 0, 1, ...), later ones over earlier ones, exactly as the reference's
+    ``draw_polygon`` paints each.  ``polygons``: a list of (k, 2) array-likes of (x, y), packed on the host - one point draws a pixel, two a
+    line - or a list of such lists, one per map, or a packed pair ``(xy, npts)`` of CUDA tensors (float64 (npoly, max_pts, 2) with int32
+    (npoly,), or with a leading n for one set per map), used where they are.  ``shifts`` (n, 2), array or tensor: map m is drawn with every
+    vertex moved by (dx, dy) = shifts[m].  -> an int32 CUDA tensor (h, w) for one set without shifts, else (n, h, w); ``out``: such a
+    tensor to write into.  A polygon with a coordinate that is not finite or beyond 2^24 draws nothing.  ``ValueError`` on bad shapes."""
+    a = _polygon_map_args(polygons, shape, values, background, None if isinstance(shifts, torch.Tensor) else shifts)
+    if isinstance(shifts, torch.Tensor):  # stays on the device: only its shape is checked
+        if shifts.dim() != 2 or shifts.shape[1] != 2 or (a.per_map and shifts.shape[0] != a.nmaps):
+            raise ValueError("polygon_map: shifts (n, 2) expected%s, not %s" % (" with n = %d sets" % a.nmaps if a.per_map else "", tuple(shifts.shape)))
+        a = a._replace(shifts=shifts, nmaps=shifts.shape[0], out_shape=(shifts.shape[0], a.h, a.w))
+    if out is not None:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != a.out_shape or not out.is_contiguous():
+            raise RuntimeError("polygon_map: out must be a contiguous int32 tensor of shape %s" % (a.out_shape,))
+        if not out.is_cuda:
+            raise RuntimeError("polygon_map: out on a CUDA device expected")
+    device = out.device if out is not None else a.xy.device if isinstance(a.xy, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+    if device.type != "cuda":
+        raise RuntimeError("polygon_map: packed polygons on a CUDA device expected")
+    if out is None:
+        out = torch.empty(a.out_shape, dtype=torch.int32, device=device)
+    if a.nmaps:
+        _polygon_map_into(*_polygon_inputs(a, device), a.per_map, background, out.view(a.nmaps, a.h, a.w))
     return out
 
 

@@ -347,6 +347,121 @@ def pixel_stats(images, sums=True, extremes=True):
     return PixelStats(*out, count=n)
 
 
+# ---- extension: polygon label maps ----------------------------------------------------------------------------------------------
+_sp.rir_polygon_map.argtypes = [ct.c_void_p] * 3 + [ct.c_int] * 4 + [ct.c_void_p] + [ct.c_int] * 3 + [ct.c_void_p]
+
+MAX_POLYGONS = 1 << 16
+MAX_POLYGON_POINTS = 1024
+MAX_MAP_PIXELS = 0x7FFF0000
+
+PolygonMapArgs = namedtuple("PolygonMapArgs", "xy npts values shifts nmaps per_map npoly max_pts h w out_shape")
+
+
+def _is_polygon(e):
+    """a (k, 2) array-like of points (an empty sequence: no point), as opposed to a list of polygons"""
+    if hasattr(e, "ndim"):
+        return e.ndim == 2 or (e.ndim == 1 and e.shape[0] == 0)
+    if not isinstance(e, (list, tuple)):
+        raise ValueError("polygon_map: polygons as (k, 2) array-likes expected, not %s" % type(e).__name__)
+    return len(e) == 0 or np.ndim(e[0]) == 1
+
+
+def _pack_polygons(sets):
+    """lists of (k, 2) array-likes, one list per set -> xy float64 (nsets, npoly, max_pts, 2), npts int32 (nsets, npoly); sets with fewer
+    polygons are filled up with polygons of no point"""
+    arrays = []
+    for s in sets:
+        row = []
+        for p in s:
+            a = np.asarray(p, np.float64)
+            if a.size == 0:
+                a = a.reshape(0, 2)
+            if a.ndim != 2 or a.shape[1] != 2:
+                raise ValueError("polygon_map: a polygon is a (k, 2) array of (x, y), not of shape %s" % (a.shape,))
+            row.append(a)
+        arrays.append(row)
+    npoly = max((len(r) for r in arrays), default=0)
+    max_pts = max((len(a) for r in arrays for a in r), default=0)
+    xy = np.zeros((len(arrays), npoly, max(1, max_pts), 2), np.float64)
+    npts = np.zeros((len(arrays), npoly), np.int32)
+    for s, r in enumerate(arrays):
+        for p, a in enumerate(r):
+            xy[s, p, :len(a)] = a
+            npts[s, p] = len(a)
+    return xy, npts
+
+
+def _polygon_map_args(polygons, shape, values=None, background=-1, shifts=None):
+    """the arguments of a polygon_map call, packed and checked without a device -> PolygonMapArgs.  ``polygons``: a list of (k, 2)
+    array-likes (one set for every map), a list of such lists (one set per map), or a packed pair (xy, npts) - xy float64
+    (npoly, max_pts, 2) with npts int32 (npoly,), or (n, npoly, max_pts, 2) with (n, npoly) - of numpy arrays or tensors, which is passed
+    on as it is.  values and shifts come back as numpy arrays (or None)."""
+    if len(shape) != 2 or int(shape[0]) != shape[0] or int(shape[1]) != shape[1] or shape[0] < 1 or shape[1] < 1 or shape[0] * shape[1] > MAX_MAP_PIXELS:
+        raise ValueError("polygon_map: shape (h, w) of at least 1x1 and at most 0x7FFF0000 pixels expected, not %r" % (shape,))
+    h, w = int(shape[0]), int(shape[1])
+    packed = isinstance(polygons, (tuple, list)) and len(polygons) == 2 and all(hasattr(a, "ndim") and hasattr(a, "dtype") for a in polygons) and \
+        polygons[0].ndim in (3, 4)
+    if packed:
+        xy, npts = polygons
+        if "float64" not in str(xy.dtype) or "int32" not in str(npts.dtype):
+            raise RuntimeError("polygon_map: packed polygons are float64 xy and int32 npts, not %s and %s" % (xy.dtype, npts.dtype))
+        if xy.shape[-1] != 2 or tuple(npts.shape) != tuple(xy.shape[:-2]):
+            raise ValueError("polygon_map: packed xy (n, npoly, max_pts, 2) with npts (n, npoly), or without n, expected, not %s and %s"
+                             % (tuple(xy.shape), tuple(npts.shape)))
+        per_map = xy.ndim == 4
+    else:
+        if not isinstance(polygons, (tuple, list)):
+            raise ValueError("polygon_map: a list of polygons, a list of such lists or a packed (xy, npts) pair expected")
+        kinds = [_is_polygon(e) for e in polygons]
+        if any(kinds) and not all(kinds):
+            raise ValueError("polygon_map: either polygons or lists of polygons expected, not both in one list")
+        per_map = len(kinds) > 0 and not kinds[0]
+        xy, npts = _pack_polygons(polygons if per_map else [polygons])
+        if not per_map:
+            xy, npts = xy[0], npts[0]
+    nsets = xy.shape[0] if per_map else 1
+    npoly, max_pts = int(xy.shape[-3]), int(xy.shape[-2])
+    if npoly > MAX_POLYGONS or not 1 <= max_pts <= MAX_POLYGON_POINTS:
+        raise ValueError("polygon_map: at most %d polygons of at most %d points expected (got %d of up to %d)"
+                         % (MAX_POLYGONS, MAX_POLYGON_POINTS, npoly, max_pts))
+    if values is not None:
+        v = np.asarray(values)
+        if v.shape != (npoly,) or v.dtype.kind not in "iu" or (v.size and (v.min() < -(1 << 31) or v.max() >= 1 << 31)):
+            raise ValueError("polygon_map: values are %d int32, one per polygon" % npoly)
+        values = np.ascontiguousarray(v, np.int32)
+    if int(background) != background or not -(1 << 31) <= background < 1 << 31:
+        raise ValueError("polygon_map: an int32 background expected, not %r" % (background,))
+    nmaps = nsets
+    if shifts is not None:
+        shifts = np.ascontiguousarray(shifts.detach().cpu().numpy() if hasattr(shifts, "detach") else shifts, np.float64)
+        if shifts.ndim != 2 or shifts.shape[1] != 2 or (per_map and shifts.shape[0] != nsets):
+            raise ValueError("polygon_map: shifts (n, 2) expected%s, not %s" % (" with n = %d sets" % nsets if per_map else "", shifts.shape))
+        nmaps = shifts.shape[0]
+    out_shape = (nmaps, h, w) if per_map or shifts is not None else (h, w)
+    return PolygonMapArgs(xy, npts, values, shifts, nmaps, int(per_map), npoly, max_pts, h, w, out_shape)
+
+
+def polygon_map(polygons, shape, values=None, background=-1, shifts=None, out=None):
+    """Extension: polygon regions of interest rasterised into int32 label maps of ``shape`` (h, w), as ``region_stats`` takes them
+    (``rir_polygon_map``): the map is filled with ``background`` (-1: what region_stats ignores) and the polygons are painted in order
+    with ``values`` (default 0, 1, ...), later ones over earlier ones, exactly as the reference's ``draw_polygon`` paints each.
+    ``polygons``: a list of (k, 2) arrays of (x, y) - one point draws a pixel, two a line - or a list of such lists, one per map, or a
+    packed ``(xy, npts)`` pair; ``shifts`` (n, 2): map m is drawn with every vertex moved by (dx, dy) = shifts[m].  -> a numpy array
+    (h, w) for one set without shifts, else (n, h, w).  A polygon with a coordinate that is not finite or beyond 2^24 draws nothing.
+    ``ValueError`` on bad shapes, ``RuntimeError`` on other dtypes and when the library fails."""
+    a = _polygon_map_args(polygons, shape, values, background, shifts)
+    xy, npts = (np.ascontiguousarray(t.cpu().numpy() if hasattr(t, "cpu") else t) for t in (a.xy, a.npts))
+    if out is None:
+        out = np.empty(a.out_shape, np.int32)
+    elif not isinstance(out, np.ndarray) or out.dtype != np.int32 or out.shape != a.out_shape or not out.flags.c_contiguous:
+        raise RuntimeError("polygon_map: out must be a contiguous int32 array of shape %s" % (a.out_shape,))
+    if a.nmaps and _sp.rir_polygon_map(xy.ctypes.data if a.npoly else None, npts.ctypes.data if a.npoly else None,
+                                       a.values.ctypes.data if a.values is not None and a.npoly else None, a.npoly, a.max_pts, a.nmaps, a.per_map,
+                                       a.shifts.ctypes.data if a.shifts is not None else None, a.w, a.h, int(background), out.ctypes.data) < 0:
+        raise RuntimeError("An error occured while calling 'polygon_map': " + (last_error() or ""))
+    return out
+
+
 # ---- time axes (host bookkeeping, csrc/time_series.cpp) -------------------------------------------------------------------------
 _sp.extract_times.argtypes = [ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p, ct.POINTER(ct.c_int)]
 _sp.resample_time_serie.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_int, ct.c_int, ct.c_double, ct.c_void_p, ct.POINTER(ct.c_int)]

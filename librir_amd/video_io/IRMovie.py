@@ -370,6 +370,42 @@ class IRMovie(object):
             _region_stats_into(fr, lab, 0, int(nregions), type(out)(*(t[k0:k0 + len(sel)] for t in out)))
         return out
 
+    def polygon_stats(self, polygons, selection=slice(None), shifts=None, values=None):
+        """Statistics of the images of ``selection`` (as ``region_stats`` takes it) over polygon regions of interest
+        (``librir_amd.device.polygon_map`` takes ``polygons`` and ``values`` the same way): a ``RegionStats`` of CUDA tensors
+        ``[len(selection)][nregions]``, region r being the pixels painted with value r - ``nregions`` is the number of polygons, or
+        ``max(values) + 1``.  Without ``shifts`` one map is drawn and ``region_stats`` runs over it.  With ``shifts`` of shape
+        ``(len(selection), 2)``, e.g. a registration table, image k is measured with every polygon moved by ``+shifts[k]``: the maps of each
+        piece of images are drawn beside it, pieces sized so that images and maps together stay within ``_STATS_PIECE_BYTES``."""
+        import torch
+
+        from ..device import _polygon_inputs, _polygon_map_args, _polygon_map_into, _region_stats_empty, _region_stats_into, polygon_map
+
+        h, w = self.image_size
+        positions = self._stats_positions(selection, "polygon_stats")
+        n = len(positions)
+        a = _polygon_map_args(polygons, (h, w), values, -1, shifts.detach().cpu().numpy() if isinstance(shifts, torch.Tensor) else shifts)
+        if (a.per_map or a.shifts is not None) and a.nmaps != n:
+            raise ValueError("polygon_stats: one shift or set of polygons per image of the selection expected (%d), not %d" % (n, a.nmaps))
+        nregions = max(1, a.npoly if a.values is None else int(a.values.max(initial=-1)) + 1)
+        if not a.per_map and a.shifts is None:
+            return self.region_stats(polygon_map(polygons, (h, w), values), selection, nregions)
+        device = a.xy.device if isinstance(a.xy, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        xy, npts, vals, moves = _polygon_inputs(a, device)
+        out = _region_stats_empty(n, nregions, device)
+        per_piece = max(1, self._STATS_PIECE_BYTES // (6 * h * w))
+        piece = torch.empty((min(per_piece, n), h, w), dtype=torch.uint16, device=device)
+        maps = torch.empty((min(per_piece, n), h, w), dtype=torch.int32, device=device)
+        for k0 in range(0, n, per_piece):
+            sel = positions[k0:k0 + per_piece]
+            k1 = k0 + len(sel)
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            _polygon_map_into(xy[k0:k1] if a.per_map else xy, npts[k0:k1] if a.per_map else npts, vals, None if moves is None else moves[k0:k1],
+                              a.per_map, -1, maps[:len(sel)])
+            _region_stats_into(fr, maps[:len(sel)], 1, nregions, type(out)(*(t[k0:k1] for t in out)))
+        return out
+
     def pixel_stats(self, selection=slice(None), sums=True, extremes=True):
         """Statistics over time of the images of ``selection`` (as ``region_stats`` takes it) - ``librir_amd.device.pixel_stats`` over the
         images ``movie[selection]`` gives (read-back filters applied): a ``PixelStats`` of CUDA tensors ``[h][w]``, per pixel the exact sum
