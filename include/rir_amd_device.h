@@ -397,6 +397,57 @@ extern "C"
 	int rir_lossy_spec_stats(int handle, int *out4, void *stream);
 	void rir_lossy_destroy(int handle);
 
+	/* ---- adaptive temporal downsampling (max-hold) on a device-resident stream -------------------------------
+	 * VideoDownsampler (reference src/cpp/video_io/h264.cpp:117-451, h264.h:13-30), the event-driven recorder: out of a sequence about one
+	 * image in `factor` is kept, more while the scene changes, and a kept image is the per-pixel maximum of everything since the last kept
+	 * one, so a flash between two kept images is not lost.  uint16 frames [n][height][width] in HBM in, the kept images in HBM out.
+	 * Parameters: 1 <= lossy_height <= height, S = width * lossy_height >= 2, factor >= 1, factor_std in [0, 1], method 1 (addImage) or
+	 * 2 (addImage2); the history holds at most 96 statistics; part = (int)(factor_std * 96) clamped to 0..95.  Per image i, in order:
+	 *   factor 1: the image is emitted as it is, nothing else is done.
+	 *   statistic (i >= 1): over the first S pixels of images i and i - 1, d = |a - b|, x = sum d, q = sum d^2 as exact integers converted
+	 *     to double once, stat = sqrt((q - (x * x) / S) / (S - 1)), every operation rounded on its own.
+	 *   hold: max_im = max(max_im, image) over the first S pixels, rows from lossy_height on copied from the image.  An emission outputs
+	 *     max_im for the current image (its time stamp and attributes go with it) and zeroes max_im: output k is the maximum over the
+	 *     images after the previous kept one up to the keeping one, its rows below lossy_height are the keeping image's.  Image 0 is always
+	 *     kept and emitted as itself.
+	 *   method 1: while the history holds fewer than 96 entries, push stat (i > 0) and keep when i % factor == 0.  After that val = the
+	 *     part-th smallest entry, (mean, std) = mean_std(history), nothing = stat < mean - 0.5 * std, false when i - last_added >= 2 * factor;
+	 *     keep when (stat > val || i - last_added >= factor) && !nothing; then, when stat < mean + 10 * std, the oldest entry is dropped and
+	 *     stat appended.
+	 *   method 2: image 0 is kept.  While the history holds fewer than 10 entries, push stat and keep when i % factor == 0.  After that
+	 *     nothing = (std / mean < 0.1) && stat < mean + 2 * std; keep when i % factor == 0 || (!nothing && stat > mean + 0.5 * std); the
+	 *     history takes stat when (stat < mean + 5 * std && stat > mean - std) || i % factor == 0 - appended below 96 entries, else slid in.
+	 *   mean_std: x += p, x2 += p * p in index order; x / n and sqrt((x2 - (x * x) / n) / (n - 1)).  A NaN result makes every comparison it
+	 *     enters false, as in the reference.
+	 * Deviations: (1) the sums are exact int64 - the reference accumulates in double, the same value while S * 65535^2 < 2^53, and squares
+	 * in int, undefined for d > 46340; S > 2^31 - 1 is refused.  (2) A negative radicand of stat, which only the rounding of x * x can
+	 * produce, gives 0 and not NaN (the reference would hand a NaN to std::nth_element): the history never holds a NaN.  (3) The reference
+	 * refuses single images whose time stamp does not increase; here a push is refused as a whole, with nothing done, when its time stamps
+	 * are not strictly increasing or do not exceed the last one pushed.  (4) Method 2 writes last_added and never reads it: not kept.
+	 *
+	 * rir_downsampler_create: a handle > 0 in the common handle namespace, 0 on failure (invalid argument, no device).
+	 * rir_downsampler_push_device: the next nframes images of the stream; returns the number of images kept by this push (written to
+	 * d_out[0 .. kept), capacity nframes images, which may not overlap d_frames), or -1 (invalid argument, time stamps, overlap, no
+	 * device: the state is untouched).  timestamps: HOST [nframes]; positions: HOST int[nframes], positions[k] = the index within this
+	 * push of the image that triggered output k, whose time stamp and attributes go with it; stats: HOST double[nframes] or NULL,
+	 * stats[i] = the statistic of image i, 0 for the very first image of the stream and for factor 1.  Two passes over the frames
+	 * (pair sums, then the maxima of the kept images) with the recurrence on the host between them: the call waits ONCE for `stream`,
+	 * after the first pass - which also serves the caller's queued work - and returns with the second pass queued.  Any split of a
+	 * sequence into pushes gives the outputs, positions and statistics of one push of the whole; the state is the previous image and
+	 * the running maximum (on the device), the history and the counters.  Integer work on the device, bitwise reproducible.  nframes 0: 0.
+	 * rir_downsampler_count: images kept so far (what the reference's close() returns), -1 for an unknown handle. */
+	int rir_downsampler_create(int width, int height, int lossy_height, int factor, double factor_std, int method);
+	int rir_downsampler_push_device(int handle, const unsigned short *d_frames, int nframes, const long long *timestamps, unsigned short *d_out,
+									int *positions, double *stats, void *stream);
+	int rir_downsampler_count(int handle);
+	void rir_downsampler_destroy(int handle);
+	/* The recurrence alone, on the host, no device involved: sums[i] = {x, q} of image i (ignored for the first image of a stream),
+	 * size = S; state: rir_downsample_state_bytes() bytes, 8-byte aligned, all zero for a stream that has seen nothing, carried from
+	 * call to call; keep[i] = 1 where image i triggers an output; stats: [n] or NULL.  Returns the number kept, -1 on an invalid argument. */
+	int rir_downsample_decide(int factor, double factor_std, int method, long long size, const long long *sums, int n, void *state, int *keep,
+							  double *stats);
+	size_t rir_downsample_state_bytes(void);
+
 	/* ---- byte planes ------------------------------------------------------------------------------
 	 * H264Capture::AddFrame (reference src/cpp/video_io/h264.cpp:1066-1082): U = v & 0xFF, V = v >> 8, Y = 0 or
 	 * the 8-bit integration-time image, rows padded to `linesize`; VideoGrabber::toArray (:3016-3051) is the

@@ -140,6 +140,13 @@ _lib.rir_lossy_status.argtypes = [ct.c_int, _vp]
 _lib.rir_lossy_path_stats.argtypes = [ct.c_int, ct.POINTER(ct.c_int), _vp]
 _lib.rir_lossy_spec_stats.argtypes = [ct.c_int, ct.POINTER(ct.c_int), _vp]
 _lib.rir_lossy_set_errors.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.c_double]
+_lib.rir_downsampler_create.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_double, ct.c_int]
+_lib.rir_downsampler_push_device.argtypes = [ct.c_int, _vp, ct.c_int, _vp, _vp, _vp, _vp, _vp]
+_lib.rir_downsampler_count.argtypes = [ct.c_int]
+_lib.rir_downsampler_destroy.argtypes = [ct.c_int]
+_lib.rir_downsampler_destroy.restype = None
+_lib.rir_downsample_decide.argtypes = [ct.c_int, ct.c_double, ct.c_int, ct.c_longlong, _vp, ct.c_int, _vp, _vp, _vp]
+_lib.rir_downsample_state_bytes.restype = ct.c_size_t
 _lib.rir_split_planes_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp, _vp, _vp, _vp]
 _lib.rir_merge_planes_device.argtypes = [_vp, _vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp, _vp, _vp]
 _lib.bad_pixels_destroy.restype = None
@@ -1192,3 +1199,110 @@ class LossyStream:
             self.close()
         except Exception:
             pass
+
+
+Downsampled = namedtuple("Downsampled", "frames timestamps positions stats")
+
+
+def _downsample_args(width, height, factor, factor_std, lossy_height, method):
+    """the checks of ``Downsampler`` that need no device; -> (width, height, lossy_height, factor, factor_std, method)"""
+    width, height, factor, method = int(width), int(height), int(factor), int(method)
+    lossy_height = height if lossy_height is None else int(lossy_height)
+    factor_std = float(factor_std)
+    if width < 1 or height < 1 or width * height > 2147483647:
+        raise ValueError("Downsampler: width, height >= 1 with width * height < 2^31 expected")
+    if not 1 <= lossy_height <= height:
+        raise ValueError("Downsampler: lossy_height in 1..height expected, not %d" % lossy_height)
+    if width * lossy_height < 2:
+        raise ValueError("Downsampler: width * lossy_height >= 2 expected")
+    if factor < 1:
+        raise ValueError("Downsampler: factor >= 1 expected, not %d" % factor)
+    if not 0.0 <= factor_std <= 1.0:
+        raise ValueError("Downsampler: factor_std in [0, 1] expected, not %r" % factor_std)
+    if method not in (1, 2):
+        raise ValueError("Downsampler: method 1 or 2 expected, not %d" % method)
+    return width, height, lossy_height, factor, factor_std, method
+
+
+def _downsample_stamps(timestamps, n, last):
+    """the time stamps of a push as int64 [n], strictly increasing from ``last`` (or None) on"""
+    ts = np.ascontiguousarray(np.asarray(timestamps).reshape(-1), dtype=np.int64)
+    if ts.size != n:
+        raise ValueError("Downsampler.push: %d time stamps for %d frames" % (ts.size, n))
+    if (n > 1 and not (ts[1:] > ts[:-1]).all()) or (n and last is not None and ts[0] <= last):
+        raise ValueError("Downsampler.push: the time stamps must increase strictly, from the last one pushed on")
+    return ts
+
+
+class Downsampler:
+    """Adaptive temporal downsampling with max-hold of device-resident frames (reference ``VideoDownsampler``, C ABI
+    ``rir_downsampler_*``): about one image in ``factor`` is kept, more while the scene changes (``factor_std`` in [0, 1]: the quantile of
+    the recent frame-to-frame statistics an image must exceed; ``method`` 1 = ``addImage``, 2 = ``addImage2``), and every kept image is
+    the per-pixel maximum of the images since the last kept one over the first ``lossy_height`` rows."""
+
+    def __init__(self, width, height, factor, factor_std, lossy_height=None, method=1):
+        self.handle = 0
+        width, height, lossy_height, factor, factor_std, method = _downsample_args(width, height, factor, factor_std, lossy_height, method)
+        self.shape = (height, width)
+        self.lossy_height, self.factor, self.factor_std, self.method = lossy_height, factor, factor_std, method
+        self._last = None
+        self.handle = _lib.rir_downsampler_create(width, height, lossy_height, factor, factor_std, method)
+        if self.handle <= 0:
+            raise RuntimeError("rir_downsampler_create failed: %s" % last_error())
+
+    def push(self, frames, timestamps, out=None):
+        """The next images of the stream: ``frames`` (n, h, w) uint16 on the device, ``timestamps`` n strictly increasing integers ->
+        ``Downsampled(frames, timestamps, positions, stats)``: the kept images (a CUDA tensor [kept][h][w], a view of ``out`` - capacity n
+        images, not overlapping ``frames`` - when given), their time stamps, the index within this push of the image that triggered
+        each, and the statistic of every pushed image (numpy).  Waits once for the current stream; the kept images are queued on it."""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint16:
+            raise RuntimeError("Downsampler.push: a uint16 tensor expected")
+        if frames.dim() != 3 or tuple(frames.shape[1:]) != self.shape:
+            raise RuntimeError("Downsampler.push: frames of shape (n, %d, %d) expected" % self.shape)
+        n = frames.shape[0]
+        ts = _downsample_stamps(timestamps, n, self._last)
+        fr = _frames3(frames, torch.uint16)
+        if out is None:
+            out = torch.empty_like(fr)
+        elif not out.is_cuda or out.dtype != torch.uint16 or tuple(out.shape) != tuple(fr.shape) or not out.is_contiguous():
+            raise RuntimeError("Downsampler.push: 'out' must be a C-contiguous CUDA uint16 tensor of the frames' shape")
+        positions = np.zeros(n, np.int32)
+        stats = np.zeros(n, np.float64)
+        kept = _lib.rir_downsampler_push_device(self.handle, fr.data_ptr(), n, ts.ctypes.data, out.data_ptr(), positions.ctypes.data,
+                                                stats.ctypes.data, _stream()) if n else 0
+        if kept < 0:
+            raise RuntimeError("rir_downsampler_push_device failed: %s" % last_error())
+        if n:
+            self._last = int(ts[-1])
+        positions = positions[:kept].copy()
+        return Downsampled(out[:kept], ts[positions], positions, stats)
+
+    @property
+    def count(self):
+        """images kept so far"""
+        return int(_lib.rir_downsampler_count(self.handle)) if self.handle > 0 else 0
+
+    def close(self):
+        """-> the images kept over the stream's life, as the reference's ``close()``"""
+        kept = self.count
+        if getattr(self, "handle", 0) > 0:
+            _lib.rir_downsampler_destroy(self.handle)
+            self.handle = 0
+        return kept
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def downsample(frames, timestamps, factor, factor_std, lossy_height=None, method=1, out=None):
+    """One stack through a fresh ``Downsampler`` of its size -> ``Downsampled``."""
+    if not isinstance(frames, torch.Tensor) or frames.dim() != 3:
+        raise RuntimeError("downsample: a tensor of shape (n, h, w) expected")
+    d = Downsampler(frames.shape[2], frames.shape[1], factor, factor_std, lossy_height, method)
+    try:
+        return d.push(frames, timestamps, out)
+    finally:
+        d.close()

@@ -633,8 +633,13 @@ class IRMovie(object):
         _abi.enable_motion_correction(self.handle, bool(value))
 
     # ---- writing a (part of a) movie again ---------------------------------------------------------------------------------------------
-    def to_h264(self, dst_filename, start_img=0, count=-1, clevel=8, attrs=None, times=None, frame_attributes=None, cthreads=8, cfiles=None):
-        """Record images ``start_img .. start_img + count`` into a new file, with their attributes and time stamps."""
+    def to_h264(self, dst_filename, start_img=0, count=-1, clevel=8, attrs=None, times=None, frame_attributes=None, cthreads=8, cfiles=None,
+                downsample=None):
+        """Record images ``start_img .. start_img + count`` into a new file, with their attributes and time stamps.
+
+        ``downsample=(factor, factor_std)`` or ``(factor, factor_std, method)``: the images go through a ``librir_amd.device.Downsampler``
+        on the device, piece by piece, and only the images it keeps are recorded - each the per-pixel maximum since the last kept one,
+        with the time stamp and the frame attributes of the image that triggered it."""
         available = self.images - start_img
         count = available if count < 0 else min(count, available)
         if count == 0:
@@ -650,6 +655,9 @@ class IRMovie(object):
             saver.set_global_attributes(global_attrs)
             saver.set_parameter("threads", cthreads)
             saver.set_parameter("codec", "h264")
+            if downsample is not None:
+                self._record_downsampled(saver, downsample, start_img, count, stamps, frame_attributes)
+                return
             # A recording of this library goes from its loader to the saver without leaving the device (chunks decoded into device memory,
             # their images copied device to device into the chunk the saver assembles, attributes with them): 6 us an image.  Anything
             # else - raw files, read-back filters switched on, attributes given per image - goes image by image through host memory.
@@ -666,6 +674,39 @@ class IRMovie(object):
             for written, pos in enumerate(range(start_img, start_img + count)):
                 image = self.load_pos(pos, 0)
                 saver.add_image(image, stamps[pos], attributes=self.frame_attributes if frame_attributes is None else frame_attributes[written])
+
+    def _record_downsampled(self, saver, downsample, start_img, count, stamps, frame_attributes):
+        """to_h264's images through a Downsampler: read to the device in pieces of at most ``_STATS_PIECE_BYTES``, the kept images recorded
+        one by one with the attributes of their source positions"""
+        import torch
+
+        from ..device import Downsampler
+
+        if len(downsample) not in (2, 3):
+            raise ValueError("to_h264: downsample=(factor, factor_std) or (factor, factor_std, method) expected")
+        h, w = self.image_size
+        thin = Downsampler(w, h, downsample[0], downsample[1], None, downsample[2] if len(downsample) == 3 else 1)
+        try:
+            device = torch.device("cuda", torch.cuda.current_device())
+            per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+            piece = torch.empty((min(per_piece, count), h, w), dtype=torch.uint16, device=device)
+            kept_buffer = torch.empty_like(piece)
+            for k0 in range(0, count, per_piece):
+                n = min(per_piece, count - k0)
+                first = start_img + k0
+                self.to_tensor(slice(first, first + n), out=piece[:n])
+                kept = thin.push(piece[:n], [int(stamps[pos]) for pos in range(first, first + n)], out=kept_buffer[:n])
+                images = kept.frames.cpu().numpy()
+                for image, at in zip(images, kept.positions):
+                    pos = first + int(at)
+                    if frame_attributes is None:
+                        self.load_pos(pos, 0)  # (for the attributes of the image)
+                        attributes = self.frame_attributes
+                    else:
+                        attributes = frame_attributes[pos - start_img]
+                    saver.add_image(image, stamps[pos], attributes=attributes)
+        finally:
+            thin.close()
 
     def _build_outfile(self):
         """where pcr2h264 writes by default: beside the movie, suffix ``.h264``; a movie that is encoded already names itself

@@ -109,18 +109,31 @@ class IRSaver(object):
         """Lossless: the image read back is the image given.  ``timestamp`` in nanoseconds."""
         _abi.h264_add_image_lossless(self._handle, self._frame(image, "wrong image dimension"), timestamp, attributes)
 
-    def add_images(self, frames, timestamps):
+    def add_images(self, frames, timestamps, downsampler=None):
         """Lossless, from the device: ``frames`` a CUDA ``torch.uint16`` tensor ``[n][h][w]`` (made contiguous once when it is not),
         ``timestamps`` n time stamps in nanoseconds, as ``add_image`` takes them; no per-image attributes.  Ordered after the work
         queued on the current CUDA stream; ``frames`` may be overwritten once this returns.  The file is the one ``add_image`` of the same
-        frames would make, byte for byte."""
+        frames would make, byte for byte.
+
+        ``downsampler``: a ``librir_amd.device.Downsampler`` of this saver's geometry (width, height, lossy_height); the frames go through
+        it first and only the images it keeps are recorded, with the time stamps of the images that triggered them - the file is the one
+        ``add_images`` of those kept images would make - and the number of images recorded is returned."""
         import torch
 
         if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint16:
             raise RuntimeError("add_images: a CUDA torch.uint16 tensor expected")
         if frames.dim() != 3 or tuple(frames.shape[1:]) != self._shape:
             raise RuntimeError("wrong image dimension")
-        _abi.add_images_device(self._handle, frames.contiguous(), timestamps)
+        if downsampler is None:
+            _abi.add_images_device(self._handle, frames.contiguous(), timestamps)
+            return None
+        rows = self._shape[0] if self._lossy_rows is None else int(self._lossy_rows)
+        if tuple(downsampler.shape) != self._shape or downsampler.lossy_height != rows:
+            raise RuntimeError("add_images: the downsampler's geometry is not this saver's")
+        kept = downsampler.push(frames, timestamps)
+        if len(kept.positions):
+            _abi.add_images_device(self._handle, kept.frames, kept.timestamps)
+        return len(kept.positions)
 
     def add_image_lossy(self, image_DL, timestamp, attributes=None):
         """Bounded loss: pixels may move by at most lowValueError / highValueError around their reference value
