@@ -254,6 +254,23 @@ extern "C"
 								void *d_work, size_t work_bytes, void *stream);
 	size_t rir_region_stats_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions);
 
+	/* Per-region quantiles of a uint16 stack d_frames[nframes][h][w] (extension), frames and label maps as rir_region_stats_device takes
+	 * them, nregions 1..65 536.  `percents`: HOST memory, npercents (1..8) floats in [0, 1].  For frame f, region r and percent p_j, V = the
+	 * values of the pixels of f whose label is r, c = |V| and t = (int)roundf((float)c * p_j) - the product in float32, rounded half away
+	 * from zero: the reference's masked rule (Filters.cpp:92).  d_count[f][r] = c; d_values[f][r][j] = -1 when c == 0 (find_median_pixel_mask
+	 * gives 0 there; -1 is the empty region of rir_region_stats_device), 0 when t == 0 (so p = 0 gives 0, not the minimum), else the t-th
+	 * smallest element s of V (1-based) when s < 65535, and 0 when s == 65535 or t > c (the reference counts into 65 535 bins: 65535 is
+	 * in the population but in no bin; t > c needs a (float)c that rounds up).  For c > 0 that is find_median_pixel_mask(frame f,
+	 * labels == r, p_j).  Integer arithmetic apart from t; bitwise reproducible.  d_work: device memory, 8-byte aligned, of at least
+	 * B = nregions * (1040 + 1032 * npercents) bytes; the stack is worked through in groups of work_bytes / B frames, and every size gives
+	 * the same bits.  rir_region_quantiles_workspace_bytes: B * min(max(nframes, 1), max(1, 256 MiB / B)), or 0 for refused arguments.
+	 * Asynchronous on `stream` (`percents` is read before the call returns); no output or the workspace may overlap an input or another
+	 * output.  nframes 0: nothing is done.  0 / -1 (invalid argument, null pointer, overlap, workspace too small, no device). */
+	int rir_region_quantiles_device(const unsigned short *d_frames, const int *d_labels, int w, int h, int nframes, int labels_per_frame,
+									int nregions, const float *percents /* HOST, npercents floats */, int npercents,
+									int *d_count, int *d_values, void *d_work, size_t work_bytes, void *stream);
+	size_t rir_region_quantiles_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions, int npercents);
+
 	/* Per-pixel statistics over time of a uint16 stack d_frames[nframes][h][w] (extension).  For pixel i = y * w + x, with v_f = d_frames[f][i],
 	 * f = 0 .. nframes - 1, and a time origin t0 >= 0, the outputs [h][w] are: d_sum[i] = the exact sum of the v_f, d_sumsq[i] = the exact sum
 	 * of their squares (int64), d_min[i] / d_max[i] = the extremes over f, d_argmin[i] / d_argmax[i] = t0 + f for the LOWEST f that holds the

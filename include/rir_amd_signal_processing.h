@@ -68,6 +68,11 @@ extern "C"
 	 * once.  0 / -1. */
 	int rir_region_stats(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
 						 int *count, long long *sum, long long *sumsq, int *min, int *max, int *argmin, int *argmax);
+	/* Per-region quantiles of a host stack frames[nframes][h][w] with host label maps: rir_region_quantiles_device (rir_amd_device.h, where
+	 * the rule is defined), synchronous, host outputs count[nframes][nregions] and values[nframes][nregions][npercents].  The frames go
+	 * through the device in slabs of at most 64 MiB; a shared map goes up once.  0 / -1. */
+	int rir_region_quantiles(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
+							 const float *percents, int npercents, int *count, int *values);
 	/* Per-pixel statistics over time of a host stack frames[nframes][h][w]: rir_pixel_stats_device (rir_amd_device.h) with t0 = 0,
 	 * synchronous, host outputs [h][w]; a group (sum, sumsq / min, max, argmin, argmax) may be null, not both.  The frames go through the
 	 * device in slabs of at most 64 MiB that accumulate there; the outputs come back once.  nframes 0: nothing is done.  0 / -1. */

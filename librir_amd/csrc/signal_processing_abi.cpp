@@ -16,6 +16,7 @@
 #include "label_kernels.h"
 #include "pixel_kernels.h"
 #include "polygon_kernels.h"
+#include "quantile_kernels.h"
 #include "region_kernels.h"
 #include "runtime.h"
 #include "temporal_kernels.h"
@@ -721,6 +722,89 @@ RIR_EXPORT int rir_region_stats_device(const unsigned short *d_frames, const int
 			   : -1;
 }
 
+// Per-region quantiles (quantile_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an input or
+// another output.
+namespace
+{
+	bool region_quantiles_args(int w, int h, int nframes, int labels_per_frame, int nregions, int npercents)
+	{
+		return region_stats_args(w, h, nframes, labels_per_frame, nregions) && nregions <= QUANTILE_MAX_REGIONS && npercents >= 1 &&
+			   npercents <= QUANTILE_MAX_PERCENTS;
+	}
+	constexpr size_t QUANTILE_WORK_BYTES = (size_t)256 << 20; // what the workspace query asks for at most, or one frame's need
+} // namespace
+
+RIR_EXPORT size_t rir_region_quantiles_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions, int npercents)
+{
+	if (!region_quantiles_args(w, h, nframes, labels_per_frame, nregions, npercents))
+		return 0;
+	const size_t B = region_quantiles_frame_bytes(nregions, npercents);
+	return B * std::min<size_t>((size_t)std::max(nframes, 1), std::max<size_t>(1, QUANTILE_WORK_BYTES / B));
+}
+
+RIR_EXPORT int rir_region_quantiles_device(const unsigned short *d_frames, const int *d_labels, int w, int h, int nframes, int labels_per_frame,
+											int nregions, const float *percents, int npercents, int *d_count, int *d_values, void *d_work,
+											size_t work_bytes, void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (!region_quantiles_args(w, h, nframes, labels_per_frame, nregions, npercents))
+	{
+		log_error("rir_region_quantiles_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, "
+				  "1 <= nregions <= 65536, 1 <= npercents <= 8)");
+		return -1;
+	}
+	if (!d_frames || !d_labels || !percents || !d_count || !d_values || !d_work)
+	{
+		log_error("rir_region_quantiles_device: null pointer");
+		return -1;
+	}
+	QuantilePercents pc{};
+	for (int j = 0; j < npercents; ++j)
+	{
+		if (!(percents[j] >= 0.0f && percents[j] <= 1.0f)) // NaN fails both
+		{
+			log_error("rir_region_quantiles_device: every percent must be in [0, 1]");
+			return -1;
+		}
+		pc.p[j] = percents[j];
+	}
+	if (nframes == 0)
+		return 0;
+	const size_t npx = (size_t)w * h, cells = (size_t)nframes * nregions, B = region_quantiles_frame_bytes(nregions, npercents);
+	if (work_bytes < B || (uintptr_t)d_work % 8 != 0)
+	{
+		log_error("rir_region_quantiles_device: the workspace must be 8-byte aligned and hold one frame's share of "
+				  "rir_region_quantiles_workspace_bytes() bytes");
+		return -1;
+	}
+	const size_t used = B * std::min<size_t>((size_t)nframes, work_bytes / B);
+	const struct
+	{
+		uintptr_t p;
+		size_t bytes;
+	} in[2] = {{(uintptr_t)d_frames, npx * nframes * 2}, {(uintptr_t)d_labels, npx * (labels_per_frame ? nframes : 1) * 4}},
+	  out[3] = {{(uintptr_t)d_count, cells * 4}, {(uintptr_t)d_values, cells * npercents * 4}, {(uintptr_t)d_work, used}};
+	for (int i = 0; i < 3; ++i)
+	{
+		bool overlap = false;
+		for (const auto &a : in)
+			overlap |= out[i].p < a.p + a.bytes && a.p < out[i].p + out[i].bytes;
+		for (int j = 0; j < i; ++j)
+			overlap |= out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
+		if (overlap)
+		{
+			log_error("rir_region_quantiles_device: an output or the workspace overlaps an input or another output");
+			return -1;
+		}
+	}
+	return hip_ok(launch_region_quantiles(d_frames, d_labels, (int64_t)npx, nframes, labels_per_frame, nregions, pc, npercents, d_count, d_values, d_work,
+										  work_bytes, as_stream(stream)),
+				  "region_quantiles")
+			   ? 0
+			   : -1;
+}
+
 // Per-pixel statistics over time (pixel_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap the input
 // or another output.
 namespace
@@ -1167,6 +1251,53 @@ RIR_EXPORT int rir_region_stats(const unsigned short *frames, const int *labels,
 				return -1;
 		if (!hip_ok(hipMemcpyAsync(sum + at, d64, n * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
 			!hip_ok(hipMemcpyAsync(sumsq + at, d64 + cells, n * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") || !hip_ok(wait_stream(st), "region_stats"))
+			return -1;
+	}
+	return 0;
+}
+
+// Extension: per-region quantiles of a host stack, staged as rir_region_stats stages its arguments.  Synchronous.  0 / -1.
+RIR_EXPORT int rir_region_quantiles(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
+									const float *percents, int npercents, int *count, int *values)
+{
+	if (!device_ready())
+		return -1;
+	if (!region_quantiles_args(w, h, nframes, labels_per_frame, nregions, npercents) || !frames || !labels || !percents || !count || !values)
+	{
+		log_error("rir_region_quantiles: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, "
+				  "1 <= nregions <= 65536, 1 <= npercents <= 8, no null pointer)");
+		return -1;
+	}
+	for (int j = 0; j < npercents; ++j)
+		if (!(percents[j] >= 0.0f && percents[j] <= 1.0f))
+		{
+			log_error("rir_region_quantiles: every percent must be in [0, 1]");
+			return -1;
+		}
+	if (nframes == 0)
+		return 0;
+	const size_t npx = (size_t)w * h, frame = npx * 2, K = (size_t)nregions, Q = (size_t)npercents;
+	const size_t per_frame_out = K * 4 * (1 + Q) + region_quantiles_frame_bytes(nregions, npercents); // outputs and workspace of one frame
+	const int slab = (int)std::max<size_t>(1, std::min<size_t>({REGION_SLAB_BYTES / frame, REGION_SLAB_BYTES / per_frame_out, (size_t)nframes}));
+	const size_t cells = (size_t)slab * K, work = rir_region_quantiles_workspace_bytes(w, h, slab, labels_per_frame, nregions, npercents);
+	DeviceBuffer fr, lab, o32, ws;
+	if (!fr.reserve(frame * slab) || !lab.reserve(npx * 4 * (labels_per_frame ? slab : 1)) || !o32.reserve(cells * 4 * (1 + Q)) || !ws.reserve(work))
+		return -1;
+	hipStream_t st = default_stream();
+	if (!labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels, npx * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))
+		return -1;
+	int *d_count = o32.as<int>(), *d_values = d_count + cells;
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int c = std::min(slab, nframes - o);
+		const size_t n = (size_t)c * K, at = (size_t)o * K;
+		if (!hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, frame * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
+			(labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels + (size_t)o * npx, npx * 4 * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
+			rir_region_quantiles_device(fr.as<unsigned short>(), lab.as<int>(), w, h, c, labels_per_frame, nregions, percents, npercents, d_count, d_values,
+										ws.ptr, work, st) != 0 ||
+			!hip_ok(hipMemcpyAsync(count + at, d_count, n * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+			!hip_ok(hipMemcpyAsync(values + at * Q, d_values, n * Q * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+			!hip_ok(wait_stream(st), "region_quantiles"))
 			return -1;
 	}
 	return 0;

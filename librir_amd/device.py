@@ -10,7 +10,8 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
-from .signal_processing.rir_signal_processing import (PixelStats, RegionStats, _pixel_stats_args, _polygon_map_args,  # noqa: F401 (API)
+from .signal_processing.rir_signal_processing import (PixelStats, RegionQuantiles, RegionStats, _pixel_stats_args,  # noqa: F401 (API)
+                                                      _polygon_map_args, _region_quantiles_args, _region_quantiles_percents,
                                                       _region_stats_args, _temporal_median_args)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
@@ -114,6 +115,9 @@ _lib.rir_temporal_median_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_i
 _lib.rir_region_stats_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp] * 8 + [ct.c_size_t, _vp]
 _lib.rir_region_stats_workspace_bytes.argtypes = [ct.c_int] * 5
 _lib.rir_region_stats_workspace_bytes.restype = ct.c_size_t
+_lib.rir_region_quantiles_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp, ct.c_int, _vp, _vp, _vp, ct.c_size_t, _vp]
+_lib.rir_region_quantiles_workspace_bytes.argtypes = [ct.c_int] * 6
+_lib.rir_region_quantiles_workspace_bytes.restype = ct.c_size_t
 _lib.rir_pixel_stats_device.argtypes = [_vp] + [ct.c_int] * 5 + [_vp] * 7 + [ct.c_size_t, _vp]
 _lib.rir_pixel_stats_workspace_bytes.argtypes = [ct.c_int] * 3
 _lib.rir_pixel_stats_workspace_bytes.restype = ct.c_size_t
@@ -722,15 +726,16 @@ class TemporalMedian:
         return out
 
 
-def _region_inputs(frames, labels, nregions):
-    """region_stats' checks, in the order that needs no device for the shapes, dtypes and nregions; -> (frames, labels, n, h, w, per_frame)"""
+def _region_inputs(frames, labels, nregions, what="region_stats", args=_region_stats_args):
+    """region_stats' checks (region_quantiles' with its `what` and `args`), in the order that needs no device for the shapes, dtypes and
+    nregions; -> (frames, labels, n, h, w, per_frame)"""
     if frames.dtype != torch.uint16:
-        raise RuntimeError("region_stats: uint16 frames expected, not %s" % frames.dtype)
+        raise RuntimeError("%s: uint16 frames expected, not %s" % (what, frames.dtype))
     if labels.dtype != torch.int32:
-        raise RuntimeError("region_stats: int32 labels expected, not %s" % labels.dtype)
-    n, h, w, per_frame = _region_stats_args(tuple(frames.shape), tuple(labels.shape), nregions)
+        raise RuntimeError("%s: int32 labels expected, not %s" % (what, labels.dtype))
+    n, h, w, per_frame = args(tuple(frames.shape), tuple(labels.shape), nregions)
     if not frames.is_cuda or not labels.is_cuda or frames.device != labels.device:
-        raise RuntimeError("region_stats: frames and labels on one CUDA device expected")
+        raise RuntimeError("%s: frames and labels on one CUDA device expected" % what)
     return _frames3(frames), labels.contiguous(), n, h, w, per_frame
 
 
@@ -760,6 +765,39 @@ def region_stats(frames, labels, nregions=None):
     out = _region_stats_empty(n, int(nregions), fr.device)
     if n:
         _region_stats_into(fr, lab, per_frame, int(nregions), out)
+    return out
+
+
+def _region_quantiles_into(fr, lab, per_frame, nregions, percents, out):
+    """queue the quantiles of fr [n][h][w] over lab at percents (float32 numpy) into out (a RegionQuantiles of contiguous tensors)"""
+    n, h, w = fr.shape
+    need = _lib.rir_region_quantiles_workspace_bytes(w, h, n, per_frame, nregions, percents.size)
+    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    _check(_lib.rir_region_quantiles_device(fr.data_ptr(), lab.data_ptr(), w, h, n, per_frame, nregions, percents.ctypes.data, percents.size,
+                                            out.count.data_ptr(), out.values.data_ptr(), work.data_ptr(), work.numel() * 8, _stream()),
+           "rir_region_quantiles_device")
+
+
+def _region_quantiles_empty(n, nregions, npercents, device):
+    return RegionQuantiles(torch.empty((n, nregions), dtype=torch.int32, device=device),
+                           torch.empty((n, nregions, npercents), dtype=torch.int32, device=device))
+
+
+def region_quantiles(frames, labels, percents, nregions=None):
+    """Quantiles of a uint16 stack ``frames (n, h, w)`` (or one ``(h, w)`` image: a stack of one) over the regions of the int32 label map
+    ``labels`` (``(h, w)`` shared by every frame, or ``(n, h, w)``) at ``percents`` (a float or 1..8 floats in [0, 1]), on the current
+    stream (C ABI ``rir_region_quantiles_device``, where the rule is defined): a ``RegionQuantiles`` of CUDA int32 tensors, count
+    ``[n][nregions]`` and values ``[n][nregions][len(percents)]`` - for a non-empty region what
+    ``find_median_pixel(frame, p, labels == r)`` gives, -1 for an empty one.  Labels outside [0, nregions) are ignored; at most 65 536
+    regions; ``nregions=None`` takes ``labels.max() + 1`` (at least 1), which synchronises."""
+    pc = _region_quantiles_percents(percents)
+    fr, lab, n, h, w, per_frame = _region_inputs(frames, labels, nregions, "region_quantiles", _region_quantiles_args)
+    if nregions is None:
+        nregions = max(1, int(lab.max()) + 1)
+        _region_quantiles_args(tuple(frames.shape), tuple(labels.shape), nregions)
+    out = _region_quantiles_empty(n, int(nregions), pc.size, fr.device)
+    if n:
+        _region_quantiles_into(fr, lab, per_frame, int(nregions), pc, out)
     return out
 
 

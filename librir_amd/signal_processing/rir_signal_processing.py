@@ -233,23 +233,24 @@ class RegionStats(namedtuple("RegionStats", "count sum sumsq min max argmin argm
         return ((self.sumsq.double() - self.sum.double() * m) / c).clamp_min(0.0).sqrt()
 
 
-def _region_stats_args(frames_shape, labels_shape, nregions):
-    """the shapes of a region_stats call, checked without a device; -> (n, h, w, labels_per_frame).  nregions None is left to the caller."""
+def _region_stats_args(frames_shape, labels_shape, nregions, what="region_stats", max_regions=MAX_REGIONS):
+    """the shapes of a region_stats (or region_quantiles) call, checked without a device; -> (n, h, w, labels_per_frame).  nregions None is
+    left to the caller."""
     if len(frames_shape) == 2:
         frames_shape = (1,) + tuple(frames_shape)
     if len(frames_shape) != 3:
-        raise ValueError("region_stats: frames (n, h, w) or (h, w) expected")
+        raise ValueError("%s: frames (n, h, w) or (h, w) expected" % what)
     n, h, w = frames_shape
     if h < 1 or w < 1 or h * w >= 1 << 31:
-        raise ValueError("region_stats: frames of at least 1x1 and fewer than 2^31 pixels expected")
+        raise ValueError("%s: frames of at least 1x1 and fewer than 2^31 pixels expected" % what)
     if tuple(labels_shape) == (h, w):
         per_frame = 0
     elif tuple(labels_shape) == (n, h, w):
         per_frame = 1
     else:
-        raise ValueError("region_stats: labels of shape %s or %s expected, not %s" % ((h, w), (n, h, w), tuple(labels_shape)))
-    if nregions is not None and (int(nregions) != nregions or not 1 <= nregions <= MAX_REGIONS):
-        raise ValueError("region_stats: nregions must be in 1..2^24 (got %r)" % (nregions,))
+        raise ValueError("%s: labels of shape %s or %s expected, not %s" % (what, (h, w), (n, h, w), tuple(labels_shape)))
+    if nregions is not None and (int(nregions) != nregions or not 1 <= nregions <= max_regions):
+        raise ValueError("%s: nregions must be in 1..2^%d (got %r)" % (what, max_regions.bit_length() - 1, nregions))
     return n, h, w, per_frame
 
 
@@ -272,6 +273,61 @@ def region_stats(images, labels, nregions=None):
     out = RegionStats(*(np.empty((n, k), dt) for dt in (np.int32, np.int64, np.int64, np.int32, np.int32, np.int32, np.int32)))
     if n and _sp.rir_region_stats(img.ctypes.data, lab.ctypes.data, w, h, n, per_frame, k, *(a.ctypes.data for a in out)) < 0:
         raise RuntimeError("An error occured while calling 'region_stats': " + (last_error() or ""))
+    return out
+
+
+# ---- extension: per-region quantiles ---------------------------------------------------------------------------------------------
+_sp.rir_region_quantiles.argtypes = [ct.c_void_p, ct.c_void_p] + [ct.c_int] * 5 + [ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_void_p]
+
+MAX_QUANTILE_REGIONS = 1 << 16
+MAX_PERCENTS = 8
+
+
+class RegionQuantiles(namedtuple("RegionQuantiles", "count values")):
+    """Quantiles per (frame, region): count ``[n][nregions]`` and values ``[n][nregions][len(percents)]`` (int32).  With c = count and
+    t = (int)roundf((float)c * p) - float32, half away from zero, the reference's ``find_median_pixel_mask`` rule - a value is -1 for an
+    empty region, 0 when t == 0, else the t-th smallest value of the region, and 0 where that is 65535 (which the reference counts in no
+    bin).  numpy arrays (``signal_processing.region_quantiles``) or CUDA tensors (``device.region_quantiles``)."""
+
+    __slots__ = ()
+
+
+def _region_quantiles_percents(percents):
+    """a float or a sequence of 1..8 floats in [0, 1]; -> float32 array"""
+    p = np.atleast_1d(np.asarray(percents, dtype=np.float64))
+    if p.ndim != 1 or not 1 <= p.size <= MAX_PERCENTS:
+        raise ValueError("region_quantiles: 1..%d percents expected" % MAX_PERCENTS)
+    if not np.all((p >= 0.0) & (p <= 1.0)):  # NaN fails both
+        raise ValueError("region_quantiles: every percent must be in [0, 1] (got %r)" % (p.tolist(),))
+    return np.ascontiguousarray(p, dtype=np.float32)
+
+
+def _region_quantiles_args(frames_shape, labels_shape, nregions):
+    return _region_stats_args(frames_shape, labels_shape, nregions, "region_quantiles", MAX_QUANTILE_REGIONS)
+
+
+def region_quantiles(images, labels, percents, nregions=None):
+    """Extension: quantiles of a uint16 stack ``images[n][h][w]`` (or one ``(h, w)`` image) over the regions of the int32 label map
+    ``labels`` (``(h, w)`` shared by every image, or ``(n, h, w)``) at ``percents`` (a float or 1..8 floats in [0, 1]): a
+    ``RegionQuantiles`` of numpy arrays (``rir_region_quantiles``).  Labels outside [0, nregions) are ignored; ``nregions=None`` takes
+    labels.max() + 1 (at least 1); at most 65 536 regions.  ``ValueError`` on bad shapes, ``nregions`` or percents, ``RuntimeError`` on
+    other dtypes and when the library fails."""
+    img = np.ascontiguousarray(images)
+    lab = np.ascontiguousarray(labels)
+    if img.dtype != np.uint16:
+        raise RuntimeError("region_quantiles: uint16 images expected, not %s" % img.dtype)
+    if lab.dtype != np.int32:
+        raise RuntimeError("region_quantiles: int32 labels expected, not %s" % lab.dtype)
+    pc = _region_quantiles_percents(percents)
+    n, h, w, per_frame = _region_quantiles_args(img.shape, lab.shape, nregions)
+    if nregions is None:
+        nregions = max(1, int(lab.max()) + 1 if lab.size else 1)
+        _region_quantiles_args(img.shape, lab.shape, nregions)
+    k = int(nregions)
+    out = RegionQuantiles(np.empty((n, k), np.int32), np.empty((n, k, pc.size), np.int32))
+    if n and _sp.rir_region_quantiles(img.ctypes.data, lab.ctypes.data, w, h, n, per_frame, k, pc.ctypes.data, pc.size, out.count.ctypes.data,
+                                      out.values.ctypes.data) < 0:
+        raise RuntimeError("An error occured while calling 'region_quantiles': " + (last_error() or ""))
     return out
 
 

@@ -370,6 +370,39 @@ class IRMovie(object):
             _region_stats_into(fr, lab, 0, int(nregions), type(out)(*(t[k0:k0 + len(sel)] for t in out)))
         return out
 
+    def region_quantiles(self, labels, percents, selection=slice(None), nregions=None):
+        """Quantiles of the images of ``selection`` over the regions of one int32 label map ``labels`` (h, w), numpy or CUDA, at
+        ``percents`` (a float or 1..8 floats in [0, 1]) - what ``librir_amd.device.region_quantiles`` over the images ``movie[selection]``
+        gives (read-back filters applied): a ``RegionQuantiles`` of CUDA tensors, count ``[len(selection)][nregions]`` and values
+        ``[len(selection)][nregions][len(percents)]``.  Labels, selection, ``nregions`` and the pieces the recording is read in are those
+        of ``region_stats``."""
+        import torch
+
+        from ..device import (_region_inputs, _region_quantiles_args, _region_quantiles_empty, _region_quantiles_into,
+                              _region_quantiles_percents)
+
+        h, w = self.image_size
+        pc = _region_quantiles_percents(percents)
+        if isinstance(labels, np.ndarray):
+            if labels.dtype != np.int32:
+                raise RuntimeError("region_quantiles: int32 labels expected, not %s" % labels.dtype)
+            labels = torch.from_numpy(np.ascontiguousarray(labels)).to(torch.device("cuda", torch.cuda.current_device()))
+        probe = torch.empty((0, h, w), dtype=torch.uint16, device=labels.device if labels.is_cuda else "cpu")
+        _, lab, _, _, _, _ = _region_inputs(probe, labels, nregions, "region_quantiles", _region_quantiles_args)
+        if nregions is None:
+            nregions = max(1, int(lab.max()) + 1)
+            _region_inputs(probe, labels, nregions, "region_quantiles", _region_quantiles_args)
+        positions = self._stats_positions(selection, "region_quantiles")
+        out = _region_quantiles_empty(len(positions), int(nregions), pc.size, lab.device)
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=lab.device)
+        for k0 in range(0, len(positions), per_piece):
+            sel = positions[k0:k0 + per_piece]
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            _region_quantiles_into(fr, lab, 0, int(nregions), pc, type(out)(*(t[k0:k0 + len(sel)] for t in out)))
+        return out
+
     def polygon_stats(self, polygons, selection=slice(None), shifts=None, values=None):
         """Statistics of the images of ``selection`` (as ``region_stats`` takes it) over polygon regions of interest
         (``librir_amd.device.polygon_map`` takes ``polygons`` and ``values`` the same way): a ``RegionStats`` of CUDA tensors
