@@ -289,6 +289,42 @@ extern "C"
 							   void *d_work, size_t work_bytes, void *stream);
 	size_t rir_pixel_stats_workspace_bytes(int w, int h, int nframes);
 
+	/* Per-pixel quantiles over time of a uint16 stack d_frames[nframes][h][w] (extension): the rule of rir_region_quantiles_device applied
+	 * to the time series of each pixel.  `percents`: HOST memory, npercents (1..8) floats in [0, 1].  For pixel i = y * w + x and percent
+	 * p_j, V = the nframes values d_frames[f][i], c = nframes and t = (int)roundf((float)c * p_j) - the product in float32, rounded half
+	 * away from zero.  d_values[j][y][x] (int32 [npercents][h][w], one image per percent) = -1 when c == 0, 0 when t == 0 or t > c, else the
+	 * t-th smallest element s of V (1-based) when s < 65535, and 0 when s == 65535.  For c > 0 that is find_median_pixel(series of pixel i,
+	 * p_j, mask of ones), and rir_region_quantiles_device over the stack viewed as one nframes x (h * w) image labelled by column.
+	 * Bounds: w, h >= 1, w * h < 2^31, frames in all <= 2^31 - 1.  Integer arithmetic apart from t; bitwise reproducible, independent of the
+	 * order the workgroups run in, of how a sequence is split into pushes and of the order of the pushes within a pass.
+	 *
+	 * The method is a radix select, P = rir_pixel_quantiles_passes() passes over the frames.  One call over a resident stack:
+	 * rir_pixel_quantiles_device, with d_work device memory, 8-byte aligned, of at least rir_pixel_quantiles_workspace_bytes(w, h, nframes,
+	 * npercents) = rir_pixel_quantiles_state_bytes(w, h, npercents) bytes (never 0 for valid arguments); nframes 0 fills d_values with -1.
+	 *
+	 * A sequence that is not resident is streamed P times.  The device state is opaque, rir_pixel_quantiles_state_bytes(w, h, npercents)
+	 * = 72 * npercents * w * h bytes (0: arguments refused), 8-byte aligned; the ALL-ZERO state is the empty state, which the caller makes
+	 * with a memset on the stream before the first push.  The host keeps the pass number and the frame count.  For pass = 0 .. P - 1:
+	 * rir_pixel_quantiles_push_device for every batch of the sequence, in any order (nframes 0: nothing is done), then
+	 * rir_pixel_quantiles_resolve_device once, with the same percents every time and total_frames = the frames of the whole sequence, the
+	 * same in every pass.  The resolve of pass P - 1 writes d_values (null is accepted before); with total_frames 0 it fills them with -1.
+	 * Every pass must see the same frames; the counts of states kept on several devices over parts of a sequence simply add.
+	 *
+	 * All calls are asynchronous on `stream`; `percents` is read before the call returns.  The values, the state or workspace and the
+	 * frames may not overlap.  0 / -1 (invalid argument, null pointer, overlap, workspace or state too small, pass out of range, no
+	 * device). */
+	int    rir_pixel_quantiles_passes(void);
+	size_t rir_pixel_quantiles_state_bytes(int w, int h, int npercents);
+	size_t rir_pixel_quantiles_workspace_bytes(int w, int h, int nframes, int npercents);
+	int    rir_pixel_quantiles_device(const unsigned short *d_frames, int w, int h, int nframes,
+									  const float *percents /* HOST */, int npercents, int *d_values /* [npercents][h][w] */,
+									  void *d_work, size_t work_bytes, void *stream);
+	int    rir_pixel_quantiles_push_device(const unsigned short *d_frames, int w, int h, int nframes, int npercents, int pass,
+										   void *d_state, size_t state_bytes, void *stream);
+	int    rir_pixel_quantiles_resolve_device(int w, int h, const float *percents /* HOST */, int npercents, int pass,
+											  long long total_frames, void *d_state, size_t state_bytes,
+											  int *d_values /* written when pass == P - 1, may be null before */, void *stream);
+
 	/* Connected components tracked through time (extension).  d_labels: int32 label maps [nframes][h][w] as rir_label_images_device writes
 	 * them; d_counts: int[nframes], components + 1 per frame as it returns them, or null; nlabels = K >= 1.  Component k of frame t exists
 	 * when 1 <= k < min(K, d_counts[t]) (1 <= k < K without d_counts); every other label value is background.  Components (t, a) and

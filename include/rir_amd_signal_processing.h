@@ -78,6 +78,11 @@ extern "C"
 	 * device in slabs of at most 64 MiB that accumulate there; the outputs come back once.  nframes 0: nothing is done.  0 / -1. */
 	int rir_pixel_stats(const unsigned short *frames, int w, int h, int nframes, long long *sum, long long *sumsq, int *min, int *max,
 						int *argmin, int *argmax);
+	/* Per-pixel quantiles over time of a host stack frames[nframes][h][w]: rir_pixel_quantiles_device (rir_amd_device.h, where the rule is
+	 * defined), synchronous, host output values[npercents][h][w].  A stack of at most 256 MiB goes up once; a larger one goes through the
+	 * device in slabs of at most 64 MiB, once per pass, through the streaming form: the same bits.  nframes 0: -1 everywhere.  0 / -1. */
+	int rir_pixel_quantiles(const unsigned short *frames, int w, int h, int nframes,
+							const float *percents, int npercents, int *values);
 	/* Polygon label maps into host memory dst[nmaps][h][w] from host polygons: rir_polygon_map_device (rir_amd_device.h, where the fill is
 	 * defined), synchronous.  The polygons, values and shifts go up once; the maps come back in slabs of at most 64 MiB.  values and shifts
 	 * may be null.  nmaps 0: nothing is done.  0 / -1. */

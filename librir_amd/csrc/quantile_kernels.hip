@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "quantile_kernels.h"
+#include "quantile_rank.h"
 
 namespace rir
 {
@@ -36,9 +37,6 @@ namespace rir
 	static_assert(QT_ITEM % QT_STEP == 0, "an item is whole steps");
 	static_assert(QUANTILE_LDS_MAX * 1024 <= QT_LDS_BYTES, "the LDS form fits one CU");
 	static_assert(QUANTILE_MAX_PERCENTS == 8, "codes are 8 x 16 bits per region");
-
-	// The reference's masked rule (Filters.cpp:92), as quantile_select_kernel states it: the product in float32, rounded half away from zero.
-	__device__ __forceinline__ uint32_t qt_rank(uint32_t c, float percent) { return (uint32_t)(int)roundf(__fmul_rn((float)c, percent)); }
 
 	template <bool LDS>
 	__device__ __forceinline__ void qt_add(uint32_t *p, uint32_t v)

@@ -15,6 +15,7 @@
 #include "filter_kernels.h"
 #include "label_kernels.h"
 #include "pixel_kernels.h"
+#include "pixel_quantile_kernels.h"
 #include "polygon_kernels.h"
 #include "quantile_kernels.h"
 #include "region_kernels.h"
@@ -877,6 +878,160 @@ RIR_EXPORT int rir_pixel_stats_device(const unsigned short *d_frames, int w, int
 			   : -1;
 }
 
+// Per-pixel quantiles over time (pixel_quantile_kernels.hip).  Every argument is checked here; neither the values nor the state (the
+// workspace of the one-call form) may overlap the frames or each other.
+namespace
+{
+	bool pixel_quantiles_args(int w, int h, int npercents)
+	{
+		return w > 0 && h > 0 && (long long)w * h < (1ll << 31) && npercents >= 1 && npercents <= QUANTILE_MAX_PERCENTS;
+	}
+	bool pixel_quantiles_percents(const char *who, const float *percents, int npercents, QuantilePercents &pc)
+	{
+		for (int j = 0; j < npercents; ++j)
+		{
+			if (!(percents[j] >= 0.0f && percents[j] <= 1.0f)) // NaN fails both
+			{
+				log_error(std::string(who) + ": every percent must be in [0, 1]");
+				return false;
+			}
+			pc.p[j] = percents[j];
+		}
+		return true;
+	}
+	bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+	{
+		return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
+	}
+} // namespace
+
+RIR_EXPORT int rir_pixel_quantiles_passes(void) { return PIXEL_QUANTILE_PASSES; }
+
+RIR_EXPORT size_t rir_pixel_quantiles_state_bytes(int w, int h, int npercents)
+{
+	return pixel_quantiles_args(w, h, npercents) ? pixel_quantiles_state_bytes((int64_t)w * h, npercents) : 0;
+}
+
+RIR_EXPORT size_t rir_pixel_quantiles_workspace_bytes(int w, int h, int nframes, int npercents)
+{
+	return nframes >= 0 ? rir_pixel_quantiles_state_bytes(w, h, npercents) : 0;
+}
+
+RIR_EXPORT int rir_pixel_quantiles_push_device(const unsigned short *d_frames, int w, int h, int nframes, int npercents, int pass, void *d_state,
+											   size_t state_bytes, void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (!pixel_quantiles_args(w, h, npercents) || nframes < 0 || pass < 0 || pass >= PIXEL_QUANTILE_PASSES)
+	{
+		log_error("rir_pixel_quantiles_push_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, 1 <= npercents <= 8, "
+				  "0 <= pass < rir_pixel_quantiles_passes())");
+		return -1;
+	}
+	if (!d_frames || !d_state)
+	{
+		log_error("rir_pixel_quantiles_push_device: null pointer");
+		return -1;
+	}
+	const size_t npx = (size_t)w * h, need = pixel_quantiles_state_bytes((int64_t)npx, npercents);
+	if (state_bytes < need || (uintptr_t)d_state % 8 != 0)
+	{
+		log_error("rir_pixel_quantiles_push_device: the state must be 8-byte aligned and hold rir_pixel_quantiles_state_bytes() bytes");
+		return -1;
+	}
+	if (nframes == 0)
+		return 0;
+	if (ranges_overlap(d_state, need, d_frames, npx * nframes * 2))
+	{
+		log_error("rir_pixel_quantiles_push_device: the state overlaps the frames");
+		return -1;
+	}
+	return hip_ok(launch_pixel_quantiles_count(d_frames, (int64_t)npx, nframes, npercents, pass, d_state, as_stream(stream)), "pixel_quantiles_push") ? 0
+																																						: -1;
+}
+
+RIR_EXPORT int rir_pixel_quantiles_resolve_device(int w, int h, const float *percents, int npercents, int pass, long long total_frames, void *d_state,
+												  size_t state_bytes, int *d_values, void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (!pixel_quantiles_args(w, h, npercents) || pass < 0 || pass >= PIXEL_QUANTILE_PASSES || total_frames < 0 || total_frames > 2147483647ll)
+	{
+		log_error("rir_pixel_quantiles_resolve_device: invalid argument (w, h >= 1 with w * h < 2^31, 1 <= npercents <= 8, "
+				  "0 <= pass < rir_pixel_quantiles_passes(), 0 <= total_frames <= 2^31 - 1)");
+		return -1;
+	}
+	const bool last = pass == PIXEL_QUANTILE_PASSES - 1;
+	if (!percents || !d_state || (last && !d_values))
+	{
+		log_error("rir_pixel_quantiles_resolve_device: null pointer");
+		return -1;
+	}
+	QuantilePercents pc{};
+	if (!pixel_quantiles_percents("rir_pixel_quantiles_resolve_device", percents, npercents, pc))
+		return -1;
+	const size_t npx = (size_t)w * h, need = pixel_quantiles_state_bytes((int64_t)npx, npercents);
+	if (state_bytes < need || (uintptr_t)d_state % 8 != 0)
+	{
+		log_error("rir_pixel_quantiles_resolve_device: the state must be 8-byte aligned and hold rir_pixel_quantiles_state_bytes() bytes");
+		return -1;
+	}
+	if (last && ranges_overlap(d_values, npx * npercents * 4, d_state, need))
+	{
+		log_error("rir_pixel_quantiles_resolve_device: the values overlap the state");
+		return -1;
+	}
+	return hip_ok(launch_pixel_quantiles_resolve((int64_t)npx, pc, npercents, pass, (uint32_t)total_frames, d_state, last ? d_values : nullptr,
+												 as_stream(stream)),
+				  "pixel_quantiles_resolve")
+			   ? 0
+			   : -1;
+}
+
+RIR_EXPORT int rir_pixel_quantiles_device(const unsigned short *d_frames, int w, int h, int nframes, const float *percents, int npercents,
+										  int *d_values, void *d_work, size_t work_bytes, void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (!pixel_quantiles_args(w, h, npercents) || nframes < 0)
+	{
+		log_error("rir_pixel_quantiles_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, 1 <= npercents <= 8)");
+		return -1;
+	}
+	if ((nframes > 0 && !d_frames) || !percents || !d_values || !d_work)
+	{
+		log_error("rir_pixel_quantiles_device: null pointer");
+		return -1;
+	}
+	QuantilePercents pc{};
+	if (!pixel_quantiles_percents("rir_pixel_quantiles_device", percents, npercents, pc))
+		return -1;
+	const size_t npx = (size_t)w * h, need = pixel_quantiles_state_bytes((int64_t)npx, npercents), out = npx * npercents * 4;
+	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
+	{
+		log_error("rir_pixel_quantiles_device: the workspace must be 8-byte aligned and hold rir_pixel_quantiles_workspace_bytes() bytes");
+		return -1;
+	}
+	if (ranges_overlap(d_values, out, d_work, need) ||
+		(nframes > 0 && (ranges_overlap(d_values, out, d_frames, npx * nframes * 2) || ranges_overlap(d_work, need, d_frames, npx * nframes * 2))))
+	{
+		log_error("rir_pixel_quantiles_device: the values or the workspace overlap the frames or each other");
+		return -1;
+	}
+	hipStream_t st = as_stream(stream);
+	if (nframes == 0) // no population: -1 everywhere
+		return hip_ok(hipMemsetAsync(d_values, 0xFF, out, st), "hipMemsetAsync") ? 0 : -1;
+	if (!hip_ok(hipMemsetAsync(d_work, 0, need, st), "hipMemsetAsync")) // the empty state
+		return -1;
+	for (int pass = 0; pass < PIXEL_QUANTILE_PASSES; ++pass)
+		if (!hip_ok(launch_pixel_quantiles_count(d_frames, (int64_t)npx, nframes, npercents, pass, d_work, st), "pixel_quantiles") ||
+			!hip_ok(launch_pixel_quantiles_resolve((int64_t)npx, pc, npercents, pass, (uint32_t)nframes, d_work,
+												   pass == PIXEL_QUANTILE_PASSES - 1 ? d_values : nullptr, st),
+					"pixel_quantiles"))
+			return -1;
+	return 0;
+}
+
 // Components tracked through time (track_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an
 // input or another output, except d_dst == d_labels (relabelling in place).
 RIR_EXPORT size_t rir_track_components_workspace_bytes(int w, int h, int nframes, int nlabels) { return track_workspace_bytes(w, h, nframes, nlabels); }
@@ -1345,6 +1500,58 @@ RIR_EXPORT int rir_pixel_stats(const unsigned short *frames, int w, int h, int n
 		if (!hip_ok(hipMemcpyAsync(outs32[k], d32 + (size_t)k * npx, npx * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync"))
 			return -1;
 	return hip_ok(wait_stream(st), "pixel_stats") ? 0 : -1;
+}
+
+// Extension: per-pixel quantiles over time of a host stack.  A stack of at most PIXEL_QUANTILES_RESIDENT_BYTES goes up once and runs the one-call
+// form; a larger one goes up in slabs of at most REGION_SLAB_BYTES, once per pass, through the streaming form: the same bits.  Synchronous.  0 / -1.
+constexpr size_t PIXEL_QUANTILES_RESIDENT_BYTES = (size_t)256 << 20;
+
+RIR_EXPORT int rir_pixel_quantiles(const unsigned short *frames, int w, int h, int nframes, const float *percents, int npercents, int *values)
+{
+	if (!device_ready())
+		return -1;
+	if (!pixel_quantiles_args(w, h, npercents) || nframes < 0 || (nframes > 0 && !frames) || !percents || !values)
+	{
+		log_error("rir_pixel_quantiles: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, 1 <= npercents <= 8, no null pointer)");
+		return -1;
+	}
+	QuantilePercents pc{};
+	if (!pixel_quantiles_percents("rir_pixel_quantiles", percents, npercents, pc))
+		return -1;
+	const size_t npx = (size_t)w * h, frame = npx * 2, out = npx * npercents * 4, state = pixel_quantiles_state_bytes((int64_t)npx, npercents);
+	const bool resident = frame * (size_t)nframes <= PIXEL_QUANTILES_RESIDENT_BYTES;
+	const int slab = resident ? nframes : (int)std::max<size_t>(1, REGION_SLAB_BYTES / frame);
+	DeviceBuffer fr, o32, ws;
+	if ((nframes > 0 && !fr.reserve(frame * slab)) || !o32.reserve(out) || !ws.reserve(state))
+		return -1;
+	hipStream_t st = default_stream();
+	if (resident)
+	{
+		if ((nframes > 0 && !hip_ok(hipMemcpyAsync(fr.ptr, frames, frame * nframes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
+			rir_pixel_quantiles_device(fr.as<unsigned short>(), w, h, nframes, percents, npercents, o32.as<int>(), ws.ptr, state, st) != 0)
+			return -1;
+	}
+	else
+	{
+		if (!hip_ok(hipMemsetAsync(ws.ptr, 0, state, st), "hipMemsetAsync"))
+			return -1;
+		for (int pass = 0; pass < PIXEL_QUANTILE_PASSES; ++pass)
+		{
+			for (int o = 0; o < nframes; o += slab)
+			{
+				const int c = std::min(slab, nframes - o);
+				// the copy waits for the kernels that read the slab before it: one stream
+				if (!hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, frame * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
+					rir_pixel_quantiles_push_device(fr.as<unsigned short>(), w, h, c, npercents, pass, ws.ptr, state, st) != 0)
+					return -1;
+			}
+			if (rir_pixel_quantiles_resolve_device(w, h, percents, npercents, pass, nframes, ws.ptr, state, o32.as<int>(), st) != 0)
+				return -1;
+		}
+	}
+	if (!hip_ok(hipMemcpyAsync(values, o32.ptr, out, hipMemcpyDeviceToHost, st), "hipMemcpyAsync"))
+		return -1;
+	return hip_ok(wait_stream(st), "pixel_quantiles") ? 0 : -1;
 }
 
 // Extension: polygon label maps into host memory.  The polygons, values and shifts go up once; the maps are made on the device in slabs of at

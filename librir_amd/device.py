@@ -10,8 +10,8 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
-from .signal_processing.rir_signal_processing import (PixelStats, RegionQuantiles, RegionStats, _pixel_stats_args,  # noqa: F401 (API)
-                                                      _polygon_map_args, _region_quantiles_args, _region_quantiles_percents,
+from .signal_processing.rir_signal_processing import (PixelStats, RegionQuantiles, RegionStats, _pixel_quantiles_args,  # noqa: F401 (API)
+                                                      _pixel_stats_args, _polygon_map_args, _region_quantiles_args, _region_quantiles_percents,
                                                       _region_stats_args, _temporal_median_args)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
@@ -121,6 +121,14 @@ _lib.rir_region_quantiles_workspace_bytes.restype = ct.c_size_t
 _lib.rir_pixel_stats_device.argtypes = [_vp] + [ct.c_int] * 5 + [_vp] * 7 + [ct.c_size_t, _vp]
 _lib.rir_pixel_stats_workspace_bytes.argtypes = [ct.c_int] * 3
 _lib.rir_pixel_stats_workspace_bytes.restype = ct.c_size_t
+_lib.rir_pixel_quantiles_passes.argtypes = []
+_lib.rir_pixel_quantiles_state_bytes.argtypes = [ct.c_int] * 3
+_lib.rir_pixel_quantiles_state_bytes.restype = ct.c_size_t
+_lib.rir_pixel_quantiles_workspace_bytes.argtypes = [ct.c_int] * 4
+_lib.rir_pixel_quantiles_workspace_bytes.restype = ct.c_size_t
+_lib.rir_pixel_quantiles_device.argtypes = [_vp] + [ct.c_int] * 3 + [_vp, ct.c_int, _vp, _vp, ct.c_size_t, _vp]
+_lib.rir_pixel_quantiles_push_device.argtypes = [_vp] + [ct.c_int] * 5 + [_vp, ct.c_size_t, _vp]
+_lib.rir_pixel_quantiles_resolve_device.argtypes = [ct.c_int, ct.c_int, _vp, ct.c_int, ct.c_int, ct.c_longlong, _vp, ct.c_size_t, _vp, _vp]
 _lib.rir_track_components_device.argtypes = [_vp, _vp] + [ct.c_int] * 4 + [_vp] * 6 + [ct.c_int, _vp, _vp, ct.c_size_t, _vp]
 _lib.rir_track_components_workspace_bytes.argtypes = [ct.c_int] * 4
 _lib.rir_track_components_workspace_bytes.restype = ct.c_size_t
@@ -960,6 +968,111 @@ class PixelStatsAccumulator:
             dev = torch.device("cuda", torch.cuda.current_device()) if self._device0 is None else torch.device(self._device0)
             return PixelStats(*_pixel_stats_state(0, 0, dev, self.sums, self.extremes, empty=True), count=0)
         return PixelStats(*(None if t is None else t.clone() for t in self._out), count=self.count)
+
+
+def _pixel_quantile_inputs(frames, what="pixel_quantiles"):
+    """pixel_quantiles' checks on the frames, those that need no device first; -> (frames, n, h, w)"""
+    if frames.dtype != torch.uint16:
+        raise RuntimeError("%s: uint16 frames expected, not %s" % (what, frames.dtype))
+    n, h, w = _pixel_quantiles_args(tuple(frames.shape), what)
+    if not frames.is_cuda:
+        raise RuntimeError("%s: frames on a CUDA device expected" % what)
+    return _frames3(frames), n, h, w
+
+
+def pixel_quantiles(frames, percents):
+    """Quantiles over time of a uint16 stack ``frames (n, h, w)`` (or one ``(h, w)`` image: a stack of one) at ``percents`` (a float or 1..8
+    floats in [0, 1]), on the current stream (C ABI ``rir_pixel_quantiles_device``, where the rule is defined): an int32 CUDA tensor
+    ``(len(percents), h, w)``, one image per percent - ``pixel_quantiles(frames, 0.5)[0]`` is the median image.  Per pixel it is what
+    ``find_median_pixel(series of the pixel, p, mask of ones)`` gives, the rule of ``region_quantiles``; -1 everywhere for no frames."""
+    pc = _region_quantiles_percents(percents)
+    fr, n, h, w = _pixel_quantile_inputs(frames)
+    out = torch.empty((pc.size, h, w), dtype=torch.int32, device=fr.device)
+    need = _lib.rir_pixel_quantiles_workspace_bytes(w, h, n, pc.size)
+    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    _check(_lib.rir_pixel_quantiles_device(fr.data_ptr() if n else None, w, h, n, pc.ctypes.data, pc.size, out.data_ptr(), work.data_ptr(),
+                                           work.numel() * 8, _stream()), "rir_pixel_quantiles_device")
+    return out
+
+
+class PixelQuantileSelector:
+    """``pixel_quantiles`` over a sequence that is not resident: the sequence is streamed ``passes`` times.  In every pass ``push(frames)``
+    takes the batches of the sequence, in any order, and ``next_pass()`` closes the pass; after the last one ``result()`` is the int32
+    ``(len(percents), h, w)`` tensor, bit for bit that of one ``pixel_quantiles`` call over the whole sequence.  Every pass must see the
+    same frames: closing a later pass with another frame count than pass 0 raises ``RuntimeError``.  ``reset()`` starts over.  The frame
+    size is that of the first batch, or ``shape=(h, w)`` when given; with no frames pushed ``result()`` is all -1 of that size, or of shape
+    ``(len(percents), 0, 0)`` when none is known.  The state is 72 bytes per pixel and percent, whatever the length of the sequence.
+    Digit counts add: shards of a sequence on several devices could be merged by adding their states before each pass is closed (not
+    built)."""
+
+    def __init__(self, percents, shape=None, device=None):
+        self._pc = _region_quantiles_percents(percents)
+        if shape is not None:
+            _pixel_quantiles_args((0,) + tuple(shape), "PixelQuantileSelector")
+        self.passes = int(_lib.rir_pixel_quantiles_passes())
+        self._shape0 = None if shape is None else (int(shape[0]), int(shape[1]))
+        self._device0 = device
+        self.reset()
+
+    def reset(self):
+        self.pass_index = 0  # the open pass; == passes: all closed
+        self.count = 0  # frames pushed in the open pass
+        self._total = None  # frames of pass 0
+        self._state = self._values = None
+
+    def _device(self):
+        if self._device0 is None:
+            return torch.device("cuda", torch.cuda.current_device())
+        d = torch.device(self._device0)
+        return torch.device("cuda", torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
+
+    def _make(self, h, w, device):
+        need = _lib.rir_pixel_quantiles_state_bytes(w, h, self._pc.size)
+        self._state = torch.zeros(need // 8 + 1, dtype=torch.int64, device=device)  # all zero: the empty state
+        self._values = torch.empty((self._pc.size, h, w), dtype=torch.int32, device=device)
+
+    def push(self, frames):
+        fr, n, h, w = _pixel_quantile_inputs(frames, "PixelQuantileSelector")
+        if self.pass_index >= self.passes:
+            raise RuntimeError("PixelQuantileSelector: every pass is closed; reset() starts a new sequence")
+        if self._shape0 is not None and (h, w) != self._shape0:
+            raise RuntimeError("PixelQuantileSelector: frames of %s expected, not %s" % (self._shape0, (h, w)))
+        if self._device0 is not None and fr.device != self._device():
+            raise RuntimeError("PixelQuantileSelector: frames on %s expected, not on %s" % (self._device(), fr.device))
+        if self._state is None:
+            self._make(h, w, fr.device)
+        if tuple(self._values.shape[1:]) != (h, w) or self._values.device != fr.device:
+            raise RuntimeError("PixelQuantileSelector: frames of %s on %s expected, not %s on %s"
+                               % (tuple(self._values.shape[1:]), self._values.device, (h, w), fr.device))
+        if n:
+            _check(_lib.rir_pixel_quantiles_push_device(fr.data_ptr(), w, h, n, self._pc.size, self.pass_index, self._state.data_ptr(),
+                                                        self._state.numel() * 8, _stream()), "rir_pixel_quantiles_push_device")
+            self.count += n
+
+    def next_pass(self):
+        if self.pass_index >= self.passes:
+            raise RuntimeError("PixelQuantileSelector: every pass is closed")
+        if self.pass_index == 0:
+            self._total = self.count
+        elif self.count != self._total:
+            raise RuntimeError("PixelQuantileSelector: pass %d saw %d frames, pass 0 saw %d" % (self.pass_index, self.count, self._total))
+        if self._state is None and self._shape0 is not None:
+            self._make(*self._shape0, self._device())
+        if self._state is not None:
+            _, h, w = self._values.shape
+            _check(_lib.rir_pixel_quantiles_resolve_device(w, h, self._pc.ctypes.data, self._pc.size, self.pass_index, self._total,
+                                                           self._state.data_ptr(), self._state.numel() * 8, self._values.data_ptr(), _stream()),
+                   "rir_pixel_quantiles_resolve_device")
+        self.pass_index += 1
+        self.count = 0
+
+    def result(self):
+        if self.pass_index < self.passes:
+            raise RuntimeError("PixelQuantileSelector: result() after pass %d of %d; push the sequence and call next_pass() for each"
+                               % (self.pass_index, self.passes))
+        if self._values is None:
+            return torch.full((self._pc.size, 0, 0), -1, dtype=torch.int32, device=self._device())
+        return self._values.clone()
 
 
 def _label_args(image, background):

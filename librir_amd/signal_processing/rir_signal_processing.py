@@ -403,6 +403,38 @@ def pixel_stats(images, sums=True, extremes=True):
     return PixelStats(*out, count=n)
 
 
+# ---- extension: per-pixel quantiles over time -----------------------------------------------------------------------------------
+_sp.rir_pixel_quantiles.argtypes = [ct.c_void_p] + [ct.c_int] * 3 + [ct.c_void_p, ct.c_int, ct.c_void_p]
+
+
+def _pixel_quantiles_args(frames_shape, what="pixel_quantiles"):
+    """the shape of a pixel_quantiles call, checked without a device; -> (n, h, w)"""
+    if len(frames_shape) == 2:
+        frames_shape = (1,) + tuple(frames_shape)
+    if len(frames_shape) != 3:
+        raise ValueError("%s: frames (n, h, w) or (h, w) expected" % what)
+    n, h, w = frames_shape
+    if h < 1 or w < 1 or h * w >= 1 << 31 or n > (1 << 31) - 1:
+        raise ValueError("%s: frames of at least 1x1 and fewer than 2^31 pixels, at most 2^31 - 1 of them, expected" % what)
+    return n, h, w
+
+
+def pixel_quantiles(images, percents):
+    """Extension: quantiles over time of a uint16 stack ``images[n][h][w]`` (or one ``(h, w)`` image) at ``percents`` (a float or 1..8
+    floats in [0, 1]): an int32 numpy array ``(len(percents), h, w)``, one image per percent (``rir_pixel_quantiles``) -
+    ``pixel_quantiles(images, 0.5)[0]`` is the median image over time.  Per pixel the rule of ``region_quantiles``; -1 everywhere for no
+    images.  ``ValueError`` on bad shapes or percents, ``RuntimeError`` on other dtypes and when the library fails."""
+    img = np.ascontiguousarray(images)
+    if img.dtype != np.uint16:
+        raise RuntimeError("pixel_quantiles: uint16 images expected, not %s" % img.dtype)
+    pc = _region_quantiles_percents(percents)
+    n, h, w = _pixel_quantiles_args(img.shape)
+    out = np.empty((pc.size, h, w), np.int32)
+    if _sp.rir_pixel_quantiles(img.ctypes.data if n else None, w, h, n, pc.ctypes.data, pc.size, out.ctypes.data) < 0:
+        raise RuntimeError("An error occured while calling 'pixel_quantiles': " + (last_error() or ""))
+    return out
+
+
 # ---- extension: polygon label maps ----------------------------------------------------------------------------------------------
 _sp.rir_polygon_map.argtypes = [ct.c_void_p] * 3 + [ct.c_int] * 4 + [ct.c_void_p] + [ct.c_int] * 3 + [ct.c_void_p]
 

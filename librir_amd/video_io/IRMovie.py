@@ -462,6 +462,42 @@ class IRMovie(object):
             acc.push(fr, k0)
         return acc.result()
 
+    _QUANTILE_RESIDENT_BYTES = 1 << 30  # uint16 images that pixel_quantiles decodes into one stack
+
+    def pixel_quantiles(self, percents, selection=slice(None)):
+        """Quantiles over time of the images of ``selection`` (as ``region_stats`` takes it) at ``percents`` (a float or 1..8 floats in
+        [0, 1]) - ``librir_amd.device.pixel_quantiles`` over the images ``movie[selection]`` gives (read-back filters applied): an int32
+        CUDA tensor ``(len(percents), h, w)``; ``mov.pixel_quantiles(0.5)[0]`` is the median image, a background that hot spots do not
+        pull up, and ``mov.pixel_quantiles(0.5)[0] + margin`` is a per-pixel threshold that ``track_hot_spots`` accepts.  A selection of at
+        most ``_QUANTILE_RESIDENT_BYTES`` of images is decoded once into one stack; a longer one is read once per pass in pieces of at most
+        ``_STATS_PIECE_BYTES`` into a ``PixelQuantileSelector``, so the device memory used does not grow with the selection.  The bits are
+        the same either way."""
+        import torch
+
+        from ..device import PixelQuantileSelector, _region_quantiles_percents, pixel_quantiles
+
+        h, w = self.image_size
+        pc = _region_quantiles_percents(percents)
+        positions = self._stats_positions(selection, "pixel_quantiles")
+        n = len(positions)
+        device = torch.device("cuda", torch.cuda.current_device())
+        if 2 * h * w * n <= self._QUANTILE_RESIDENT_BYTES:
+            stack = torch.empty((n, h, w), dtype=torch.uint16, device=device)
+            if n:
+                self.to_tensor(slice(positions.start, positions.stop, positions.step), out=stack)
+            return pixel_quantiles(stack, pc)
+        select = PixelQuantileSelector(pc, shape=(h, w), device=device)
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, n), h, w), dtype=torch.uint16, device=device)
+        for _ in range(select.passes):
+            for k0 in range(0, n, per_piece):
+                sel = positions[k0:k0 + per_piece]
+                fr = piece[:len(sel)]
+                self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+                select.push(fr)
+            select.next_pass()
+        return select.result()
+
     def track_hot_spots(self, threshold, selection=slice(None), table_entries=None, stats=True):
         """The hot spots of the images of ``selection`` (as ``region_stats`` takes it) as tracks through time: every image ``movie[selection]``
         gives (read-back filters applied) is thresholded - ``image > threshold``, an int or an ``(h, w)`` array or tensor for a per-pixel
