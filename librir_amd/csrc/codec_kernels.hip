@@ -418,9 +418,9 @@ namespace rir
 	// The two plane words of a lane and where they go.  A position is (index of the word in the wave's payload) * SCALE, or NONE for a
 	// lane without a plane: each target asks for the form it consumes as it is - the direct slot for byte offsets of buffer stores
 	// (SCALE 8, RIR_OOB), the staged target for word indices (SCALE 1, RIR_NONE) - so neither converts after the fact.
-	// The two 8-byte stores of a record are issued by the sink, outside the wave-uniform tier branch: with every vector-memory
-	// operation of the frame loop unconditional the compiler keeps exact s_waitcnt vmcnt(N) counts (a store inside the branch made
-	// it fall back to vmcnt(0) on half of the steps).
+	// The words are stored by the sink, outside the wave-uniform tier branch: the direct sink's two 8-byte stores of a record are
+	// unconditional, so that the compiler keeps exact s_waitcnt vmcnt(N) counts (a store inside the branch made it fall back to vmcnt(0)
+	// on half of the steps); the staged sink writes LDS only.
 	struct RecordWords
 	{
 		v2u32 va, vb;
@@ -496,12 +496,16 @@ namespace rir
 
 	// ---- where a record's words go: the two sinks of encode_run ------------------------------------------
 	// sink.emit<DIR>(residuals, mode, base, pos, ...) files the record that begins at word `pos` of what the wave has produced so far
-	// and returns its header.  Either sink issues exactly two unconditional buffer stores per record, out of range when unused.
+	// and returns its header.  GUARDED_STEPS tells the frame walk whether a record's work may sit under a condition: not the direct sink's,
+	// which issues two unconditional buffer stores per record (out of range for a lane without a plane); the staged sink's, which issues none.
 	//
 	// The direct sink: the segment's slot in the workspace (rirb1_encode_tiles), filled from word 0 in the order of production.
 	struct DirectSink
 	{
+		static constexpr bool GUARDED_STEPS = false; // its stores must not sit under a condition
 		__amdgpu_buffer_rsrc_t out;
+		__device__ __forceinline__ void keep_key(const v4u32 &, int) {} // (walks forwards only)
+		__device__ __forceinline__ v4u32 kept_key(int) { return v4u32{}; }
 		template <int DIR>
 		__device__ __forceinline__ uint64_t emit(const Px8 &r, uint32_t mode, uint32_t base, uint32_t pos, const LaneConsts &lc,
 												 const TransposeConsts &tc, uint32_t *words)
@@ -518,90 +522,97 @@ namespace rir
 	// first word of an extent of `need` words, ~0 when the arena is full (the launch is marked); wave-uniform
 	__device__ __noinline__ uint64_t staging_take_extent(unsigned long long *cursor, uint32_t need, uint64_t arena_words, uint32_t *error_word)
 	{
+		// (the lane from the execution mask: threadIdx would be one more register that the caller has to hand over)
+		const bool first_lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0;
 		unsigned long long off = 0;
-		if ((threadIdx.x & 63u) == 0)
+		if (first_lane)
 			off = __hip_atomic_fetch_add(cursor, (unsigned long long)need, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)off);
 		const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(off >> 32));
 		off = ((unsigned long long)hi << 32) | lo;
 		if (off + need > arena_words)
-		{ // no room: the caller's descriptor stays empty (every store is dropped by the range check)
-			if ((threadIdx.x & 63u) == 0)
+		{ // no room: the caller keeps no extent and stores nothing
+			if (first_lane)
 				__hip_atomic_fetch_or(error_word, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 			return ~0ull;
 		}
 		return off;
 	}
 
-	// The staged sink (single-pass encoders): the first records go into the wave's LDS region, from the first record that does not fit
-	// (wave-uniform decision) everything into its spill area in the workspace.
-	// Two kinds of spill area.  STATIC (arena == nullptr): `spill` is the wave's own worst-case slot, there from the start
-	// (rirb1_encode_dense).  DYNAMIC (rirb1_encode_packed): nothing is reserved; the wave that starts to spill takes an extent
-	// of `need` words - the worst case of its share of the chunk - from a bump cursor in the workspace, once (a returning
-	// atomic inside the rare, wave-uniform branch), and an arena that is full raises bit 1 of the error word and leaves the
-	// descriptor empty: the stores go nowhere, the segment is reported unusable, nothing is written out of bounds.
-	// DIR > 0: the wave walks its frames forwards and fills its region (and its extent) upwards from word 0.  DIR < 0: it walks them
-	// backwards and fills both DOWNWARDS from the top, so that what it leaves is still its records in frame order, contiguous, ending
-	// at the top: the indices of a record are taken relative to the record (pos = 0) and the wave-uniform first word of the record,
-	// top - words so far - words of this record, is added to them.
+	// The flush of the staged sink: the n words at `src` (the wave's LDS region) go to dst (its spill area), with coalesced 8-byte stores
+	// as in copy_wave_words.  Out of line, and a word at a time: the registers it uses are registers the frame loop cannot keep across
+	// the call.
+	typedef const __attribute__((address_space(3))) uint64_t *lds_words_ptr;
+	typedef __attribute__((address_space(1))) uint64_t *global_words_ptr;
+	__device__ __noinline__ void staging_flush(global_words_ptr dst, lds_words_ptr src, uint32_t n)
+	{
+#pragma unroll 1
+		for (uint32_t j = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); j < n; j += 64)
+			dst[j] = src[j];
+	}
+
+	// The staged sink (single-pass encoders): every record is filed in the wave's LDS region and emit() issues no vector-memory
+	// operation.  When a record does not fit, staging_flush() copies what the region holds - the records the wave produced FIRST - to
+	// the wave's spill area in the workspace and the region is empty again; a record is at most RIRB1_REC_MAX_WORDS <= the region, so
+	// one flush always makes room.
+	// Two kinds of spill area.  STATIC (cursor == nullptr): `area` is the wave's own worst-case slot, there from the start
+	// (rirb1_encode_dense).  DYNAMIC (rirb1_encode_packed): nothing is reserved; the wave that flushes for the first time takes an
+	// extent of `need` words - the worst case of its share of the chunk - from a bump cursor in the workspace, once.
+	// DIR > 0: the wave walks its frames forwards and fills its region and its area upwards from word 0; its words in stream order are
+	// area, then region.  DIR < 0: it walks them backwards and fills both DOWNWARDS from the top, each flush below the one before, so
+	// that what it leaves is still its records in frame order: region (ending at its top), then area (ending at its top).  The word
+	// indices of a record are taken relative to the record and the wave-uniform first word of the record is added to them.
 	struct Staging
 	{
-		uint64_t *lds;	   // this wave's region
-		uint32_t cap;	   // its capacity in words
-		uint32_t lds_used; // words in LDS once spilling has started
-		bool spilling;
-		__amdgpu_buffer_rsrc_t spill;
+		static constexpr bool GUARDED_STEPS = true;
+		uint64_t *lds; // this wave's region
+		uint32_t cap;  // its capacity in words
+		uint32_t fill; // words it holds now
 		uint32_t need; // words of the spill area: the worst case of the wave's share of the chunk
+		uint64_t *area; // the static area, or the arena
+		uint64_t extent; // first word of the wave's part of `area`: 0 (static), its extent once granted, else ~0
 		// dynamic spill extents
-		uint64_t *arena;			// nullptr: static
-		unsigned long long *cursor; // words handed out so far
+		unsigned long long *cursor; // words handed out so far; nullptr: static
 		uint64_t arena_words;
-		uint64_t extent; // first word of its extent (valid once spilling and granted)
 		uint32_t *error_word;
+		v4u32 *key_lds; // 64 x 16 bytes for the key frame of a wave that walks backwards
 
-		// wave w's region of `cap` words, empty, and a static spill area (none yet: the caller sets `spill`, or the arena's fields)
+		// wave w's region of `cap` words, empty, and no spill area (the caller sets `area` and `extent` = 0, or the arena's fields)
 		__device__ __forceinline__ Staging(uint64_t *lds_all, int w, int cap_, int nrec)
-			: lds(lds_all + (size_t)w * cap_), cap((uint32_t)cap_), lds_used(0), spilling(false), need((uint32_t)(nrec > 0 ? nrec : 0) * RIRB1_REC_MAX_WORDS),
-			  arena(nullptr), cursor(nullptr), arena_words(0), extent(~0ull), error_word(nullptr)
+			: lds(lds_all + (size_t)w * cap_), cap((uint32_t)cap_), fill(0), need((uint32_t)(nrec > 0 ? nrec : 0) * RIRB1_REC_MAX_WORDS), area(nullptr),
+			  extent(~0ull), cursor(nullptr), arena_words(0), error_word(nullptr), key_lds(nullptr)
 		{
 		}
+		__device__ __forceinline__ void keep_key(const v4u32 &v, int lane) { key_lds[lane] = v; }
+		__device__ __forceinline__ v4u32 kept_key(int lane) { return key_lds[lane]; }
 
+		// pos: words the wave has produced so far; pos - fill of them have been flushed
 		template <int DIR>
 		__device__ __forceinline__ uint64_t emit(const Px8 &r, uint32_t mode, uint32_t base, uint32_t pos, const LaneConsts &lc, const TransposeConsts &tc,
 												 uint32_t *words)
 		{
 			RecordWords rw;
-			const uint64_t h = emit_words<1u, RIR_NONE>(r, mode, base, rw, DIR > 0 ? pos : 0u, lc, tc, words);
-			if (!spilling && pos + *words > cap)
-			{
-				spilling = true, lds_used = pos;
-				if (arena)
-				{
-					// (the extent comes back from a call: vector registers, "divergent" for the compiler - and with it the branch below and the
-					// descriptor it sets, which then lived in VGPRs and cost every record two waterfall loops, 12 vector + 12 scalar
-					// instructions, around its two stores.  It is wave-uniform: say so.)
+			const uint64_t h = emit_words<1u, RIR_NONE>(r, mode, base, rw, 0u, lc, tc, words);
+			if (fill + *words > cap)
+			{ // rare: flush what the region holds, below (backwards) or above (forwards) what was flushed before
+				const uint32_t flushed = pos - fill;
+				if (cursor != nullptr && flushed == 0)
+				{ // (what comes back from a call is in vector registers, "divergent" for the compiler; it is wave-uniform: say so)
 					const uint64_t ext = staging_take_extent(cursor, need, arena_words, error_word);
 					extent = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(ext >> 32)) << 32) |
 							 (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)ext);
-					if (extent != ~0ull)
-						spill = make_rsrc(arena + extent, need * 8u);
 				}
+				if (extent != ~0ull)
+					staging_flush((global_words_ptr)(area + extent + (DIR > 0 ? flushed : need - flushed - fill)),
+								  (lds_words_ptr)(DIR > 0 ? lds : lds + (cap - fill)), fill);
+				fill = 0;
 			}
-			if (!spilling)
-			{ // LDS operations only inside this (wave-uniform) branch: the vector-memory stream below stays unconditional
-				uint64_t *rec = DIR > 0 ? lds : lds + (cap - pos - *words); // (pos + words <= cap here)
-				if (rw.pa != RIR_NONE)
-					rec[rw.pa] = ((uint64_t)rw.va.y << 32) | rw.va.x;
-				if (rw.pb != RIR_NONE)
-					rec[rw.pb] = ((uint64_t)rw.vb.y << 32) | rw.vb.x;
-			}
-			// two stores per record whatever happens (counted waits, see RecordWords): out of range unless the wave spills.  A backward
-			// wave's extent ends with its first spilled record: need - words spilled so far - words of this record is where this one starts
-			const uint32_t add = !spilling ? RIR_OOB : DIR > 0 ? 0u - lds_used * 8u : (need - (pos - lds_used) - *words) * 8u;
-			const uint32_t oa = rw.pa != RIR_NONE ? rw.pa * 8u + add : RIR_OOB;
-			const uint32_t ob = rw.pb != RIR_NONE ? rw.pb * 8u + add : RIR_OOB;
-			__builtin_amdgcn_raw_buffer_store_b64(rw.va, spill, oa, 0, SPARSE_STORE_AUX);
-			__builtin_amdgcn_raw_buffer_store_b64(rw.vb, spill, ob, 0, SPARSE_STORE_AUX);
+			uint64_t *rec = DIR > 0 ? lds + fill : lds + (cap - fill - *words);
+			if (rw.pa != RIR_NONE)
+				rec[rw.pa] = ((uint64_t)rw.va.y << 32) | rw.va.x;
+			if (rw.pb != RIR_NONE)
+				rec[rw.pb] = ((uint64_t)rw.vb.y << 32) | rw.vb.x;
+			fill += *words;
 			return h;
 		}
 	};
@@ -626,7 +637,7 @@ namespace rir
 		const uint32_t lane_off = (uint32_t)lane * 16u;
 		// FAST: whole tile inside the frame and 16-byte aligned rows -> raw-buffer loads, unconditional.  They are compiler-visible
 		// builtins: the waits are the compiler's own counted s_waitcnt, which stay exact because no vector-memory operation of the
-		// frame loop sits inside a branch.  Frames are loaded strictly in order (of time, or against it: 0,1,2,3 up front, then the
+		// frame loop sits inside a branch (the staged sink's flush is out of line, behind a call).  Frames are loaded strictly in order (of time, or against it: 0,1,2,3 up front, then the
 		// (k+3)-th at step k), so the address is a running wave-uniform pointer (2 scalar adds per load instead of a 64-bit multiply
 		// chain); a request past the wave's last frame is an out-of-range offset: the instruction is issued (the waits stay counted)
 		// and touches no memory.
@@ -681,17 +692,32 @@ namespace rir
 		};
 		// Ring of 4 frame slots: what was loaded k-th lives in slot k % 4, three frames are in flight ahead of the one being packed.
 		// The loop is unrolled by 4 so that slots are fixed registers (a register copy of a loaded value would force an early wait
-		// on the load).
+		// on the load): every load must go into the registers of the frame it replaces.
 		v4u32 s0, s1, s2, s3;
+		// (in this order: a wait counts the loads issued AFTER the one it needs, and the scheduler is otherwise free to issue slot 1's
+		// load last - then the wait at the loop's head is vmcnt(0) for good)
 		load(0, s0);
+		if (Sink::GUARDED_STEPS)
+			__builtin_amdgcn_sched_barrier(0);
 		load(1, s1);
+		if (Sink::GUARDED_STEPS)
+			__builtin_amdgcn_sched_barrier(0);
 		load(2, s2);
+		if (Sink::GUARDED_STEPS)
+			__builtin_amdgcn_sched_barrier(0);
 		load(3, s3);
+		if (Sink::GUARDED_STEPS)
+			__builtin_amdgcn_sched_barrier(0);
 		if (!BACK && has_key)
 			key_record(as_px8(s0));
 		// step K: NEW was loaded K-th, OLD (K-1)-th; forwards NEW is the record's frame and OLD the one before it, backwards OLD is
-		// the record's frame and NEW the one before it.  OLD's slot is free afterwards: the (K+3)-th load goes there.
-#define RIR_ENC_STEP(K, NEW, OLD)                                                             \
+		// the record's frame and NEW the one before it.  OLD's slot is free afterwards: the (K+3)-th load goes there.  The load is
+		// issued whatever LIVE says; the record's work - which holds no vector-memory operation for a sink without stores of its own -
+		// only when LIVE (wave-uniform).  The empty asm is no instruction: it keeps the difference in front of the load.  Without it
+		// the compiler sinks the difference into the LIVE branch, behind the load, which then cannot reuse OLD's registers: the slots
+		// wander through eight register quads, come back with copies (and a drain) at the loop's edge, and 64 registers no longer do.  Backwards the key frame is the NEW of the last live step: the sink keeps it (in LDS: four
+		// more registers across the loop do not fit 64), because the loads of the steps that are not live go on overwriting the slots.
+#define RIR_ENC_STEP(K, NEW, OLD, LIVE)                                                       \
 	{                                                                                          \
 		const int k_ = (K);                                                                    \
 		Px8 d;                                                                                 \
@@ -699,41 +725,66 @@ namespace rir
 			const Px8 c_ = as_px8(BACK ? OLD : NEW), p_ = as_px8(BACK ? NEW : OLD);            \
 			_Pragma("unroll") for (int k = 0; k < 4; ++k) d.d[k] = pk_sub16(c_.d[k], p_.d[k]); \
 		}                                                                                      \
+		if (Sink::GUARDED_STEPS)                                                               \
+			asm volatile("" : "+v"(d.d[0]), "+v"(d.d[1]), "+v"(d.d[2]), "+v"(d.d[3]));        \
 		load(k_ + 3, OLD);                                                                     \
-		const uint32_t base = tile_base(d, true);                                              \
-		const uint32_t b2 = base | (base << 16);                                               \
-		_Pragma("unroll") for (int k = 0; k < 4; ++k) d.d[k] = pk_sub16(d.d[k], b2);          \
-		uint32_t words;                                                                        \
-		const uint64_t h = sink.template emit<DIR>(d, RIRB1_MODE_TEMPORAL, base, pos, lc, tc, &words); \
-		if (lane == ((k_ - 1) & 63))                                                           \
-			hdr_reg = h;                                                                       \
-		pos += words;                                                                          \
+		if (LIVE)                                                                              \
+		{                                                                                      \
+			if (BACK && Sink::GUARDED_STEPS && has_key && k_ == nload - 1)                     \
+				sink.keep_key(NEW, lane);                                                      \
+			const uint32_t base = tile_base(d, true);                                          \
+			const uint32_t b2 = base | (base << 16);                                           \
+			_Pragma("unroll") for (int k = 0; k < 4; ++k) d.d[k] = pk_sub16(d.d[k], b2);      \
+			uint32_t words;                                                                    \
+			const uint64_t h = sink.template emit<DIR>(d, RIRB1_MODE_TEMPORAL, base, pos, lc, tc, &words); \
+			if (lane == ((k_ - 1) & 63))                                                       \
+				hdr_reg = h;                                                                   \
+			pos += words;                                                                      \
+		}                                                                                      \
 	}
-		// Steps come in groups of 64 (one header per lane of hdr_reg, flushed with one coalesced store per group) and the steady-state
-		// loop runs whole iterations of 4 steps with NO condition around any vector-memory operation: that is what lets the compiler
-		// keep counted waits, i.e. keeps the loads of the next frames in flight across the packing of the current one.
+		// Steps come in groups of 64 (one header per lane of hdr_reg, flushed with one coalesced store per group).  What lets the
+		// compiler keep counted waits - the loads of the next frames in flight across the packing of the current one - is that no
+		// vector-memory operation of the loop sits under a condition.
 		int fb = 1;
 		while (fb < nload)
 		{
 			const int g0 = fb, gend = min(fb + 64, nload); // this group: steps [g0, gend), header of step k in lane k - g0
-			for (; fb + 3 < gend; fb += 4)
+			if (Sink::GUARDED_STEPS)
 			{
-				RIR_ENC_STEP(fb, s1, s0)
-				RIR_ENC_STEP(fb + 1, s2, s1)
-				RIR_ENC_STEP(fb + 2, s3, s2)
-				RIR_ENC_STEP(fb + 3, s0, s3)
-			}
-			if (fb < gend)
-			{ // up to three left-over steps of the run's last group (64 % 4 == 0: the slot rotation stays aligned)
-				RIR_ENC_STEP(fb, s1, s0)
-				if (fb + 1 < gend)
+				// A sink without stores: ONE loop whose steps past the group's end only issue their (out-of-range) loads.  There is no
+				// remainder code, so every wait before the use of a frame - the loop's head included - allows the two younger loads, and
+				// the ring is never drained.  64 % 4 == 0: the slot rotation stays aligned.
+				for (; fb < gend; fb += 4)
 				{
-					RIR_ENC_STEP(fb + 1, s2, s1)
-					if (fb + 2 < gend)
-						RIR_ENC_STEP(fb + 2, s3, s2)
+					RIR_ENC_STEP(fb, s1, s0, true)
+					RIR_ENC_STEP(fb + 1, s2, s1, fb + 1 < gend)
+					RIR_ENC_STEP(fb + 2, s3, s2, fb + 2 < gend)
+					RIR_ENC_STEP(fb + 3, s0, s3, fb + 3 < gend)
 				}
-				fb = gend;
 			}
+			else
+			{
+				// A sink with two stores per record: they stay unconditional in whole iterations of 4 steps, and up to three left-over
+				// steps follow the run's last group (64 % 4 == 0: the slot rotation stays aligned)
+				for (; fb + 3 < gend; fb += 4)
+				{
+					RIR_ENC_STEP(fb, s1, s0, true)
+					RIR_ENC_STEP(fb + 1, s2, s1, true)
+					RIR_ENC_STEP(fb + 2, s3, s2, true)
+					RIR_ENC_STEP(fb + 3, s0, s3, true)
+				}
+				if (fb < gend)
+				{
+					RIR_ENC_STEP(fb, s1, s0, true)
+					if (fb + 1 < gend)
+					{
+						RIR_ENC_STEP(fb + 1, s2, s1, true)
+						if (fb + 2 < gend)
+							RIR_ENC_STEP(fb + 2, s3, s2, true)
+					}
+				}
+			}
+			fb = gend;
 			// lane l holds the header of step g0 + l: the record of frame g0 + l forwards, of frame nload - (g0 + l) backwards
 			if (g0 + lane < gend)
 				hdr_first[BACK ? nload - (g0 + lane) : g0 + lane] = hdr_reg;
@@ -741,10 +792,8 @@ namespace rir
 		}
 #undef RIR_ENC_STEP
 		if (BACK && has_key)
-		{ // the key frame was loaded last, (nload - 1)-th: it is in slot (nload - 1) % 4
-			const int ks = (nload - 1) & 3;
-			const v4u32 kv = ks == 0 ? s0 : ks == 1 ? s1 : ks == 2 ? s2 : s3;
-			key_record(as_px8(kv));
+		{ // the key frame was loaded last, (nload - 1)-th: the run's only frame, or what the last step gave the sink to keep
+			key_record(as_px8(nload > 1 ? sink.kept_key(lane) : s0));
 		}
 		return pos;
 	}
@@ -1014,7 +1063,7 @@ namespace rir
 	}
 
 	// The end of a wave's walk, before the barrier: the workgroup defines the table entries a short last chunk leaves unused, the wave
-	// publishes its words and how many of them are in LDS, and what it spilled has left it before another wave reads it.
+	// publishes its words and how many of them are in LDS, and what it flushed has left it before another wave reads it.
 	template <int WAVES>
 	__device__ __forceinline__ void staged_publish(uint64_t *__restrict__ my_hdr, int nf, int gop, const Staging &sg, uint32_t pos, int w, int lane,
 												   uint32_t *sh_words, uint32_t *sh_lds_words)
@@ -1024,23 +1073,23 @@ namespace rir
 		if (lane == 0)
 		{
 			sh_words[w] = pos;
-			sh_lds_words[w] = sg.spilling ? sg.lds_used : pos;
+			sh_lds_words[w] = sg.fill;
 		}
-		if (sg.spilling)
+		if (sg.fill != pos)
 			asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 	}
 
-	// Copies one wave's n_all words to dst in frame order: n_lds of them are in its LDS region (`cap` words), the rest in its spill area,
-	// which spill_area(need) describes (its size in words goes to `need`) and which is asked for only when there is a rest.  A forward
-	// wave's words: its region from word 0, then (the later records) its area from word 0.  A backward wave's: its area (the EARLIER
-	// records, which it packed last) up to the area's end, then its region up to the region's end.
+	// Copies one wave's n_all words to dst in frame order: n_lds of them are in its LDS region (`cap` words), the rest - the records it
+	// produced first - in its spill area, which spill_area(need) describes (its size in words goes to `need`) and which is asked for
+	// only when there is a rest.  A forward wave's words: its area from word 0, then its region from word 0.  A backward wave's: its
+	// region (the EARLIER records, which it packed last) up to the region's end, then its area up to the area's end.
 	template <class SpillArea>
 	__device__ __forceinline__ void copy_wave_words(uint64_t *__restrict__ dst, const uint64_t *region, uint32_t cap, uint32_t n_all, uint32_t n_lds, bool back,
 													int lane, SpillArea spill_area)
 	{
 		const uint32_t n_ext = n_all - n_lds;
 		const uint64_t *src = region + (back ? cap - n_lds : 0u);
-		uint64_t *dst_lds = dst + (back ? n_ext : 0u);
+		uint64_t *dst_lds = dst + (back ? 0u : n_ext);
 		uint32_t j = (uint32_t)lane;
 		for (; j + 192 < n_lds; j += 256)
 		{
@@ -1050,11 +1099,11 @@ namespace rir
 		for (; j < n_lds; j += 64)
 			dst_lds[j] = src[j];
 		if (n_ext > 0)
-		{ // what the wave spilled comes back from the workspace (sc1 loads: from L2, where its stores went)
+		{ // what the wave flushed comes back from the workspace (sc1 loads: from L2, where its stores went)
 			uint32_t need;
 			const __amdgpu_buffer_rsrc_t sp = spill_area(need);
 			const uint32_t first = back ? need - n_ext : 0u;
-			uint64_t *dst_ext = dst + (back ? 0u : n_lds);
+			uint64_t *dst_ext = dst + (back ? n_lds : 0u);
 			for (uint32_t q = (uint32_t)lane; q < n_ext; q += 64)
 			{
 				const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(sp, (first + q) * 8u, 0, 16 /* sc1 */);
@@ -1103,7 +1152,7 @@ namespace rir
 		};
 		const WaveShare sh = wave_share<enc_split>(w, WAVES, nf);
 		Staging sg(enc_lds, w, cap, sh.nrec);
-		sg.spill = spill_area(sh, sg.need);
+		sg.area = spill + (int64_t)seg * RIRB1_SLOT_WORDS(gop) + (int64_t)sh.rec0 * RIRB1_REC_MAX_WORDS, sg.extent = 0; // (spill_area's words)
 		uint32_t pos = 0;
 		if (sh.nrec > 0)
 		{
@@ -1223,7 +1272,8 @@ namespace rir
 		uint64_t *__restrict__ ctrl, uint64_t *__restrict__ arena, uint64_t arena_words, int cap)
 	{
 		extern __shared__ __attribute__((aligned(16))) uint64_t enc_lds[];
-		uint64_t *sh_u64 = enc_lds + (size_t)WAVES * cap;			  // [0] segment's first word in the stream, [1 + w] wave w's spill extent
+		v4u32 *key_lds = reinterpret_cast<v4u32 *>(enc_lds + (size_t)WAVES * cap); // the key frame while wave 0 walks back to it (1 KiB)
+		uint64_t *sh_u64 = enc_lds + (size_t)WAVES * cap + 128;	  // [0] segment's first word in the stream, [1 + w] wave w's spill extent
 		uint32_t *sh_u32 = reinterpret_cast<uint32_t *>(sh_u64 + 1 + WAVES); // [0..WAVES) words of each wave, [WAVES..2 WAVES) of them in LDS
 		const int lane = threadIdx.x & 63;
 		const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1240,8 +1290,8 @@ namespace rir
 
 		const WaveShare sh = wave_share<enc_split_mirrored>(w, WAVES, nf);
 		Staging sg(enc_lds, w, cap, sh.nrec);
-		sg.spill = make_rsrc(arena, 0); // empty until the wave takes an extent
-		sg.arena = arena, sg.cursor = spill_cursor, sg.arena_words = arena_words, sg.error_word = error_word;
+		sg.key_lds = key_lds;
+		sg.area = arena, sg.cursor = spill_cursor, sg.arena_words = arena_words, sg.error_word = error_word;
 		uint32_t pos = 0;
 		if (sh.nrec > 0)
 		{
@@ -1757,8 +1807,9 @@ namespace rir
 	}
 
 	// LDS words per wave of a staged encoder whose `waves` waves pack one segment: 14.4 KB per workgroup - 11 workgroups per CU, in the
-	// dense encoder 7 packing (28 waves) while 4 wait for their offsets (1 wave each); the reference's recipe needs 290-355 words per
-	// wave of four - and never more than the worst case of the wave's share of the chunk
+	// dense encoder 7 packing (28 waves) while 4 wait for their offsets (1 wave each); the packed encoder adds 1 KiB for the key frame of
+	// its backward wave: 10 per CU, of which 8 can pack.  The reference's recipe needs 290-355 words per wave of four - and never more
+	// than the worst case of the wave's share of the chunk
 	static int staged_lds_words(int gop, int waves)
 	{
 		const int share = (gop + 1 + waves - 1) / waves + 1;
@@ -1852,7 +1903,7 @@ namespace rir
 		}
 		constexpr int WAVES = PACKED_WAVES;
 		const int cap = staged_lds_words(gop, WAVES);
-		const size_t lds = (size_t)WAVES * cap * 8 + (1 + WAVES) * 8 + 2 * WAVES * 4;
+		const size_t lds = (size_t)WAVES * cap * 8 + 1024 + (1 + WAVES) * 8 + 2 * WAVES * 4;
 		launch_fast_then_ragged(d_frames, npx, ntiles, rirb1_encode_packed<WAVES, true>, rirb1_encode_packed<WAVES, false>, [&](auto kernel, int t0, int t1) {
 			hipLaunchKernelGGL(kernel, dim3(t1 - t0, nchunks), dim3(WAVES * 64), lds, st, d_frames, npx, ntiles, t0, nframes, gop, d_hdr, d_seg_pos, d_seg_words,
 							   d_stream, capacity_words, d_ctrl, d_arena, arena_words, cap);
