@@ -3,6 +3,7 @@ RIR_DEBUG_LOSSY_BAIL, RIR_DEBUG_ECC_BAIL).  The hooks are compiled into librir_a
 into the product library: each case runs in a process of its own that loads that build (RIR_LIBRARY_VARIANT=testhooks), started by the test.
     RIR_LIBRARY_VARIANT=testhooks python tests/hook_cases.py <case> [argument]"""
 import contextlib
+import itertools
 import os
 import sys
 import tempfile
@@ -249,20 +250,22 @@ def single_sequence_falls_back():
 def const_pairs(pairs):
     """The streaming kernel of the bounded-loss step exists for 2, 4 and 8 pixels per thread (lossy_const_pairs picks by the number of waves:
     many streams of 640x512 take 8); small test frames only ever see 2.  The hook RIR_LOSSY_CONST_PAIRS forces the others: same frames, same
-    budgets as the oracle's."""
+    budgets as the oracle's - on S1 and on the full-range scene of tests/lossy_cases.py."""
     import torch
 
     from librir_amd import device as D
     from oracle.pyoracle import Oracle
 
     sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from lossy_cases import ti_edges
     from test_gpu_lossy import CONST_CASES, _oracle_track
 
     oracle = Oracle()
     os.environ["RIR_LOSSY_CONST_PAIRS"] = str(pairs)
-    for name in ("ra8", "subtract_min", "ra64_longer_than_the_calls", "high_above_low", "ra0"):
+    # (ti_edges: the whole 16-bit range - top bits that change, values of 32 768 and more in every packed half, ring sums at their ceiling)
+    for scene, name in itertools.product(("S1", "ti_edges"), ("ra8", "subtract_min", "ra64_longer_than_the_calls", "high_above_low", "ra0")):
         c = CONST_CASES[name]
-        arr = s1_noisy_background(c["n"], c["h"], c["w"], seed=47)
+        arr = s1_noisy_background(c["n"], c["h"], c["w"], seed=47) if scene == "S1" else ti_edges(c["n"], c["h"], c["w"], c["hl"], 47).copy()
         for add_loss in (False, True):
             exp, elo, ehi = _oracle_track(oracle, arr, c["w"], c["h"], c["hl"], c["low"], c["high"], 0.0, c["ra"], c.get("subtract_min", False), add_loss)
             ls = D.LossyStream(c["w"], c["h"], c["hl"], c["low"], c["high"], 0.0, c["ra"], subtract_min=c.get("subtract_min", False))
@@ -274,8 +277,8 @@ def const_pairs(pairs):
                 if c1 - c0 >= 3:
                     offered, taken = ls.path_stats()
                     assert offered >= 1 and taken == offered, (name, c0, c1, offered, taken)
-            assert np.array_equal(torch.cat(got).cpu().numpy(), exp), (name, pairs, add_loss)
-            assert np.concatenate(lo).tolist() == elo and np.concatenate(hi).tolist() == ehi, (name, pairs, add_loss)
+            assert np.array_equal(torch.cat(got).cpu().numpy(), exp), (name, scene, pairs, add_loss)
+            assert np.concatenate(lo).tolist() == elo and np.concatenate(hi).tolist() == ehi, (name, scene, pairs, add_loss)
             ls.close()
     del os.environ["RIR_LOSSY_CONST_PAIRS"]
 
@@ -283,13 +286,14 @@ def const_pairs(pairs):
 def spec_pairs(pairs):
     """The speculative form's instantiations of the streaming kernel for 4 and 8 pixels per thread (lossy_const_pairs picks them for many
     streams; small test frames would only ever see 2): forced through RIR_LOSSY_CONST_PAIRS on static scenes with stdFactor 5 - committed,
-    frames and budgets the oracle's - and on S1 (the group goes to the general form)."""
+    frames and budgets the oracle's - and on S1 and the full-range scene of tests/lossy_cases.py (groups that go to the general form)."""
     import torch
 
     from librir_amd import device as D
     from oracle.pyoracle import Oracle
 
     sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from lossy_cases import ti_edges
     from test_gpu_lossy import CONST_CASES, _oracle_track
     from test_gpu_lossy_spec import static_scene
 
@@ -299,8 +303,11 @@ def spec_pairs(pairs):
     for name in ("ra8", "subtract_min", "ra64_longer_than_the_calls", "high_above_low", "ra0", "ra1"):
         c = CONST_CASES[name]
         h, w, hl = 64, 96, 64 - (c["h"] - c["hl"])
-        for scene in ("static", "S1"):
-            arr = static_scene(c["n"], h, w, seed=53) if scene == "static" else s1_noisy_background(c["n"], h, w, seed=53)
+        for scene in ("static", "S1", "ti_edges"):
+            if scene == "ti_edges":
+                arr = ti_edges(c["n"], h, w, hl, 53).copy()
+            else:
+                arr = static_scene(c["n"], h, w, seed=53) if scene == "static" else s1_noisy_background(c["n"], h, w, seed=53)
             for add_loss in (False, True):
                 exp, elo, ehi = _oracle_track(oracle, arr, w, h, hl, c["low"], c["high"], 5.0, c["ra"], c.get("subtract_min", False), add_loss)
                 ls = D.LossyStream(w, h, hl, c["low"], c["high"], 5.0, c["ra"], subtract_min=c.get("subtract_min", False))
