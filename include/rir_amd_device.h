@@ -254,6 +254,24 @@ extern "C"
 								void *d_work, size_t work_bytes, void *stream);
 	size_t rir_region_stats_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions);
 
+	/* Per-region geometry of int32 label maps (extension): where every region is and how it is spread, optionally weighted by a uint16
+	 * stack d_frames[nframes][h][w].  d_labels, labels_per_frame, nregions (1..2^24) and the rule that labels outside [0, nregions) are
+	 * ignored are those of rir_region_stats_device.  For frame f and region r, P = the pixels of f whose label is r, x = i % w, y = i / w
+	 * for the flat index i, v = the pixel's value.  Outputs, [nframes][nregions] leading: d_count = |P| (int32); d_bbox[..][4] = xmin,
+	 * ymin, xmax, ymax over P, inclusive (int32; -1, -1, -1, -1 for an empty region); d_moments[..][5] = the exact sums over P of x, y,
+	 * x^2, x * y, y^2 (int64; zeros for an empty region); d_weighted[..][3] = the exact sums over P of v, v * x, v * y (int64), written
+	 * only when frames are given: d_weighted is null exactly when d_frames is.  With d_frames null only the labels are read and nframes
+	 * counts label maps: labels_per_frame 1, or nframes <= 1.  With frames and one shared map every frame still gets its own row of all
+	 * outputs.  Bounds: w, h <= 32768 and w * h < 2^31; every sum is then below 2^62 (the largest is 65535 * 32767 * 2^31).  All
+	 * combination is integer add, min and max: bitwise reproducible, whatever the launch geometry.  d_work: device memory, 8-byte aligned,
+	 * at least rir_region_geometry_workspace_bytes(...) bytes (0: arguments refused; `weighted` 1 when frames will be given, else 0).
+	 * Asynchronous on `stream`; no output or the workspace may overlap an input or another output.  nframes 0: nothing is done.  0 / -1
+	 * (invalid argument, null pointer, overlap, workspace too small, no device). */
+	int rir_region_geometry_device(const int *d_labels, const unsigned short *d_frames /* or null */, int w, int h, int nframes,
+								   int labels_per_frame, int nregions, int *d_count, int *d_bbox, long long *d_moments,
+								   long long *d_weighted /* null iff d_frames is null */, void *d_work, size_t work_bytes, void *stream);
+	size_t rir_region_geometry_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions, int weighted);
+
 	/* Per-region quantiles of a uint16 stack d_frames[nframes][h][w] (extension), frames and label maps as rir_region_stats_device takes
 	 * them, nregions 1..65 536.  `percents`: HOST memory, npercents (1..8) floats in [0, 1].  For frame f, region r and percent p_j, V = the
 	 * values of the pixels of f whose label is r, c = |V| and t = (int)roundf((float)c * p_j) - the product in float32, rounded half away

@@ -68,6 +68,12 @@ extern "C"
 	 * once.  0 / -1. */
 	int rir_region_stats(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
 						 int *count, long long *sum, long long *sumsq, int *min, int *max, int *argmin, int *argmax);
+	/* Per-region geometry of host label maps, weighted by a host stack frames[nframes][h][w] when `frames` is not null:
+	 * rir_region_geometry_device (rir_amd_device.h, where the outputs are defined), synchronous, host outputs count[nframes][nregions],
+	 * bbox[..][4], moments[..][5] and, with frames, weighted[..][3] (null exactly when frames is).  The frames and per-frame maps go
+	 * through the device in slabs of at most 64 MiB; a shared map goes up once.  0 / -1. */
+	int rir_region_geometry(const int *labels, const unsigned short *frames /* or null */, int w, int h, int nframes, int labels_per_frame,
+							int nregions, int *count, int *bbox, long long *moments, long long *weighted /* null iff frames is null */);
 	/* Per-region quantiles of a host stack frames[nframes][h][w] with host label maps: rir_region_quantiles_device (rir_amd_device.h, where
 	 * the rule is defined), synchronous, host outputs count[nframes][nregions] and values[nframes][nregions][npercents].  The frames go
 	 * through the device in slabs of at most 64 MiB; a shared map goes up once.  0 / -1. */

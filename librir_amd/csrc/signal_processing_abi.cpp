@@ -13,6 +13,7 @@
 #include <map>
 
 #include "filter_kernels.h"
+#include "geometry_kernels.h"
 #include "label_kernels.h"
 #include "pixel_kernels.h"
 #include "pixel_quantile_kernels.h"
@@ -723,6 +724,76 @@ RIR_EXPORT int rir_region_stats_device(const unsigned short *d_frames, const int
 			   : -1;
 }
 
+// Per-region geometry (geometry_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an input or
+// another output.
+namespace
+{
+	// region_stats' arguments with both sides at most 32768 (every sum then stays below 2^62); without weights nframes counts label maps
+	bool region_geometry_args(int w, int h, int nframes, int labels_per_frame, int nregions, int weighted)
+	{
+		return region_stats_args(w, h, nframes, labels_per_frame, nregions) && w <= 32768 && h <= 32768 && (weighted == 0 || weighted == 1) &&
+			   (weighted || labels_per_frame || nframes <= 1);
+	}
+	const char *const REGION_GEOMETRY_ARGS = "invalid argument (1 <= w, h <= 32768 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, "
+											 "1 <= nregions <= 2^24; without frames labels_per_frame 1 or nframes <= 1)";
+} // namespace
+
+RIR_EXPORT size_t rir_region_geometry_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions, int weighted)
+{
+	return region_geometry_args(w, h, nframes, labels_per_frame, nregions, weighted) ? GEOMETRY_WORK_BYTES : 0;
+}
+
+RIR_EXPORT int rir_region_geometry_device(const int *d_labels, const unsigned short *d_frames, int w, int h, int nframes, int labels_per_frame, int nregions,
+										  int *d_count, int *d_bbox, long long *d_moments, long long *d_weighted, void *d_work, size_t work_bytes,
+										  void *stream)
+{
+	if (!device_ready())
+		return -1;
+	if (!region_geometry_args(w, h, nframes, labels_per_frame, nregions, d_frames != nullptr))
+	{
+		log_error(std::string("rir_region_geometry_device: ") + REGION_GEOMETRY_ARGS);
+		return -1;
+	}
+	if (nframes == 0)
+		return 0;
+	if (!d_labels || !d_count || !d_bbox || !d_moments || !d_work || (d_frames != nullptr) != (d_weighted != nullptr))
+	{
+		log_error("rir_region_geometry_device: null pointer (d_weighted is null exactly when d_frames is)");
+		return -1;
+	}
+	if (work_bytes < GEOMETRY_WORK_BYTES || (uintptr_t)d_work % 8 != 0)
+	{
+		log_error("rir_region_geometry_device: the workspace must be 8-byte aligned and hold rir_region_geometry_workspace_bytes() bytes");
+		return -1;
+	}
+	const size_t npx = (size_t)w * h, cells = (size_t)nframes * nregions;
+	const struct
+	{
+		uintptr_t p;
+		size_t bytes;
+	} in[2] = {{(uintptr_t)d_labels, npx * (labels_per_frame ? nframes : 1) * 4}, {(uintptr_t)d_frames, d_frames ? npx * nframes * 2 : 0}},
+	  out[5] = {{(uintptr_t)d_count, cells * 4}, {(uintptr_t)d_bbox, cells * 16}, {(uintptr_t)d_moments, cells * 40},
+				{(uintptr_t)d_work, GEOMETRY_WORK_BYTES}, {(uintptr_t)d_weighted, d_weighted ? cells * 24 : 0}};
+	for (int i = 0; i < 5; ++i)
+	{
+		bool overlap = false;
+		for (const auto &a : in)
+			overlap |= out[i].p < a.p + a.bytes && a.p < out[i].p + out[i].bytes;
+		for (int j = 0; j < i; ++j)
+			overlap |= out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
+		if (overlap)
+		{
+			log_error("rir_region_geometry_device: an output or the workspace overlaps an input or another output");
+			return -1;
+		}
+	}
+	return hip_ok(launch_region_geometry(d_labels, d_frames, w, h, nframes, labels_per_frame, nregions, d_count, d_bbox, (int64_t *)d_moments,
+										 (int64_t *)d_weighted, as_stream(stream)),
+				  "region_geometry")
+			   ? 0
+			   : -1;
+}
+
 // Per-region quantiles (quantile_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an input or
 // another output.
 namespace
@@ -1406,6 +1477,53 @@ RIR_EXPORT int rir_region_stats(const unsigned short *frames, const int *labels,
 				return -1;
 		if (!hip_ok(hipMemcpyAsync(sum + at, d64, n * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
 			!hip_ok(hipMemcpyAsync(sumsq + at, d64 + cells, n * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") || !hip_ok(wait_stream(st), "region_stats"))
+			return -1;
+	}
+	return 0;
+}
+
+// Extension: per-region geometry of host label maps, weighted by a host stack when `frames` is given; staged as rir_region_stats stages its
+// arguments (without frames the slabs are label maps).  Synchronous.  0 / -1.
+RIR_EXPORT int rir_region_geometry(const int *labels, const unsigned short *frames, int w, int h, int nframes, int labels_per_frame, int nregions,
+								   int *count, int *bbox, long long *moments, long long *weighted)
+{
+	if (!device_ready())
+		return -1;
+	if (!region_geometry_args(w, h, nframes, labels_per_frame, nregions, frames != nullptr) || !labels || !count || !bbox || !moments ||
+		(frames != nullptr) != (weighted != nullptr))
+	{
+		log_error(std::string("rir_region_geometry: ") + REGION_GEOMETRY_ARGS + ", or a null pointer (weighted is null exactly when frames is)");
+		return -1;
+	}
+	if (nframes == 0)
+		return 0;
+	const size_t npx = (size_t)w * h, frame = npx * (frames ? 2 : 0) + npx * (labels_per_frame ? 4 : 0), K = (size_t)nregions;
+	const size_t per_frame_out = K * (4 + 16 + 40 + 24); // the outputs of one frame on the device
+	const int slab =
+		(int)std::max<size_t>(1, std::min<size_t>({REGION_SLAB_BYTES / std::max<size_t>(frame, 1), REGION_SLAB_BYTES / per_frame_out, (size_t)nframes}));
+	const size_t cells = (size_t)slab * K;
+	DeviceBuffer fr, lab, o32, o64, ws;
+	if ((frames && !fr.reserve(npx * 2 * slab)) || !lab.reserve(npx * 4 * (labels_per_frame ? slab : 1)) || !o32.reserve(cells * 4 * 5) ||
+		!o64.reserve(cells * 8 * 8) || !ws.reserve(GEOMETRY_WORK_BYTES))
+		return -1;
+	hipStream_t st = default_stream();
+	if (!labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels, npx * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))
+		return -1;
+	int *d_count = o32.as<int>(), *d_bbox = d_count + cells;
+	long long *d_mom = o64.as<long long>(), *d_wgt = frames ? d_mom + 5 * cells : nullptr;
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int c = std::min(slab, nframes - o);
+		const size_t n = (size_t)c * K, at = (size_t)o * K;
+		if ((frames && !hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, npx * 2 * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
+			(labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels + (size_t)o * npx, npx * 4 * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
+			rir_region_geometry_device(lab.as<int>(), frames ? fr.as<unsigned short>() : nullptr, w, h, c, labels_per_frame, nregions, d_count, d_bbox, d_mom,
+									   d_wgt, ws.ptr, GEOMETRY_WORK_BYTES, st) != 0 ||
+			!hip_ok(hipMemcpyAsync(count + at, d_count, n * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+			!hip_ok(hipMemcpyAsync(bbox + at * 4, d_bbox, n * 16, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+			!hip_ok(hipMemcpyAsync(moments + at * 5, d_mom, n * 40, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+			(frames && !hip_ok(hipMemcpyAsync(weighted + at * 3, d_wgt, n * 24, hipMemcpyDeviceToHost, st), "hipMemcpyAsync")) ||
+			!hip_ok(wait_stream(st), "region_geometry"))
 			return -1;
 	}
 	return 0;

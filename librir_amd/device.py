@@ -10,9 +10,10 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
-from .signal_processing.rir_signal_processing import (PixelStats, RegionQuantiles, RegionStats, _pixel_quantiles_args,  # noqa: F401 (API)
-                                                      _pixel_stats_args, _polygon_map_args, _region_quantiles_args, _region_quantiles_percents,
-                                                      _region_stats_args, _temporal_median_args)
+from .signal_processing.rir_signal_processing import (PixelStats, RegionGeometry, RegionQuantiles, RegionStats,  # noqa: F401 (API)
+                                                      _pixel_quantiles_args, _pixel_stats_args, _polygon_map_args, _region_geometry_args,
+                                                      _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
+                                                      _temporal_median_args)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -115,6 +116,9 @@ _lib.rir_temporal_median_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_i
 _lib.rir_region_stats_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp] * 8 + [ct.c_size_t, _vp]
 _lib.rir_region_stats_workspace_bytes.argtypes = [ct.c_int] * 5
 _lib.rir_region_stats_workspace_bytes.restype = ct.c_size_t
+_lib.rir_region_geometry_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp] * 5 + [ct.c_size_t, _vp]
+_lib.rir_region_geometry_workspace_bytes.argtypes = [ct.c_int] * 6
+_lib.rir_region_geometry_workspace_bytes.restype = ct.c_size_t
 _lib.rir_region_quantiles_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp, ct.c_int, _vp, _vp, _vp, ct.c_size_t, _vp]
 _lib.rir_region_quantiles_workspace_bytes.argtypes = [ct.c_int] * 6
 _lib.rir_region_quantiles_workspace_bytes.restype = ct.c_size_t
@@ -773,6 +777,54 @@ def region_stats(frames, labels, nregions=None):
     out = _region_stats_empty(n, int(nregions), fr.device)
     if n:
         _region_stats_into(fr, lab, per_frame, int(nregions), out)
+    return out
+
+
+def _region_geometry_inputs(labels, frames, nregions):
+    """region_geometry's checks, in the order that needs no device for the shapes, dtypes and nregions; -> (labels [h][w] or [n][h][w],
+    frames [n][h][w] or None, n, h, w, per_frame)"""
+    if frames is not None and frames.dtype != torch.uint16:
+        raise RuntimeError("region_geometry: uint16 frames expected, not %s" % frames.dtype)
+    if labels.dtype != torch.int32:
+        raise RuntimeError("region_geometry: int32 labels expected, not %s" % labels.dtype)
+    n, h, w, per_frame = _region_geometry_args(tuple(labels.shape), None if frames is None else tuple(frames.shape), nregions)
+    if not labels.is_cuda or (frames is not None and (not frames.is_cuda or frames.device != labels.device)):
+        raise RuntimeError("region_geometry: labels%s on one CUDA device expected" % ("" if frames is None else " and frames"))
+    return labels.contiguous(), None if frames is None else _frames3(frames), n, h, w, per_frame
+
+
+def _region_geometry_into(lab, fr, n, per_frame, nregions, out):
+    """queue the geometry of lab ([h][w], or [n][h][w] with per_frame) weighted by fr ([n][h][w], or None) into out (a RegionGeometry of
+    contiguous tensors, [n][nregions] leading)"""
+    h, w = lab.shape[-2:]
+    need = _lib.rir_region_geometry_workspace_bytes(w, h, n, per_frame, nregions, int(fr is not None))
+    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=lab.device)
+    _check(_lib.rir_region_geometry_device(lab.data_ptr(), None if fr is None else fr.data_ptr(), w, h, n, per_frame, nregions, out.count.data_ptr(),
+                                           out.bbox.data_ptr(), out.moments.data_ptr(), None if fr is None else out.weighted.data_ptr(),
+                                           work.data_ptr(), work.numel() * 8, _stream()), "rir_region_geometry_device")
+
+
+def _region_geometry_empty(n, nregions, weighted, device):
+    return RegionGeometry(torch.empty((n, nregions), dtype=torch.int32, device=device), torch.empty((n, nregions, 4), dtype=torch.int32, device=device),
+                          torch.empty((n, nregions, 5), dtype=torch.int64, device=device),
+                          torch.empty((n, nregions, 3), dtype=torch.int64, device=device) if weighted else None)
+
+
+def region_geometry(labels, nregions=None, frames=None):
+    """Where the regions of the int32 label map ``labels`` (``(h, w)``, or ``(n, h, w)``) are and how they are spread, on the current stream
+    (C ABI ``rir_region_geometry_device``): a ``RegionGeometry`` of CUDA tensors, ``[n][nregions]`` leading - count, the bounding box
+    ``[..][4]`` = xmin, ymin, xmax, ymax (-1 for an empty region), the exact sums ``[..][5]`` of x, y, x^2, x*y, y^2 over the region and,
+    with ``frames`` (uint16 ``(n, h, w)`` or one ``(h, w)`` image; a shared ``(h, w)`` map then serves every frame, each with its own
+    row), the sums ``[..][3]`` of v, v*x, v*y; ``weighted`` is None without frames.  ``centroid()``, ``weighted_centroid()``,
+    ``covariance()`` and ``ellipse()`` of the result give the derived float64 quantities.  Labels outside [0, nregions) are ignored;
+    ``nregions=None`` takes ``labels.max() + 1`` (at least 1), which synchronises.  At most 32 768 rows and columns."""
+    lab, fr, n, h, w, per_frame = _region_geometry_inputs(labels, frames, nregions)
+    if nregions is None:
+        nregions = max(1, int(lab.max()) + 1)
+        _region_geometry_args(tuple(labels.shape), None if frames is None else tuple(frames.shape), nregions)
+    out = _region_geometry_empty(n, int(nregions), fr is not None, lab.device)
+    if n:
+        _region_geometry_into(lab, fr, n, per_frame, int(nregions), out)
     return out
 
 

@@ -276,6 +276,120 @@ def region_stats(images, labels, nregions=None):
     return out
 
 
+# ---- extension: per-region geometry ------------------------------------------------------------------------------------------------
+_sp.rir_region_geometry.argtypes = [ct.c_void_p, ct.c_void_p] + [ct.c_int] * 5 + [ct.c_void_p] * 4
+
+MAX_GEOMETRY_SIDE = 32768
+
+
+def _f64(a):
+    return a.astype(np.float64) if isinstance(a, np.ndarray) else a.double()
+
+
+def _stack_last(parts):
+    if isinstance(parts[0], np.ndarray):
+        return np.stack(parts, -1)
+    import torch
+
+    return torch.stack(parts, -1)
+
+
+class RegionGeometry(namedtuple("RegionGeometry", "count bbox moments weighted")):
+    """Geometry per (frame, region), ``[n][nregions]`` leading: count (int32), bbox ``[..][4]`` = xmin, ymin, xmax, ymax inclusive (int32;
+    -1 four times for an empty region), moments ``[..][5]`` = the exact sums of x, y, x^2, x*y, y^2 over the region's pixels (int64) and
+    weighted ``[..][3]`` = the exact sums of v, v*x, v*y (int64; None when no frames were given).  numpy arrays
+    (``signal_processing.region_geometry``) or CUDA tensors (``device.region_geometry``).
+
+    The helpers are float64 arithmetic on these exact integers (the integers are converted first: exact below 2^53): the centroids carry
+    one rounding of the division, and the rounding error of ``covariance`` - a difference of two terms of size up to w^2 + h^2 - is
+    bounded by about 4 * 2^-53 * (w^2 + h^2): 7.3e-10 at 1024x768, where 2.5e-11 was observed against rational arithmetic."""
+
+    __slots__ = ()
+
+    def _ratios(self, num, den):
+        """num[..][k] / den[..] in float64; NaN where den == 0"""
+        num, den = _f64(num), _f64(den)[..., None]
+        if isinstance(num, np.ndarray):
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return np.where(den == 0, np.nan, num / den)
+        return (num / den).masked_fill(den == 0, float("nan"))
+
+    def centroid(self):
+        """float64 ``[..][2]`` = (sum x / count, sum y / count); NaN where count == 0"""
+        return self._ratios(self.moments[..., 0:2], self.count)
+
+    def weighted_centroid(self):
+        """float64 ``[..][2]`` = (sum v*x / sum v, sum v*y / sum v); NaN where sum v == 0"""
+        if self.weighted is None:
+            raise ValueError("weighted_centroid: the geometry was computed without frames")
+        return self._ratios(self.weighted[..., 1:3], self.weighted[..., 0])
+
+    def covariance(self):
+        """float64 ``[..][3]`` = (cxx, cxy, cyy) = (sum x^2 / c - mx^2, sum x*y / c - mx * my, sum y^2 / c - my^2), the population covariance
+        of the pixel coordinates; NaN where count == 0"""
+        m = self._ratios(self.moments, self.count)
+        mx, my = m[..., 0], m[..., 1]
+        return _stack_last([m[..., 2] - mx * mx, m[..., 3] - mx * my, m[..., 4] - my * my])
+
+    def ellipse(self):
+        """float64 ``[..][3]`` = (major, minor, angle) of the ellipse with the region's covariance: the full axis lengths 4 * sqrt(l+) and
+        4 * sqrt(l-), l+- = (cxx + cyy) / 2 +- sqrt(((cxx - cyy) / 2)^2 + cxy^2) clamped at 0, and the angle of the major axis from +x
+        towards +y, atan2(2 cxy, cxx - cyy) / 2 in (-pi/2, pi/2] (0 for a single pixel or a disc); NaN where count == 0"""
+        c = self.covariance()
+        cxx, cxy, cyy = c[..., 0], c[..., 1], c[..., 2]
+        half, diff = (cxx + cyy) / 2, (cxx - cyy) / 2
+        if isinstance(c, np.ndarray):
+            root = np.sqrt(diff * diff + cxy * cxy)
+            return np.stack([4 * np.sqrt(np.maximum(half + root, 0.0)), 4 * np.sqrt(np.maximum(half - root, 0.0)),
+                             0.5 * np.arctan2(2 * cxy, cxx - cyy)], -1)
+        import torch
+
+        root = (diff * diff + cxy * cxy).sqrt()
+        return torch.stack([4 * (half + root).clamp_min(0.0).sqrt(), 4 * (half - root).clamp_min(0.0).sqrt(),
+                            0.5 * torch.atan2(2 * cxy, cxx - cyy)], -1)
+
+
+def _region_geometry_args(labels_shape, frames_shape, nregions, what="region_geometry"):
+    """the shapes of a region_geometry call, checked without a device; -> (n, h, w, labels_per_frame).  frames_shape None: no weights, and
+    the labels alone give n.  nregions None is left to the caller."""
+    labels_shape = tuple(labels_shape)
+    if frames_shape is None:
+        if len(labels_shape) not in (2, 3):
+            raise ValueError("%s: labels (h, w) or (n, h, w) expected, not %s" % (what, labels_shape))
+        frames_shape = labels_shape
+    n, h, w, per_frame = _region_stats_args(tuple(frames_shape), labels_shape, nregions, what)
+    if h > MAX_GEOMETRY_SIDE or w > MAX_GEOMETRY_SIDE:
+        raise ValueError("%s: at most %d rows and columns expected" % (what, MAX_GEOMETRY_SIDE))
+    return n, h, w, per_frame
+
+
+def region_geometry(labels, nregions=None, frames=None):
+    """Extension: where the regions of the int32 label map ``labels`` (``(h, w)``, or ``(n, h, w)``) are and how they are spread - a
+    ``RegionGeometry`` of numpy arrays (``rir_region_geometry``): count, bounding box, the exact first and second moments of the pixel
+    coordinates and, with ``frames`` (uint16 ``(n, h, w)`` or one ``(h, w)`` image; a shared ``(h, w)`` map then serves every image), the
+    sums weighted by the pixel values; ``weighted`` is None without frames.  Labels outside [0, nregions) are ignored; ``nregions=None``
+    takes labels.max() + 1 (at least 1).  ``ValueError`` on bad shapes or ``nregions``, ``RuntimeError`` on other dtypes and when the
+    library fails."""
+    lab = np.ascontiguousarray(labels)
+    img = None if frames is None else np.ascontiguousarray(frames)
+    if img is not None and img.dtype != np.uint16:
+        raise RuntimeError("region_geometry: uint16 frames expected, not %s" % img.dtype)
+    if lab.dtype != np.int32:
+        raise RuntimeError("region_geometry: int32 labels expected, not %s" % lab.dtype)
+    shapes = (lab.shape, None if img is None else img.shape)
+    n, h, w, per_frame = _region_geometry_args(*shapes, nregions)
+    if nregions is None:
+        nregions = max(1, int(lab.max()) + 1 if lab.size else 1)
+        _region_geometry_args(*shapes, nregions)
+    k = int(nregions)
+    out = RegionGeometry(np.empty((n, k), np.int32), np.empty((n, k, 4), np.int32), np.empty((n, k, 5), np.int64),
+                         None if img is None else np.empty((n, k, 3), np.int64))
+    if n and _sp.rir_region_geometry(lab.ctypes.data, None if img is None else img.ctypes.data, w, h, n, per_frame, k, out.count.ctypes.data,
+                                     out.bbox.ctypes.data, out.moments.ctypes.data, None if img is None else out.weighted.ctypes.data) < 0:
+        raise RuntimeError("An error occured while calling 'region_geometry': " + (last_error() or ""))
+    return out
+
+
 # ---- extension: per-region quantiles ---------------------------------------------------------------------------------------------
 _sp.rir_region_quantiles.argtypes = [ct.c_void_p, ct.c_void_p] + [ct.c_int] * 5 + [ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_void_p]
 

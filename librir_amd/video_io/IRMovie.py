@@ -370,6 +370,39 @@ class IRMovie(object):
             _region_stats_into(fr, lab, 0, int(nregions), type(out)(*(t[k0:k0 + len(sel)] for t in out)))
         return out
 
+    def region_geometry(self, labels, selection=slice(None), nregions=None):
+        """Geometry of the regions of one int32 label map ``labels`` (h, w), numpy or CUDA, weighted by the images of ``selection`` - what
+        ``librir_amd.device.region_geometry(labels, nregions, frames=movie[selection])`` gives (read-back filters applied): a
+        ``RegionGeometry`` of CUDA tensors ``[len(selection)][nregions]`` leading; count, bbox and moments repeat for every image, the
+        weighted sums follow the recording.  Labels, selection, ``nregions`` and the pieces the recording is read in are those of
+        ``region_stats``."""
+        import torch
+
+        from ..device import _region_geometry_empty, _region_geometry_inputs, _region_geometry_into
+
+        h, w = self.image_size
+        if isinstance(labels, np.ndarray):
+            if labels.dtype != np.int32:
+                raise RuntimeError("region_geometry: int32 labels expected, not %s" % labels.dtype)
+            labels = torch.from_numpy(np.ascontiguousarray(labels)).to(torch.device("cuda", torch.cuda.current_device()))
+        if labels.dim() != 2:
+            raise ValueError("region_geometry: one label map (h, w) expected, not shape %s" % (tuple(labels.shape),))
+        probe = torch.empty((0, h, w), dtype=torch.uint16, device=labels.device if labels.is_cuda else "cpu")
+        lab, _, _, _, _, _ = _region_geometry_inputs(labels, probe, nregions)
+        if nregions is None:
+            nregions = max(1, int(lab.max()) + 1)
+            _region_geometry_inputs(labels, probe, nregions)
+        positions = self._stats_positions(selection, "region_geometry")
+        out = _region_geometry_empty(len(positions), int(nregions), True, lab.device)
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=lab.device)
+        for k0 in range(0, len(positions), per_piece):
+            sel = positions[k0:k0 + per_piece]
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            _region_geometry_into(lab, fr, len(sel), 0, int(nregions), type(out)(*(t[k0:k0 + len(sel)] for t in out)))
+        return out
+
     def region_quantiles(self, labels, percents, selection=slice(None), nregions=None):
         """Quantiles of the images of ``selection`` over the regions of one int32 label map ``labels`` (h, w), numpy or CUDA, at
         ``percents`` (a float or 1..8 floats in [0, 1]) - what ``librir_amd.device.region_quantiles`` over the images ``movie[selection]``
@@ -506,10 +539,22 @@ class IRMovie(object):
         RegionStats or None)``: the tracks, with ``tracks`` the int32 track map ``[len(selection)][h][w]``, and with ``stats`` the
         ``region_stats`` of every image over its track map, ``[len(selection)][ntracks]`` - the time trace of every hot spot (``count`` is
         its area in each image).  The recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of images (twice with ``stats``), but
-        the label stack of the whole selection stays on the device: 4 bytes a pixel and image."""
+        the label stack of the whole selection stays on the device: 4 bytes a pixel and image.  ``track_hot_spots_geometry`` adds the
+        box, centroid and extent of every hot spot."""
+        return self._track_hot_spots(threshold, selection, table_entries, stats, False)
+
+    def track_hot_spots_geometry(self, threshold, selection=slice(None), table_entries=None, stats=True):
+        """``track_hot_spots`` with a third element: -> ``(ComponentTracks, RegionStats or None, RegionGeometry)``, the geometry of every image
+        over its track map (``librir_amd.device.region_geometry``), ``[len(selection)][ntracks]`` leading and weighted by the images - the
+        box, centroid and extent of every hot spot over time; its ``count`` is that of the statistics.  It is computed in the same second
+        pass over the recording as the statistics (a pass of its own with ``stats=False``)."""
+        return self._track_hot_spots(threshold, selection, table_entries, stats, True)
+
+    def _track_hot_spots(self, threshold, selection, table_entries, stats, geometry):
         import torch
 
-        from ..device import _label_images_into, _region_stats_empty, _region_stats_into, _track_args, track_components
+        from ..device import (_label_images_into, _region_geometry_empty, _region_geometry_into, _region_stats_empty, _region_stats_into,
+                              _track_args, track_components)
 
         h, w = self.image_size
         positions = self._stats_positions(selection, "track_hot_spots")
@@ -546,13 +591,17 @@ class IRMovie(object):
             _label_images_into(hot, 0, stack[k0:k1], xy[:k1 - k0], area[:k1 - k0], counts[k0:k1])
         nlabels = max(1, int(counts.max())) if n else 1
         tracks = track_components(stack, counts, nlabels, table_entries, out=stack)
-        if not stats:
+        if not stats and not geometry:
             return tracks, None
         ntracks = int(tracks.ntracks)
-        out = _region_stats_empty(n, ntracks, device)
+        out = _region_stats_empty(n, ntracks, device) if stats else None
+        geo = _region_geometry_empty(n, ntracks, True, device) if geometry else None
         for k0, k1, fr in pieces():
-            _region_stats_into(fr, stack[k0:k1], 1, ntracks, type(out)(*(t[k0:k1] for t in out)))
-        return tracks, out
+            if stats:
+                _region_stats_into(fr, stack[k0:k1], 1, ntracks, type(out)(*(t[k0:k1] for t in out)))
+            if geometry:
+                _region_geometry_into(stack[k0:k1], fr, k1 - k0, 1, ntracks, type(geo)(*(t[k0:k1] for t in geo)))
+        return (tracks, out, geo) if geometry else (tracks, out)
 
     def _stats_positions(self, selection, what="region_stats"):
         """the positions of an int or a slice with a positive step, as to_tensor takes them"""
