@@ -18,34 +18,18 @@
 //
 // Every combination is a 32-bit integer add (ds_add_u32 / global_atomic_add), so the result does not depend on the order the workgroups
 // run in; the only floating-point operation is the rank, qt_rank().
-#include <algorithm>
-
 #include "quantile_kernels.h"
 #include "quantile_rank.h"
+#include "region_walk.h"
 
 namespace rir
 {
-	constexpr int QT_BLOCK = 256;
-	constexpr int QT_PX = 8;					  // pixels per thread and step
-	constexpr int QT_STEP = QT_BLOCK * QT_PX;	  // pixels per workgroup and step
-	constexpr int QT_ITEM = 16384;				  // pixels per work item
-	constexpr int QT_BLOCKS_PER_CU = 8;			  // counting grid: at most this many workgroups per CU
-	constexpr int QT_LDS_BYTES = 160 * 1024;	  // LDS per CU
+	constexpr int QT_BLOCK = WALK_BLOCK, QT_PX = WALK_PX, QT_STEP = WALK_STEP, QT_ITEM = WALK_ITEM; // the items and steps of region_walk.h
 	constexpr int QT_SCAN_GRID = 65536;			  // select / finish: workgroups at most (grid-stride)
 	constexpr int QT_WAVES = QT_BLOCK / 64;		  // select / finish: waves per workgroup
 	constexpr unsigned QT_NO_CODE = 0xFFFFu;	  // codes: no low-byte histogram for this percent
-	static_assert(QT_ITEM % QT_STEP == 0, "an item is whole steps");
-	static_assert(QUANTILE_LDS_MAX * 1024 <= QT_LDS_BYTES, "the LDS form fits one CU");
+	static_assert(QUANTILE_LDS_MAX * 1024 <= WALK_LDS_BYTES, "the LDS form fits one CU");
 	static_assert(QUANTILE_MAX_PERCENTS == 8, "codes are 8 x 16 bits per region");
-
-	template <bool LDS>
-	__device__ __forceinline__ void qt_add(uint32_t *p, uint32_t v)
-	{
-		if constexpr (LDS)
-			__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-		else
-			__hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	}
 
 	// A pixel's counter within its frame, -1 for none.  High pass: label * 256 + (v >> 8).  Low pass: the codes of the thread's current label
 	// are kept in registers (8 x 16 bits, read again where the label changes); the slot whose code is the pixel's high byte counts v & 255.
@@ -104,9 +88,9 @@ namespace rir
 		if (r.key >= 0 && r.cnt != 0)
 		{
 			if (r.key < lds_bins)
-				qt_add<true>(lds + r.key, r.cnt);
+				walk_add<WALK_WG>(lds + r.key, r.cnt);
 			else
-				qt_add<false>(hist + r.key, r.cnt);
+				walk_add<WALK_AGENT>(hist + r.key, r.cnt);
 		}
 		r.key = next;
 		r.cnt = 0;
@@ -147,7 +131,7 @@ namespace rir
 						const uint32_t c = qt_lds[i];
 						if (c == 0)
 							continue;
-						qt_add<false>(hf + i, c);
+						walk_add<WALK_AGENT>(hf + i, c);
 						qt_lds[i] = 0;
 					}
 					__syncthreads();
@@ -165,31 +149,12 @@ namespace rir
 			for (int64_t s = lo; s < hi; s += QT_STEP)
 			{
 				const int64_t p = s + threadIdx.x * QT_PX;
-				uint32_t v[QT_PX];
+				unsigned v[QT_PX];
 				int lab[QT_PX];
-				if (vec && p + QT_PX <= hi)
-				{
-					const uint4 x = *reinterpret_cast<const uint4 *>(f + p);
-					const int4 a = *reinterpret_cast<const int4 *>(l + p), b = *reinterpret_cast<const int4 *>(l + p + 4);
-					const uint32_t d[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-					for (int j = 0; j < 4; ++j)
-					{
-						v[2 * j] = d[j] & 0xFFFFu;
-						v[2 * j + 1] = d[j] >> 16;
-					}
-					lab[0] = a.x, lab[1] = a.y, lab[2] = a.z, lab[3] = a.w, lab[4] = b.x, lab[5] = b.y, lab[6] = b.z, lab[7] = b.w;
-				}
+				if (p + QT_PX <= hi) // a pixel past the end gets label -1, no region: it counts nowhere
+					load8<false, true>(f, l, p, hi, vec, -1, v, lab);
 				else
-				{
-#pragma unroll
-					for (int j = 0; j < QT_PX; ++j)
-					{
-						const bool in = p + j < hi;
-						v[j] = in ? f[p + j] : 0u;
-						lab[j] = in ? l[p + j] : -1; // no region: counts nowhere
-					}
-				}
+					load8<true, true>(f, l, p, hi, vec, -1, v, lab);
 				int idx[QT_PX];
 				bool same = true;
 #pragma unroll
@@ -338,13 +303,10 @@ namespace rir
 		void launch_count(const uint16_t *frames, const int32_t *labels, int64_t npx, int n, int per_frame, int nregions, int nq, int cus,
 						  const uint2 *codes, uint32_t *hist, hipStream_t st)
 		{
-			const int per_item_frame = (int)((npx + QT_ITEM - 1) / QT_ITEM);
-			const int64_t items = (int64_t)n * per_item_frame;
-			const int vec = npx % QT_PX == 0 && (uintptr_t)frames % 16 == 0 && (uintptr_t)labels % 16 == 0;
 			const size_t lds = (size_t)std::min<int64_t>((int64_t)nregions * (LOW ? nq : 1), QUANTILE_LDS_MAX) * 1024;
-			const int per_cu = (int)std::max<size_t>(1, std::min<size_t>(QT_BLOCKS_PER_CU, QT_LDS_BYTES / lds));
-			const unsigned grid = (unsigned)std::min<int64_t>(items, (int64_t)cus * per_cu);
-			region_quantiles_count<LOW><<<grid, QT_BLOCK, lds, st>>>(frames, labels, npx, per_frame, nregions, nq, items, per_item_frame, vec, codes, hist);
+			const WalkShape s = walk_launch_shape(npx, n, lds, cus);
+			region_quantiles_count<LOW><<<s.grid, QT_BLOCK, lds, st>>>(frames, labels, npx, per_frame, nregions, nq, s.items, s.per_item_frame,
+																	   walk_vec(npx, labels, frames), codes, hist);
 		}
 	} // namespace
 
@@ -357,10 +319,8 @@ namespace rir
 		const size_t frame_bytes = region_quantiles_frame_bytes(nregions, npercents);
 		if (work_bytes < frame_bytes)
 			return hipErrorInvalidValue;
-		int dev = 0, cus = 0;
-		hipError_t e = hipGetDevice(&dev);
-		if (e == hipSuccess)
-			e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+		int cus = 0;
+		hipError_t e = cu_count(&cus);
 		if (e != hipSuccess)
 			return e;
 		const int group = (int)std::min<size_t>((size_t)n, work_bytes / frame_bytes);

@@ -10,6 +10,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 
 #include "filter_kernels.h"
@@ -30,6 +31,30 @@ namespace
 {
 	// the caller's stream, taken literally: NULL is HIP's null (legacy default) stream
 	hipStream_t as_stream(void *s) { return (hipStream_t)s; }
+
+	struct Span // a byte range of device memory; null or zero bytes: absent
+	{
+		const void *p;
+		size_t bytes;
+	};
+
+	// Whether an output overlaps an input or an earlier output; absent spans overlap nothing.
+	bool outputs_overlap(std::initializer_list<Span> in, std::initializer_list<Span> out)
+	{
+		const auto hit = [](const Span &a, const Span &b) {
+			return a.p && b.p && a.bytes && b.bytes && (uintptr_t)a.p < (uintptr_t)b.p + b.bytes && (uintptr_t)b.p < (uintptr_t)a.p + a.bytes;
+		};
+		for (const Span *o = out.begin(); o != out.end(); ++o)
+		{
+			for (const Span &a : in)
+				if (hit(*o, a))
+					return true;
+			for (const Span *e = out.begin(); e != o; ++e)
+				if (hit(*o, *e))
+					return true;
+		}
+		return false;
+	}
 
 	int strategy_from_string(const char *s)
 	{ // signal_processing.cpp:20-41: NULL, "" and "noborder" leave border pixels untouched
@@ -697,25 +722,12 @@ RIR_EXPORT int rir_region_stats_device(const unsigned short *d_frames, const int
 		log_error("rir_region_stats_device: the workspace must be 8-byte aligned and hold rir_region_stats_workspace_bytes() bytes");
 		return -1;
 	}
-	const struct
+	if (outputs_overlap({{d_frames, npx * nframes * 2}, {d_labels, npx * (labels_per_frame ? nframes : 1) * 4}},
+						{{d_count, cells * 4}, {d_sum, cells * 8}, {d_sumsq, cells * 8}, {d_min, cells * 4}, {d_max, cells * 4}, {d_argmin, cells * 4},
+						 {d_argmax, cells * 4}, {d_work, need}}))
 	{
-		uintptr_t p;
-		size_t bytes;
-	} in[2] = {{(uintptr_t)d_frames, npx * nframes * 2}, {(uintptr_t)d_labels, npx * (labels_per_frame ? nframes : 1) * 4}},
-	  out[8] = {{(uintptr_t)d_count, cells * 4}, {(uintptr_t)d_sum, cells * 8}, {(uintptr_t)d_sumsq, cells * 8}, {(uintptr_t)d_min, cells * 4},
-				{(uintptr_t)d_max, cells * 4},	 {(uintptr_t)d_argmin, cells * 4}, {(uintptr_t)d_argmax, cells * 4}, {(uintptr_t)d_work, need}};
-	for (int i = 0; i < 8; ++i)
-	{
-		bool overlap = false;
-		for (const auto &a : in)
-			overlap |= out[i].p < a.p + a.bytes && a.p < out[i].p + out[i].bytes;
-		for (int j = 0; j < i; ++j)
-			overlap |= out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
-		if (overlap)
-		{
-			log_error("rir_region_stats_device: an output or the workspace overlaps an input or another output");
-			return -1;
-		}
+		log_error("rir_region_stats_device: an output or the workspace overlaps an input or another output");
+		return -1;
 	}
 	return hip_ok(launch_region_stats(d_frames, d_labels, (int64_t)npx, nframes, labels_per_frame, nregions, d_count, (int64_t *)d_sum, (int64_t *)d_sumsq,
 									  d_min, d_max, d_argmin, d_argmax, d_work, as_stream(stream)),
@@ -767,25 +779,11 @@ RIR_EXPORT int rir_region_geometry_device(const int *d_labels, const unsigned sh
 		return -1;
 	}
 	const size_t npx = (size_t)w * h, cells = (size_t)nframes * nregions;
-	const struct
+	if (outputs_overlap({{d_labels, npx * (labels_per_frame ? nframes : 1) * 4}, {d_frames, npx * nframes * 2}},
+						{{d_count, cells * 4}, {d_bbox, cells * 16}, {d_moments, cells * 40}, {d_work, GEOMETRY_WORK_BYTES}, {d_weighted, cells * 24}}))
 	{
-		uintptr_t p;
-		size_t bytes;
-	} in[2] = {{(uintptr_t)d_labels, npx * (labels_per_frame ? nframes : 1) * 4}, {(uintptr_t)d_frames, d_frames ? npx * nframes * 2 : 0}},
-	  out[5] = {{(uintptr_t)d_count, cells * 4}, {(uintptr_t)d_bbox, cells * 16}, {(uintptr_t)d_moments, cells * 40},
-				{(uintptr_t)d_work, GEOMETRY_WORK_BYTES}, {(uintptr_t)d_weighted, d_weighted ? cells * 24 : 0}};
-	for (int i = 0; i < 5; ++i)
-	{
-		bool overlap = false;
-		for (const auto &a : in)
-			overlap |= out[i].p < a.p + a.bytes && a.p < out[i].p + out[i].bytes;
-		for (int j = 0; j < i; ++j)
-			overlap |= out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
-		if (overlap)
-		{
-			log_error("rir_region_geometry_device: an output or the workspace overlaps an input or another output");
-			return -1;
-		}
+		log_error("rir_region_geometry_device: an output or the workspace overlaps an input or another output");
+		return -1;
 	}
 	return hip_ok(launch_region_geometry(d_labels, d_frames, w, h, nframes, labels_per_frame, nregions, d_count, d_bbox, (int64_t *)d_moments,
 										 (int64_t *)d_weighted, as_stream(stream)),
@@ -851,24 +849,11 @@ RIR_EXPORT int rir_region_quantiles_device(const unsigned short *d_frames, const
 		return -1;
 	}
 	const size_t used = B * std::min<size_t>((size_t)nframes, work_bytes / B);
-	const struct
+	if (outputs_overlap({{d_frames, npx * nframes * 2}, {d_labels, npx * (labels_per_frame ? nframes : 1) * 4}},
+						{{d_count, cells * 4}, {d_values, cells * npercents * 4}, {d_work, used}}))
 	{
-		uintptr_t p;
-		size_t bytes;
-	} in[2] = {{(uintptr_t)d_frames, npx * nframes * 2}, {(uintptr_t)d_labels, npx * (labels_per_frame ? nframes : 1) * 4}},
-	  out[3] = {{(uintptr_t)d_count, cells * 4}, {(uintptr_t)d_values, cells * npercents * 4}, {(uintptr_t)d_work, used}};
-	for (int i = 0; i < 3; ++i)
-	{
-		bool overlap = false;
-		for (const auto &a : in)
-			overlap |= out[i].p < a.p + a.bytes && a.p < out[i].p + out[i].bytes;
-		for (int j = 0; j < i; ++j)
-			overlap |= out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
-		if (overlap)
-		{
-			log_error("rir_region_quantiles_device: an output or the workspace overlaps an input or another output");
-			return -1;
-		}
+		log_error("rir_region_quantiles_device: an output or the workspace overlaps an input or another output");
+		return -1;
 	}
 	return hip_ok(launch_region_quantiles(d_frames, d_labels, (int64_t)npx, nframes, labels_per_frame, nregions, pc, npercents, d_count, d_values, d_work,
 										  work_bytes, as_stream(stream)),
@@ -922,25 +907,11 @@ RIR_EXPORT int rir_pixel_stats_device(const unsigned short *d_frames, int w, int
 		log_error("rir_pixel_stats_device: the workspace must be 8-byte aligned and hold rir_pixel_stats_workspace_bytes() bytes");
 		return -1;
 	}
-	const struct
+	if (outputs_overlap({{d_frames, npx * nframes * 2}}, {{d_sum, npx * 8}, {d_sumsq, npx * 8}, {d_min, npx * 4}, {d_max, npx * 4}, {d_argmin, npx * 4},
+															{d_argmax, npx * 4}, {d_work, need}})) // the group not asked for is null: absent
 	{
-		uintptr_t p;
-		size_t bytes;
-	} in = {(uintptr_t)d_frames, npx * nframes * 2}, out[7] = {{(uintptr_t)d_sum, npx * 8},	  {(uintptr_t)d_sumsq, npx * 8}, {(uintptr_t)d_min, npx * 4},
-															   {(uintptr_t)d_max, npx * 4},	  {(uintptr_t)d_argmin, npx * 4}, {(uintptr_t)d_argmax, npx * 4},
-															   {(uintptr_t)d_work, need}};
-	for (int i = 0; i < 7; ++i)
-	{
-		if (!out[i].p)
-			continue;
-		bool overlap = out[i].p < in.p + in.bytes && in.p < out[i].p + out[i].bytes;
-		for (int j = 0; j < i; ++j)
-			overlap |= out[j].p && out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
-		if (overlap)
-		{
-			log_error("rir_pixel_stats_device: an output or the workspace overlaps the input or another output");
-			return -1;
-		}
+		log_error("rir_pixel_stats_device: an output or the workspace overlaps the input or another output");
+		return -1;
 	}
 	return hip_ok(launch_pixel_stats(d_frames, (int64_t)npx, nframes, t0, accumulate, (int64_t *)d_sum, (int64_t *)d_sumsq, d_min, d_max, d_argmin,
 									 d_argmax, d_work, as_stream(stream)),
@@ -970,10 +941,7 @@ namespace
 		}
 		return true;
 	}
-	bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-	{
-		return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
-	}
+	bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) { return outputs_overlap({{a, na}}, {{b, nb}}); }
 } // namespace
 
 RIR_EXPORT int rir_pixel_quantiles_passes(void) { return PIXEL_QUANTILE_PASSES; }
@@ -1131,27 +1099,13 @@ RIR_EXPORT int rir_track_components_device(const int *d_labels, const int *d_cou
 		return -1;
 	}
 	const size_t stack = npx * nframes * 4, table = (size_t)table_entries * 4;
-	const struct
+	// d_dst == d_labels: the labels are left out of the inputs, their range is checked against everything else as the last output, d_dst
+	if (outputs_overlap({{d_dst == d_labels ? nullptr : d_labels, stack}, {d_counts, (size_t)nframes * 4}},
+						{{d_track_of, nodes * 4}, {d_info, 8}, {d_first_frame, table}, {d_last_frame, table}, {d_first_label, table},
+						 {d_components, table}, {d_work, need}, {d_dst, stack}}))
 	{
-		uintptr_t p;
-		size_t bytes;
-	} in[2] = {{(uintptr_t)d_labels, stack}, {(uintptr_t)d_counts, d_counts ? (size_t)nframes * 4 : 0}},
-	  out[8] = {{(uintptr_t)d_track_of, nodes * 4},	  {(uintptr_t)d_info, 8},			   {(uintptr_t)d_first_frame, table}, {(uintptr_t)d_last_frame, table},
-				{(uintptr_t)d_first_label, table}, {(uintptr_t)d_components, table}, {(uintptr_t)d_work, need},		  {(uintptr_t)d_dst, d_dst ? stack : 0}};
-	for (int i = 0; i < 8; ++i)
-	{
-		if (out[i].bytes == 0)
-			continue;
-		bool overlap = false;
-		for (int j = 0; j < 2; ++j)
-			overlap |= in[j].bytes != 0 && !(i == 7 && j == 0 && d_dst == d_labels) && out[i].p < in[j].p + in[j].bytes && in[j].p < out[i].p + out[i].bytes;
-		for (int j = 0; j < i; ++j)
-			overlap |= out[j].bytes != 0 && out[i].p < out[j].p + out[j].bytes && out[j].p < out[i].p + out[i].bytes;
-		if (overlap)
-		{
-			log_error("rir_track_components_device: an output or the workspace overlaps an input or another output (only d_dst == d_labels may)");
-			return -1;
-		}
+		log_error("rir_track_components_device: an output or the workspace overlaps an input or another output (only d_dst == d_labels may)");
+		return -1;
 	}
 	return hip_ok(launch_track_components(d_labels, d_counts, w, h, nframes, nlabels, d_track_of, d_info, d_first_frame, d_last_frame, d_first_label,
 										  d_components, table_entries, d_dst, d_work, as_stream(stream)),
@@ -1191,20 +1145,8 @@ RIR_EXPORT int rir_polygon_map_device(const double *d_xy, const int *d_npts, con
 		return -1;
 	}
 	const size_t polys = (size_t)npoly * (sets_per_map ? nmaps : 1);
-	const struct
-	{
-		uintptr_t p;
-		size_t bytes;
-	} in[4] = {{(uintptr_t)d_xy, polys * max_pts * 16},
-			   {(uintptr_t)d_npts, polys * 4},
-			   {(uintptr_t)d_values, d_values ? (size_t)npoly * 4 : 0},
-			   {(uintptr_t)d_shifts, d_shifts ? (size_t)nmaps * 16 : 0}},
-	  out[2] = {{(uintptr_t)d_dst, (size_t)w * h * nmaps * 4}, {(uintptr_t)d_work, need}};
-	bool overlap = out[0].p < out[1].p + out[1].bytes && out[1].p < out[0].p + out[0].bytes;
-	for (const auto &o : out)
-		for (const auto &a : in)
-			overlap |= a.bytes != 0 && o.p < a.p + a.bytes && a.p < o.p + o.bytes;
-	if (overlap)
+	if (outputs_overlap({{d_xy, polys * max_pts * 16}, {d_npts, polys * 4}, {d_values, (size_t)npoly * 4}, {d_shifts, (size_t)nmaps * 16}},
+						{{d_dst, (size_t)w * h * nmaps * 4}, {d_work, need}}))
 	{
 		log_error("rir_polygon_map_device: the maps or the workspace overlap an input or each other");
 		return -1;

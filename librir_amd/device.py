@@ -751,11 +751,23 @@ def _region_inputs(frames, labels, nregions, what="region_stats", args=_region_s
     return _frames3(frames), labels.contiguous(), n, h, w, per_frame
 
 
+def _nregions(nregions, lab, check):
+    """nregions as an int; for None, lab.max() + 1 (at least 1, synchronises), which check(nregions) sees again"""
+    if nregions is None:
+        nregions = max(1, int(lab.max()) + 1)
+        check(nregions)
+    return int(nregions)
+
+
+def _workspace(need, device):
+    """an 8-byte aligned workspace of at least `need` bytes on `device`: work.data_ptr(), work.numel() * 8"""
+    return torch.empty(need // 8 + 1, dtype=torch.int64, device=device)
+
+
 def _region_stats_into(fr, lab, per_frame, nregions, out):
     """queue the statistics of fr [n][h][w] over lab into out (a RegionStats of contiguous [n][nregions] tensors)"""
     n, h, w = fr.shape
-    need = _lib.rir_region_stats_workspace_bytes(w, h, n, per_frame, nregions)
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    work = _workspace(_lib.rir_region_stats_workspace_bytes(w, h, n, per_frame, nregions), fr.device)
     _check(_lib.rir_region_stats_device(fr.data_ptr(), lab.data_ptr(), w, h, n, per_frame, nregions, *(t.data_ptr() for t in out), work.data_ptr(),
                                         work.numel() * 8, _stream()), "rir_region_stats_device")
 
@@ -771,12 +783,10 @@ def region_stats(frames, labels, nregions=None):
     ``RegionStats`` of CUDA tensors ``[n][nregions]`` - count, exact sum and sum of squares, min, max and the lowest flat index y * w + x of
     each.  Labels outside [0, nregions) are ignored; ``nregions=None`` takes ``labels.max() + 1`` (at least 1), which synchronises."""
     fr, lab, n, h, w, per_frame = _region_inputs(frames, labels, nregions)
-    if nregions is None:
-        nregions = max(1, int(lab.max()) + 1)
-        _region_stats_args(tuple(frames.shape), tuple(labels.shape), nregions)
-    out = _region_stats_empty(n, int(nregions), fr.device)
+    nregions = _nregions(nregions, lab, lambda k: _region_stats_args(tuple(frames.shape), tuple(labels.shape), k))
+    out = _region_stats_empty(n, nregions, fr.device)
     if n:
-        _region_stats_into(fr, lab, per_frame, int(nregions), out)
+        _region_stats_into(fr, lab, per_frame, nregions, out)
     return out
 
 
@@ -797,8 +807,7 @@ def _region_geometry_into(lab, fr, n, per_frame, nregions, out):
     """queue the geometry of lab ([h][w], or [n][h][w] with per_frame) weighted by fr ([n][h][w], or None) into out (a RegionGeometry of
     contiguous tensors, [n][nregions] leading)"""
     h, w = lab.shape[-2:]
-    need = _lib.rir_region_geometry_workspace_bytes(w, h, n, per_frame, nregions, int(fr is not None))
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=lab.device)
+    work = _workspace(_lib.rir_region_geometry_workspace_bytes(w, h, n, per_frame, nregions, int(fr is not None)), lab.device)
     _check(_lib.rir_region_geometry_device(lab.data_ptr(), None if fr is None else fr.data_ptr(), w, h, n, per_frame, nregions, out.count.data_ptr(),
                                            out.bbox.data_ptr(), out.moments.data_ptr(), None if fr is None else out.weighted.data_ptr(),
                                            work.data_ptr(), work.numel() * 8, _stream()), "rir_region_geometry_device")
@@ -819,20 +828,17 @@ def region_geometry(labels, nregions=None, frames=None):
     ``covariance()`` and ``ellipse()`` of the result give the derived float64 quantities.  Labels outside [0, nregions) are ignored;
     ``nregions=None`` takes ``labels.max() + 1`` (at least 1), which synchronises.  At most 32 768 rows and columns."""
     lab, fr, n, h, w, per_frame = _region_geometry_inputs(labels, frames, nregions)
-    if nregions is None:
-        nregions = max(1, int(lab.max()) + 1)
-        _region_geometry_args(tuple(labels.shape), None if frames is None else tuple(frames.shape), nregions)
-    out = _region_geometry_empty(n, int(nregions), fr is not None, lab.device)
+    nregions = _nregions(nregions, lab, lambda k: _region_geometry_args(tuple(labels.shape), None if frames is None else tuple(frames.shape), k))
+    out = _region_geometry_empty(n, nregions, fr is not None, lab.device)
     if n:
-        _region_geometry_into(lab, fr, n, per_frame, int(nregions), out)
+        _region_geometry_into(lab, fr, n, per_frame, nregions, out)
     return out
 
 
 def _region_quantiles_into(fr, lab, per_frame, nregions, percents, out):
     """queue the quantiles of fr [n][h][w] over lab at percents (float32 numpy) into out (a RegionQuantiles of contiguous tensors)"""
     n, h, w = fr.shape
-    need = _lib.rir_region_quantiles_workspace_bytes(w, h, n, per_frame, nregions, percents.size)
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    work = _workspace(_lib.rir_region_quantiles_workspace_bytes(w, h, n, per_frame, nregions, percents.size), fr.device)
     _check(_lib.rir_region_quantiles_device(fr.data_ptr(), lab.data_ptr(), w, h, n, per_frame, nregions, percents.ctypes.data, percents.size,
                                             out.count.data_ptr(), out.values.data_ptr(), work.data_ptr(), work.numel() * 8, _stream()),
            "rir_region_quantiles_device")
@@ -852,12 +858,10 @@ def region_quantiles(frames, labels, percents, nregions=None):
     regions; ``nregions=None`` takes ``labels.max() + 1`` (at least 1), which synchronises."""
     pc = _region_quantiles_percents(percents)
     fr, lab, n, h, w, per_frame = _region_inputs(frames, labels, nregions, "region_quantiles", _region_quantiles_args)
-    if nregions is None:
-        nregions = max(1, int(lab.max()) + 1)
-        _region_quantiles_args(tuple(frames.shape), tuple(labels.shape), nregions)
-    out = _region_quantiles_empty(n, int(nregions), pc.size, fr.device)
+    nregions = _nregions(nregions, lab, lambda k: _region_quantiles_args(tuple(frames.shape), tuple(labels.shape), k))
+    out = _region_quantiles_empty(n, nregions, pc.size, fr.device)
     if n:
-        _region_quantiles_into(fr, lab, per_frame, int(nregions), pc, out)
+        _region_quantiles_into(fr, lab, per_frame, nregions, pc, out)
     return out
 
 
