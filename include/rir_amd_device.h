@@ -241,6 +241,21 @@ extern "C"
 	int rir_temporal_median_device(const unsigned short *d_src, unsigned short *d_dst, int w, int h, int nframes, int first, int count, int step,
 								   int window, int threshold, int rows, void *stream);
 
+	/* Flat morphology of a stack d_src[nframes][h][w] into d_dst (same type and shape; extension).  type: 'H' uint16, 'B' uint8, '?' bool
+	 * (one byte, 0 / 1).  The structuring element is a centred rectangle size_y x size_x, both odd, 1..15.  The image is the first `rows`
+	 * (0..h) rows of a frame: rows y >= `rows` are copied unchanged and no window reads them.  With W(y, x) the window around (y, x)
+	 * CLIPPED to the image (truncated, never padded), E(f)(y, x) = min of f over W(y, x), D(f)(y, x) = max of f over W(y, x), and
+	 *   op 0 erode E(f)   1 dilate D(f)   2 open D(E(f))   3 close E(D(f))   4 tophat f - D(E(f))   5 blackhat E(D(f)) - f
+	 *   6 gradient D(f) - E(f)
+	 * each stage of open / close with its own clipped windows (the second stage never sees a first-stage value outside the image); the
+	 * three differences are never negative.  Per frame this is scipy.ndimage.minimum_filter / maximum_filter(size=(size_y, size_x),
+	 * mode="nearest") composed stage by stage.  Size 1 x 1: ops 0-3 copy, ops 4-6 give zeros; a window larger than the image clips.
+	 * One launch that reads the stack once and writes it once, whatever the op and the size: there is no workspace.  Asynchronous on
+	 * `stream`; d_dst may not overlap d_src.  nframes 0: nothing is done, 0.  -1 with the reason logged (argument errors before the device
+	 * is looked for): unknown type or op, an even size or one outside 1..15, rows outside 0..h, w or h < 1, nframes < 0, a null pointer,
+	 * overlap, no device. */
+	int rir_morphology_device(int type, const void *d_src, void *d_dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows, void *stream);
+
 	/* Per-region statistics of a uint16 stack d_frames[nframes][h][w] (extension).  d_labels: int32, one map [h][w] for every frame
 	 * (labels_per_frame 0) or one per frame [nframes][h][w] (1).  For frame f and region r < nregions (1..2^24), P = the flat indices
 	 * i = y * w + x whose label is r; labels outside [0, nregions) are ignored.  Outputs [nframes][nregions]: d_count = |P|, d_sum and

@@ -63,6 +63,14 @@ extern "C"
 	/* Temporal median of a host stack src[nframes][h][w] into dst (same shape): rir_temporal_median_device over the whole stack (first 0,
 	 * step 1), synchronous.  Large stacks go through the device in slabs with window / 2 frames of halo.  0 / -1. */
 	int rir_temporal_median(const unsigned short *src, unsigned short *dst, int w, int h, int nframes, int window, int threshold, int rows);
+	/* Flat morphology of a host stack src[nframes][h][w] into dst (same type and shape): rir_morphology_device (rir_amd_device.h) over the
+	 * stack, synchronous.  type 'H' uint16, 'B' uint8, '?' bool; op 0 erode (min over the size_y x size_x window clipped to the image),
+	 * 1 dilate (max), 2 open (dilate of erode), 3 close (erode of dilate), 4 tophat (src - open), 5 blackhat (close - src), 6 gradient
+	 * (dilate - erode); sizes odd, 1..15; the image is the first `rows` (0..h) rows, the others are copied.  Large stacks go through the
+	 * device in slabs of at most 64 MiB (frames are independent).  dst == src is allowed, any other overlap is not.  nframes 0: 0.
+	 * -1 with the reason logged on a bad argument (before the device is looked for) and without a device ("no usable HIP device", dst
+	 * untouched: there is no CPU fallback). */
+	int rir_morphology(int type, const void *src, void *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows);
 	/* Per-region statistics of a host stack frames[nframes][h][w] with host label maps: rir_region_stats_device (rir_amd_device.h),
 	 * synchronous, host outputs [nframes][nregions].  The frames go through the device in slabs of at most 64 MiB; a shared map goes up
 	 * once.  0 / -1. */

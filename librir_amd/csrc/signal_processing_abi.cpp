@@ -16,6 +16,7 @@
 #include "filter_kernels.h"
 #include "geometry_kernels.h"
 #include "label_kernels.h"
+#include "morphology_kernels.h"
 #include "pixel_kernels.h"
 #include "pixel_quantile_kernels.h"
 #include "polygon_kernels.h"
@@ -677,6 +678,46 @@ RIR_EXPORT int rir_temporal_median_device(const unsigned short *d_src, unsigned 
 	return hip_ok(launch_temporal_median(d_src, d_dst, w, h, nframes, first, count, step, window, threshold, rows, as_stream(stream)), "temporal_median")
 			   ? 0
 			   : -1;
+}
+
+// Flat morphology (morphology_kernels.hip).  Every argument is checked here, before the device is looked for; the byte ranges of the source
+// and the destination may not overlap.
+namespace
+{
+	// 0, or what is wrong with the arguments of rir_morphology / rir_morphology_device
+	const char *morphology_args(int type, const void *src, const void *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows)
+	{
+		if (type != 'H' && type != 'B' && type != '?')
+			return "unknown type (uint16 'H', uint8 'B' or bool '?')";
+		if (op < 0 || op >= MORPH_OPS)
+			return "unknown op (0 erode, 1 dilate, 2 open, 3 close, 4 tophat, 5 blackhat, 6 gradient)";
+		if (size_x < 1 || size_x > 15 || size_x % 2 == 0 || size_y < 1 || size_y > 15 || size_y % 2 == 0)
+			return "size_x and size_y must be odd, 1..15";
+		if (w < 1 || h < 1 || nframes < 0 || rows < 0 || rows > h)
+			return "invalid shape (w, h >= 1, nframes >= 0, 0 <= rows <= h)";
+		if (!src || !dst)
+			return "null pointer";
+		return nullptr;
+	}
+} // namespace
+
+RIR_EXPORT int rir_morphology_device(int type, const void *d_src, void *d_dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows,
+									 void *stream)
+{
+	const char *bad = morphology_args(type, d_src, d_dst, w, h, nframes, op, size_x, size_y, rows);
+	const uintptr_t bytes = (uintptr_t)w * h * (type == 'H' ? 2 : 1) * (bad ? 0 : nframes), s = (uintptr_t)d_src, d = (uintptr_t)d_dst;
+	if (!bad && s < d + bytes && d < s + bytes)
+		bad = "the source and the destination overlap";
+	if (bad)
+	{
+		log_error(std::string("rir_morphology_device: ") + bad);
+		return -1;
+	}
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	return hip_ok(launch_morphology(type, d_src, d_dst, w, h, nframes, op, size_x, size_y, rows, as_stream(stream)), "morphology") ? 0 : -1;
 }
 
 // Per-region statistics (region_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an input or
@@ -1369,6 +1410,42 @@ RIR_EXPORT int rir_temporal_median(const unsigned short *src, unsigned short *ds
 			rir_temporal_median_device(in.as<unsigned short>(), out.as<unsigned short>(), w, h, hi - lo, o - lo, count, 1, window, threshold, rows, st) != 0 ||
 			!hip_ok(hipMemcpyAsync(dst + (size_t)o * w * h, out.ptr, frame * count, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
 			!hip_ok(wait_stream(st), "temporal_median"))
+			return -1;
+	}
+	return 0;
+}
+
+// Extension: flat morphology of a host stack, sent through the device in slabs of at most MORPHOLOGY_SLAB_BYTES of frames (frames are
+// independent: any split gives the same bits).  dst may be src.  Synchronous.  0 / -1.
+constexpr size_t MORPHOLOGY_SLAB_BYTES = (size_t)64 << 20;
+RIR_EXPORT int rir_morphology(int type, const void *src, void *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows)
+{
+	const char *bad = morphology_args(type, src, dst, w, h, nframes, op, size_x, size_y, rows);
+	const size_t frame = (size_t)w * h * (type == 'H' ? 2 : 1);
+	const uintptr_t bytes = bad ? 0 : frame * (size_t)nframes, s = (uintptr_t)src, d = (uintptr_t)dst;
+	if (!bad && s != d && s < d + bytes && d < s + bytes)
+		bad = "the source and the destination overlap (dst == src is allowed)";
+	if (bad)
+	{
+		log_error(std::string("rir_morphology: ") + bad);
+		return -1;
+	}
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	const int slab = (int)std::max<size_t>(1, std::min<size_t>(MORPHOLOGY_SLAB_BYTES / frame, (size_t)nframes));
+	DeviceBuffer in, out;
+	if (!in.reserve(frame * slab) || !out.reserve(frame * slab))
+		return -1;
+	hipStream_t st = default_stream();
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int count = std::min(slab, nframes - o);
+		if (!hip_ok(hipMemcpyAsync(in.ptr, static_cast<const char *>(src) + frame * o, frame * count, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
+			rir_morphology_device(type, in.ptr, out.ptr, w, h, count, op, size_x, size_y, rows, st) != 0 ||
+			!hip_ok(hipMemcpyAsync(static_cast<char *>(dst) + frame * o, out.ptr, frame * count, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
+			!hip_ok(wait_stream(st), "morphology"))
 			return -1;
 	}
 	return 0;

@@ -13,7 +13,7 @@ from .low_level.misc import _lib, last_error
 from .signal_processing.rir_signal_processing import (PixelStats, RegionGeometry, RegionQuantiles, RegionStats,  # noqa: F401 (API)
                                                       _pixel_quantiles_args, _pixel_stats_args, _polygon_map_args, _region_geometry_args,
                                                       _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
-                                                      _temporal_median_args)
+                                                      _morphology_args, _temporal_median_args)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -113,7 +113,8 @@ _lib.rir_remove_bad_pixels_device.argtypes = [ct.c_int, _vp, ct.c_int, ct.c_int,
 _lib.rir_remove_motion_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp, _vp]
 _lib.rir_median_filter_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, _vp]
 _lib.rir_temporal_median_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp]
-_lib.rir_region_stats_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp] * 8 + [ct.c_size_t, _vp]
+_lib.rir_morphology_device.argtypes = [ct.c_int, _vp, _vp] + [ct.c_int] * 7 + [_vp]
+_lib.rir_region_stats_device.argtypes =[_vp, _vp] + [ct.c_int] * 5 + [_vp] * 8 + [ct.c_size_t, _vp]
 _lib.rir_region_stats_workspace_bytes.argtypes = [ct.c_int] * 5
 _lib.rir_region_stats_workspace_bytes.restype = ct.c_size_t
 _lib.rir_region_geometry_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp] * 5 + [ct.c_size_t, _vp]
@@ -674,6 +675,63 @@ def temporal_median(frames, window, threshold=0, rows=None, first=0, count=None,
         _check(_lib.rir_temporal_median_device(fr.data_ptr(), out.data_ptr(), w, h, n, int(first), count, int(step), int(window), int(threshold), rows,
                                                _stream()), "rir_temporal_median_device")
     return out
+
+
+def morphology(frames, op, size, rows=None, out=None):
+    """Flat morphology of a uint16, uint8 or bool stack ``frames[n][h][w]`` (or one image ``[h][w]``) with a centred rectangle ``size`` (an
+    odd int, or ``(size_y, size_x)``, each 1..15) (C ABI ``rir_morphology_device``), one launch on the current stream.  ``op``: "erode" /
+    "dilate" - min / max over the window clipped to the image, never padded -, "open" (dilate of erode), "close" (erode of dilate),
+    "tophat" (frames - open), "blackhat" (close - frames), "gradient" (dilate - erode).  The image is the first ``rows`` rows of a frame
+    (default: all); the others are copied.  Returns a tensor of the input's dtype and shape (``out`` when given: a contiguous CUDA tensor
+    of that dtype and shape that does not overlap ``frames``)."""
+    shape = tuple(frames.shape)
+    dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
+    type_char, op_number, size_y, size_x, rows = _morphology_args((1,) + shape if len(shape) == 2 else shape, dtype_name, op, size, rows)
+    if out is not None and (not out.is_cuda or out.dtype != frames.dtype or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise RuntimeError("morphology: out must be a contiguous %s CUDA tensor of shape %s" % (frames.dtype, shape))
+    fr = _frames3(frames)
+    n, h, w = fr.shape
+    if out is None:
+        out = torch.empty(shape, dtype=fr.dtype, device=fr.device)
+    if n:
+        _check(_lib.rir_morphology_device(type_char, fr.data_ptr(), out.data_ptr(), w, h, n, op_number, size_x, size_y, rows, _stream()),
+               "rir_morphology_device")
+    return out
+
+
+def erode(frames, size, rows=None, out=None):
+    """``morphology(frames, "erode", ...)``: the minimum over the clipped window"""
+    return morphology(frames, "erode", size, rows, out)
+
+
+def dilate(frames, size, rows=None, out=None):
+    """``morphology(frames, "dilate", ...)``: the maximum over the clipped window"""
+    return morphology(frames, "dilate", size, rows, out)
+
+
+def morph_open(frames, size, rows=None, out=None):
+    """``morphology(frames, "open", ...)``: dilate(erode(frames)) - removes bright details smaller than the window"""
+    return morphology(frames, "open", size, rows, out)
+
+
+def morph_close(frames, size, rows=None, out=None):
+    """``morphology(frames, "close", ...)``: erode(dilate(frames)) - fills dark details smaller than the window"""
+    return morphology(frames, "close", size, rows, out)
+
+
+def top_hat(frames, size, rows=None, out=None):
+    """``morphology(frames, "tophat", ...)``: frames - open(frames), the bright details on a flattened background"""
+    return morphology(frames, "tophat", size, rows, out)
+
+
+def black_hat(frames, size, rows=None, out=None):
+    """``morphology(frames, "blackhat", ...)``: close(frames) - frames, the dark details"""
+    return morphology(frames, "blackhat", size, rows, out)
+
+
+def morph_gradient(frames, size, rows=None, out=None):
+    """``morphology(frames, "gradient", ...)``: dilate(frames) - erode(frames)"""
+    return morphology(frames, "gradient", size, rows, out)
 
 
 class TemporalMedian:

@@ -201,6 +201,55 @@ def temporal_median(images, window, threshold=0, rows=None):
     return out
 
 
+# ---- extension: flat morphology ------------------------------------------------------------------------------------------------
+_sp.rir_morphology.argtypes = [ct.c_int, ct.c_void_p, ct.c_void_p] + [ct.c_int] * 7
+
+MORPHOLOGY_OPS = ("erode", "dilate", "open", "close", "tophat", "blackhat", "gradient")  # the op numbers of the C ABI
+_MORPHOLOGY_TYPES = {"uint16": "H", "uint8": "B", "bool": "?"}
+
+
+def _morphology_args(shape, dtype_name, op, size, rows):
+    """the parameters of a morphology call over a stack of `shape`, checked without a device; -> (type char, op number, size_y, size_x, rows)"""
+    if len(shape) != 3:
+        raise ValueError("morphology: a stack [n][h][w] expected")
+    if dtype_name not in _MORPHOLOGY_TYPES:
+        raise ValueError("morphology: uint16, uint8 or bool frames expected, not %s" % dtype_name)
+    if op not in MORPHOLOGY_OPS:
+        raise ValueError("morphology: op must be one of %s (got %r)" % (", ".join(MORPHOLOGY_OPS), op))
+    sizes = tuple(size) if isinstance(size, (tuple, list)) else (size, size)
+    if len(sizes) != 2 or not all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in sizes):
+        raise ValueError("morphology: size must be an odd int or (size_y, size_x)")
+    for s in sizes:
+        if not 1 <= s <= 15 or s % 2 == 0:
+            raise ValueError("morphology: sizes must be odd, 1 to 15 (got %r)" % (size,))
+    _, h, w = shape
+    if h < 1 or w < 1:
+        raise ValueError("morphology: empty frames")
+    rows = h if rows is None else int(rows)
+    if not 0 <= rows <= h:
+        raise ValueError("morphology: rows must be in 0..h")
+    return ord(_MORPHOLOGY_TYPES[dtype_name]), MORPHOLOGY_OPS.index(op), int(sizes[0]), int(sizes[1]), rows
+
+
+def morphology(images, op, size, rows=None):
+    """Extension: flat morphology of a uint16, uint8 or bool stack ``images[n][h][w]`` (or one image ``[h][w]``) with a centred rectangle
+    ``size`` (an odd int, or ``(size_y, size_x)``, each 1..15) (``rir_morphology``).  ``op``: "erode" / "dilate" - min / max over the
+    window clipped to the image -, "open" (dilate of erode), "close" (erode of dilate), "tophat" (image - open), "blackhat" (close -
+    image), "gradient" (dilate - erode).  Per image this is ``scipy.ndimage.minimum_filter`` / ``maximum_filter(size=size,
+    mode="nearest")`` composed stage by stage.  The image is its first ``rows`` rows (default: all); the others are copied.  Returns an
+    array of the input's dtype and shape.  ``ValueError`` on bad parameters, ``RuntimeError`` when the library fails."""
+    img = np.ascontiguousarray(images)
+    if img.ndim not in (2, 3):
+        raise ValueError("morphology: an image [h][w] or a stack [n][h][w] expected")
+    stack = img.reshape((-1,) + img.shape[-2:])
+    type_char, op_number, size_y, size_x, rows = _morphology_args(stack.shape, img.dtype.name, op, size, rows)
+    out = np.empty_like(stack)
+    n, h, w = stack.shape
+    if n and _sp.rir_morphology(type_char, stack.ctypes.data, out.ctypes.data, w, h, n, op_number, size_x, size_y, rows) < 0:
+        raise RuntimeError("An error occured while calling 'morphology': " + (last_error() or ""))
+    return out.reshape(img.shape)
+
+
 # ---- extension: per-region statistics ------------------------------------------------------------------------------------------
 _sp.rir_region_stats.argtypes = [ct.c_void_p, ct.c_void_p] + [ct.c_int] * 5 + [ct.c_void_p] * 7
 

@@ -495,6 +495,41 @@ class IRMovie(object):
             acc.push(fr, k0)
         return acc.result()
 
+    def morphology(self, op, size, selection=slice(None), rows=None, out=None):
+        """Flat morphology of the images of ``selection`` (as ``region_stats`` takes it) - ``librir_amd.device.morphology(frames, op, size,
+        rows)`` over the images ``to_tensor(selection)`` gives (read-back filters applied), filtered on the device: a uint16 CUDA tensor
+        ``[len(selection)][h][w]`` (``out`` when given: a contiguous uint16 CUDA tensor of that shape).  ``op`` is "erode", "dilate",
+        "open", "close", "tophat", "blackhat" or "gradient", ``size`` an odd int or ``(size_y, size_x)``, each 1..15; ``rows=None``
+        filters all rows, otherwise rows ``>= rows`` are copied.  The recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of
+        images; images are filtered one by one, so any split gives the same bits.
+
+        The other analysis calls take no morphology parameter; they compose with it::
+
+            mask = mov.morphology("tophat", 9) > t                  # small hot spots on a spatially varying background
+            mask = librir_amd.device.morph_open(mask, 3)            # drop single-pixel noise ...
+            labels = librir_amd.device.label_images(mask)           # ... before labelling and track_components
+        """
+        import torch
+
+        from ..device import _morphology_args, morphology
+
+        h, w = self.image_size
+        _morphology_args((1, h, w), "uint16", op, size, rows)
+        positions = self._stats_positions(selection, "morphology")
+        shape = (len(positions), h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint16, device=torch.device("cuda", torch.cuda.current_device()))
+        elif not out.is_cuda or out.dtype != torch.uint16 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise RuntimeError("morphology: 'out' must be a C-contiguous uint16 CUDA tensor of shape %s" % (shape,))
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=out.device)
+        for k0 in range(0, len(positions), per_piece):
+            sel = positions[k0:k0 + per_piece]
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            morphology(fr, op, size, rows, out=out[k0:k0 + len(sel)])
+        return out
+
     _QUANTILE_RESIDENT_BYTES = 1 << 30  # uint16 images that pixel_quantiles decodes into one stack
 
     def pixel_quantiles(self, percents, selection=slice(None)):

@@ -34,6 +34,15 @@ bp = D.BadPixels(t16[0])
 rec("bad_pixels_correct (%d px)" % bp.count, timeit(lambda: bp.correct(t16)), 4 * WH)
 rec("find_median_pixel", timeit(lambda: D.find_median_pixel(t16, 0.5)), 2 * WH)
 rec("median_filter 3x3", timeit(lambda: D.median_filter(t16)), 4 * WH)
+# flat morphology: one launch whatever the op; squares 3 / 5 / 7 in registers, other sizes through an LDS tile
+morph_out = torch.empty_like(t16)
+for size in (3, 5, 7, 9, 15):
+    for op in ("erode", "dilate", "open", "close", "tophat", "blackhat", "gradient"):
+        rec("morphology %s %dx%d" % (op, size, size), timeit(lambda: D.morphology(t16, op, size, out=morph_out)), 4 * WH)
+t8 = torch.from_numpy((fr >> 8).astype(np.uint8)).cuda()
+morph_out8 = torch.empty_like(t8)
+for op in ("erode", "open", "tophat"):
+    rec("morphology %s 3x3 uint8" % op, timeit(lambda: D.morphology(t8, op, 3, out=morph_out8)), 2 * WH)
 sh = torch.zeros((n, 2), dtype=torch.float32, device="cuda"); sh[:, 0] = 1.25; sh[:, 1] = -2.5
 rec("remove_motion (read-back)", timeit(lambda: D.remove_motion(t16, sh, rows=h - 3)), 4 * WH)
 t0 = time.perf_counter(); bp2 = D.BadPixels(t16[0]); torch.cuda.synchronize(); print("bad_pixels_create (detector, once per stream): %.2f ms" % ((time.perf_counter() - t0) * 1e3))
