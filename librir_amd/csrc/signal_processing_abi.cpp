@@ -57,6 +57,37 @@ namespace
 		return false;
 	}
 
+	// What an extension entry says when it refuses a call: "<its name>: <text>" in the log, -1 to the caller.
+	int refuse(const char *who, const std::string &text)
+	{
+		log_error(std::string(who) + ": " + text);
+		return -1;
+	}
+
+	// A workspace or a state (`what`) of `have` bytes at p: 8-byte aligned and at least `need`, the bytes that `holds` names; refused otherwise.
+	bool workspace_ok(const char *who, const void *p, size_t have, size_t need, const char *what, const char *holds)
+	{
+		if (have >= need && (uintptr_t)p % 8 == 0)
+			return true;
+		refuse(who, std::string("the ") + what + " must be 8-byte aligned and hold " + holds + " bytes");
+		return false;
+	}
+
+	// The percents of a quantile entry into pc; NaN and values outside [0, 1] are refused.
+	bool percents_ok(const char *who, const float *percents, int npercents, QuantilePercents &pc)
+	{
+		for (int j = 0; j < npercents; ++j)
+		{
+			if (!(percents[j] >= 0.0f && percents[j] <= 1.0f)) // NaN fails both
+			{
+				refuse(who, "every percent must be in [0, 1]");
+				return false;
+			}
+			pc.p[j] = percents[j];
+		}
+		return true;
+	}
+
 	int strategy_from_string(const char *s)
 	{ // signal_processing.cpp:20-41: NULL, "" and "noborder" leave border pixels untouched
 		if (!s || std::strlen(s) == 0 || std::strcmp(s, "noborder") == 0)
@@ -368,10 +399,7 @@ RIR_EXPORT int rir_translate_device(int type, const void *d_src, void *d_dst, in
 		return -1;
 	const int s = strategy_from_string(strategy);
 	if (s < 0 || dtype_size(type) == 0 || w <= 0 || h <= 0 || nframes <= 0 || !d_src || !d_dst || !d_offsets || !background)
-	{
-		log_error("rir_translate_device: invalid argument");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument");
 	return hip_ok(launch_translate(type, d_src, d_dst, background, w, h, nframes, d_offsets, per_frame_offsets, s, as_stream(stream)), "translate") ? 0 : -1;
 }
 
@@ -380,10 +408,7 @@ RIR_EXPORT int rir_gaussian_filter_device(const float *d_src, float *d_dst, int 
 	if (!device_ready())
 		return -1;
 	if (w <= 0 || h <= 0 || nframes <= 0 || !d_src || !d_dst || !(sigma > 0))
-	{
-		log_error("rir_gaussian_filter_device: invalid argument");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument");
 	const int radius = gaussian_radius(sigma);
 	const GaussTable table = gaussian_table_device(sigma, radius); // held until the launch below has been queued
 	if (!table)
@@ -398,10 +423,7 @@ RIR_EXPORT int rir_gaussian_filter_u16_device(const unsigned short *d_src, float
 	if (!device_ready())
 		return -1;
 	if (w <= 0 || h <= 0 || nframes <= 0 || !d_src || !d_dst || !(sigma > 0) || gaussian_radius(sigma) > 4)
-	{
-		log_error("rir_gaussian_filter_u16_device: invalid argument (sigma must be < 2.5 for the uint16 entry)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (sigma must be < 2.5 for the uint16 entry)");
 	const int radius = gaussian_radius(sigma);
 	const GaussTable table = gaussian_table_device(sigma, radius); // held until the launch below has been queued
 	if (!table)
@@ -419,10 +441,7 @@ RIR_EXPORT int rir_translate_f32_u16_device(const float *d_src, unsigned short *
 		return -1;
 	const int s = strategy_from_string(strategy);
 	if (s < 0 || w <= 0 || h <= 0 || nframes <= 0 || !d_src || !d_dst || !d_offsets || !background)
-	{
-		log_error("rir_translate_f32_u16_device: invalid argument");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument");
 	return hip_ok(launch_translate('F', d_src, d_dst, background, w, h, nframes, d_offsets, per_frame_offsets, s, as_stream(stream)), "translate") ? 0 : -1;
 }
 
@@ -434,10 +453,7 @@ RIR_EXPORT int rir_split_planes_device(const unsigned short *d_img, const unsign
 	if (!device_ready())
 		return -1;
 	if (!d_img || !d_Y || !d_U || !d_V || w <= 0 || h <= 0 || nframes <= 0 || linesize < w)
-	{
-		log_error("rir_split_planes_device: invalid argument");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument");
 	return hip_ok(launch_split_planes(d_img, d_it, w, h, nframes, linesize, d_Y, d_U, d_V, as_stream(stream)), "split_planes") ? 0 : -1;
 }
 RIR_EXPORT int rir_merge_planes_device(const unsigned char *d_Y, const unsigned char *d_U, const unsigned char *d_V, int linesize, int w, int h,
@@ -446,10 +462,7 @@ RIR_EXPORT int rir_merge_planes_device(const unsigned char *d_Y, const unsigned 
 	if (!device_ready())
 		return -1;
 	if (!d_img || !d_U || !d_V || (d_it && !d_Y) || w <= 0 || h <= 0 || nframes <= 0 || linesize < w)
-	{
-		log_error("rir_merge_planes_device: invalid argument");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument");
 	return hip_ok(launch_merge_planes(d_Y, d_U, d_V, linesize, w, h, nframes, d_img, d_it, as_stream(stream)), "merge_planes") ? 0 : -1;
 }
 
@@ -460,10 +473,7 @@ RIR_EXPORT int rir_find_median_pixel_device(const unsigned short *d_img, const u
 	if (!device_ready())
 		return -1;
 	if (size <= 0 || nframes <= 0 || !d_img || !d_result)
-	{
-		log_error("rir_find_median_pixel_device: invalid argument");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument");
 	(void)d_hist; // the counting happens in LDS, one quarter of the value range at a time: no histogram in memory
 	// 65 535 bins, as the reference (Filters.cpp:59)
 	return hip_ok(launch_quantile_select(d_img, d_mask, size, nframes, percent, 65535, d_result, as_stream(stream)), "find_median_pixel") ? 0 : -1;
@@ -493,10 +503,7 @@ RIR_EXPORT int rir_bad_pixels_correct_device(int handle, const unsigned short *d
 		return -1;
 	auto bp = lookup_as<BadPixelsObject>(handle);
 	if (!bp || !d_in || !d_out || nframes <= 0)
-	{
-		log_error("rir_bad_pixels_correct_device: invalid handle or argument");
-		return -1;
-	}
+		return refuse(__func__, "invalid handle or argument");
 	return hip_ok(launch_bad_pixels_correct(d_in, d_out, bp->width, bp->height, nframes, bp->d_xy.as<int>(), bp->count(), bp->floor_correct,
 											as_stream(stream)),
 				  "bad_pixels_correct")
@@ -518,19 +525,13 @@ RIR_EXPORT int rir_filter_chain_device(int bad_pixels_handle, const unsigned sho
 	const int s = strategy_from_string(strategy);
 	if ((s != TRANSLATE_NEAREST && s != TRANSLATE_CONSTANT) || w <= 0 || h <= 0 || nframes <= 0 || !d_src || !d_dst || d_src == d_dst || !d_offsets ||
 		!(sigma > 0) || gaussian_radius(sigma) > 4 || (s == TRANSLATE_CONSTANT && !background))
-	{
-		log_error("rir_filter_chain_device: invalid argument (strategies: nearest, background; sigma < 2.5; out of place)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (strategies: nearest, background; sigma < 2.5; out of place)");
 	std::shared_ptr<BadPixelsObject> bp;
 	if (bad_pixels_handle > 0)
 	{
 		bp = lookup_as<BadPixelsObject>(bad_pixels_handle);
 		if (!bp || bp->width != w || bp->height != h)
-		{
-			log_error("rir_filter_chain_device: invalid bad pixels handle, or created for another image size");
-			return -1;
-		}
+			return refuse(__func__, "invalid bad pixels handle, or created for another image size");
 	}
 	if (gaussian_reference_order())
 	{
@@ -598,10 +599,7 @@ RIR_EXPORT int rir_remove_bad_pixels_device(int handle, unsigned short *d_img, i
 		return -1;
 	auto bp = lookup_as<BadPixelsObject>(handle);
 	if (!bp || !d_img || nframes <= 0 || rows <= 0 || rows > bp->height)
-	{
-		log_error("rir_remove_bad_pixels_device: invalid handle or argument");
-		return -1;
-	}
+		return refuse(__func__, "invalid handle or argument");
 	return hip_ok(launch_remove_bad_pixels(d_img, bp->width, bp->height, rows, nframes, bp->d_xy.as<int>(), bp->count(), bp->d_bitmap.as<uint8_t>(),
 										   as_stream(stream)),
 				  "remove_bad_pixels")
@@ -636,10 +634,7 @@ RIR_EXPORT int rir_remove_motion_device(const unsigned short *d_src, unsigned sh
 	if (!device_ready())
 		return -1;
 	if (!d_src || !d_dst || d_src == d_dst || w <= 0 || h <= 0 || rows <= 0 || rows > h || nframes <= 0 || !d_shifts)
-	{
-		log_error("rir_remove_motion_device: invalid argument");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument");
 	return hip_ok(launch_remove_motion(d_src, d_dst, w, h, rows, nframes, d_shifts, as_stream(stream)), "remove_motion") ? 0 : -1;
 }
 
@@ -648,10 +643,7 @@ RIR_EXPORT int rir_median_filter_device(const unsigned short *d_src, unsigned sh
 	if (!device_ready())
 		return -1;
 	if (!d_src || !d_dst || w < 3 || h < 3 || nframes <= 0)
-	{
-		log_error("rir_median_filter_device: invalid argument (needs w,h >= 3)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (needs w,h >= 3)");
 	return hip_ok(launch_median3x3(d_src, d_dst, w, h, nframes, as_stream(stream)), "median_filter") ? 0 : -1;
 }
 
@@ -663,18 +655,12 @@ RIR_EXPORT int rir_temporal_median_device(const unsigned short *d_src, unsigned 
 		return -1;
 	if (w <= 0 || h <= 0 || nframes <= 0 || window < 1 || window > 63 || window % 2 == 0 || threshold < 0 || threshold > 65535 || rows < 0 || rows > h ||
 		step < 1 || count < 0 || first < 0 || first > nframes || (count > 0 && first + (long long)(count - 1) * step > nframes - 1))
-	{
-		log_error("rir_temporal_median_device: invalid argument (odd window 1..63, threshold 0..65535, 0 <= rows <= h, outputs inside the stack)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (odd window 1..63, threshold 0..65535, 0 <= rows <= h, outputs inside the stack)");
 	if (count == 0)
 		return 0;
 	const uintptr_t frame = (uintptr_t)w * h * 2, s = (uintptr_t)d_src, d = (uintptr_t)d_dst;
 	if (!d_src || !d_dst || (s < d + frame * count && d < s + frame * nframes))
-	{
-		log_error("rir_temporal_median_device: null pointer, or the source and destination overlap");
-		return -1;
-	}
+		return refuse(__func__, "null pointer, or the source and destination overlap");
 	return hip_ok(launch_temporal_median(d_src, d_dst, w, h, nframes, first, count, step, window, threshold, rows, as_stream(stream)), "temporal_median")
 			   ? 0
 			   : -1;
@@ -709,10 +695,7 @@ RIR_EXPORT int rir_morphology_device(int type, const void *d_src, void *d_dst, i
 	if (!bad && s < d + bytes && d < s + bytes)
 		bad = "the source and the destination overlap";
 	if (bad)
-	{
-		log_error(std::string("rir_morphology_device: ") + bad);
-		return -1;
-	}
+		return refuse(__func__, bad);
 	if (nframes == 0)
 		return 0;
 	if (!device_ready())
@@ -745,31 +728,18 @@ RIR_EXPORT int rir_region_stats_device(const unsigned short *d_frames, const int
 	if (!device_ready())
 		return -1;
 	if (!region_stats_args(w, h, nframes, labels_per_frame, nregions))
-	{
-		log_error("rir_region_stats_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, "
-				  "1 <= nregions <= 2^24)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, 1 <= nregions <= 2^24)");
 	if (nframes == 0)
 		return 0;
 	const size_t npx = (size_t)w * h, cells = (size_t)nframes * nregions, need = region_stats_workspace((int64_t)npx, nframes, nregions);
 	if (!d_frames || !d_labels || !d_count || !d_sum || !d_sumsq || !d_min || !d_max || !d_argmin || !d_argmax || !d_work)
-	{
-		log_error("rir_region_stats_device: null pointer");
+		return refuse(__func__, "null pointer");
+	if (!workspace_ok(__func__, d_work, work_bytes, need, "workspace", "rir_region_stats_workspace_bytes()"))
 		return -1;
-	}
-	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
-	{
-		log_error("rir_region_stats_device: the workspace must be 8-byte aligned and hold rir_region_stats_workspace_bytes() bytes");
-		return -1;
-	}
 	if (outputs_overlap({{d_frames, npx * nframes * 2}, {d_labels, npx * (labels_per_frame ? nframes : 1) * 4}},
 						{{d_count, cells * 4}, {d_sum, cells * 8}, {d_sumsq, cells * 8}, {d_min, cells * 4}, {d_max, cells * 4}, {d_argmin, cells * 4},
 						 {d_argmax, cells * 4}, {d_work, need}}))
-	{
-		log_error("rir_region_stats_device: an output or the workspace overlaps an input or another output");
-		return -1;
-	}
+		return refuse(__func__, "an output or the workspace overlaps an input or another output");
 	return hip_ok(launch_region_stats(d_frames, d_labels, (int64_t)npx, nframes, labels_per_frame, nregions, d_count, (int64_t *)d_sum, (int64_t *)d_sumsq,
 									  d_min, d_max, d_argmin, d_argmax, d_work, as_stream(stream)),
 				  "region_stats")
@@ -803,29 +773,17 @@ RIR_EXPORT int rir_region_geometry_device(const int *d_labels, const unsigned sh
 	if (!device_ready())
 		return -1;
 	if (!region_geometry_args(w, h, nframes, labels_per_frame, nregions, d_frames != nullptr))
-	{
-		log_error(std::string("rir_region_geometry_device: ") + REGION_GEOMETRY_ARGS);
-		return -1;
-	}
+		return refuse(__func__, REGION_GEOMETRY_ARGS);
 	if (nframes == 0)
 		return 0;
 	if (!d_labels || !d_count || !d_bbox || !d_moments || !d_work || (d_frames != nullptr) != (d_weighted != nullptr))
-	{
-		log_error("rir_region_geometry_device: null pointer (d_weighted is null exactly when d_frames is)");
+		return refuse(__func__, "null pointer (d_weighted is null exactly when d_frames is)");
+	if (!workspace_ok(__func__, d_work, work_bytes, GEOMETRY_WORK_BYTES, "workspace", "rir_region_geometry_workspace_bytes()"))
 		return -1;
-	}
-	if (work_bytes < GEOMETRY_WORK_BYTES || (uintptr_t)d_work % 8 != 0)
-	{
-		log_error("rir_region_geometry_device: the workspace must be 8-byte aligned and hold rir_region_geometry_workspace_bytes() bytes");
-		return -1;
-	}
 	const size_t npx = (size_t)w * h, cells = (size_t)nframes * nregions;
 	if (outputs_overlap({{d_labels, npx * (labels_per_frame ? nframes : 1) * 4}, {d_frames, npx * nframes * 2}},
 						{{d_count, cells * 4}, {d_bbox, cells * 16}, {d_moments, cells * 40}, {d_work, GEOMETRY_WORK_BYTES}, {d_weighted, cells * 24}}))
-	{
-		log_error("rir_region_geometry_device: an output or the workspace overlaps an input or another output");
-		return -1;
-	}
+		return refuse(__func__, "an output or the workspace overlaps an input or another output");
 	return hip_ok(launch_region_geometry(d_labels, d_frames, w, h, nframes, labels_per_frame, nregions, d_count, d_bbox, (int64_t *)d_moments,
 										 (int64_t *)d_weighted, as_stream(stream)),
 				  "region_geometry")
@@ -860,42 +818,22 @@ RIR_EXPORT int rir_region_quantiles_device(const unsigned short *d_frames, const
 	if (!device_ready())
 		return -1;
 	if (!region_quantiles_args(w, h, nframes, labels_per_frame, nregions, npercents))
-	{
-		log_error("rir_region_quantiles_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, "
-				  "1 <= nregions <= 65536, 1 <= npercents <= 8)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, 1 <= nregions <= 65536, "
+								"1 <= npercents <= 8)");
 	if (!d_frames || !d_labels || !percents || !d_count || !d_values || !d_work)
-	{
-		log_error("rir_region_quantiles_device: null pointer");
-		return -1;
-	}
+		return refuse(__func__, "null pointer");
 	QuantilePercents pc{};
-	for (int j = 0; j < npercents; ++j)
-	{
-		if (!(percents[j] >= 0.0f && percents[j] <= 1.0f)) // NaN fails both
-		{
-			log_error("rir_region_quantiles_device: every percent must be in [0, 1]");
-			return -1;
-		}
-		pc.p[j] = percents[j];
-	}
+	if (!percents_ok(__func__, percents, npercents, pc))
+		return -1;
 	if (nframes == 0)
 		return 0;
 	const size_t npx = (size_t)w * h, cells = (size_t)nframes * nregions, B = region_quantiles_frame_bytes(nregions, npercents);
-	if (work_bytes < B || (uintptr_t)d_work % 8 != 0)
-	{
-		log_error("rir_region_quantiles_device: the workspace must be 8-byte aligned and hold one frame's share of "
-				  "rir_region_quantiles_workspace_bytes() bytes");
+	if (!workspace_ok(__func__, d_work, work_bytes, B, "workspace", "one frame's share of rir_region_quantiles_workspace_bytes()"))
 		return -1;
-	}
 	const size_t used = B * std::min<size_t>((size_t)nframes, work_bytes / B);
 	if (outputs_overlap({{d_frames, npx * nframes * 2}, {d_labels, npx * (labels_per_frame ? nframes : 1) * 4}},
 						{{d_count, cells * 4}, {d_values, cells * npercents * 4}, {d_work, used}}))
-	{
-		log_error("rir_region_quantiles_device: an output or the workspace overlaps an input or another output");
-		return -1;
-	}
+		return refuse(__func__, "an output or the workspace overlaps an input or another output");
 	return hip_ok(launch_region_quantiles(d_frames, d_labels, (int64_t)npx, nframes, labels_per_frame, nregions, pc, npercents, d_count, d_values, d_work,
 										  work_bytes, as_stream(stream)),
 				  "region_quantiles")
@@ -924,36 +862,20 @@ RIR_EXPORT int rir_pixel_stats_device(const unsigned short *d_frames, int w, int
 	if (!device_ready())
 		return -1;
 	if (!pixel_stats_args(w, h, nframes) || t0 < 0 || (long long)t0 + nframes > 2147483647ll || (accumulate != 0 && accumulate != 1))
-	{
-		log_error("rir_pixel_stats_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, t0 >= 0 with t0 + nframes <= 2^31 - 1, "
-				  "accumulate 0 or 1)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, t0 >= 0 with t0 + nframes <= 2^31 - 1, accumulate 0 or 1)");
 	if (nframes == 0)
 		return 0;
 	const bool sums = d_sum || d_sumsq, extremes = d_min || d_max || d_argmin || d_argmax;
 	if ((sums && (!d_sum || !d_sumsq)) || (extremes && (!d_min || !d_max || !d_argmin || !d_argmax)) || (!sums && !extremes))
-	{
-		log_error("rir_pixel_stats_device: a group of outputs (sum, sumsq / min, max, argmin, argmax) is all given or all null, and one is given");
-		return -1;
-	}
+		return refuse(__func__, "a group of outputs (sum, sumsq / min, max, argmin, argmax) is all given or all null, and one is given");
 	if (!d_frames || !d_work)
-	{
-		log_error("rir_pixel_stats_device: null pointer");
-		return -1;
-	}
+		return refuse(__func__, "null pointer");
 	const size_t npx = (size_t)w * h, need = pixel_stats_workspace((int64_t)npx, nframes);
-	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
-	{
-		log_error("rir_pixel_stats_device: the workspace must be 8-byte aligned and hold rir_pixel_stats_workspace_bytes() bytes");
+	if (!workspace_ok(__func__, d_work, work_bytes, need, "workspace", "rir_pixel_stats_workspace_bytes()"))
 		return -1;
-	}
 	if (outputs_overlap({{d_frames, npx * nframes * 2}}, {{d_sum, npx * 8}, {d_sumsq, npx * 8}, {d_min, npx * 4}, {d_max, npx * 4}, {d_argmin, npx * 4},
 															{d_argmax, npx * 4}, {d_work, need}})) // the group not asked for is null: absent
-	{
-		log_error("rir_pixel_stats_device: an output or the workspace overlaps the input or another output");
-		return -1;
-	}
+		return refuse(__func__, "an output or the workspace overlaps the input or another output");
 	return hip_ok(launch_pixel_stats(d_frames, (int64_t)npx, nframes, t0, accumulate, (int64_t *)d_sum, (int64_t *)d_sumsq, d_min, d_max, d_argmin,
 									 d_argmax, d_work, as_stream(stream)),
 				  "pixel_stats")
@@ -969,20 +891,6 @@ namespace
 	{
 		return w > 0 && h > 0 && (long long)w * h < (1ll << 31) && npercents >= 1 && npercents <= QUANTILE_MAX_PERCENTS;
 	}
-	bool pixel_quantiles_percents(const char *who, const float *percents, int npercents, QuantilePercents &pc)
-	{
-		for (int j = 0; j < npercents; ++j)
-		{
-			if (!(percents[j] >= 0.0f && percents[j] <= 1.0f)) // NaN fails both
-			{
-				log_error(std::string(who) + ": every percent must be in [0, 1]");
-				return false;
-			}
-			pc.p[j] = percents[j];
-		}
-		return true;
-	}
-	bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) { return outputs_overlap({{a, na}}, {{b, nb}}); }
 } // namespace
 
 RIR_EXPORT int rir_pixel_quantiles_passes(void) { return PIXEL_QUANTILE_PASSES; }
@@ -1003,29 +911,17 @@ RIR_EXPORT int rir_pixel_quantiles_push_device(const unsigned short *d_frames, i
 	if (!device_ready())
 		return -1;
 	if (!pixel_quantiles_args(w, h, npercents) || nframes < 0 || pass < 0 || pass >= PIXEL_QUANTILE_PASSES)
-	{
-		log_error("rir_pixel_quantiles_push_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, 1 <= npercents <= 8, "
-				  "0 <= pass < rir_pixel_quantiles_passes())");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, 1 <= npercents <= 8, "
+								"0 <= pass < rir_pixel_quantiles_passes())");
 	if (!d_frames || !d_state)
-	{
-		log_error("rir_pixel_quantiles_push_device: null pointer");
-		return -1;
-	}
+		return refuse(__func__, "null pointer");
 	const size_t npx = (size_t)w * h, need = pixel_quantiles_state_bytes((int64_t)npx, npercents);
-	if (state_bytes < need || (uintptr_t)d_state % 8 != 0)
-	{
-		log_error("rir_pixel_quantiles_push_device: the state must be 8-byte aligned and hold rir_pixel_quantiles_state_bytes() bytes");
+	if (!workspace_ok(__func__, d_state, state_bytes, need, "state", "rir_pixel_quantiles_state_bytes()"))
 		return -1;
-	}
 	if (nframes == 0)
 		return 0;
-	if (ranges_overlap(d_state, need, d_frames, npx * nframes * 2))
-	{
-		log_error("rir_pixel_quantiles_push_device: the state overlaps the frames");
-		return -1;
-	}
+	if (outputs_overlap({{d_frames, npx * nframes * 2}}, {{d_state, need}}))
+		return refuse(__func__, "the state overlaps the frames");
 	return hip_ok(launch_pixel_quantiles_count(d_frames, (int64_t)npx, nframes, npercents, pass, d_state, as_stream(stream)), "pixel_quantiles_push") ? 0
 																																						: -1;
 }
@@ -1036,31 +932,19 @@ RIR_EXPORT int rir_pixel_quantiles_resolve_device(int w, int h, const float *per
 	if (!device_ready())
 		return -1;
 	if (!pixel_quantiles_args(w, h, npercents) || pass < 0 || pass >= PIXEL_QUANTILE_PASSES || total_frames < 0 || total_frames > 2147483647ll)
-	{
-		log_error("rir_pixel_quantiles_resolve_device: invalid argument (w, h >= 1 with w * h < 2^31, 1 <= npercents <= 8, "
-				  "0 <= pass < rir_pixel_quantiles_passes(), 0 <= total_frames <= 2^31 - 1)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, 1 <= npercents <= 8, 0 <= pass < rir_pixel_quantiles_passes(), "
+								"0 <= total_frames <= 2^31 - 1)");
 	const bool last = pass == PIXEL_QUANTILE_PASSES - 1;
 	if (!percents || !d_state || (last && !d_values))
-	{
-		log_error("rir_pixel_quantiles_resolve_device: null pointer");
-		return -1;
-	}
+		return refuse(__func__, "null pointer");
 	QuantilePercents pc{};
-	if (!pixel_quantiles_percents("rir_pixel_quantiles_resolve_device", percents, npercents, pc))
+	if (!percents_ok(__func__, percents, npercents, pc))
 		return -1;
 	const size_t npx = (size_t)w * h, need = pixel_quantiles_state_bytes((int64_t)npx, npercents);
-	if (state_bytes < need || (uintptr_t)d_state % 8 != 0)
-	{
-		log_error("rir_pixel_quantiles_resolve_device: the state must be 8-byte aligned and hold rir_pixel_quantiles_state_bytes() bytes");
+	if (!workspace_ok(__func__, d_state, state_bytes, need, "state", "rir_pixel_quantiles_state_bytes()"))
 		return -1;
-	}
-	if (last && ranges_overlap(d_values, npx * npercents * 4, d_state, need))
-	{
-		log_error("rir_pixel_quantiles_resolve_device: the values overlap the state");
-		return -1;
-	}
+	if (last && outputs_overlap({{d_state, need}}, {{d_values, npx * npercents * 4}}))
+		return refuse(__func__, "the values overlap the state");
 	return hip_ok(launch_pixel_quantiles_resolve((int64_t)npx, pc, npercents, pass, (uint32_t)total_frames, d_state, last ? d_values : nullptr,
 												 as_stream(stream)),
 				  "pixel_quantiles_resolve")
@@ -1074,30 +958,17 @@ RIR_EXPORT int rir_pixel_quantiles_device(const unsigned short *d_frames, int w,
 	if (!device_ready())
 		return -1;
 	if (!pixel_quantiles_args(w, h, npercents) || nframes < 0)
-	{
-		log_error("rir_pixel_quantiles_device: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, 1 <= npercents <= 8)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, 1 <= npercents <= 8)");
 	if ((nframes > 0 && !d_frames) || !percents || !d_values || !d_work)
-	{
-		log_error("rir_pixel_quantiles_device: null pointer");
-		return -1;
-	}
+		return refuse(__func__, "null pointer");
 	QuantilePercents pc{};
-	if (!pixel_quantiles_percents("rir_pixel_quantiles_device", percents, npercents, pc))
+	if (!percents_ok(__func__, percents, npercents, pc))
 		return -1;
 	const size_t npx = (size_t)w * h, need = pixel_quantiles_state_bytes((int64_t)npx, npercents), out = npx * npercents * 4;
-	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
-	{
-		log_error("rir_pixel_quantiles_device: the workspace must be 8-byte aligned and hold rir_pixel_quantiles_workspace_bytes() bytes");
+	if (!workspace_ok(__func__, d_work, work_bytes, need, "workspace", "rir_pixel_quantiles_workspace_bytes()"))
 		return -1;
-	}
-	if (ranges_overlap(d_values, out, d_work, need) ||
-		(nframes > 0 && (ranges_overlap(d_values, out, d_frames, npx * nframes * 2) || ranges_overlap(d_work, need, d_frames, npx * nframes * 2))))
-	{
-		log_error("rir_pixel_quantiles_device: the values or the workspace overlap the frames or each other");
-		return -1;
-	}
+	if (outputs_overlap({{d_frames, npx * nframes * 2}}, {{d_values, out}, {d_work, need}})) // no frames: zero bytes, absent
+		return refuse(__func__, "the values or the workspace overlap the frames or each other");
 	hipStream_t st = as_stream(stream);
 	if (nframes == 0) // no population: -1 everywhere
 		return hip_ok(hipMemsetAsync(d_values, 0xFF, out, st), "hipMemsetAsync") ? 0 : -1;
@@ -1123,31 +994,19 @@ RIR_EXPORT int rir_track_components_device(const int *d_labels, const int *d_cou
 	if (!device_ready())
 		return -1;
 	if (!track_geometry_ok(w, h, nframes, nlabels) || table_entries < 1)
-	{
-		log_error("rir_track_components_device: invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, nframes >= 0, nlabels >= 1 with "
-				  "nframes * nlabels <= 0x7FFF0000, table_entries >= 1)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, nframes >= 0, nlabels >= 1 with "
+								"nframes * nlabels <= 0x7FFF0000, table_entries >= 1)");
 	if (!d_info || !d_first_frame || !d_last_frame || !d_first_label || !d_components || !d_work || (nframes > 0 && (!d_labels || !d_track_of)))
-	{
-		log_error("rir_track_components_device: null pointer");
-		return -1;
-	}
+		return refuse(__func__, "null pointer");
 	const size_t npx = (size_t)w * h, nodes = (size_t)nframes * nlabels, need = track_workspace_bytes(w, h, nframes, nlabels);
-	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
-	{
-		log_error("rir_track_components_device: the workspace must be 8-byte aligned and hold rir_track_components_workspace_bytes() bytes");
+	if (!workspace_ok(__func__, d_work, work_bytes, need, "workspace", "rir_track_components_workspace_bytes()"))
 		return -1;
-	}
 	const size_t stack = npx * nframes * 4, table = (size_t)table_entries * 4;
 	// d_dst == d_labels: the labels are left out of the inputs, their range is checked against everything else as the last output, d_dst
 	if (outputs_overlap({{d_dst == d_labels ? nullptr : d_labels, stack}, {d_counts, (size_t)nframes * 4}},
 						{{d_track_of, nodes * 4}, {d_info, 8}, {d_first_frame, table}, {d_last_frame, table}, {d_first_label, table},
 						 {d_components, table}, {d_work, need}, {d_dst, stack}}))
-	{
-		log_error("rir_track_components_device: an output or the workspace overlaps an input or another output (only d_dst == d_labels may)");
-		return -1;
-	}
+		return refuse(__func__, "an output or the workspace overlaps an input or another output (only d_dst == d_labels may)");
 	return hip_ok(launch_track_components(d_labels, d_counts, w, h, nframes, nlabels, d_track_of, d_info, d_first_frame, d_last_frame, d_first_label,
 										  d_components, table_entries, d_dst, d_work, as_stream(stream)),
 				  "track_components")
@@ -1167,31 +1026,19 @@ RIR_EXPORT int rir_polygon_map_device(const double *d_xy, const int *d_npts, con
 	if (!device_ready())
 		return -1;
 	if (!polygon_geometry_ok(w, h, nmaps, npoly, max_pts) || (sets_per_map != 0 && sets_per_map != 1))
-	{
-		log_error("rir_polygon_map_device: invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, nmaps >= 0, 0 <= npoly <= 65536, 1 <= max_pts <= 1024, "
-				  "sets_per_map 0 or 1)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, nmaps >= 0, 0 <= npoly <= 65536, 1 <= max_pts <= 1024, "
+								"sets_per_map 0 or 1)");
 	if (nmaps == 0)
 		return 0;
 	if (!d_dst || !d_work || (npoly > 0 && (!d_xy || !d_npts)))
-	{
-		log_error("rir_polygon_map_device: null pointer");
-		return -1;
-	}
+		return refuse(__func__, "null pointer");
 	const size_t need = polygon_map_workspace(w, h, nmaps, npoly, max_pts);
-	if (work_bytes < need || (uintptr_t)d_work % 8 != 0)
-	{
-		log_error("rir_polygon_map_device: the workspace must be 8-byte aligned and hold rir_polygon_map_workspace_bytes() bytes");
+	if (!workspace_ok(__func__, d_work, work_bytes, need, "workspace", "rir_polygon_map_workspace_bytes()"))
 		return -1;
-	}
 	const size_t polys = (size_t)npoly * (sets_per_map ? nmaps : 1);
 	if (outputs_overlap({{d_xy, polys * max_pts * 16}, {d_npts, polys * 4}, {d_values, (size_t)npoly * 4}, {d_shifts, (size_t)nmaps * 16}},
 						{{d_dst, (size_t)w * h * nmaps * 4}, {d_work, need}}))
-	{
-		log_error("rir_polygon_map_device: the maps or the workspace overlap an input or each other");
-		return -1;
-	}
+		return refuse(__func__, "the maps or the workspace overlap an input or each other");
 	return hip_ok(launch_polygon_map(d_xy, d_npts, d_values, npoly, max_pts, nmaps, sets_per_map, d_shifts, w, h, background, d_dst, d_work,
 									 as_stream(stream)),
 				  "polygon_map")
@@ -1383,77 +1230,116 @@ RIR_EXPORT int rir_filter_chain(int bad_pixels_handle, unsigned short *in, unsig
 	return hand_out(s, out, dst, bytes, st) ? 0 : -1;
 }
 
-// Extension: the temporal median of a host stack, in slabs of at most TEMPORAL_SLAB_BYTES of output frames, each read with r frames of halo
-// on either side (the windows of a slab's outputs are then those of the whole stack).  Synchronous.  0 / -1.
-constexpr size_t TEMPORAL_SLAB_BYTES = (size_t)64 << 20;
+// ---- extension entries on host stacks: through the device in slabs, synchronous, 0 / -1 ---------------------------------------------------
+namespace
+{
+	constexpr size_t HOST_SLAB_BYTES = (size_t)64 << 20; // what one slab of a host stack takes on the device at most, per kind of buffer
+
+	struct Out // an output of a host stack entry: `cell` bytes per cell, at `dev` for the slab; a null `host`: not asked for
+	{
+		void *host;
+		const void *dev;
+		size_t cell;
+	};
+
+	// What a host stack entry queues on the library's stream.  A copy with a null address on either side is a group that was not asked for
+	// (or an input that went up once): nothing is queued.  An entry with a failed step leaves through fail(), so that no copy is still on
+	// its way into the caller's memory, or out of it, when the caller has the error.
+	struct Stager
+	{
+		hipStream_t st = default_stream();
+
+		// frames per slab: what HOST_SLAB_BYTES hold at each of the per-frame costs, at least one, at most nframes
+		static int slab(int nframes, std::initializer_list<size_t> per_frame_bytes)
+		{
+			size_t n = (size_t)nframes;
+			for (size_t b : per_frame_bytes)
+				n = std::min(n, HOST_SLAB_BYTES / b);
+			return (int)std::max<size_t>(1, n);
+		}
+		bool copy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) const
+		{
+			return !dst || !src || hip_ok(hipMemcpyAsync(dst, src, bytes, kind, st), "hipMemcpyAsync");
+		}
+		bool up(void *dev, const void *host, size_t bytes) const { return copy(dev, host, bytes, hipMemcpyHostToDevice); }
+		bool down(void *host, const void *dev, size_t bytes) const { return copy(host, dev, bytes, hipMemcpyDeviceToHost); }
+		// the slab's n cells of every output, to cell `at` of the caller's arrays
+		template <size_t N>
+		bool down(const Out (&outs)[N], size_t at, size_t n) const
+		{
+			for (const Out &o : outs)
+				if (!down(o.host ? static_cast<char *>(o.host) + at * o.cell : nullptr, o.dev, n * o.cell))
+					return false;
+			return true;
+		}
+		bool wait(const char *what) const { return hip_ok(wait_stream(st), what); }
+		int fail() const
+		{
+			(void)wait_stream(st); // what was queued is done before the buffers go
+			return -1;
+		}
+	};
+} // namespace
+
+// The temporal median of a host stack, in slabs of output frames, each read with r frames of halo on either side (the windows of a slab's
+// outputs are then those of the whole stack).
 RIR_EXPORT int rir_temporal_median(const unsigned short *src, unsigned short *dst, int w, int h, int nframes, int window, int threshold, int rows)
 {
 	if (!device_ready())
 		return -1;
 	if (!src || !dst || w <= 0 || h <= 0 || nframes <= 0 || window < 1 || window > 63 || window % 2 == 0 || threshold < 0 || threshold > 65535 ||
 		rows < 0 || rows > h)
-	{
-		log_error("rir_temporal_median: invalid argument (odd window 1..63, threshold 0..65535, 0 <= rows <= h)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (odd window 1..63, threshold 0..65535, 0 <= rows <= h)");
 	const int r = window / 2;
-	const size_t frame = (size_t)w * h * 2;
-	const int slab = (int)std::max<size_t>(1, std::min<size_t>(TEMPORAL_SLAB_BYTES / frame, (size_t)nframes));
+	const size_t npx = (size_t)w * h, frame = npx * 2;
+	const int slab = Stager::slab(nframes, {frame});
 	DeviceBuffer in, out;
 	if (!in.reserve(frame * (size_t)std::min(nframes, slab + 2 * r)) || !out.reserve(frame * slab))
 		return -1;
-	hipStream_t st = default_stream();
+	Stager s;
 	for (int o = 0; o < nframes; o += slab)
 	{
 		const int count = std::min(slab, nframes - o), lo = std::max(0, o - r), hi = std::min(nframes, o + count + r);
-		if (!hip_ok(hipMemcpyAsync(in.ptr, src + (size_t)lo * w * h, frame * (hi - lo), hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
-			rir_temporal_median_device(in.as<unsigned short>(), out.as<unsigned short>(), w, h, hi - lo, o - lo, count, 1, window, threshold, rows, st) != 0 ||
-			!hip_ok(hipMemcpyAsync(dst + (size_t)o * w * h, out.ptr, frame * count, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
-			!hip_ok(wait_stream(st), "temporal_median"))
-			return -1;
+		if (!s.up(in.ptr, src + lo * npx, frame * (hi - lo)) ||
+			rir_temporal_median_device(in.as<unsigned short>(), out.as<unsigned short>(), w, h, hi - lo, o - lo, count, 1, window, threshold, rows, s.st) != 0 ||
+			!s.down(dst + o * npx, out.ptr, frame * count) || !s.wait("temporal_median"))
+			return s.fail();
 	}
 	return 0;
 }
 
-// Extension: flat morphology of a host stack, sent through the device in slabs of at most MORPHOLOGY_SLAB_BYTES of frames (frames are
-// independent: any split gives the same bits).  dst may be src.  Synchronous.  0 / -1.
-constexpr size_t MORPHOLOGY_SLAB_BYTES = (size_t)64 << 20;
+// Flat morphology of a host stack (frames are independent: any split gives the same bits).  dst may be src.
 RIR_EXPORT int rir_morphology(int type, const void *src, void *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows)
 {
 	const char *bad = morphology_args(type, src, dst, w, h, nframes, op, size_x, size_y, rows);
 	const size_t frame = (size_t)w * h * (type == 'H' ? 2 : 1);
-	const uintptr_t bytes = bad ? 0 : frame * (size_t)nframes, s = (uintptr_t)src, d = (uintptr_t)dst;
-	if (!bad && s != d && s < d + bytes && d < s + bytes)
+	const uintptr_t bytes = bad ? 0 : frame * (size_t)nframes, from = (uintptr_t)src, to = (uintptr_t)dst;
+	if (!bad && from != to && from < to + bytes && to < from + bytes)
 		bad = "the source and the destination overlap (dst == src is allowed)";
 	if (bad)
-	{
-		log_error(std::string("rir_morphology: ") + bad);
-		return -1;
-	}
+		return refuse(__func__, bad);
 	if (nframes == 0)
 		return 0;
 	if (!device_ready())
 		return -1;
-	const int slab = (int)std::max<size_t>(1, std::min<size_t>(MORPHOLOGY_SLAB_BYTES / frame, (size_t)nframes));
+	const int slab = Stager::slab(nframes, {frame});
 	DeviceBuffer in, out;
 	if (!in.reserve(frame * slab) || !out.reserve(frame * slab))
 		return -1;
-	hipStream_t st = default_stream();
+	Stager s;
 	for (int o = 0; o < nframes; o += slab)
 	{
 		const int count = std::min(slab, nframes - o);
-		if (!hip_ok(hipMemcpyAsync(in.ptr, static_cast<const char *>(src) + frame * o, frame * count, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
-			rir_morphology_device(type, in.ptr, out.ptr, w, h, count, op, size_x, size_y, rows, st) != 0 ||
-			!hip_ok(hipMemcpyAsync(static_cast<char *>(dst) + frame * o, out.ptr, frame * count, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
-			!hip_ok(wait_stream(st), "morphology"))
-			return -1;
+		if (!s.up(in.ptr, static_cast<const char *>(src) + frame * o, frame * count) ||
+			rir_morphology_device(type, in.ptr, out.ptr, w, h, count, op, size_x, size_y, rows, s.st) != 0 ||
+			!s.down(static_cast<char *>(dst) + frame * o, out.ptr, frame * count) || !s.wait("morphology"))
+			return s.fail();
 	}
 	return 0;
 }
 
-// Extension: per-region statistics of a host stack, sent in slabs of at most REGION_SLAB_BYTES of frames (with their label maps when there
-// is one per frame; a shared map goes up once).  Synchronous.  0 / -1.
-constexpr size_t REGION_SLAB_BYTES = (size_t)64 << 20;
+// Per-region statistics of a host stack: a shared label map goes up once, per-frame maps go up with their frames; a slab is also bounded by
+// what its outputs and workspace take on the device.
 RIR_EXPORT int rir_region_stats(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
 								int *count, long long *sum, long long *sumsq, int *min, int *max, int *argmin, int *argmax)
 {
@@ -1461,48 +1347,38 @@ RIR_EXPORT int rir_region_stats(const unsigned short *frames, const int *labels,
 		return -1;
 	if (!region_stats_args(w, h, nframes, labels_per_frame, nregions) || !frames || !labels || !count || !sum || !sumsq || !min || !max || !argmin ||
 		!argmax)
-	{
-		log_error("rir_region_stats: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, 1 <= nregions <= 2^24, "
-				  "no null pointer)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, 1 <= nregions <= 2^24, "
+								"no null pointer)");
 	if (nframes == 0)
 		return 0;
-	const size_t npx = (size_t)w * h, frame = npx * 2, K = (size_t)nregions;
-	const size_t per_frame_out = K * (5 * 4 + 2 * 8 + 32); // outputs and workspace of one frame on the device
-	const int slab = (int)std::max<size_t>(1, std::min<size_t>({REGION_SLAB_BYTES / frame, REGION_SLAB_BYTES / per_frame_out, (size_t)nframes}));
+	const size_t npx = (size_t)w * h, K = (size_t)nregions;
+	const int slab = Stager::slab(nframes, {npx * 2, K * (5 * 4 + 2 * 8 + 32)}); // a frame; its outputs and workspace
 	const size_t cells = (size_t)slab * K, work = region_stats_workspace((int64_t)npx, slab, nregions);
 	DeviceBuffer fr, lab, o32, o64, ws;
-	if (!fr.reserve(frame * slab) || !lab.reserve(npx * 4 * (labels_per_frame ? slab : 1)) || !o32.reserve(cells * 4 * 5) || !o64.reserve(cells * 8 * 2) ||
+	if (!fr.reserve(npx * 2 * slab) || !lab.reserve(npx * 4 * (labels_per_frame ? slab : 1)) || !o32.reserve(cells * 4 * 5) || !o64.reserve(cells * 8 * 2) ||
 		!ws.reserve(work))
-		return -1;
-	hipStream_t st = default_stream();
-	if (!labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels, npx * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))
 		return -1;
 	int *d32 = o32.as<int>();
 	long long *d64 = o64.as<long long>();
+	const Out outs[] = {{count, d32, 4}, {min, d32 + cells, 4}, {max, d32 + 2 * cells, 4}, {argmin, d32 + 3 * cells, 4}, {argmax, d32 + 4 * cells, 4},
+						{sum, d64, 8}, {sumsq, d64 + cells, 8}};
+	Stager s;
+	if (!s.up(lab.ptr, labels_per_frame ? nullptr : labels, npx * 4))
+		return s.fail();
 	for (int o = 0; o < nframes; o += slab)
 	{
 		const int c = std::min(slab, nframes - o);
-		const size_t n = (size_t)c * K, at = (size_t)o * K;
-		if (!hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, frame * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
-			(labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels + (size_t)o * npx, npx * 4 * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
+		if (!s.up(fr.ptr, frames + o * npx, npx * 2 * c) || !s.up(lab.ptr, labels_per_frame ? labels + o * npx : nullptr, npx * 4 * c) ||
 			rir_region_stats_device(fr.as<unsigned short>(), lab.as<int>(), w, h, c, labels_per_frame, nregions, d32, d64, d64 + cells, d32 + cells,
-									d32 + 2 * cells, d32 + 3 * cells, d32 + 4 * cells, ws.ptr, work, st) != 0)
-			return -1;
-		int *outs32[5] = {count + at, min + at, max + at, argmin + at, argmax + at};
-		for (int k = 0; k < 5; ++k)
-			if (!hip_ok(hipMemcpyAsync(outs32[k], d32 + (size_t)k * cells, n * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync"))
-				return -1;
-		if (!hip_ok(hipMemcpyAsync(sum + at, d64, n * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
-			!hip_ok(hipMemcpyAsync(sumsq + at, d64 + cells, n * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") || !hip_ok(wait_stream(st), "region_stats"))
-			return -1;
+									d32 + 2 * cells, d32 + 3 * cells, d32 + 4 * cells, ws.ptr, work, s.st) != 0 ||
+			!s.down(outs, o * K, c * K) || !s.wait("region_stats"))
+			return s.fail();
 	}
 	return 0;
 }
 
-// Extension: per-region geometry of host label maps, weighted by a host stack when `frames` is given; staged as rir_region_stats stages its
-// arguments (without frames the slabs are label maps).  Synchronous.  0 / -1.
+// Per-region geometry of host label maps, weighted by a host stack when `frames` is given; staged as rir_region_stats stages its arguments
+// (without frames the slabs are label maps).
 RIR_EXPORT int rir_region_geometry(const int *labels, const unsigned short *frames, int w, int h, int nframes, int labels_per_frame, int nregions,
 								   int *count, int *bbox, long long *moments, long long *weighted)
 {
@@ -1510,93 +1386,73 @@ RIR_EXPORT int rir_region_geometry(const int *labels, const unsigned short *fram
 		return -1;
 	if (!region_geometry_args(w, h, nframes, labels_per_frame, nregions, frames != nullptr) || !labels || !count || !bbox || !moments ||
 		(frames != nullptr) != (weighted != nullptr))
-	{
-		log_error(std::string("rir_region_geometry: ") + REGION_GEOMETRY_ARGS + ", or a null pointer (weighted is null exactly when frames is)");
-		return -1;
-	}
+		return refuse(__func__, std::string(REGION_GEOMETRY_ARGS) + ", or a null pointer (weighted is null exactly when frames is)");
 	if (nframes == 0)
 		return 0;
 	const size_t npx = (size_t)w * h, frame = npx * (frames ? 2 : 0) + npx * (labels_per_frame ? 4 : 0), K = (size_t)nregions;
-	const size_t per_frame_out = K * (4 + 16 + 40 + 24); // the outputs of one frame on the device
-	const int slab =
-		(int)std::max<size_t>(1, std::min<size_t>({REGION_SLAB_BYTES / std::max<size_t>(frame, 1), REGION_SLAB_BYTES / per_frame_out, (size_t)nframes}));
+	const int slab = Stager::slab(nframes, {std::max<size_t>(frame, 1), K * (4 + 16 + 40 + 24)}); // what goes up per frame; a frame's outputs
 	const size_t cells = (size_t)slab * K;
 	DeviceBuffer fr, lab, o32, o64, ws;
 	if ((frames && !fr.reserve(npx * 2 * slab)) || !lab.reserve(npx * 4 * (labels_per_frame ? slab : 1)) || !o32.reserve(cells * 4 * 5) ||
 		!o64.reserve(cells * 8 * 8) || !ws.reserve(GEOMETRY_WORK_BYTES))
 		return -1;
-	hipStream_t st = default_stream();
-	if (!labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels, npx * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))
-		return -1;
 	int *d_count = o32.as<int>(), *d_bbox = d_count + cells;
 	long long *d_mom = o64.as<long long>(), *d_wgt = frames ? d_mom + 5 * cells : nullptr;
+	const Out outs[] = {{count, d_count, 4}, {bbox, d_bbox, 16}, {moments, d_mom, 40}, {weighted, d_wgt, 24}};
+	Stager s;
+	if (!s.up(lab.ptr, labels_per_frame ? nullptr : labels, npx * 4))
+		return s.fail();
 	for (int o = 0; o < nframes; o += slab)
 	{
 		const int c = std::min(slab, nframes - o);
-		const size_t n = (size_t)c * K, at = (size_t)o * K;
-		if ((frames && !hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, npx * 2 * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
-			(labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels + (size_t)o * npx, npx * 4 * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
+		if (!s.up(fr.ptr, frames ? frames + o * npx : nullptr, npx * 2 * c) || !s.up(lab.ptr, labels_per_frame ? labels + o * npx : nullptr, npx * 4 * c) ||
 			rir_region_geometry_device(lab.as<int>(), frames ? fr.as<unsigned short>() : nullptr, w, h, c, labels_per_frame, nregions, d_count, d_bbox, d_mom,
-									   d_wgt, ws.ptr, GEOMETRY_WORK_BYTES, st) != 0 ||
-			!hip_ok(hipMemcpyAsync(count + at, d_count, n * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
-			!hip_ok(hipMemcpyAsync(bbox + at * 4, d_bbox, n * 16, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
-			!hip_ok(hipMemcpyAsync(moments + at * 5, d_mom, n * 40, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
-			(frames && !hip_ok(hipMemcpyAsync(weighted + at * 3, d_wgt, n * 24, hipMemcpyDeviceToHost, st), "hipMemcpyAsync")) ||
-			!hip_ok(wait_stream(st), "region_geometry"))
-			return -1;
+									   d_wgt, ws.ptr, GEOMETRY_WORK_BYTES, s.st) != 0 ||
+			!s.down(outs, o * K, c * K) || !s.wait("region_geometry"))
+			return s.fail();
 	}
 	return 0;
 }
 
-// Extension: per-region quantiles of a host stack, staged as rir_region_stats stages its arguments.  Synchronous.  0 / -1.
+// Per-region quantiles of a host stack, staged as rir_region_stats stages its arguments.
 RIR_EXPORT int rir_region_quantiles(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
 									const float *percents, int npercents, int *count, int *values)
 {
 	if (!device_ready())
 		return -1;
 	if (!region_quantiles_args(w, h, nframes, labels_per_frame, nregions, npercents) || !frames || !labels || !percents || !count || !values)
-	{
-		log_error("rir_region_quantiles: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, "
-				  "1 <= nregions <= 65536, 1 <= npercents <= 8, no null pointer)");
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, labels_per_frame 0 or 1, 1 <= nregions <= 65536, "
+								"1 <= npercents <= 8, no null pointer)");
+	QuantilePercents pc{};
+	if (!percents_ok(__func__, percents, npercents, pc))
 		return -1;
-	}
-	for (int j = 0; j < npercents; ++j)
-		if (!(percents[j] >= 0.0f && percents[j] <= 1.0f))
-		{
-			log_error("rir_region_quantiles: every percent must be in [0, 1]");
-			return -1;
-		}
 	if (nframes == 0)
 		return 0;
-	const size_t npx = (size_t)w * h, frame = npx * 2, K = (size_t)nregions, Q = (size_t)npercents;
-	const size_t per_frame_out = K * 4 * (1 + Q) + region_quantiles_frame_bytes(nregions, npercents); // outputs and workspace of one frame
-	const int slab = (int)std::max<size_t>(1, std::min<size_t>({REGION_SLAB_BYTES / frame, REGION_SLAB_BYTES / per_frame_out, (size_t)nframes}));
+	const size_t npx = (size_t)w * h, K = (size_t)nregions, Q = (size_t)npercents;
+	const int slab = Stager::slab(nframes, {npx * 2, K * 4 * (1 + Q) + region_quantiles_frame_bytes(nregions, npercents)}); // as rir_region_stats
 	const size_t cells = (size_t)slab * K, work = rir_region_quantiles_workspace_bytes(w, h, slab, labels_per_frame, nregions, npercents);
 	DeviceBuffer fr, lab, o32, ws;
-	if (!fr.reserve(frame * slab) || !lab.reserve(npx * 4 * (labels_per_frame ? slab : 1)) || !o32.reserve(cells * 4 * (1 + Q)) || !ws.reserve(work))
-		return -1;
-	hipStream_t st = default_stream();
-	if (!labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels, npx * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))
+	if (!fr.reserve(npx * 2 * slab) || !lab.reserve(npx * 4 * (labels_per_frame ? slab : 1)) || !o32.reserve(cells * 4 * (1 + Q)) || !ws.reserve(work))
 		return -1;
 	int *d_count = o32.as<int>(), *d_values = d_count + cells;
+	const Out outs[] = {{count, d_count, 4}, {values, d_values, Q * 4}};
+	Stager s;
+	if (!s.up(lab.ptr, labels_per_frame ? nullptr : labels, npx * 4))
+		return s.fail();
 	for (int o = 0; o < nframes; o += slab)
 	{
 		const int c = std::min(slab, nframes - o);
-		const size_t n = (size_t)c * K, at = (size_t)o * K;
-		if (!hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, frame * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
-			(labels_per_frame && !hip_ok(hipMemcpyAsync(lab.ptr, labels + (size_t)o * npx, npx * 4 * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
+		if (!s.up(fr.ptr, frames + o * npx, npx * 2 * c) || !s.up(lab.ptr, labels_per_frame ? labels + o * npx : nullptr, npx * 4 * c) ||
 			rir_region_quantiles_device(fr.as<unsigned short>(), lab.as<int>(), w, h, c, labels_per_frame, nregions, percents, npercents, d_count, d_values,
-										ws.ptr, work, st) != 0 ||
-			!hip_ok(hipMemcpyAsync(count + at, d_count, n * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
-			!hip_ok(hipMemcpyAsync(values + at * Q, d_values, n * Q * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
-			!hip_ok(wait_stream(st), "region_quantiles"))
-			return -1;
+										ws.ptr, work, s.st) != 0 ||
+			!s.down(outs, o * K, c * K) || !s.wait("region_quantiles"))
+			return s.fail();
 	}
 	return 0;
 }
 
-// Extension: per-pixel statistics over time of a host stack, sent in slabs of at most REGION_SLAB_BYTES of frames that accumulate on the
-// device; the outputs come back once.  A group (sum, sumsq / min, max, argmin, argmax) may be null.  Synchronous.  0 / -1.
+// Per-pixel statistics over time of a host stack: the slabs accumulate on the device, the outputs come back once.  A group (sum, sumsq /
+// min, max, argmin, argmax) may be null.
 RIR_EXPORT int rir_pixel_stats(const unsigned short *frames, int w, int h, int nframes, long long *sum, long long *sumsq, int *min, int *max,
 							   int *argmin, int *argmax)
 {
@@ -1605,42 +1461,32 @@ RIR_EXPORT int rir_pixel_stats(const unsigned short *frames, int w, int h, int n
 	const bool sums = sum || sumsq, extremes = min || max || argmin || argmax;
 	if (!pixel_stats_args(w, h, nframes) || !frames || (sums && (!sum || !sumsq)) || (extremes && (!min || !max || !argmin || !argmax)) ||
 		(!sums && !extremes))
-	{
-		log_error("rir_pixel_stats: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, frames given, each group of outputs all given "
-				  "or all null and one given)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, frames given, each group of outputs all given "
+								"or all null and one given)");
 	if (nframes == 0)
 		return 0;
-	const size_t npx = (size_t)w * h, frame = npx * 2;
-	const int slab = (int)std::max<size_t>(1, std::min<size_t>(REGION_SLAB_BYTES / frame, (size_t)nframes));
+	const size_t npx = (size_t)w * h;
+	const int slab = Stager::slab(nframes, {npx * 2});
 	const size_t work = pixel_stats_workspace((int64_t)npx, slab);
 	DeviceBuffer fr, o32, o64, ws;
-	if (!fr.reserve(frame * slab) || !ws.reserve(work) || (sums && !o64.reserve(npx * 8 * 2)) || (extremes && !o32.reserve(npx * 4 * 4)))
+	if (!fr.reserve(npx * 2 * slab) || !ws.reserve(work) || (sums && !o64.reserve(npx * 8 * 2)) || (extremes && !o32.reserve(npx * 4 * 4)))
 		return -1;
-	hipStream_t st = default_stream();
-	long long *d64 = sums ? o64.as<long long>() : nullptr;
-	int *d32 = extremes ? o32.as<int>() : nullptr;
+	const auto d64 = [&](int k) { return sums ? o64.as<long long>() + k * npx : nullptr; }; // a group not asked for stays null
+	const auto d32 = [&](int k) { return extremes ? o32.as<int>() + k * npx : nullptr; };
+	const Out outs[] = {{sum, d64(0), 8}, {sumsq, d64(1), 8}, {min, d32(0), 4}, {max, d32(1), 4}, {argmin, d32(2), 4}, {argmax, d32(3), 4}};
+	Stager s;
 	for (int o = 0; o < nframes; o += slab)
 	{
 		const int c = std::min(slab, nframes - o);
-		if (!hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, frame * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
-			rir_pixel_stats_device(fr.as<unsigned short>(), w, h, c, o, o != 0, d64, sums ? d64 + npx : nullptr, d32, extremes ? d32 + npx : nullptr,
-								   extremes ? d32 + 2 * npx : nullptr, extremes ? d32 + 3 * npx : nullptr, ws.ptr, work, st) != 0)
-			return -1;
+		if (!s.up(fr.ptr, frames + o * npx, npx * 2 * c) ||
+			rir_pixel_stats_device(fr.as<unsigned short>(), w, h, c, o, o != 0, d64(0), d64(1), d32(0), d32(1), d32(2), d32(3), ws.ptr, work, s.st) != 0)
+			return s.fail();
 	}
-	if (sums && (!hip_ok(hipMemcpyAsync(sum, d64, npx * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") ||
-				 !hip_ok(hipMemcpyAsync(sumsq, d64 + npx, npx * 8, hipMemcpyDeviceToHost, st), "hipMemcpyAsync")))
-		return -1;
-	int *outs32[4] = {min, max, argmin, argmax};
-	for (int k = 0; extremes && k < 4; ++k)
-		if (!hip_ok(hipMemcpyAsync(outs32[k], d32 + (size_t)k * npx, npx * 4, hipMemcpyDeviceToHost, st), "hipMemcpyAsync"))
-			return -1;
-	return hip_ok(wait_stream(st), "pixel_stats") ? 0 : -1;
+	return s.down(outs, 0, npx) && s.wait("pixel_stats") ? 0 : s.fail();
 }
 
-// Extension: per-pixel quantiles over time of a host stack.  A stack of at most PIXEL_QUANTILES_RESIDENT_BYTES goes up once and runs the one-call
-// form; a larger one goes up in slabs of at most REGION_SLAB_BYTES, once per pass, through the streaming form: the same bits.  Synchronous.  0 / -1.
+// Per-pixel quantiles over time of a host stack.  A stack of at most PIXEL_QUANTILES_RESIDENT_BYTES goes up once and runs the one-call form; a
+// larger one goes up in slabs, once per pass, through the streaming form: the same bits.
 constexpr size_t PIXEL_QUANTILES_RESIDENT_BYTES = (size_t)256 << 20;
 
 RIR_EXPORT int rir_pixel_quantiles(const unsigned short *frames, int w, int h, int nframes, const float *percents, int npercents, int *values)
@@ -1648,51 +1494,41 @@ RIR_EXPORT int rir_pixel_quantiles(const unsigned short *frames, int w, int h, i
 	if (!device_ready())
 		return -1;
 	if (!pixel_quantiles_args(w, h, npercents) || nframes < 0 || (nframes > 0 && !frames) || !percents || !values)
-	{
-		log_error("rir_pixel_quantiles: invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, 1 <= npercents <= 8, no null pointer)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h < 2^31, nframes >= 0, 1 <= npercents <= 8, no null pointer)");
 	QuantilePercents pc{};
-	if (!pixel_quantiles_percents("rir_pixel_quantiles", percents, npercents, pc))
+	if (!percents_ok(__func__, percents, npercents, pc))
 		return -1;
 	const size_t npx = (size_t)w * h, frame = npx * 2, out = npx * npercents * 4, state = pixel_quantiles_state_bytes((int64_t)npx, npercents);
 	const bool resident = frame * (size_t)nframes <= PIXEL_QUANTILES_RESIDENT_BYTES;
-	const int slab = resident ? nframes : (int)std::max<size_t>(1, REGION_SLAB_BYTES / frame);
+	const int slab = resident ? nframes : Stager::slab(nframes, {frame});
 	DeviceBuffer fr, o32, ws;
 	if ((nframes > 0 && !fr.reserve(frame * slab)) || !o32.reserve(out) || !ws.reserve(state))
 		return -1;
-	hipStream_t st = default_stream();
-	if (resident)
-	{
-		if ((nframes > 0 && !hip_ok(hipMemcpyAsync(fr.ptr, frames, frame * nframes, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) ||
-			rir_pixel_quantiles_device(fr.as<unsigned short>(), w, h, nframes, percents, npercents, o32.as<int>(), ws.ptr, state, st) != 0)
-			return -1;
-	}
+	Stager s;
+	bool ok;
+	if (resident) // (no frames: nothing goes up, and the one-call form writes -1 everywhere)
+		ok = s.up(fr.ptr, frames, frame * nframes) &&
+			 rir_pixel_quantiles_device(fr.as<unsigned short>(), w, h, nframes, percents, npercents, o32.as<int>(), ws.ptr, state, s.st) == 0;
 	else
 	{
-		if (!hip_ok(hipMemsetAsync(ws.ptr, 0, state, st), "hipMemsetAsync"))
-			return -1;
-		for (int pass = 0; pass < PIXEL_QUANTILE_PASSES; ++pass)
+		ok = hip_ok(hipMemsetAsync(ws.ptr, 0, state, s.st), "hipMemsetAsync");
+		for (int pass = 0; ok && pass < PIXEL_QUANTILE_PASSES; ++pass)
 		{
-			for (int o = 0; o < nframes; o += slab)
+			for (int o = 0; ok && o < nframes; o += slab)
 			{
 				const int c = std::min(slab, nframes - o);
 				// the copy waits for the kernels that read the slab before it: one stream
-				if (!hip_ok(hipMemcpyAsync(fr.ptr, frames + (size_t)o * npx, frame * c, hipMemcpyHostToDevice, st), "hipMemcpyAsync") ||
-					rir_pixel_quantiles_push_device(fr.as<unsigned short>(), w, h, c, npercents, pass, ws.ptr, state, st) != 0)
-					return -1;
+				ok = s.up(fr.ptr, frames + o * npx, frame * c) &&
+					 rir_pixel_quantiles_push_device(fr.as<unsigned short>(), w, h, c, npercents, pass, ws.ptr, state, s.st) == 0;
 			}
-			if (rir_pixel_quantiles_resolve_device(w, h, percents, npercents, pass, nframes, ws.ptr, state, o32.as<int>(), st) != 0)
-				return -1;
+			ok = ok && rir_pixel_quantiles_resolve_device(w, h, percents, npercents, pass, nframes, ws.ptr, state, o32.as<int>(), s.st) == 0;
 		}
 	}
-	if (!hip_ok(hipMemcpyAsync(values, o32.ptr, out, hipMemcpyDeviceToHost, st), "hipMemcpyAsync"))
-		return -1;
-	return hip_ok(wait_stream(st), "pixel_quantiles") ? 0 : -1;
+	return ok && s.down(values, o32.ptr, out) && s.wait("pixel_quantiles") ? 0 : s.fail();
 }
 
-// Extension: polygon label maps into host memory.  The polygons, values and shifts go up once; the maps are made on the device in slabs of at
-// most REGION_SLAB_BYTES and come back slab by slab.  Synchronous.  0 / -1.
+// Polygon label maps into host memory.  The polygons, values and shifts go up once; the maps are made on the device slab by slab, each slab
+// from its own sets and shifts, and come back slab by slab.
 RIR_EXPORT int rir_polygon_map(const double *xy, const int *npts, const int *values, int npoly, int max_pts, int nmaps, int sets_per_map,
 							   const double *shifts, int w, int h, int background, int *dst)
 {
@@ -1700,39 +1536,32 @@ RIR_EXPORT int rir_polygon_map(const double *xy, const int *npts, const int *val
 		return -1;
 	if (!polygon_geometry_ok(w, h, nmaps, npoly, max_pts) || (sets_per_map != 0 && sets_per_map != 1) || (nmaps > 0 && !dst) ||
 		(nmaps > 0 && npoly > 0 && (!xy || !npts)))
-	{
-		log_error("rir_polygon_map: invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, nmaps >= 0, 0 <= npoly <= 65536, 1 <= max_pts <= 1024, "
-				  "sets_per_map 0 or 1, no null pointer)");
-		return -1;
-	}
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, nmaps >= 0, 0 <= npoly <= 65536, 1 <= max_pts <= 1024, "
+								"sets_per_map 0 or 1, no null pointer)");
 	if (nmaps == 0)
 		return 0;
 	const size_t npx = (size_t)w * h, polys = (size_t)npoly * (sets_per_map ? nmaps : 1), set_doubles = (size_t)npoly * max_pts * 2;
-	const int slab = (int)std::max<size_t>(1, std::min<size_t>(REGION_SLAB_BYTES / (npx * 4), (size_t)nmaps));
+	const int slab = Stager::slab(nmaps, {npx * 4});
 	const size_t work = polygon_map_workspace(w, h, slab, npoly, max_pts);
-	DeviceBuffer dxy, dn, dv, ds, maps, ws;
-	hipStream_t st = default_stream();
-	const bool with_values = npoly > 0 && values;
+	DeviceBuffer dxy, dn, dv, ds, maps, ws; // those of inputs that are not given stay null
 	if (!maps.reserve(npx * 4 * slab) || !ws.reserve(work) || (npoly > 0 && (!dxy.reserve(polys * max_pts * 16) || !dn.reserve(polys * 4))) ||
-		(with_values && !dv.reserve((size_t)npoly * 4)) || (shifts && !ds.reserve((size_t)nmaps * 16)))
-		return -1; // nothing is queued yet
-	bool ok = (npoly == 0 || (hip_ok(hipMemcpyAsync(dxy.ptr, xy, polys * max_pts * 16, hipMemcpyHostToDevice, st), "hipMemcpyAsync") &&
-							  hip_ok(hipMemcpyAsync(dn.ptr, npts, polys * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync"))) &&
-			  (!with_values || hip_ok(hipMemcpyAsync(dv.ptr, values, (size_t)npoly * 4, hipMemcpyHostToDevice, st), "hipMemcpyAsync")) &&
-			  (!shifts || hip_ok(hipMemcpyAsync(ds.ptr, shifts, (size_t)nmaps * 16, hipMemcpyHostToDevice, st), "hipMemcpyAsync"));
-	for (int o = 0; ok && o < nmaps; o += slab)
+		(npoly > 0 && values && !dv.reserve((size_t)npoly * 4)) || (shifts && !ds.reserve((size_t)nmaps * 16)))
+		return -1;
+	Stager s;
+	if (!s.up(dxy.ptr, xy, polys * max_pts * 16) || !s.up(dn.ptr, npts, polys * 4) || !s.up(dv.ptr, values, (size_t)npoly * 4) ||
+		!s.up(ds.ptr, shifts, (size_t)nmaps * 16))
+		return s.fail();
+	for (int o = 0; o < nmaps; o += slab)
 	{
 		const int c = std::min(slab, nmaps - o);
 		const size_t set = sets_per_map ? (size_t)o : 0;
-		ok = rir_polygon_map_device(npoly > 0 ? dxy.as<double>() + set * set_doubles : nullptr, npoly > 0 ? dn.as<int>() + set * npoly : nullptr,
-									with_values ? dv.as<int>() : nullptr, npoly, max_pts, c, sets_per_map, shifts ? ds.as<double>() + (size_t)o * 2 : nullptr, w,
-									h, background, maps.as<int>(), ws.ptr, work, st) == 0 &&
-			 hip_ok(hipMemcpyAsync(dst + (size_t)o * npx, maps.ptr, npx * 4 * c, hipMemcpyDeviceToHost, st), "hipMemcpyAsync") &&
-			 hip_ok(wait_stream(st), "polygon_map");
+		if (rir_polygon_map_device(dxy.ptr ? dxy.as<double>() + set * set_doubles : nullptr, dn.ptr ? dn.as<int>() + set * npoly : nullptr, dv.as<int>(),
+								   npoly, max_pts, c, sets_per_map, ds.ptr ? ds.as<double>() + (size_t)o * 2 : nullptr, w, h, background, maps.as<int>(),
+								   ws.ptr, work, s.st) != 0 ||
+			!s.down(dst + o * npx, maps.ptr, npx * 4 * c) || !s.wait("polygon_map"))
+			return s.fail();
 	}
-	if (!ok)
-		(void)wait_stream(st); // what was queued is done before the buffers go
-	return ok ? 0 : -1;
+	return 0;
 }
 
 RIR_EXPORT void bad_pixels_destroy(int handle)

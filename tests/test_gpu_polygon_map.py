@@ -1,6 +1,7 @@
 """GPU: polygon label maps, bit for bit against the oracle of polygon_cases.py (which test_polygon_map_cpu.py pins to the reference's own
 maps) - every case through device.polygon_map, signal_processing.polygon_map and the raw C entry, into memory pre-filled with garbage, twice;
-packed tensors, out= at every alignment, a side stream, refused arguments, and IRMovie.polygon_stats with shared and moving regions."""
+the host entry across slabs, packed tensors, out= at every alignment, a side stream, refused arguments, and IRMovie.polygon_stats with shared
+and moving regions."""
 import ctypes as ct
 import functools
 
@@ -75,6 +76,26 @@ def test_every_route_equals_the_oracle(lib, name):
     torch.cuda.synchronize()
     raw = dst.cpu().numpy()
     assert np.array_equal(raw, expected(name)), differs(raw, expected(name), "rir_polygon_map_device")
+
+
+@pytest.mark.parametrize("per_map", [True, False])
+def test_host_entry_in_slabs(per_map):
+    """five maps of 2048x2048 are 80 MiB: the host entry makes them in slabs of four and one, and the second slab starts at its own polygon
+    set and its own shift.  Against device.polygon_map, which the cases above pin to the oracle."""
+    from librir_amd import device as D
+    from librir_amd import signal_processing as S
+
+    shape, n = (2048, 2048), 5
+    shifts = np.array([(0.5, 0.5), (-20.5, 3.25), (64, -8), (300.25, 900), (1500, 1200.5)])
+    if per_map:
+        polygons = [PC._kinds(310 + m, (17, 130), 1) for m in range(n)]
+    else:
+        polygons = PC._kinds(301, (33, 70), 1) + [[(3, 3), (30, 20)], [(40, 9)]]
+    want = D.polygon_map(polygons, shape, shifts=shifts).cpu().numpy()
+    assert want.shape == (n,) + shape and all((want[m] >= 0).any() for m in range(n))
+    assert all(not np.array_equal(want[a], want[b]) for a in range(n) for b in range(a))  # a slab at another map's offset shows
+    host = S.polygon_map(polygons, shape, shifts=shifts)
+    assert host.dtype == np.int32 and np.array_equal(host, want), differs(host, want, "signal_processing.polygon_map in slabs")
 
 
 def test_no_polygon_and_no_map(lib):

@@ -398,6 +398,16 @@ def test_host_entry_equals_device_entry():
     check(S.region_quantiles(f, lab, PERCENTS, 65536), oracle(f, lab, 65536, PERCENTS), "frame by frame")
 
 
+def test_host_entry_frame_by_frame_with_per_frame_maps():
+    """65 536 regions at eight percents again, now with one map per frame: every frame is its own slab and takes its own map up with it"""
+    from librir_amd import signal_processing as S
+
+    f = frames_of(3, 17, 33, seed=10)
+    lab = np.random.default_rng(10).integers(65500, 65537, (3, 17, 33)).astype(np.int32)
+    assert not np.array_equal(lab[0], lab[1]) and not np.array_equal(lab[1], lab[2])
+    check(S.region_quantiles(f, lab, PERCENTS, 65536), oracle(f, lab, 65536, PERCENTS), "frame by frame, per-frame maps")
+
+
 def record(path, frames):
     from librir_amd.video_io import IRSaver
 
