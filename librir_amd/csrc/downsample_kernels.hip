@@ -2,7 +2,7 @@
 // Two streaming passes over the frames, the keep / drop recurrence runs on the host between them (downsample.cpp):
 //
 //   ds_pair_sums   one workgroup per (tile of DS_TILE pixels, slab of DS_SLAB frames).  A lane owns 8 adjacent pixels (one 16-byte load per
-//                  frame) and walks the slab's frames in order with the previous frame's pixels in registers, so every frame is read once
+//                  frame) and walks the slab's frames in order (walk_frames, time_walk.h) with the previous frame's pixels in registers, so every frame is read once
 //                  (the frame before a slab is read a second time: 1 / DS_SLAB more).  Per frame the lane has a 32-bit sum of |d| and a 64-bit
 //                  sum of d^2 (8 * 65535^2 does not fit 32 bits); the wave adds them up with shuffles, the four waves meet in LDS, and the
 //                  workgroup leaves one pair of int64 per frame in the partials [n][tiles][2].
@@ -18,35 +18,16 @@
 #include <algorithm>
 
 #include "downsample_kernels.h"
+#include "time_walk.h"
 
 namespace rir
 {
 	constexpr int DS_BLOCK = 256;
 	constexpr int DS_WAVES = DS_BLOCK / 64;
-	constexpr int DS_PX = 8;				 // pixels per lane
-	constexpr int DS_TILE = DS_BLOCK * DS_PX; // pixels per workgroup
-	constexpr int DS_DEPTH = 4;				 // frames per set of loads; a wave has one or two sets in flight
-	static_assert(DS_SLAB <= DS_BLOCK && DS_SLAB % (2 * DS_DEPTH) == 0, "a thread per frame of the slab writes the partials");
+	constexpr int DS_TILE = DS_BLOCK * TW_PX; // pixels per workgroup
+	static_assert(DS_SLAB <= DS_BLOCK && DS_SLAB % (2 * TW_DEPTH) == 0, "a thread per frame of the slab writes the partials");
 
-	typedef unsigned ds_v4u __attribute__((ext_vector_type(4)));
 	typedef unsigned short ds_v8h __attribute__((ext_vector_type(8)));
-
-	// The lane's 8 pixels of one frame.  VEC: one 16-byte load (the launcher has checked the alignment).  Else pixel by pixel at the offsets
-	// `off`, which are clamped into the frame: what is loaded for a pixel past the end is masked out.
-	template <bool VEC>
-	__device__ __forceinline__ ds_v4u ds_load(const uint16_t *__restrict__ frame, const unsigned (&off)[DS_PX])
-	{
-		if constexpr (VEC)
-			return __builtin_nontemporal_load(reinterpret_cast<const ds_v4u *>(frame + off[0]));
-		else
-		{
-			ds_v4u x;
-#pragma unroll
-			for (int j = 0; j < 4; ++j)
-				x[j] = (unsigned)__builtin_nontemporal_load(frame + off[2 * j]) | (unsigned)__builtin_nontemporal_load(frame + off[2 * j + 1]) << 16;
-			return x;
-		}
-	}
 
 	template <bool VEC>
 	__global__ __launch_bounds__(DS_BLOCK) void ds_pair_sums(const uint16_t *__restrict__ frames, const uint16_t *__restrict__ prev, int64_t npx,
@@ -55,13 +36,11 @@ namespace rir
 		__shared__ unsigned long long lds[DS_SLAB][DS_WAVES][2];
 		const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 		const int f0 = blockIdx.y * DS_SLAB, cnt = min(DS_SLAB, n - f0);
-		const int64_t p = (int64_t)blockIdx.x * DS_TILE + (int64_t)threadIdx.x * DS_PX;
+		const int64_t p = (int64_t)blockIdx.x * DS_TILE + (int64_t)threadIdx.x * TW_PX;
 
-		unsigned off[DS_PX];
-		ds_v4u mask; // the pixels below `size`
-#pragma unroll
-		for (int j = 0; j < DS_PX; ++j)
-			off[j] = VEC ? (unsigned)(p < size ? p : 0) : (unsigned)min(p + j, npx - 1);
+		unsigned off[TW_PX];
+		tw_offsets<VEC>(off, p, size, npx);
+		tw_v4u mask; // the pixels below `size`: what is loaded for the others is masked out
 #pragma unroll
 		for (int j = 0; j < 4; ++j)
 			mask[j] = (p + 2 * j < size ? 0xFFFFu : 0u) | (p + 2 * j + 1 < size ? 0xFFFF0000u : 0u);
@@ -72,9 +51,10 @@ namespace rir
 			const int64_t f = (int64_t)f0 + min(k, cnt - 1);
 			return f >= 0 ? frames + f * npx : (prev ? prev : frames);
 		};
-		ds_v4u before = ds_load<VEC>(frame(-1), off) & mask;
-		auto step = [&](ds_v4u x, int k) {
+		tw_v4u before = tw_load<VEC>(frame(-1), off) & mask;
+		auto step = [&](tw_v4u x, int k) {
 			x &= mask;
+			asm("" : "+v"(before)); // one frame at a time, behind its own wait
 			unsigned sx = 0;
 			unsigned long long sq = 0;
 #pragma unroll
@@ -100,30 +80,7 @@ namespace rir
 			}
 		};
 
-		// two sets of DS_DEPTH frames, named so that no set is ever copied: while one is reduced the other is in flight
-		ds_v4u a0[DS_DEPTH], b0[DS_DEPTH];
-#pragma unroll
-		for (int d = 0; d < DS_DEPTH; ++d)
-			a0[d] = ds_load<VEC>(frame(d), off);
-		for (int k = 0; k < cnt; k += 2 * DS_DEPTH)
-		{
-#pragma unroll
-			for (int d = 0; d < DS_DEPTH; ++d)
-				b0[d] = ds_load<VEC>(frame(k + DS_DEPTH + d), off);
-			__builtin_amdgcn_sched_barrier(0); // the loads stay ahead of the arithmetic
-#pragma unroll
-			for (int d = 0; d < DS_DEPTH; ++d)
-				if (k + d < cnt)
-					step(a0[d], k + d);
-#pragma unroll
-			for (int d = 0; d < DS_DEPTH; ++d)
-				a0[d] = ds_load<VEC>(frame(k + 2 * DS_DEPTH + d), off);
-			__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-			for (int d = 0; d < DS_DEPTH; ++d)
-				if (k + DS_DEPTH + d < cnt)
-					step(b0[d], k + DS_DEPTH + d);
-		}
+		walk_frames<VEC>(cnt, off, frame, step);
 		__syncthreads();
 		if ((int)threadIdx.x < cnt)
 		{
@@ -174,7 +131,7 @@ namespace rir
 		const int64_t tile = (int64_t)blockIdx.x * DS_TILE;
 		if constexpr (VEC)
 		{
-			const int64_t p = tile + (int64_t)threadIdx.x * DS_PX;
+			const int64_t p = tile + (int64_t)threadIdx.x * TW_PX;
 			if (p >= npx) // npx is a multiple of 8 here: a lane's pixels are all inside or all outside
 				return;
 			ds_v8h m = 0;
@@ -182,23 +139,23 @@ namespace rir
 				m = *reinterpret_cast<const ds_v8h *>(max_in + p);
 			const uint16_t *at = first + p;
 			int k = 0;
-			for (; k + DS_DEPTH <= cnt; k += DS_DEPTH)
+			for (; k + TW_DEPTH <= cnt; k += TW_DEPTH)
 			{
-				ds_v8h x[DS_DEPTH];
+				ds_v8h x[TW_DEPTH];
 #pragma unroll
-				for (int d = 0; d < DS_DEPTH; ++d)
+				for (int d = 0; d < TW_DEPTH; ++d)
 					x[d] = __builtin_nontemporal_load(reinterpret_cast<const ds_v8h *>(at + (int64_t)(k + d) * npx));
 #pragma unroll
-				for (int d = 0; d < DS_DEPTH; ++d)
+				for (int d = 0; d < TW_DEPTH; ++d)
 					m = __builtin_elementwise_max(m, x[d]);
 			}
 			for (; k < cnt; ++k)
 				m = __builtin_elementwise_max(m, __builtin_nontemporal_load(reinterpret_cast<const ds_v8h *>(at + (int64_t)k * npx)));
-			if (p + DS_PX > size) // the rows that are not held: the last frame's
+			if (p + TW_PX > size) // the rows that are not held: the last frame's
 			{
 				const ds_v8h l = *reinterpret_cast<const ds_v8h *>(last + p);
 #pragma unroll
-				for (int j = 0; j < DS_PX; ++j)
+				for (int j = 0; j < TW_PX; ++j)
 					if (p + j >= size)
 						m[j] = l[j];
 			}
@@ -207,7 +164,7 @@ namespace rir
 		else
 		{
 #pragma unroll 1
-			for (int j = 0; j < DS_PX; ++j)
+			for (int j = 0; j < TW_PX; ++j)
 			{
 				const int64_t i = tile + j * DS_BLOCK + threadIdx.x;
 				if (i >= npx)
@@ -229,7 +186,6 @@ namespace rir
 	namespace
 	{
 		int64_t ds_tiles(int64_t px) { return (px + DS_TILE - 1) / DS_TILE; }
-		bool ds_aligned(const void *p) { return (uintptr_t)p % 16 == 0; }
 	} // namespace
 
 	size_t downsample_partials_bytes(int64_t size, int n) { return (size_t)ds_tiles(size) * (size_t)n * 2 * sizeof(int64_t); }
@@ -242,7 +198,7 @@ namespace rir
 			return hipErrorInvalidValue;
 		const int tiles = (int)ds_tiles(size);
 		const dim3 grid((unsigned)tiles, (unsigned)slabs);
-		if (npx % DS_PX == 0 && ds_aligned(frames) && ds_aligned(prev)) // then every frame starts on a 16-byte boundary
+		if (frames_are_16_byte_aligned(npx, frames, prev))
 			ds_pair_sums<true><<<grid, DS_BLOCK, 0, st>>>(frames, prev, npx, size, n, tiles, partials);
 		else
 			ds_pair_sums<false><<<grid, DS_BLOCK, 0, st>>>(frames, prev, npx, size, n, tiles, partials);
@@ -255,7 +211,7 @@ namespace rir
 	{
 		if (nsegs <= 0 || size < 1 || size > npx || npx >= (1ll << 31))
 			return hipErrorInvalidValue;
-		const bool vec = npx % DS_PX == 0 && ds_aligned(frames) && ds_aligned(max_in) && ds_aligned(max_out) && ds_aligned(out);
+		const bool vec = frames_are_16_byte_aligned(npx, frames, max_in, max_out, out);
 		for (int s0 = 0; s0 < nsegs; s0 += 65535) // (the grid's second dimension)
 		{
 			const dim3 grid((unsigned)ds_tiles(npx), (unsigned)std::min(65535, nsegs - s0));

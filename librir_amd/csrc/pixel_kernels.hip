@@ -1,9 +1,9 @@
 // Per-pixel statistics over time of a uint16 frame stack (the definition is with rir_pixel_stats_device, include/rir_amd_device.h).  Two kernels:
 //
 //   pixel_stats_slab  one workgroup per (tile of PS_TILE pixels, slab of frames).  A lane owns 8 adjacent pixels (one 16-byte load per frame);
-//                     the four waves take the same pixels and every fourth frame of the slab each, PS_DEPTH to 2 * PS_DEPTH loads in
-//                     flight per wave, and keep per pixel a 32-bit sum, a 64-bit sum of squares and two 32-bit keys (value << 16 | frame index in the slab, the
-//                     index complemented for the maximum so that the lowest index wins a tie).  The waves are combined in LDS, after which
+//                     the four waves take the same pixels and every fourth frame of the slab each (walk_frames, time_walk.h), and keep per
+//                     pixel a 32-bit sum, a 64-bit sum of squares and two 32-bit keys (value << 16 | frame index in the slab, the index
+//                     complemented for the maximum so that the lowest index wins a tie).  The waves are combined in LDS, after which
 //                     thread t holds pixels t and t + 256 of the tile: the stores are one element a lane, whatever the alignment.  With one
 //                     slab (DIRECT) these go into the outputs, merged with what they hold when accumulating; else into the workspace.
 //   pixel_stats_fold  (more than one slab) one thread a pixel walks the slabs' partials in order and writes or merges the outputs.
@@ -13,21 +13,17 @@
 #include <algorithm>
 
 #include "pixel_kernels.h"
+#include "time_walk.h"
 
 namespace rir
 {
 	constexpr int PS_BLOCK = 256;
 	constexpr int PS_WAVES = PS_BLOCK / 64;	  // the waves split the frames of a slab
-	constexpr int PS_PX = 8;				  // pixels per lane
-	constexpr int PS_TILE = 64 * PS_PX;		  // pixels per workgroup
-	constexpr int PS_DEPTH = 4;				  // frames per set; a wave has one or two sets in flight
+	constexpr int PS_TILE = TW_TILE;		  // pixels per workgroup: its waves take the same ones
 	constexpr int PS_SLAB_MAX = 65536;		  // frames per slab at most: the index fits 16 bits of a key and the sum 32 bits
 	constexpr int PS_SLAB_MIN = 256;		  // frames per slab at least (unless the stack is shorter): bounds the partials' traffic
-	constexpr int PS_TARGET_BLOCKS = 1024;	  // slabs are added while the grid stays within 4 workgroups on each of 256 CUs
 	static_assert((long long)PS_SLAB_MAX * 65535 < (1ll << 32), "a slab's sum fits 32 bits");
 	static_assert(PS_TILE == 2 * PS_BLOCK, "after the LDS combine a thread holds two pixels of the tile");
-
-	typedef unsigned ps_v4u __attribute__((ext_vector_type(4)));
 
 	struct PsOut
 	{
@@ -43,16 +39,24 @@ namespace rir
 
 	struct PsAcc // a lane's 8 pixels over its wave's frames
 	{
-		unsigned sum[PS_PX];
-		unsigned long long sq[PS_PX];
-		unsigned kmin[PS_PX]; // min of value << 16 | index
-		unsigned kmax[PS_PX]; // max of value << 16 | (0xFFFF - index)
+		unsigned sum[TW_PX];
+		unsigned long long sq[TW_PX];
+		unsigned kmin[TW_PX]; // min of value << 16 | index
+		unsigned kmax[TW_PX]; // max of value << 16 | (0xFFFF - index)
 	};
 
-	template <bool SUMS, bool EXTR>
-	__device__ __forceinline__ void ps_frame(PsAcc &a, ps_v4u x, unsigned idx)
+	// One frame.  PIN (the 16-byte loads): the sums stay one frame's adds - left free, the frames of a set are summed first, behind one wait
+	// for all of them, at 1.5 to 1.7 times the registers.  Not with the 2-byte loads, where pinned sums have the second set's loads wait pair by pair.
+	template <bool SUMS, bool EXTR, bool PIN>
+	__device__ __forceinline__ void ps_frame(PsAcc &a, tw_v4u x, unsigned idx)
 	{
 		const unsigned idxc = 0xFFFFu - idx;
+		if constexpr (SUMS && PIN)
+		{
+#pragma unroll
+			for (int j = 0; j < TW_PX; ++j)
+				asm("" : "+v"(a.sq[j]), "+v"(a.sum[j]));
+		}
 #pragma unroll
 		for (int j = 0; j < 4; ++j)
 		{
@@ -71,23 +75,6 @@ namespace rir
 				a.kmax[2 * j] = max(a.kmax[2 * j], w << 16 | idxc);
 				a.kmax[2 * j + 1] = max(a.kmax[2 * j + 1], (w & 0xFFFF0000u) | idxc);
 			}
-		}
-	}
-
-	// The lane's 8 pixels of one frame.  VEC: one 16-byte load (the launcher has checked the alignment).  Else pixel by pixel at the offsets
-	// `off`, which are clamped into the frame: what is loaded for a pixel past the end is never stored.
-	template <bool VEC>
-	__device__ __forceinline__ ps_v4u ps_load(const uint16_t *__restrict__ frame, const unsigned (&off)[PS_PX])
-	{
-		if constexpr (VEC)
-			return __builtin_nontemporal_load(reinterpret_cast<const ps_v4u *>(frame + off[0]));
-		else
-		{
-			ps_v4u x;
-#pragma unroll
-			for (int j = 0; j < 4; ++j)
-				x[j] = (unsigned)__builtin_nontemporal_load(frame + off[2 * j]) | (unsigned)__builtin_nontemporal_load(frame + off[2 * j + 1]) << 16;
-			return x;
 		}
 	}
 
@@ -132,73 +119,33 @@ namespace rir
 		const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 		const int64_t f0 = (int64_t)blockIdx.y * per_slab, f1 = min(f0 + per_slab, (int64_t)n);
 		const int cnt = f1 - f0 > wave ? (int)((f1 - f0 - wave + PS_WAVES - 1) / PS_WAVES) : 0; // this wave's frames: f0 + wave + PS_WAVES * k
-		const int64_t tile = (int64_t)blockIdx.x * PS_TILE, p = tile + lane * PS_PX;
+		const int64_t tile = (int64_t)blockIdx.x * PS_TILE, p = tile + lane * TW_PX;
 
-		unsigned off[PS_PX];
-#pragma unroll
-		for (int j = 0; j < PS_PX; ++j)
-			off[j] = VEC ? (unsigned)(p < npx ? p : 0) : (unsigned)min(p + j, npx - 1);
-
+		unsigned off[TW_PX]; // what is loaded for a pixel past the end is never stored
+		tw_offsets<VEC>(off, p, npx, npx);
 		PsAcc a;
 #pragma unroll
-		for (int j = 0; j < PS_PX; ++j)
+		for (int j = 0; j < TW_PX; ++j)
 		{
 			a.sum[j] = 0;
 			a.sq[j] = 0;
 			a.kmin[j] = 0xFFFFFFFFu;
 			a.kmax[j] = 0;
 		}
-		if (cnt > 0)
-		{
-			// the frame of step k, clamped to the wave's last one: the loads past the end stay in bounds and are not used
-			auto frame = [&](int k) { return frames + (f0 + wave + (int64_t)PS_WAVES * min(k, cnt - 1)) * npx; };
-			// two sets of PS_DEPTH frames, named so that no set is ever copied: while one is reduced the other is in flight
-			ps_v4u a0[PS_DEPTH], b0[PS_DEPTH];
-#pragma unroll
-			for (int d = 0; d < PS_DEPTH; ++d)
-				a0[d] = ps_load<VEC>(frame(d), off);
-			int k = 0;
-			for (; k + 2 * PS_DEPTH <= cnt; k += 2 * PS_DEPTH)
-			{
-#pragma unroll
-				for (int d = 0; d < PS_DEPTH; ++d)
-					b0[d] = ps_load<VEC>(frame(k + PS_DEPTH + d), off);
-				__builtin_amdgcn_sched_barrier(0); // the loads stay ahead of the arithmetic
-#pragma unroll
-				for (int d = 0; d < PS_DEPTH; ++d)
-					ps_frame<SUMS, EXTR>(a, a0[d], (unsigned)(wave + PS_WAVES * (k + d)));
-#pragma unroll
-				for (int d = 0; d < PS_DEPTH; ++d)
-					a0[d] = ps_load<VEC>(frame(k + 2 * PS_DEPTH + d), off);
-				__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-				for (int d = 0; d < PS_DEPTH; ++d)
-					ps_frame<SUMS, EXTR>(a, b0[d], (unsigned)(wave + PS_WAVES * (k + PS_DEPTH + d)));
-			}
-			// fewer than 2 * PS_DEPTH frames are left, the first PS_DEPTH of them loaded
-#pragma unroll
-			for (int d = 0; d < PS_DEPTH; ++d)
-				b0[d] = ps_load<VEC>(frame(k + PS_DEPTH + d), off);
-#pragma unroll
-			for (int d = 0; d < PS_DEPTH; ++d)
-				if (k + d < cnt)
-					ps_frame<SUMS, EXTR>(a, a0[d], (unsigned)(wave + PS_WAVES * (k + d)));
-#pragma unroll
-			for (int d = 0; d < PS_DEPTH - 1; ++d)
-				if (k + PS_DEPTH + d < cnt)
-					ps_frame<SUMS, EXTR>(a, b0[d], (unsigned)(wave + PS_WAVES * (k + PS_DEPTH + d)));
-		}
+		walk_frames<VEC>( // the frame of step k is clamped to the wave's last one
+			cnt, off, [&](int k) { return frames + (f0 + wave + (int64_t)PS_WAVES * min(k, cnt - 1)) * npx; },
+			[&](tw_v4u x, int k) { ps_frame<SUMS, EXTR, VEC>(a, x, (unsigned)(wave + PS_WAVES * k)); });
 
 		// combine the waves: afterwards thread t holds pixels t and t + 256 of the tile
 		unsigned long long rsum[2] = {0, 0}, rsq[2] = {0, 0};
 		unsigned rmin[2] = {0xFFFFFFFFu, 0xFFFFFFFFu}, rmax[2] = {0, 0};
-		const int at = wave * PS_TILE + lane * PS_PX;
+		const int at = wave * PS_TILE + lane * TW_PX;
 		if constexpr (SUMS)
 		{
 			unsigned long long *lsq = lds;
 			unsigned *lsum = reinterpret_cast<unsigned *>(lds + PS_WAVES * PS_TILE);
 #pragma unroll
-			for (int j = 0; j < PS_PX; ++j)
+			for (int j = 0; j < TW_PX; ++j)
 			{
 				lsq[at + j] = a.sq[j];
 				lsum[at + j] = a.sum[j];
@@ -219,7 +166,7 @@ namespace rir
 		{
 			unsigned *lmin = reinterpret_cast<unsigned *>(lds), *lmax = lmin + PS_WAVES * PS_TILE;
 #pragma unroll
-			for (int j = 0; j < PS_PX; ++j)
+			for (int j = 0; j < TW_PX; ++j)
 			{
 				lmin[at + j] = a.kmin[j];
 				lmax[at + j] = a.kmax[j];
@@ -291,12 +238,8 @@ namespace rir
 
 	PixelStatsPlan pixel_stats_plan(int64_t npx, int n)
 	{
-		const int64_t tiles = (npx + PS_TILE - 1) / PS_TILE;
-		const int64_t want = std::max<int64_t>(1, PS_TARGET_BLOCKS / tiles);
-		int64_t per_slab = std::max<int64_t>(((int64_t)n + want - 1) / want, PS_SLAB_MIN);
-		per_slab = std::min<int64_t>(per_slab, PS_SLAB_MAX);
-		const int64_t slabs = std::max<int64_t>(1, ((int64_t)n + per_slab - 1) / per_slab);
-		return PixelStatsPlan{(int)slabs, (int)per_slab};
+		const TimeSlabs t = time_slab_plan(npx, n, PS_SLAB_MIN, PS_SLAB_MAX);
+		return PixelStatsPlan{t.slabs, t.per_slab};
 	}
 
 	size_t pixel_stats_workspace(int64_t npx, int n)
@@ -317,7 +260,7 @@ namespace rir
 			wk.sum = reinterpret_cast<unsigned *>(wk.sq + cells);
 			wk.kmin = wk.sum + cells;
 			wk.kmax = wk.kmin + cells;
-			const bool vec = npx % PS_PX == 0 && (uintptr_t)frames % 16 == 0; // then every frame starts on a 16-byte boundary
+			const bool vec = frames_are_16_byte_aligned(npx, frames);
 			const dim3 grid((unsigned)((npx + PS_TILE - 1) / PS_TILE), (unsigned)plan.slabs);
 			if (plan.slabs == 1)
 			{

@@ -2,11 +2,11 @@
 // MSB-first radix select over the 16-bit value, 4 bits a pass.  Per (percent, pixel) the state holds the prefix fixed so far and the rank
 // left inside that prefix's bucket (pixel_quantile_kernels.h).  Each pass has two kernels:
 //
-//   pixel_quantiles_count    one workgroup per (tile of PQ_TILE pixels, slab of frames), for a group of G percents.  pixel_stats_slab's walk:
+//   pixel_quantiles_count    one workgroup per (tile of PQ_TILE pixels, slab of frames), for a group of G percents.  The walk of time_walk.h:
 //                            a lane owns 8 adjacent pixels (one 16-byte load per frame), the waves take the same pixels and every
-//                            PQ_WAVES-th frame of the slab each, PQ_DEPTH to 2 * PQ_DEPTH loads in flight per wave.  Per (percent, pixel) a
+//                            WAVES-th frame of the slab each, TW_DEPTH to 2 * TW_DEPTH loads in flight per wave.  Per (percent, pixel) a
 //                            lane keeps one 64-bit accumulator of sixteen 4-bit fields: a sample whose high bits equal the prefix adds
-//                            1 << (4 * digit), no register is indexed at run time.  Every PQ_FLUSH_SETS * PQ_DEPTH frames, before a field
+//                            1 << (4 * digit), no register is indexed at run time.  Every PQ_FLUSH_SETS * TW_DEPTH frames, before a field
 //                            can wrap, the fields are added to the workgroup's 32-bit counters in LDS, laid out [percent][digit][pixel
 //                            of the lane][lane] so that the bank is the lane (ds_add_u32, shared by the waves).  At the end the workgroup
 //                            adds its non-zero counters to the state: plain loads and stores where the tile has one owner in the launch
@@ -17,23 +17,23 @@
 //
 // Every combination is a 32-bit integer add, so the result depends neither on the order the workgroups run in nor on how the sequence is
 // split into calls.
+#include <limits.h>
+
 #include <algorithm>
 
 #include "pixel_quantile_kernels.h"
 #include "quantile_rank.h"
+#include "time_walk.h"
 
 namespace rir
 {
-	constexpr int PQ_PX = 8;				// pixels per lane
-	constexpr int PQ_TILE = 64 * PQ_PX;		// pixels per workgroup
-	constexpr int PQ_DEPTH = 4;				// frames per set; a wave has one or two sets in flight
+	constexpr int PQ_TILE = TW_TILE;		// pixels per workgroup: its waves take the same ones
 	constexpr int PQ_FLUSH_SETS = 3;		// sets between two flushes of the 4-bit fields
 	constexpr int PQ_DIGITS = 16;			// buckets of a pass
 	constexpr int PQ_SLAB_MIN = 512;		// frames per slab at least (unless the stack is shorter)
-	constexpr int PQ_TARGET_BLOCKS = 1024;	// slabs are added while the grid stays within this many workgroups
 	constexpr int PQ_RESOLVE_BLOCK = 256;
-	// between two flushes a field counts at most PQ_FLUSH_SETS * PQ_DEPTH frames, or (PQ_FLUSH_SETS - 1) * PQ_DEPTH and the tail of a wave
-	static_assert(PQ_FLUSH_SETS * PQ_DEPTH <= 15 && (PQ_FLUSH_SETS - 1) * PQ_DEPTH + 2 * PQ_DEPTH - 1 <= 15, "a 4-bit field cannot wrap");
+	// between two flushes a field counts at most PQ_FLUSH_SETS * TW_DEPTH frames, or (PQ_FLUSH_SETS - 1) * TW_DEPTH and the tail of a wave
+	static_assert(PQ_FLUSH_SETS * TW_DEPTH <= 15 && (PQ_FLUSH_SETS - 1) * TW_DEPTH + 2 * TW_DEPTH - 1 <= 15, "a 4-bit field cannot wrap");
 	static_assert(PIXEL_QUANTILE_PASSES * 4 == 16 && PIXEL_QUANTILE_ROWS == PQ_DIGITS + 2, "4 bits a pass; counts, prefix, rank");
 	static_assert(PIXEL_QUANTILE_GROUP == 4 && QUANTILE_MAX_PERCENTS == 8, "the launcher instantiates groups of 1 .. 4 percents");
 
@@ -41,33 +41,20 @@ namespace rir
 	// four waves on a CU, more percents for fewer, larger ones
 	constexpr int pq_block(int G) { return G == 1 ? 256 : 512; }
 
-	typedef unsigned pq_v4u __attribute__((ext_vector_type(4)));
-
 	__device__ __forceinline__ uint32_t *pq_row(uint32_t *state, int64_t npx, int percent, int row)
 	{
 		return state + ((int64_t)percent * PIXEL_QUANTILE_ROWS + row) * npx;
 	}
 
-	// The lane's 8 pixels of one frame, as pixel_stats_slab loads them.
-	template <bool VEC>
-	__device__ __forceinline__ pq_v4u pq_load(const uint16_t *__restrict__ frame, const unsigned (&off)[PQ_PX])
-	{
-		if constexpr (VEC)
-			return __builtin_nontemporal_load(reinterpret_cast<const pq_v4u *>(frame + off[0]));
-		else
-		{
-			pq_v4u x;
-#pragma unroll
-			for (int j = 0; j < 4; ++j)
-				x[j] = (unsigned)__builtin_nontemporal_load(frame + off[2 * j]) | (unsigned)__builtin_nontemporal_load(frame + off[2 * j + 1]) << 16;
-			return x;
-		}
-	}
-
 	// One frame: v >> shift is the sample's prefix and digit; it counts where the prefix is the pixel's (pre = prefix << 4).
 	template <int G>
-	__device__ __forceinline__ void pq_frame(unsigned long long (&acc)[G][PQ_PX], const unsigned (&pre)[G][PQ_PX], pq_v4u x, int shift)
+	__device__ __forceinline__ void pq_frame(unsigned long long (&acc)[G][TW_PX], const unsigned (&pre)[G][TW_PX], tw_v4u x, int shift)
 	{
+#pragma unroll
+		for (int g = 0; g < G; ++g) // the fields stay one frame's adds: left free, the frames of a set are summed first, behind one wait for all
+#pragma unroll
+			for (int j = 0; j < TW_PX; ++j)
+				asm("" : "+v"(acc[g][j]));
 #pragma unroll
 		for (int j = 0; j < 4; ++j)
 		{
@@ -84,7 +71,7 @@ namespace rir
 
 	// Add the 4-bit fields to the workgroup's counters lds[g][digit][pixel of the lane][lane] and clear them.
 	template <int G>
-	__device__ __forceinline__ void pq_flush(unsigned long long (&acc)[G][PQ_PX], uint32_t *lds, int lane)
+	__device__ __forceinline__ void pq_flush(unsigned long long (&acc)[G][TW_PX], uint32_t *lds, int lane)
 	{
 #pragma unroll 1
 		for (int d = 0; d < PQ_DIGITS / 2; ++d) // digits d (low word) and d + 8 (high word)
@@ -92,17 +79,17 @@ namespace rir
 #pragma unroll
 			for (int g = 0; g < G; ++g)
 #pragma unroll
-				for (int j = 0; j < PQ_PX; ++j)
+				for (int j = 0; j < TW_PX; ++j)
 				{
 					const uint32_t lo = ((uint32_t)acc[g][j] >> (4 * d)) & 15u, hi = ((uint32_t)(acc[g][j] >> 32) >> (4 * d)) & 15u;
-					__hip_atomic_fetch_add(lds + ((g * PQ_DIGITS + d) * PQ_PX + j) * 64 + lane, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-					__hip_atomic_fetch_add(lds + ((g * PQ_DIGITS + d + 8) * PQ_PX + j) * 64 + lane, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+					__hip_atomic_fetch_add(lds + ((g * PQ_DIGITS + d) * TW_PX + j) * 64 + lane, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+					__hip_atomic_fetch_add(lds + ((g * PQ_DIGITS + d + 8) * TW_PX + j) * 64 + lane, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 				}
 		}
 #pragma unroll
 		for (int g = 0; g < G; ++g)
 #pragma unroll
-			for (int j = 0; j < PQ_PX; ++j)
+			for (int j = 0; j < TW_PX; ++j)
 				acc[g][j] = 0;
 	}
 
@@ -116,18 +103,18 @@ namespace rir
 		const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
 		const int64_t f0 = (int64_t)blockIdx.y * per_slab, f1 = min(f0 + per_slab, (int64_t)n);
 		const int cnt = f1 - f0 > wave ? (int)((f1 - f0 - wave + WAVES - 1) / WAVES) : 0; // this wave's frames: f0 + wave + WAVES * k
-		const int64_t tile = (int64_t)blockIdx.x * PQ_TILE, p = tile + lane * PQ_PX;
+		const int64_t tile = (int64_t)blockIdx.x * PQ_TILE, p = tile + lane * TW_PX;
 
 		for (int i = threadIdx.x; i < CELLS; i += BLOCK)
 			lds[i] = 0;
-		unsigned off[PQ_PX];
-		unsigned pre[G][PQ_PX];
-		unsigned long long acc[G][PQ_PX];
+		unsigned off[TW_PX];
+		unsigned pre[G][TW_PX];
+		unsigned long long acc[G][TW_PX];
+		tw_offsets<VEC>(off, p, npx, npx);
 #pragma unroll
-		for (int j = 0; j < PQ_PX; ++j)
+		for (int j = 0; j < TW_PX; ++j)
 		{
 			const int64_t at = min(p + j, npx - 1); // a pixel past the end counts what the last one does, and is never stored
-			off[j] = VEC ? (unsigned)(p < npx ? p : 0) : (unsigned)at;
 #pragma unroll
 			for (int g = 0; g < G; ++g)
 			{
@@ -137,57 +124,19 @@ namespace rir
 		}
 		__syncthreads();
 
+		int sets = 0; // sets counted since the last flush: at most PQ_FLUSH_SETS - 1 when the walk's tail begins
+		walk_frames<VEC>( // the frame of step k is clamped to the wave's last one
+			cnt, off, [&](int k) { return frames + (f0 + wave + (int64_t)WAVES * min(k, cnt - 1)) * npx; },
+			[&](tw_v4u x, int) { pq_frame<G>(acc, pre, x, shift); },
+			[&] {
+				if (++sets == PQ_FLUSH_SETS)
+				{
+					pq_flush<G>(acc, lds, lane);
+					sets = 0;
+				}
+			});
 		if (cnt > 0)
-		{
-			// the frame of step k, clamped to the wave's last one: the loads past the end stay in bounds and are not used
-			auto frame = [&](int k) { return frames + (f0 + wave + (int64_t)WAVES * min(k, cnt - 1)) * npx; };
-			// two sets of PQ_DEPTH frames, named so that no set is ever copied: while one is counted the other is in flight
-			pq_v4u a0[PQ_DEPTH], b0[PQ_DEPTH];
-#pragma unroll
-			for (int d = 0; d < PQ_DEPTH; ++d)
-				a0[d] = pq_load<VEC>(frame(d), off);
-			int k = 0, sets = 0; // sets counted since the last flush
-			for (; k + 2 * PQ_DEPTH <= cnt; k += 2 * PQ_DEPTH)
-			{
-#pragma unroll
-				for (int d = 0; d < PQ_DEPTH; ++d)
-					b0[d] = pq_load<VEC>(frame(k + PQ_DEPTH + d), off);
-				__builtin_amdgcn_sched_barrier(0); // the loads stay ahead of the arithmetic
-#pragma unroll
-				for (int d = 0; d < PQ_DEPTH; ++d)
-					pq_frame<G>(acc, pre, a0[d], shift);
-				if (++sets == PQ_FLUSH_SETS)
-				{
-					pq_flush<G>(acc, lds, lane);
-					sets = 0;
-				}
-#pragma unroll
-				for (int d = 0; d < PQ_DEPTH; ++d)
-					a0[d] = pq_load<VEC>(frame(k + 2 * PQ_DEPTH + d), off);
-				__builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-				for (int d = 0; d < PQ_DEPTH; ++d)
-					pq_frame<G>(acc, pre, b0[d], shift);
-				if (++sets == PQ_FLUSH_SETS)
-				{
-					pq_flush<G>(acc, lds, lane);
-					sets = 0;
-				}
-			}
-			// fewer than 2 * PQ_DEPTH frames are left, the first PQ_DEPTH of them loaded; at most PQ_FLUSH_SETS - 1 sets are unflushed
-#pragma unroll
-			for (int d = 0; d < PQ_DEPTH; ++d)
-				b0[d] = pq_load<VEC>(frame(k + PQ_DEPTH + d), off);
-#pragma unroll
-			for (int d = 0; d < PQ_DEPTH; ++d)
-				if (k + d < cnt)
-					pq_frame<G>(acc, pre, a0[d], shift);
-#pragma unroll
-			for (int d = 0; d < PQ_DEPTH - 1; ++d)
-				if (k + PQ_DEPTH + d < cnt)
-					pq_frame<G>(acc, pre, b0[d], shift);
 			pq_flush<G>(acc, lds, lane);
-		}
 		__syncthreads();
 
 		// counter e = (g * 16 + digit) * PQ_TILE + q of pixel tile + q: consecutive threads, consecutive pixels
@@ -197,7 +146,7 @@ namespace rir
 			const int64_t i = tile + q;
 			if (i >= npx)
 				continue;
-			const uint32_t c = lds[(gd * PQ_PX + q % PQ_PX) * 64 + q / PQ_PX];
+			const uint32_t c = lds[(gd * TW_PX + q % TW_PX) * 64 + q / TW_PX];
 			if (c == 0)
 				continue;
 			uint32_t *dst = pq_row(state, npx, j0 + gd / PQ_DIGITS, gd % PQ_DIGITS) + i;
@@ -275,23 +224,20 @@ namespace rir
 		template <int G>
 		void pq_launch(const uint16_t *frames, int64_t npx, int n, int shift, int j0, uint32_t *state, hipStream_t st)
 		{
-			const int64_t tiles = (npx + PQ_TILE - 1) / PQ_TILE;
-			const int64_t want = std::max<int64_t>(1, PQ_TARGET_BLOCKS / tiles);
-			const int64_t per_slab = std::max<int64_t>(((int64_t)n + want - 1) / want, PQ_SLAB_MIN);
-			const int64_t slabs = ((int64_t)n + per_slab - 1) / per_slab;
-			const bool vec = npx % PQ_PX == 0 && (uintptr_t)frames % 16 == 0; // then every frame starts on a 16-byte boundary
-			const dim3 grid((unsigned)tiles, (unsigned)slabs);
-			if (slabs == 1)
+			const TimeSlabs plan = time_slab_plan(npx, n, PQ_SLAB_MIN, INT_MAX); // no cap: the counters are 32-bit
+			const bool vec = frames_are_16_byte_aligned(npx, frames);
+			const dim3 grid((unsigned)((npx + PQ_TILE - 1) / PQ_TILE), (unsigned)plan.slabs);
+			if (plan.slabs == 1)
 			{
 				if (vec)
-					pixel_quantiles_count<G, true, false><<<grid, pq_block(G), 0, st>>>(frames, npx, n, (int)per_slab, shift, j0, state);
+					pixel_quantiles_count<G, true, false><<<grid, pq_block(G), 0, st>>>(frames, npx, n, plan.per_slab, shift, j0, state);
 				else
-					pixel_quantiles_count<G, false, false><<<grid, pq_block(G), 0, st>>>(frames, npx, n, (int)per_slab, shift, j0, state);
+					pixel_quantiles_count<G, false, false><<<grid, pq_block(G), 0, st>>>(frames, npx, n, plan.per_slab, shift, j0, state);
 			}
 			else if (vec)
-				pixel_quantiles_count<G, true, true><<<grid, pq_block(G), 0, st>>>(frames, npx, n, (int)per_slab, shift, j0, state);
+				pixel_quantiles_count<G, true, true><<<grid, pq_block(G), 0, st>>>(frames, npx, n, plan.per_slab, shift, j0, state);
 			else
-				pixel_quantiles_count<G, false, true><<<grid, pq_block(G), 0, st>>>(frames, npx, n, (int)per_slab, shift, j0, state);
+				pixel_quantiles_count<G, false, true><<<grid, pq_block(G), 0, st>>>(frames, npx, n, plan.per_slab, shift, j0, state);
 		}
 	} // namespace
 

@@ -73,7 +73,7 @@ def test_parameter_sets(factor, factor_std, method):
 
 
 @pytest.mark.parametrize("h,w,lossy", [(40, 132, 37), (17, 33, 14)])
-@pytest.mark.parametrize("n", [1, 2, CUT - 1, CUT, CUT + 1, 2 * CUT - 1, 2 * CUT, 2 * CUT + 1])
+@pytest.mark.parametrize("n", [1, 2, 7, 8, 9, 15, 16, 17, CUT - 1, CUT, CUT + 1, 2 * CUT - 1, 2 * CUT, 2 * CUT + 1])  # (7 .. 17: the walk's sets of 4 + 4 frames)
 def test_lengths_around_the_time_slab_cut(n, h, w, lossy):
     f = scene(h, w)
     check(f[:n], 4, .75, lossy, 2, what=("whole", n))

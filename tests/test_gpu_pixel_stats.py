@@ -1,5 +1,5 @@
 """GPU: per-pixel statistics over time, bit for bit against the oracle of test_pixel_stats_cpu.py - shapes, stack lengths around the number
-of waves that split the time axis, each group of outputs alone and both, ties, long thin stacks that are cut into slabs, the largest sums,
+of waves that split the time axis and around the sets of frames a wave walks, each group of outputs alone and both, ties, long thin stacks that are cut into slabs, the largest sums,
 accumulating in and out of order, sliced inputs, refused arguments, stream order, reproducibility, the host entry and recordings read
 through IRMovie.pixel_stats."""
 import ctypes as ct
@@ -8,6 +8,7 @@ import time
 import numpy as np
 import pytest
 
+from test_gpu_pixel_quantiles import LENGTHS
 from test_gpu_region_stats import dev16, frames_of, record
 from test_pixel_stats_cpu import DEV_ARGS, FIELDS, SUMS, empty_state, four_values
 from test_pixel_stats_cpu import pixel_stats_oracle as small_oracle
@@ -54,12 +55,14 @@ def check_groups(frames_dev, exp, what, t0=0):
         check(ps, exp, (what, sums, extremes), sums, extremes)
 
 
-SHAPES = [(1, 1), (3, 5), (17, 33), (512, 640), (768, 1024)]
+SMALL_SHAPES, LARGE_SHAPES = [(1, 1), (3, 5), (17, 33)], [(512, 640), (768, 1024)]
+# four waves split the frames; a wave enters the walk's main loop at 8 frames and ends on 0 .. 7 left over: every count of a wave around its
+# multiples of 8 (test_gpu_pixel_quantiles.py's list) on the small shapes, the lengths around the number of waves on the large ones
+LENGTHS_AND_SHAPES = [(n, h, w) for n in LENGTHS for h, w in SMALL_SHAPES] + [(n, h, w) for n in [1, 2, 3, 4, 5, 7, 257] for h, w in LARGE_SHAPES]
 
 
-@pytest.mark.parametrize("h,w", SHAPES)
-@pytest.mark.parametrize("n", [1, 2, 3, 4, 5, 7, 257])
-def test_shapes_and_lengths(h, w, n):
+@pytest.mark.parametrize("n,h,w", LENGTHS_AND_SHAPES)
+def test_shapes_and_lengths(n, h, w):
     f = frames_of(n, h, w, seed=h * 3 + n)
     check_groups(dev16(f), oracle(f), (h, w, n))
 

@@ -150,6 +150,18 @@ def test_size_queries(lib):
     assert work(5, 5, -1, 1) == 0
 
 
+def test_size_queries_do_not_depend_on_the_cut_along_time(lib):
+    """the grid of test_pixel_stats_cpu.py's plan test: 72 bytes per (percent, pixel), however many slabs the counting launch has"""
+    from test_pixel_stats_cpu import PLAN_LENGTHS, PLAN_SHAPES
+
+    state, work, _ = size_queries(lib)
+    for w, h in PLAN_SHAPES:
+        for q in (1, 3, 8):
+            assert state(w, h, q) == 72 * q * w * h, (w, h, q)
+            for n in PLAN_LENGTHS:
+                assert work(w, h, n, q) == 72 * q * w * h, (w, h, n, q)
+
+
 PUSH_ARGS = [ct.c_void_p] + [ct.c_int] * 5 + [ct.c_void_p, ct.c_size_t, ct.c_void_p]
 RESOLVE_ARGS = [ct.c_int, ct.c_int, ct.c_void_p, ct.c_int, ct.c_int, ct.c_longlong, ct.c_void_p, ct.c_size_t, ct.c_void_p, ct.c_void_p]
 DEV_ARGS = [ct.c_void_p] + [ct.c_int] * 3 + [ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_size_t, ct.c_void_p]

@@ -124,6 +124,26 @@ def test_workspace_query(lib):
     assert f(1024, 512, 65536) == 8 and f(1024, 512, 65537) == 2 * 20 * 1024 * 512  # a slab holds at most 65 536 frames: 16 bits of index
 
 
+PLAN_SHAPES = [(1, 1), (5, 3), (511, 1), (512, 1), (513, 1), (80, 64), (640, 512)]  # w * h = 1, 15, 511, 512, 513, 5120, 327680
+PLAN_LENGTHS = [1, 255, 256, 257, 5000, 65536, 65537, 70001]
+
+
+@pytest.mark.parametrize("w,h", PLAN_SHAPES)
+def test_workspace_follows_the_time_slab_plan(lib, w, h):
+    """the cut along time in closed form: tiles of 512 pixels, slabs added while the grid stays within 1 024 workgroups, 256 to 65 536
+    frames a slab; 20 bytes per (slab, pixel) when there is more than one slab, else 8"""
+    f = lib.rir_pixel_stats_workspace_bytes
+    f.argtypes = [ct.c_int] * 3
+    f.restype = ct.c_size_t
+    npx = w * h
+    for n in PLAN_LENGTHS:
+        tiles = (npx + 511) // 512
+        want = max(1, 1024 // tiles)
+        per_slab = min(max((n + want - 1) // want, 256), 65536)
+        slabs = max(1, (n + per_slab - 1) // per_slab)
+        assert f(w, h, n) == (slabs * npx * 20 if slabs > 1 else 8), (w, h, n, slabs, per_slab)
+
+
 DEV_ARGS = [ct.c_void_p] + [ct.c_int] * 5 + [ct.c_void_p] * 7 + [ct.c_size_t, ct.c_void_p]
 HOST_ARGS = [ct.c_void_p] + [ct.c_int] * 3 + [ct.c_void_p] * 6
 
