@@ -424,6 +424,28 @@ extern "C"
 	int rir_keep_largest_area_device(int type, const void *d_src, int *d_dst, int w, int h, const void *background, int foreground, void *d_work,
 									 size_t work_bytes, void *stream);
 
+	/* Hot spots labelled straight from the frames (extension): detection, filtering and numbering of the components of uint16 frames
+	 * d_frames [nframes][h][w] above a threshold, without a mask in memory.  Pixel (y, x) of a frame is foreground when y < rows and its
+	 * value v > low - d_low_map[y][x] when the map (int [h][w], shared by the frames) is given, else `low`; compared as int32, so a
+	 * threshold < 0 takes every pixel and one >= 65535 none.  Components are the 4-connected sets of foreground pixels: what
+	 * rir_label_images_device gives for the boolean mask.  A component is KEPT when all of these hold: use_high is 0, or it holds a pixel
+	 * with v > high (d_high_map[y][x] when given, else `high`); min_area <= its pixel count <= max_area; clear_border is 0, or it has no
+	 * pixel in row 0, row rows - 1, column 0 or column w - 1.  Kept components are numbered 1, 2, ... per frame in the raster order of
+	 * their first pixel; pixels of dropped components and background pixels get 0 - d_dst int32 [nframes][h][w] is bit for bit the
+	 * labelling of the mask of the kept components.  Per frame `table_entries` entries of d_area (pixel counts) and d_first (the raster
+	 * index y * w + x of the component's first pixel), of which the first min(count, table_entries) are written, entry 0 being the
+	 * background's (0, -1); d_count int[nframes] = kept components + 1.  Integer work, bitwise reproducible.  With no filter asked for
+	 * (use_high 0, min_area 1, max_area >= w * h, clear_border 0) the launches are the five of rir_label_images_device; a filter adds
+	 * one small pass over the roots - use_high and clear_border are gathered with the pixel counts, in no pass of their own.  Bounds: those of rir_label_images_device
+	 * (w * h <= 0x7FFF0000, 1 <= nframes <= 65535), 1 <= rows <= h, 1 <= min_area <= max_area, table_entries >= 1.  d_work: device memory,
+	 * 8-byte aligned, at least rir_label_hot_spots_workspace_bytes(w, h, nframes) (0: geometry refused).  Asynchronous on `stream`; no
+	 * output or the workspace may overlap an input or another output.  0 / -1 (invalid argument, null pointer, overlap, workspace too
+	 * small, no device). */
+	size_t rir_label_hot_spots_workspace_bytes(int w, int h, int nframes);
+	int rir_label_hot_spots_device(const unsigned short *d_frames, int w, int h, int nframes, int rows, int low, const int *d_low_map, int use_high,
+								   int high, const int *d_high_map, int min_area, int max_area, int clear_border, int *d_dst, int *d_first, int *d_area,
+								   int table_entries, int *d_count, void *d_work, size_t work_bytes, void *stream);
+
 	/* ---- page-locked memory for the caller's images ------------------------------------------------------
 	 * The reference's entry points take host pointers and hand the buffers back on return: every image crosses host memory
 	 * once more than the link asks for (a copy into page-locked staging, a copy out of it).  A caller that keeps its images in memory

@@ -20,6 +20,10 @@
 // across tile borders, the only ones made with global atomics; (3) every pixel learns its final root, tile roots hand their counts to
 // it; (4) one workgroup turns the per-block root counts into offsets; (5) labels and tables out.  Every pass reads or
 // writes each pixel once, coalesced along x; no MFMA.
+//
+// Hot spots (label_hot_spots, an extension): the same forest over uint16 frames whose pixels are classified against a threshold inside
+// launches 1 and 2 - no mask in memory - and, where components can be dropped (too weak, too small, too large, on the image's edge), a
+// small pass over the roots between launches 3 and 4 that leaves only the kept roots to be numbered.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -52,19 +56,91 @@ namespace rir
 			int64_t table;	// entries of the per-image tables the caller gave room for
 		};
 
+		// What the tile and border walks ask of an image: a pixel's cell, whether a cell belongs to a component, and whether a pixel of a
+		// component continues the run of its left neighbour.  at(i, y): the cell of pixel i (of row y) of this launch's image.
+		// The reference's rule: a cell is its value, the background is one value, a run is made of equal values.
+		template <class C>
+		struct EqualCells
+		{
+			typedef C Cell;
+			const C *__restrict__ src;
+			C bg;
+			__device__ void image(int64_t cells) { src += blockIdx.y * cells; }
+			__device__ Cell at(int i, int) const { return src[i]; }
+			__device__ Cell outside() const { return bg; }
+			__device__ bool foreground(Cell v) const { return v != bg; }
+			__device__ bool joins(Cell left, Cell v) const { return left == v; }
+			// (inside a tile: asked by all 64 lanes of a row piece)
+			__device__ bool joins_left(bool fg, int i, int x, int, Cell v) const { return fg && x > 0 && src[i - 1] == v; }
+		};
+		// Hot spots: uint16 cells above a threshold - one number, or a map shared by the images - in the rows above `rows`; the cell is
+		// that answer, and a run is made of neighbours that both are.  The comparison is made in int32: a threshold below 0 takes every
+		// pixel, one from 65 535 on none.
+		struct AboveThreshold
+		{
+			typedef bool Cell;
+			const uint16_t *__restrict__ src;
+			const int *__restrict__ map; // or null: `level` everywhere
+			int level, rows;
+			__device__ void image(int64_t cells) { src += blockIdx.y * cells; }
+			__device__ Cell at(int i, int y) const { return y < rows && (int)src[i] > (map ? map[i] : level); }
+			__device__ Cell outside() const { return false; }
+			__device__ bool foreground(Cell v) const { return v; }
+			__device__ bool joins(Cell left, Cell) const { return left; }
+			// (the left neighbour's answer comes from its lane: the map is read once a pixel; lane 0's is never asked for inside a tile)
+			__device__ bool joins_left(bool fg, int, int, int, Cell v) const
+			{
+				const int left = __shfl_up((int)v, 1);
+				return fg && (threadIdx.x & 63) > 0 && left != 0;
+			}
+		};
+
+		// The marks of a hot spot: 1, `strong` - it holds a pixel above `high` - and 2, `edge` - it holds a pixel of the first or last row or
+		// column.  They travel with the pixel counts: launch 1 gathers them per tile-local root in LDS and leaves them at the tile root,
+		// launch 3 hands a tile root's marks to its final root, a bit in each of two bitmaps laid out as root_bits.  (Against a pass of
+		// its own over frames and final roots after launch 3: DESIGN.md 7.)  NoMarks: the labelling of images, which carries none.
+		struct NoMarks
+		{
+			static constexpr bool kOn = false;
+		};
+		struct RootMarks
+		{
+			static constexpr bool kOn = true;
+			AboveThreshold above_high;
+			bool use_high, clear_border;
+			uint8_t *__restrict__ at_tile_root; // [frames][pitch.plane] bytes, written and read at tile roots only
+			unsigned long long *strong, *edge;	// [frames][pitch.waves], zero before launch 3
+			__device__ void image(const Pitch &pitch)
+			{
+				above_high.image(pitch.cells), at_tile_root += blockIdx.y * pitch.plane, strong += blockIdx.y * pitch.waves, edge += blockIdx.y * pitch.waves;
+			}
+			// (of a pixel that belongs to a component)
+			__device__ int of(int i, int x, int y, int w) const
+			{
+				return (use_high && above_high.at(i, y) ? 1 : 0) |
+					   (clear_border && (x == 0 || x == w - 1 || y == 0 || y == above_high.rows - 1) ? 2 : 0);
+			}
+		};
+
 		// Launch 1: one workgroup per tile, its rows dealt to the wavefronts (two each), row after row.  A pixel starts linked to the first pixel of its
 		// horizontal run inside the tile (a run = neighbours with equal values), then every pixel is joined with the pixel above it.  A
 		// vertical join is implied (and skipped) when the pixel and the one above both continue their left neighbour's run: that
 		// neighbour pair is joined already - a flat tile makes one join per row instead of one per pixel.  Out: L[i] = the image index of
 		// the pixel's tile-local root (-1 on the background), cnt[i] = the tile-local component's pixel count at that root, 0 elsewhere.
-		template <class C>
-		__global__ __launch_bounds__(kTileThreads) void ccl_tile_kernel(const C *__restrict__ src, C bg, int w, int h, int tiles_x, int *__restrict__ L,
+		template <class Cells, class Marks>
+		__global__ __launch_bounds__(kTileThreads) void ccl_tile_kernel(Cells cells, Marks marks, int w, int h, int tiles_x, int *__restrict__ L,
 																  int *__restrict__ cnt, unsigned long long *__restrict__ best, Pitch pitch)
 		{
+			typedef typename Cells::Cell Cell;
 			__shared__ int lab[kTileW * kTileH];
 			__shared__ int num[kTileW * kTileH];
 			__shared__ uint8_t flags[kTileW * kTileH]; // 1: belongs to a component, 2: continues its left neighbour's run
-			src += blockIdx.y * pitch.cells, L += blockIdx.y * pitch.plane, cnt += blockIdx.y * pitch.plane;
+			constexpr int kMarkShift = 12; // (a tile-local root's marks ride above its pixel count in `num`)
+			static_assert(kTileW * kTileH < (1 << kMarkShift), "a tile's pixel count fits below the marks");
+			int mark[kRowsPerWave];
+			cells.image(pitch.cells), L += blockIdx.y * pitch.plane, cnt += blockIdx.y * pitch.plane;
+			if constexpr (Marks::kOn)
+				marks.image(pitch);
 			if (blockIdx.x == 0 && threadIdx.x == 0)
 				best[blockIdx.y] = 0ull;
 			const int ty = (int)blockIdx.x / tiles_x, tx = (int)blockIdx.x - ty * tiles_x;
@@ -76,14 +152,16 @@ namespace rir
 				const int ly = wv * kRowsPerWave + j, y = y0 + ly, t = ly * kTileW + lane;
 				const bool in = x < w && y < h;
 				const int i = in ? y * w + x : 0;
-				const C v = in ? src[i] : bg;
-				const bool fg = in && v != bg;
-				const bool joins_left = fg && x > 0 && src[i - 1] == v;
+				const Cell v = in ? cells.at(i, y) : cells.outside();
+				const bool fg = in && cells.foreground(v);
+				const bool joins_left = cells.joins_left(fg, i, x, y, v);
 				const uint64_t m = __ballot(joins_left && lane > 0);
 				const uint64_t open = ~m & ((2ull << lane) - 1ull); // lanes at or below this one that start a run (lane 0 always does)
 				lab[t] = fg ? ly * kTileW + 63 - __builtin_clzll(open) : -1;
 				num[t] = 0;
 				flags[t] = (uint8_t)((fg ? 1 : 0) | (joins_left ? 2 : 0));
+				if constexpr (Marks::kOn)
+					mark[j] = fg ? marks.of(i, x, y, w) : 0;
 			}
 			__syncthreads();
 #pragma unroll
@@ -107,6 +185,9 @@ namespace rir
 				{
 					root[j] = find_root<kTile>(lab, t);
 					atomicAdd(&num[root[j]], 1);
+					if constexpr (Marks::kOn)
+						if (mark[j])
+							atomicOr(&num[root[j]], mark[j] << kMarkShift);
 				}
 			}
 			__syncthreads();
@@ -118,7 +199,14 @@ namespace rir
 				{
 					const int i = y * w + x, r = root[j];
 					L[i] = r >= 0 ? (y0 + (r >> 6)) * w + tx * kTileW + (r & 63) : -1;
-					cnt[i] = r == t ? num[t] : 0;
+					if constexpr (Marks::kOn)
+					{
+						cnt[i] = r == t ? num[t] & ((1 << kMarkShift) - 1) : 0;
+						if (r == t)
+							marks.at_tile_root[i] = (uint8_t)(num[t] >> kMarkShift);
+					}
+					else
+						cnt[i] = r == t ? num[t] : 0;
 				}
 			}
 		}
@@ -126,18 +214,19 @@ namespace rir
 		// Launch 2: the joins across tile borders - the first row of every tile but the top ones with the row above (same skipping rule:
 		// the pair to the left is on the same border), the first column of every tile but the left ones with the pixel to its left when
 		// the run continues.
-		template <class C>
-		__global__ __launch_bounds__(kBlock) void ccl_border_kernel(const C *__restrict__ src, C bg, int w, int h, int rows, int cols, int *L, Pitch pitch)
+		template <class Cells>
+		__global__ __launch_bounds__(kBlock) void ccl_border_kernel(Cells cells, int w, int h, int rows, int cols, int *L, Pitch pitch)
 		{
-			src += blockIdx.y * pitch.cells, L += blockIdx.y * pitch.plane;
+			typedef typename Cells::Cell Cell;
+			cells.image(pitch.cells), L += blockIdx.y * pitch.plane;
 			const int k = (int)(blockIdx.x * (unsigned)kBlock + threadIdx.x);
 			if (k < rows * w)
 			{
 				const int y = (k / w + 1) * kTileH, x = k - (k / w) * w, i = y * w + x;
-				const C v = src[i], u = src[i - w];
-				if (v == bg || u == bg)
+				const Cell v = cells.at(i, y), u = cells.at(i - w, y - 1);
+				if (!cells.foreground(v) || !cells.foreground(u))
 					return;
-				if (x > 0 && src[i - 1] == v && src[i - w - 1] == u)
+				if (x > 0 && cells.joins(cells.at(i - 1, y), v) && cells.joins(cells.at(i - w - 1, y - 1), u))
 					return;
 				unite<kImage>(L, i, i - w);
 				return;
@@ -146,8 +235,8 @@ namespace rir
 			if (q < cols * h)
 			{
 				const int x = (q / h + 1) * kTileW, y = q - (q / h) * h, i = y * w + x;
-				const C v = src[i];
-				if (v != bg && src[i - 1] == v)
+				const Cell v = cells.at(i, y);
+				if (cells.foreground(v) && cells.joins(cells.at(i - 1, y), v))
 					unite<kImage>(L, i, i - 1);
 			}
 		}
@@ -160,7 +249,8 @@ namespace rir
 		// does, the others take its answer - instead of asking the same few addresses 64 times each.
 		// Every store to a link that other waves climb through (the tile roots: cnt > 0) lowers it - atomicMin - so that a
 		// path-shortening store of another wave that lands late cannot put an ancestor back where the root has been written.
-		__global__ __launch_bounds__(kBlock) void ccl_flatten_kernel(int *L, int n, int *__restrict__ cnt, unsigned long long *__restrict__ root_bits,
+		template <class Marks>
+		__global__ __launch_bounds__(kBlock) void ccl_flatten_kernel(int *L, int n, int *__restrict__ cnt, Marks marks, unsigned long long *__restrict__ root_bits,
 																	 int *__restrict__ wave_before, int *__restrict__ block_roots, Pitch pitch)
 		{
 			__shared__ int wave_roots[kBlock / 64];
@@ -170,6 +260,12 @@ namespace rir
 			const int lane = (int)(threadIdx.x & 63), wv = (int)(threadIdx.x >> 6);
 			const int first = i < n ? link_load<kImage>(&L[i]) : -1;
 			const int c = i < n ? cnt[i] : 0;
+			int m = 0;
+			if constexpr (Marks::kOn)
+			{ // (asked for before the climb, which hides the answer's way)
+				marks.image(pitch);
+				m = c > 0 ? marks.at_tile_root[i] : 0;
+			}
 			const int left = __shfl_up(first, 1);
 			const bool head = first >= 0 && (lane == 0 || left != first);
 			int r = -1;
@@ -199,6 +295,13 @@ namespace rir
 			}
 			if (c > 0 && r != i)
 				atomicAdd(&cnt[r], c);
+			if constexpr (Marks::kOn)
+			{ // (a tile root's marks become its final root's: a few atomics a component, one for every tile it reaches into)
+				if (m & 1)
+					atomicOr(&marks.strong[r >> 6], 1ull << (r & 63));
+				if (m & 2)
+					atomicOr(&marks.edge[r >> 6], 1ull << (r & 63));
+			}
 			const uint64_t roots = __ballot(r >= 0 && r == i);
 			if (lane == 0)
 			{
@@ -220,6 +323,44 @@ namespace rir
 					s += wave_roots[q];
 				block_roots[blockIdx.x] = s;
 			}
+		}
+
+		// Hot spots: the roots that keep their number - area within [min_area, max_area], strong when `use_high`, off the edge when
+		// `clear_border` - in place of all roots, as launch 3 leaves them for launches 4 and 5.  A pass over the roots, not the pixels:
+		// a thread takes the kBlock / 64 bitmap words of one block of launch 3 and looks up the area of the roots that are left in them.
+		__global__ __launch_bounds__(kBlock) void ccl_select_kernel(int nb, const int *__restrict__ cnt, int min_area, int max_area, bool use_high,
+																	bool clear_border, const unsigned long long *__restrict__ strong,
+																	const unsigned long long *__restrict__ edge, unsigned long long *__restrict__ root_bits,
+																	int *__restrict__ wave_before, int *__restrict__ block_roots, Pitch pitch)
+		{
+			cnt += blockIdx.y * pitch.plane, strong += blockIdx.y * pitch.waves, edge += blockIdx.y * pitch.waves, root_bits += blockIdx.y * pitch.waves,
+				wave_before += blockIdx.y * pitch.waves, block_roots += blockIdx.y * pitch.blocks;
+			const int b = (int)(blockIdx.x * (unsigned)kBlock + threadIdx.x);
+			if (b >= nb)
+				return;
+			int before = 0;
+			for (int q = 0; q < kBlock / 64; ++q)
+			{
+				const int word = b * (kBlock / 64) + q;
+				unsigned long long roots = root_bits[word];
+				if (use_high)
+					roots &= strong[word];
+				if (clear_border)
+					roots &= ~edge[word];
+				unsigned long long kept = 0ull;
+				while (roots)
+				{
+					const int bit = __builtin_ctzll(roots);
+					roots &= roots - 1ull;
+					const int area = cnt[word * 64 + bit];
+					if (area >= min_area && area <= max_area)
+						kept |= 1ull << bit;
+				}
+				root_bits[word] = kept;
+				wave_before[word] = before;
+				before += __popcll(kept);
+			}
+			block_roots[b] = before;
 		}
 
 		// (one workgroup) per-block root counts -> number of roots before each block; count[0] = components + 1 (the reference's table
@@ -265,32 +406,56 @@ namespace rir
 
 		// Launch 5: labels and tables out.  A root's number = the roots before it in raster order + 1; the table's x AND y entries both
 		// receive the first pixel's x (signal_processing.cpp:262-263 stores first.x() twice); entry 0 is the background's: (-1, -1), area 0.
+		// The hot spots' table holds the first pixel's raster index instead, -1 for the background, and a root without its bit - a
+		// component that was dropped - is background.
+		struct FirstColumnTwice
+		{
+			static constexpr bool kEveryRootNumbered = true;
+			double *__restrict__ xy;
+			__device__ void image(int64_t table) { xy += blockIdx.y * table * 2; }
+			__device__ void put(int64_t k, int i, int w) const
+			{
+				const double x = i < 0 ? -1.0 : (double)(i % w);
+				xy[2 * k] = x;
+				xy[2 * k + 1] = x;
+			}
+		};
+		struct FirstIndex
+		{
+			static constexpr bool kEveryRootNumbered = false;
+			int *__restrict__ first;
+			__device__ void image(int64_t table) { first += blockIdx.y * table; }
+			__device__ void put(int64_t k, int i, int) const { first[k] = i; }
+		};
+		template <class Table>
 		__global__ __launch_bounds__(kBlock) void ccl_labels_kernel(const int *__restrict__ R, int n, int w, const int *__restrict__ cnt,
 																	const unsigned long long *__restrict__ root_bits, const int *__restrict__ wave_before,
-																	const int *__restrict__ block_before, int *__restrict__ dst, double *__restrict__ xy,
+																	const int *__restrict__ block_before, int *__restrict__ dst, Table table,
 																	int *__restrict__ area, Pitch pitch)
 		{
 			R += blockIdx.y * pitch.plane, cnt += blockIdx.y * pitch.plane, root_bits += blockIdx.y * pitch.waves, wave_before += blockIdx.y * pitch.waves,
-				block_before += blockIdx.y * pitch.blocks, dst += blockIdx.y * pitch.cells, xy += blockIdx.y * pitch.table * 2, area += blockIdx.y * pitch.table;
+				block_before += blockIdx.y * pitch.blocks, dst += blockIdx.y * pitch.cells, table.image(pitch.table), area += blockIdx.y * pitch.table;
 			const int i = (int)(blockIdx.x * (unsigned)kBlock + threadIdx.x);
 			if (i >= n)
 				return;
 			if (i == 0)
 			{
-				xy[0] = -1.0;
-				xy[1] = -1.0;
+				table.put(0, -1, w);
 				area[0] = 0;
 			}
 			const int r = R[i];
 			int k = 0;
 			if (r >= 0)
-				k = block_before[r / kBlock] + wave_before[r >> 6] + __popcll(root_bits[r >> 6] & ((1ull << (r & 63)) - 1ull)) + 1;
-			dst[i] = k;
-			if (r == i && k < pitch.table) // (a table with less room than the image has components keeps its first entries; the count says how many there are)
 			{
-				const double x = (double)(i % w);
-				xy[2 * (int64_t)k] = x;
-				xy[2 * (int64_t)k + 1] = x;
+				const unsigned long long bits = root_bits[r >> 6];
+				if (Table::kEveryRootNumbered || ((bits >> (r & 63)) & 1ull))
+					k = block_before[r / kBlock] + wave_before[r >> 6] + __popcll(bits & ((1ull << (r & 63)) - 1ull)) + 1;
+			}
+			dst[i] = k;
+			// (a table with less room than the image has components keeps its first entries; the count says how many there are)
+			if (r == i && k > 0 && k < pitch.table)
+			{
+				table.put(k, i, w);
 				area[k] = cnt[i];
 			}
 		}
@@ -390,39 +555,45 @@ namespace rir
 			return k;
 		}
 
-		template <class C>
-		hipError_t forest(const void *d_src, const void *background, int w, int h, int frames, const Work &k, hipStream_t st)
+		template <class Cells, class Marks>
+		hipError_t forest(const Cells &cells, const Marks &marks, int w, int h, int frames, const Work &k, hipStream_t st)
 		{
-			C bg;
-			__builtin_memcpy(&bg, background, sizeof(C));
 			const int tiles_x = (w + kTileW - 1) / kTileW, tiles_y = (h + kTileH - 1) / kTileH;
 			const unsigned fy = (unsigned)frames;
-			hipLaunchKernelGGL(ccl_tile_kernel<C>, dim3((unsigned)(tiles_x * tiles_y), fy), dim3(kTileThreads), 0, st, static_cast<const C *>(d_src), bg, w, h,
-							   tiles_x, k.L, k.cnt, k.best, k.pitch);
+			hipLaunchKernelGGL((ccl_tile_kernel<Cells, Marks>), dim3((unsigned)(tiles_x * tiles_y), fy), dim3(kTileThreads), 0, st, cells, marks, w, h, tiles_x,
+							   k.L, k.cnt, k.best, k.pitch);
 			const int64_t joins = (int64_t)(tiles_y - 1) * w + (int64_t)(tiles_x - 1) * h;
 			if (joins > 0)
-				hipLaunchKernelGGL(ccl_border_kernel<C>, dim3((unsigned)((joins + kBlock - 1) / kBlock), fy), dim3(kBlock), 0, st,
-								   static_cast<const C *>(d_src), bg, w, h, tiles_y - 1, tiles_x - 1, k.L, k.pitch);
-			hipLaunchKernelGGL(ccl_flatten_kernel, dim3((unsigned)k.nb, fy), dim3(kBlock), 0, st, k.L, k.n, k.cnt, k.root_bits, k.wave_before, k.block_roots,
-							   k.pitch);
+				hipLaunchKernelGGL(ccl_border_kernel<Cells>, dim3((unsigned)((joins + kBlock - 1) / kBlock), fy), dim3(kBlock), 0, st, cells, w, h, tiles_y - 1,
+								   tiles_x - 1, k.L, k.pitch);
+			hipLaunchKernelGGL(ccl_flatten_kernel<Marks>, dim3((unsigned)k.nb, fy), dim3(kBlock), 0, st, k.L, k.n, k.cnt, marks, k.root_bits, k.wave_before,
+							   k.block_roots, k.pitch);
 			return hipGetLastError();
+		}
+		template <class C>
+		hipError_t forest_equal(const void *d_src, const void *background, int w, int h, int frames, const Work &k, hipStream_t st)
+		{
+			EqualCells<C> cells;
+			cells.src = static_cast<const C *>(d_src);
+			__builtin_memcpy(&cells.bg, background, sizeof(C));
+			return forest(cells, NoMarks{}, w, h, frames, k, st);
 		}
 		hipError_t forest_of(int cell_bytes, const void *d_src, const void *background, int w, int h, int frames, const Work &k, hipStream_t st)
 		{
 			switch (cell_bytes)
 			{
 			case 1:
-				return forest<uint8_t>(d_src, background, w, h, frames, k, st);
+				return forest_equal<uint8_t>(d_src, background, w, h, frames, k, st);
 			case 2:
-				return forest<uint16_t>(d_src, background, w, h, frames, k, st);
+				return forest_equal<uint16_t>(d_src, background, w, h, frames, k, st);
 			case 4:
-				return forest<uint32_t>(d_src, background, w, h, frames, k, st);
+				return forest_equal<uint32_t>(d_src, background, w, h, frames, k, st);
 			case 8:
-				return forest<uint64_t>(d_src, background, w, h, frames, k, st);
+				return forest_equal<uint64_t>(d_src, background, w, h, frames, k, st);
 			case -4:
-				return forest<float>(d_src, background, w, h, frames, k, st);
+				return forest_equal<float>(d_src, background, w, h, frames, k, st);
 			case -8:
-				return forest<double>(d_src, background, w, h, frames, k, st);
+				return forest_equal<double>(d_src, background, w, h, frames, k, st);
 			default:
 				return hipErrorInvalidValue;
 			}
@@ -451,8 +622,55 @@ namespace rir
 		if (e != hipSuccess)
 			return e;
 		hipLaunchKernelGGL(ccl_scan_kernel, dim3((unsigned)frames), dim3(kScanBlock), 0, st, k.block_roots, k.nb, d_count, k.pitch);
-		hipLaunchKernelGGL(ccl_labels_kernel, dim3((unsigned)k.nb, (unsigned)frames), dim3(kBlock), 0, st, k.L, k.n, w, k.cnt, k.root_bits, k.wave_before,
-						   k.block_roots, d_dst, d_xy, d_area, k.pitch);
+		hipLaunchKernelGGL(ccl_labels_kernel<FirstColumnTwice>, dim3((unsigned)k.nb, (unsigned)frames), dim3(kBlock), 0, st, k.L, k.n, w, k.cnt, k.root_bits,
+						   k.wave_before,
+						   k.block_roots, d_dst, FirstColumnTwice{d_xy}, d_area, k.pitch);
+		return hipGetLastError();
+	}
+
+	// (the marks follow the labelling's own workspace: two bitmaps of the roots, and a byte a pixel of which the tile roots' are used)
+	size_t label_hot_spots_workspace_bytes(int w, int h, int frames)
+	{
+		const size_t base = label_workspace_bytes(w, h, frames);
+		if (!base)
+			return 0;
+		const Pitch p = pitch_of(w, h, 0);
+		return base + 2 * (size_t)frames * p.waves * sizeof(unsigned long long) + align64((size_t)frames * p.plane);
+	}
+
+	hipError_t launch_label_hot_spots(const uint16_t *d_frames, int w, int h, int frames, int rows, int low, const int *d_low_map, bool use_high, int high,
+									  const int *d_high_map, int min_area, int max_area, bool clear_border, int *d_dst, int *d_first, int *d_area,
+									  int64_t table_entries, int *d_count, void *d_work, hipStream_t st)
+	{
+		if (!geometry_ok(w, h, frames) || rows < 1 || rows > h || min_area < 1 || max_area < min_area || table_entries < 1 || !d_frames || !d_dst || !d_first ||
+			!d_area || !d_count || !d_work)
+			return hipErrorInvalidValue;
+		const Work k = carve(d_work, w, h, frames, table_entries);
+		const unsigned fy = (unsigned)frames;
+		const AboveThreshold above_low{d_frames, d_low_map, low, rows};
+		const size_t bitmap = (size_t)frames * k.pitch.waves * sizeof(unsigned long long);
+		unsigned long long *strong = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(k.best) + align64((size_t)frames * sizeof(*k.best)));
+		unsigned long long *edge = strong + (size_t)frames * k.pitch.waves;
+		hipError_t e;
+		if (use_high || clear_border)
+		{
+			e = hipMemsetAsync(strong, 0, 2 * bitmap, st);
+			if (e != hipSuccess)
+				return e;
+			const RootMarks marks{AboveThreshold{d_frames, d_high_map, high, rows}, use_high, clear_border, reinterpret_cast<uint8_t *>(edge) + bitmap, strong, edge};
+			e = forest(above_low, marks, w, h, frames, k, st);
+		}
+		else
+			e = forest(above_low, NoMarks{}, w, h, frames, k, st);
+		if (e != hipSuccess)
+			return e;
+		// (no component can be dropped otherwise: the launches are those of launch_label_images)
+		if (use_high || clear_border || min_area > 1 || max_area < k.n)
+			hipLaunchKernelGGL(ccl_select_kernel, dim3((unsigned)((k.nb + kBlock - 1) / kBlock), fy), dim3(kBlock), 0, st, k.nb, k.cnt, min_area, max_area,
+							   use_high, clear_border, strong, edge, k.root_bits, k.wave_before, k.block_roots, k.pitch);
+		hipLaunchKernelGGL(ccl_scan_kernel, dim3(fy), dim3(kScanBlock), 0, st, k.block_roots, k.nb, d_count, k.pitch);
+		hipLaunchKernelGGL(ccl_labels_kernel<FirstIndex>, dim3((unsigned)k.nb, fy), dim3(kBlock), 0, st, k.L, k.n, w, k.cnt, k.root_bits, k.wave_before,
+						   k.block_roots, d_dst, FirstIndex{d_first}, d_area, k.pitch);
 		return hipGetLastError();
 	}
 

@@ -1682,6 +1682,34 @@ RIR_EXPORT int rir_label_image_device(int type, const void *d_src, int *d_dst, i
 	return rir_label_images_device(type, d_src, d_dst, w, h, 1, background, d_xy, d_area, w * h + 1, d_count, d_work, work_bytes, stream);
 }
 
+// Hot spots labelled straight from uint16 frames (label_kernels.hip).  Refusals as rir_label_images_device's: -1.
+RIR_EXPORT size_t rir_label_hot_spots_workspace_bytes(int w, int h, int nframes) { return label_hot_spots_workspace_bytes(w, h, nframes); }
+
+RIR_EXPORT int rir_label_hot_spots_device(const unsigned short *d_frames, int w, int h, int nframes, int rows, int low, const int *d_low_map, int use_high,
+										  int high, const int *d_high_map, int min_area, int max_area, int clear_border, int *d_dst, int *d_first,
+										  int *d_area, int table_entries, int *d_count, void *d_work, size_t work_bytes, void *stream)
+{
+	if (!device_ready())
+		return -1;
+	const size_t need = label_hot_spots_workspace_bytes(w, h, nframes);
+	if (need == 0 || rows < 1 || rows > h || min_area < 1 || max_area < min_area || table_entries < 1)
+		return refuse(__func__, "invalid argument (w, h >= 1 with w * h <= 0x7FFF0000, 1 <= nframes <= 65535, 1 <= rows <= h, "
+								"1 <= min_area <= max_area, table_entries >= 1)");
+	if (!d_frames || !d_dst || !d_first || !d_area || !d_count || !d_work)
+		return refuse(__func__, "null pointer");
+	if (!workspace_ok(__func__, d_work, work_bytes, need, "workspace", "rir_label_hot_spots_workspace_bytes()"))
+		return -1;
+	const size_t npx = (size_t)w * h, table = (size_t)nframes * table_entries * 4;
+	if (outputs_overlap({{d_frames, npx * nframes * 2}, {d_low_map, npx * 4}, {use_high ? d_high_map : nullptr, npx * 4}},
+						{{d_dst, npx * nframes * 4}, {d_first, table}, {d_area, table}, {d_count, (size_t)nframes * 4}, {d_work, need}}))
+		return refuse(__func__, "an output or the workspace overlaps an input or another output");
+	return hip_ok(launch_label_hot_spots(d_frames, w, h, nframes, rows, low, d_low_map, use_high != 0, high, d_high_map, min_area, max_area,
+										 clear_border != 0, d_dst, d_first, d_area, table_entries, d_count, d_work, as_stream(stream)),
+				  "label_hot_spots")
+			   ? 0
+			   : -1;
+}
+
 RIR_EXPORT int rir_keep_largest_areas_device(int type, const void *d_src, int *d_dst, int w, int h, int nframes, const void *background, int foreground,
 											 void *d_work, size_t work_bytes, void *stream)
 {

@@ -145,7 +145,11 @@ _lib.rir_label_workspace_bytes.argtypes = [ct.c_int, ct.c_int]
 _lib.rir_label_workspace_bytes.restype = ct.c_size_t
 _lib.rir_label_workspace_bytes_batch.argtypes = [ct.c_int, ct.c_int, ct.c_int]
 _lib.rir_label_workspace_bytes_batch.restype = ct.c_size_t
-_lib.rir_label_images_device.argtypes = [ct.c_int, _vp, _vp, ct.c_int, ct.c_int, ct.c_int, _vp, _vp, _vp, ct.c_int, _vp, _vp, ct.c_size_t, _vp]
+_lib.rir_label_hot_spots_workspace_bytes.argtypes = [ct.c_int, ct.c_int, ct.c_int]
+_lib.rir_label_hot_spots_workspace_bytes.restype = ct.c_size_t
+_lib.rir_label_hot_spots_device.argtypes = ([_vp] + [ct.c_int] * 5 + [_vp, ct.c_int, ct.c_int, _vp] + [ct.c_int] * 3 + [_vp] * 3
+                                            + [ct.c_int, _vp, _vp, ct.c_size_t, _vp])
+_lib.rir_label_images_device.argtypes =[ct.c_int, _vp, _vp, ct.c_int, ct.c_int, ct.c_int, _vp, _vp, _vp, ct.c_int, _vp, _vp, ct.c_size_t, _vp]
 _lib.rir_keep_largest_areas_device.argtypes = [ct.c_int, _vp, _vp, ct.c_int, ct.c_int, ct.c_int, _vp, ct.c_int, _vp, ct.c_size_t, _vp]
 _lib.rir_label_image_device.argtypes = [ct.c_int, _vp, _vp, ct.c_int, ct.c_int, _vp, _vp, _vp, _vp, _vp, ct.c_size_t, _vp]
 _lib.rir_keep_largest_area_device.argtypes = [ct.c_int, _vp, _vp, ct.c_int, ct.c_int, _vp, ct.c_int, _vp, ct.c_size_t, _vp]
@@ -1266,6 +1270,113 @@ def label_images(frames, background=0, table_entries=None):
     count = torch.zeros(n, dtype=torch.int32, device=fr.device)
     _label_images_into(fr, background, dst, xy, area, count)
     return dst, area, xy, count
+
+
+class HotSpotFilter(namedtuple("HotSpotFilter", "low low_map use_high high high_map min_area max_area clear_border rows table_entries")):
+    """The checked parameters of a ``label_hot_spots`` call: thresholds as int32 in [-1, 65535] - a number, and None or an (h, w) int32 map
+    (numpy, or a tensor where a tensor was given) that takes its place -, the area window, and the rows that count."""
+
+    __slots__ = ()
+
+
+def _hot_spot_threshold(t, h, w, name):
+    """a threshold as label_hot_spots takes it -> (int, None) or (0, int32 (h, w) map); a float t stands for floor(t): v > t == v > floor(t) for
+    an integer v"""
+    if isinstance(t, (bool, np.bool_)):
+        raise ValueError("label_hot_spots: %s must be a number or an (h, w) map, not a bool" % name)
+    if isinstance(t, (int, np.integer)):
+        return min(max(int(t), -1), 65535), None
+    if isinstance(t, (float, np.floating)):
+        if t != t:
+            raise ValueError("label_hot_spots: %s is NaN" % name)
+        return int(np.floor(min(max(float(t), -1.0), 65535.0))), None
+    if isinstance(t, torch.Tensor):
+        if tuple(t.shape) != (h, w):
+            raise ValueError("label_hot_spots: %s must be a number or an (h, w) = %s map, not shape %s" % (name, (h, w), tuple(t.shape)))
+        f = t.to(torch.float64)
+        if bool(torch.isnan(f).any()):
+            raise ValueError("label_hot_spots: %s holds a NaN" % name)
+        return 0, f.clamp(-1.0, 65535.0).floor().to(torch.int32).contiguous()
+    a = np.asarray(t)
+    if a.dtype.kind not in "biuf":
+        raise ValueError("label_hot_spots: %s must be a number or an (h, w) map of numbers" % name)
+    if a.shape != (h, w):
+        raise ValueError("label_hot_spots: %s must be a number or an (h, w) = %s map, not shape %s" % (name, (h, w), a.shape))
+    f = a.astype(np.float64)
+    if np.isnan(f).any():
+        raise ValueError("label_hot_spots: %s holds a NaN" % name)
+    return 0, np.ascontiguousarray(np.floor(np.clip(f, -1.0, 65535.0)).astype(np.int32))
+
+
+def _label_hot_spots_args(shape, low, high=None, min_area=1, max_area=None, clear_border=False, rows=None, table_entries=None):
+    """the parameters of a label_hot_spots call over frames of `shape`, (h, w) or (n, h, w), checked without a device; -> (n, h, w, HotSpotFilter)"""
+    if len(shape) not in (2, 3):
+        raise ValueError("label_hot_spots: frames (n, h, w) or one image (h, w) expected")
+    n, h, w = (1,) + tuple(shape) if len(shape) == 2 else tuple(shape)
+    if h < 1 or w < 1 or h * w > TRACK_MAX_INDEX:
+        raise ValueError("label_hot_spots: frames of at least 1x1 and at most 0x7FFF0000 pixels expected")
+    lo, lo_map = _hot_spot_threshold(low, h, w, "low")
+    hi, hi_map = (0, None) if high is None else _hot_spot_threshold(high, h, w, "high")
+    if isinstance(min_area, bool) or not isinstance(min_area, (int, np.integer)) or min_area < 1:
+        raise ValueError("label_hot_spots: min_area must be an int >= 1 (got %r)" % (min_area,))
+    if max_area is not None and (isinstance(max_area, bool) or not isinstance(max_area, (int, np.integer)) or max_area < min_area):
+        raise ValueError("label_hot_spots: max_area must be an int >= min_area (got %r)" % (max_area,))
+    if rows is not None and (isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 1 <= rows <= h):
+        raise ValueError("label_hot_spots: rows must be in 1..h (got %r)" % (rows,))
+    if table_entries is not None and (int(table_entries) != table_entries or not 1 <= table_entries <= 0x7FFFFFFF):
+        raise ValueError("label_hot_spots: table_entries must be in 1..2^31 - 1 (got %r)" % (table_entries,))
+    cap = min(1024, h * w + 1) if table_entries is None else int(table_entries)
+    return n, h, w, HotSpotFilter(lo, lo_map, high is not None, hi, hi_map, min(int(min_area), 0x7FFFFFFF),
+                                  0x7FFFFFFF if max_area is None else min(int(max_area), 0x7FFFFFFF), bool(clear_border),
+                                  h if rows is None else int(rows), cap)
+
+
+def _hot_spot_maps_on(spec, device):
+    """the filter with its threshold maps as int32 tensors on `device`"""
+    def place(m):
+        return None if m is None else (m if isinstance(m, torch.Tensor) else torch.from_numpy(m)).to(device)
+
+    return spec._replace(low_map=place(spec.low_map), high_map=place(spec.high_map))
+
+
+def _label_hot_spots_into(frames, spec, dst, first, area, count):
+    """queue the labelling of the hot spots of uint16 frames (n, h, w) on the device under ``spec`` (a HotSpotFilter for frames of this size) into
+    dst int32 (n, h, w), first and area int32 (n, cap) and count int32 (n,), all contiguous"""
+    fr = _frames3(frames, torch.uint16)
+    n, h, w = fr.shape
+    need = _lib.rir_label_hot_spots_workspace_bytes(w, h, n)
+    if need == 0:
+        raise RuntimeError("label_hot_spots: geometry refused")
+    spec = _hot_spot_maps_on(spec, fr.device)
+    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    _check(_lib.rir_label_hot_spots_device(fr.data_ptr(), w, h, n, spec.rows, spec.low, None if spec.low_map is None else spec.low_map.data_ptr(),
+                                           int(spec.use_high), spec.high, None if spec.high_map is None else spec.high_map.data_ptr(),
+                                           spec.min_area, spec.max_area, int(spec.clear_border), dst.data_ptr(), first.data_ptr(), area.data_ptr(),
+                                           area.shape[1], count.data_ptr(), work.data_ptr(), work.numel() * 8, _stream()), "rir_label_hot_spots_device")
+
+
+def label_hot_spots(frames, low, high=None, min_area=1, max_area=None, clear_border=False, rows=None, table_entries=None):
+    """The hot spots of uint16 frames (n, h, w) (or one image) in device memory, detected, filtered and numbered without a mask in memory
+    (C ABI ``rir_label_hot_spots_device``): (labels int32 (n, h, w), area (n, table_entries), first (n, table_entries), counts (n,)), on the
+    device.  Pixel (y, x) is foreground when ``y < rows`` (default: every row) and its value is ``> low``; components are the 4-connected
+    sets of foreground pixels, as ``label_images(frames > low)`` finds them.  A component is KEPT when it holds a pixel ``> high`` (when
+    ``high`` is given; one below ``low`` filters nothing), ``min_area <= area <= max_area`` (no upper limit by default), and - with
+    ``clear_border`` - none of its pixels lies in row 0, row ``rows - 1``, column 0 or column ``w - 1``.  Kept components are numbered
+    1, 2, ... per frame in the raster order of their first pixel; everything else is 0, so ``labels`` is ``label_images(kept mask)[0]``.
+    ``area`` and ``first`` - the raster index ``y * w + x`` of the first pixel - hold one entry per component, entry 0 the background's
+    (0, -1); ``counts[i]`` = kept components of frame i + 1, and a table with fewer entries than that holds the first ``table_entries``
+    (default: 1 024, or h*w + 1 if that is less).  ``low`` and ``high`` are an int, a float or an (h, w) array or tensor; a float t stands
+    for floor(t), and thresholds are held as int32 in [-1, 65535].  ``ValueError`` on bad parameters, before any device work."""
+    shape = tuple(frames.shape)
+    n, h, w, spec = _label_hot_spots_args(shape, low, high, min_area, max_area, clear_border, rows, table_entries)
+    fr = _frames3(frames, torch.uint16)
+    cap = spec.table_entries
+    dst = torch.empty((n, h, w), dtype=torch.int32, device=fr.device)
+    first = torch.zeros((n, cap), dtype=torch.int32, device=fr.device)
+    area = torch.zeros((n, cap), dtype=torch.int32, device=fr.device)
+    count = torch.zeros(n, dtype=torch.int32, device=fr.device)
+    _label_hot_spots_into(fr, spec, dst, first, area, count)
+    return dst, area, first, count
 
 
 TRACK_MAX_INDEX = 0x7FFF0000  # pixels of a frame, and frames x nlabels, of one track_components call

@@ -575,7 +575,8 @@ class IRMovie(object):
         ``region_stats`` of every image over its track map, ``[len(selection)][ntracks]`` - the time trace of every hot spot (``count`` is
         its area in each image).  The recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of images (twice with ``stats``), but
         the label stack of the whole selection stays on the device: 4 bytes a pixel and image.  ``track_hot_spots_geometry`` adds the
-        box, centroid and extent of every hot spot."""
+        box, centroid and extent of every hot spot; ``track_kept_hot_spots`` tracks only the components that pass a hysteresis, area or
+        border filter."""
         return self._track_hot_spots(threshold, selection, table_entries, stats, False)
 
     def track_hot_spots_geometry(self, threshold, selection=slice(None), table_entries=None, stats=True):
@@ -585,18 +586,36 @@ class IRMovie(object):
         pass over the recording as the statistics (a pass of its own with ``stats=False``)."""
         return self._track_hot_spots(threshold, selection, table_entries, stats, True)
 
-    def _track_hot_spots(self, threshold, selection, table_entries, stats, geometry):
+    def track_kept_hot_spots(self, threshold, selection=slice(None), table_entries=None, stats=True, geometry=False, high=None, min_area=1,
+                             max_area=None, clear_border=False):
+        """``track_hot_spots`` (``track_hot_spots_geometry`` with ``geometry=True``) over the components that are KEPT, as
+        ``librir_amd.device.label_hot_spots`` chooses them with ``threshold`` as its ``low``: a component of ``image > threshold`` is kept
+        when it holds a pixel ``> high`` (an int, a float or an ``(h, w)`` map; hysteresis - ``None``: not asked for),
+        ``min_area <= area <= max_area`` (no upper limit by default), and - with ``clear_border`` - none of its pixels lies on the first
+        or last row or column of the image.  Dropped components are background: they join no track and count in no statistic.
+        ``threshold`` may also be a float, which stands for its floor.
+        The images are labelled straight from their pixels, no mask is stored; with all four filters at their defaults every component
+        is kept and the result is ``track_hot_spots``'.  ``ValueError`` on bad parameters, before the recording is read."""
+        return self._track_hot_spots(threshold, selection, table_entries, stats, bool(geometry),
+                                     dict(high=high, min_area=min_area, max_area=max_area, clear_border=clear_border))
+
+    def _track_hot_spots(self, threshold, selection, table_entries, stats, geometry, filters=None):
         import torch
 
-        from ..device import (_label_images_into, _region_geometry_empty, _region_geometry_into, _region_stats_empty, _region_stats_into,
-                              _track_args, track_components)
+        from ..device import (_hot_spot_maps_on, _label_hot_spots_args, _label_hot_spots_into, _label_images_into, _region_geometry_empty,
+                              _region_geometry_into, _region_stats_empty, _region_stats_into, _track_args, track_components)
 
         h, w = self.image_size
         positions = self._stats_positions(selection, "track_hot_spots")
         n = len(positions)
         _track_args((n, h, w), None, None, table_entries)
+        filtered = filters is not None  # (track_kept_hot_spots: labelled by label_hot_spots, whatever the filters)
+        if filtered:
+            kept = _label_hot_spots_args((max(n, 1), h, w), threshold, rows=None, table_entries=1, **filters)[3]
         device = torch.device("cuda", torch.cuda.current_device())
-        if isinstance(threshold, (int, np.integer)):
+        if filtered:
+            kept = _hot_spot_maps_on(kept, device)
+        elif isinstance(threshold, (int, np.integer)):
             cut = int(threshold)
         else:
             cut = threshold if isinstance(threshold, torch.Tensor) else np.asarray(threshold)
@@ -613,6 +632,7 @@ class IRMovie(object):
         piece = torch.empty((min(per_piece, n), h, w), dtype=torch.uint16, device=device)
         xy = torch.zeros((piece.shape[0], 1, 2), dtype=torch.float64, device=device)
         area = torch.zeros((piece.shape[0], 1), dtype=torch.int32, device=device)
+        first = torch.zeros_like(area) if filtered else None
 
         def pieces():
             for k0 in range(0, n, per_piece):
@@ -622,6 +642,9 @@ class IRMovie(object):
                 yield k0, k0 + len(sel), fr
 
         for k0, k1, fr in pieces():
+            if filtered:
+                _label_hot_spots_into(fr, kept, stack[k0:k1], first[:k1 - k0], area[:k1 - k0], counts[k0:k1])
+                continue
             hot = (fr.view(torch.int16).to(torch.int32) & 0xFFFF) > cut
             _label_images_into(hot, 0, stack[k0:k1], xy[:k1 - k0], area[:k1 - k0], counts[k0:k1])
         nlabels = max(1, int(counts.max())) if n else 1
