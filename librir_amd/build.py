@@ -17,7 +17,7 @@ LIB_NAME = "librir_amd.so"
 # The same library with the TEST HOOKS compiled in (-DRIR_TEST_HOOKS: fault injection through RIR_DEBUG_* variables, runtime.h).  Only the
 # tests that force a bail-out path load it (tests/hook_cases.py, RIR_LIBRARY_VARIANT=testhooks); the product library contains no hook.
 HOOKS_LIB_NAME = "librir_amd_testhooks.so"
-HOOKS_UNITS = ["video_io_abi.cpp", "registration_abi.cpp"]  # the translation units that read a hook
+HOOKS_UNITS = ["lossy_abi.cpp", "registration_abi.cpp", "video_io_abi.cpp"]  # the translation units that read a hook
 # the names the wrapper globs for, and the SONAMEs the reference's own libraries record for each other (SOVERSION = major
 # version, src/cpp/tools/CMakeLists.txt:83-84): the reference's libgeometry.so, which a drop-in keeps, NEEDs libtools.so.6
 ALIASES = ["libtools.so", "libsignal_processing.so", "libvideo_io.so", "libtools.so.6", "libsignal_processing.so.6", "libvideo_io.so.6"]

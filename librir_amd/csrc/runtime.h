@@ -58,6 +58,7 @@ namespace rir
 	// error code.
 	// Test hooks (fault injection: RIR_DEBUG_LOSSY_GIVE_UP, RIR_DEBUG_LOSSY_BAIL, RIR_DEBUG_ECC_BAIL) exist only in the build made with
 	// -DRIR_TEST_HOOKS (librir_amd/build.py: libs/librir_amd_testhooks.so, loaded by the tests that need it); the product library reads none of them.
+	// They are read in lossy_abi.cpp (the bounded-loss run), registration_abi.cpp and by the saver in video_io_abi.cpp (RIR_DEBUG_SAVER_FAIL_FLYING).
 #ifdef RIR_TEST_HOOKS
 	inline const char *test_hook(const char *name) { return getenv(name); }
 #else

@@ -25,6 +25,7 @@
 #include "file_attributes.h"
 #include "filter_kernels.h"
 #include "lossy_kernels.h"
+#include "lossy_stream.h"
 #include "rir_amd_device.h"
 #include "runtime.h"
 
@@ -47,8 +48,6 @@ static int guarded(const char *what, int on_error, F &&body)
 
 extern "C"
 {
-	int rir_bad_pixels_create_device(const unsigned short *, int, int, void *);
-	int rir_bad_pixels_correct_device(int, const unsigned short *, unsigned short *, int, void *);
 	int rir_bad_pixels_create_rows_device(const unsigned short *, int, int, int, void *);
 	int rir_remove_bad_pixels_device(int, unsigned short *, int, int, void *);
 	int rir_remove_motion_device(const unsigned short *, unsigned short *, int, int, int, int, const float *, void *);
@@ -172,276 +171,8 @@ namespace
 		}
 	};
 
-	// ---- bounded-loss step ---------------------------------------------------------------------
-	// Host side of H264_Saver::addImageLossyNoCamera / addLoss (h264.cpp:2253-2424, :2426-2607): the
-	// per-pixel work runs in lossy_kernels.hip; the error budget (40-frame window of the quirky
-	// "stdDev" statistics, h264.cpp:2335-2385) is scalar double arithmetic done here from the exact
-	// integer sums the GPU returns.
-	struct LossyState
-	{
-		int w = 0, h = 0, hl = 0;
-		int frames = 0;
-		DeviceBuffer d_img, d_tmp, d_out, d_ref, d_prev, d_last, d_sums, d_cval, d_ccnt, d_ring, d_hist, d_stats, d_min, d_budget, d_decision, d_errs, d_tickets;
-		LossyDeviceState dev{};
-		DeviceBuffer d_shadow;		   // the speculative form of a run (lossy_kernels.h: LossySpec): where a pass leaves the state after the group
-		LossyDeviceState shadow{};	   // ... carved out of it (reserve_shadow)
-		int bp_handle = 0;
-
-		~LossyState()
-		{
-			if (bp_handle > 0)
-				bad_pixels_destroy(bp_handle);
-		}
-
-		bool prepare(int w_, int h_, int hl_, int running_average, bool subtract_min)
-		{
-			w = w_, h = h_, hl = std::max(0, std::min(hl_, h_));
-			const size_t full = (size_t)w * h, s = (size_t)w * hl;
-			const int ra = std::max(0, std::min(running_average, 64));
-			if (!d_img.reserve(full * 2) || !d_tmp.reserve(full * 2) || !d_out.reserve(full * 2) || !d_ref.reserve(full * 2) ||
-				!d_prev.reserve(full * 2) || !d_last.reserve(full * 2) || !d_sums.reserve(s * 4 + 4) || !d_cval.reserve(s * 2 + 4) ||
-				!d_ccnt.reserve(s * 2 + 4) || !d_ring.reserve((size_t)std::max(ra, 1) * s * 2 + 4) || !d_hist.reserve(16384 * 4) ||
-				!d_stats.reserve(8 * sizeof(long long)) || !d_min.reserve(4) || !d_budget.reserve(sizeof(LossyBudget)) ||
-				!d_decision.reserve(sizeof(LossyDecision)) || !d_errs.reserve(2 * sizeof(int)) || !d_tickets.reserve(2 * sizeof(unsigned int)))
-				return false;
-			hipStream_t st = default_stream();
-			// histogram, sums and budget start at zero; afterwards every frame leaves the first two cleared (lossy_kernels.hip)
-			if (!hip_ok(hipMemsetAsync(d_sums.ptr, 0, s * 4 + 4, st), "memset") || !hip_ok(hipMemsetAsync(d_cval.ptr, 0, s * 2 + 4, st), "memset") ||
-				!hip_ok(hipMemsetAsync(d_ccnt.ptr, 0, s * 2 + 4, st), "memset") || !hip_ok(hipMemsetAsync(d_hist.ptr, 0, 16384 * 4, st), "memset") ||
-				!hip_ok(hipMemsetAsync(d_stats.ptr, 0, 8 * sizeof(long long), st), "memset") ||
-				!hip_ok(hipMemsetAsync(d_budget.ptr, 0, sizeof(LossyBudget), st), "memset") ||
-				!hip_ok(hipMemsetAsync(d_tickets.ptr, 0, 2 * sizeof(unsigned int), st), "memset"))
-				return false;
-			dev.refT = d_ref.as<uint16_t>(), dev.prevT = d_prev.as<uint16_t>(), dev.lastDL = d_last.as<uint16_t>();
-			dev.ra_sums = d_sums.as<uint32_t>(), dev.ra_const_value = d_cval.as<uint16_t>(), dev.ra_const_count = d_ccnt.as<int16_t>();
-			dev.ra_images = d_ring.as<uint16_t>();
-			dev.ra_count = 0, dev.ra_head = 0, dev.running_average = ra;
-			dev.subtract_min = subtract_min ? 1 : 0;
-			dev.min = 0;
-			frames = 0;
-			return hip_ok(wait_stream(st), "sync"); // the state is ready whatever stream the steps run on
-		}
-
-		// img (host, full frame) -> d_out (device, full frame), copied to `out` (host) when it is not NULL.
-		bool step(const unsigned short *img, unsigned short *out, bool add_loss, bool remove_bad_pixels, int low_value_error, int high_value_error,
-				  double std_factor, int &low_error, int &high_error)
-		{
-			hipStream_t st = default_stream();
-			const int full = w * h;
-			int e[2] = {0, 0};
-			if (!hip_ok(hipMemcpyAsync(d_img.ptr, img, (size_t)full * 2, hipMemcpyHostToDevice, st), "H2D") ||
-				!queue_frame(d_img.as<uint16_t>(), d_out.as<uint16_t>(), add_loss, remove_bad_pixels, low_value_error, high_value_error, std_factor,
-							 d_errs.as<int>(), st) ||
-				!hip_ok(hipMemcpyAsync(e, d_errs.ptr, sizeof(e), hipMemcpyDeviceToHost, st), "D2H"))
-				return false;
-			// (when out is NULL the caller consumes d_out on the same stream)
-			if (out && !hip_ok(hipMemcpyAsync(out, d_out.ptr, (size_t)full * 2, hipMemcpyDeviceToHost, st), "D2H"))
-				return false;
-			if (!hip_ok(wait_stream(st), "sync"))
-				return false;
-			low_error = e[0], high_error = e[1];
-			return true;
-		}
-
-		// pinned_img (PAGE-LOCKED host memory that stays untouched until the stream has passed this point) -> d_out (device),
-		// queued without waiting; the frame's low / high error goes to d_errors (device int[2]).
-		bool queue_host_frame(const unsigned short *pinned_img, bool add_loss, bool remove_bad_pixels, int low_value_error, int high_value_error,
-							  double std_factor, int *d_errors)
-		{
-			hipStream_t st = default_stream();
-			return hip_ok(hipMemcpyAsync(d_img.ptr, pinned_img, (size_t)w * h * 2, hipMemcpyHostToDevice, st), "H2D") &&
-				   queue_frame(d_img.as<uint16_t>(), d_out.as<uint16_t>(), add_loss, remove_bad_pixels, low_value_error, high_value_error, std_factor,
-							   d_errors, st);
-		}
-
-		// One frame, device to device, and its budget back on the host (one 8-byte read-back and a synchronisation).
-		bool step_device(const uint16_t *d_src, uint16_t *d_dst, bool add_loss, bool remove_bad_pixels, int low_value_error, int high_value_error,
-						 double std_factor, int &low_error, int &high_error, hipStream_t st)
-		{
-			int e[2] = {0, 0};
-			if (!queue_frame(d_src, d_dst, add_loss, remove_bad_pixels, low_value_error, high_value_error, std_factor, d_errs.as<int>(), st) ||
-				!hip_ok(hipMemcpyAsync(e, d_errs.ptr, sizeof(e), hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(wait_stream(st), "sync"))
-				return false;
-			low_error = e[0], high_error = e[1];
-			return true;
-		}
-
-		// One frame, device to device (d_src and d_dst: full frames, distinct), queued on `st` without waiting: statistics,
-		// error budget (lossy_budget_kernel) and update all run on the device.  d_errors: device int[2] that receives the
-		// frame's low / high error (may be NULL).  Only the very first frame of a subtractMin stream waits (its minimum
-		// becomes a parameter of every later launch).
-		bool queue_frame(const uint16_t *d_src, uint16_t *d_dst, bool add_loss, bool remove_bad_pixels, int low_value_error, int high_value_error,
-						 double std_factor, int *d_errors, hipStream_t st)
-		{
-			const int full = w * h, s = w * hl;
-			const uint16_t *tmp = d_src; // without bad-pixel repair the frame is used as it is
-			if (remove_bad_pixels && hl > 0)
-			{ // bp.init on the first image (rows < lossy_height), bp.correct on every image (h264.cpp:2259-2266)
-				if (frames == 0 && bp_handle <= 0)
-					bp_handle = rir_bad_pixels_create_device(d_src, w, hl, st);
-				uint16_t *fixed = d_tmp.as<uint16_t>();
-				if (bp_handle <= 0 || rir_bad_pixels_correct_device(bp_handle, d_src, fixed, 1, st) != 0)
-					return false;
-				if (full > s && !hip_ok(hipMemcpyAsync(fixed + s, d_src + s, (size_t)(full - s) * 2, hipMemcpyDeviceToDevice, st), "D2D"))
-					return false;
-				tmp = fixed;
-			}
-			if (frames == 0)
-			{
-				if (dev.subtract_min && s > 0)
-				{
-					unsigned int mn = 65535;
-					if (!hip_ok(launch_lossy_min(tmp, s, d_min.as<unsigned int>(), st), "lossy min") ||
-						!hip_ok(hipMemcpyAsync(&mn, d_min.ptr, 4, hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(wait_stream(st), "sync"))
-						return false;
-					dev.min = mn;
-				}
-				if (!hip_ok(launch_lossy_first(tmp, d_dst, dev, s, full, st), "lossy first"))
-					return false;
-				// the first image is stored as it is: its errors are the configured ones (h264.cpp:2290-2333)
-				if (d_errors && (!hip_ok(hipMemsetD32Async((hipDeviceptr_t)d_errors, low_value_error, 1, st), "errors") ||
-								 !hip_ok(hipMemsetD32Async((hipDeviceptr_t)(d_errors + 1), high_value_error, 1, st), "errors")))
-					return false;
-			}
-			else
-			{
-				const LossyStep step = make_step(tmp, d_src, d_dst, add_loss, low_value_error, high_value_error, std_factor, d_errors);
-				if (!hip_ok(launch_lossy_step(&step, nullptr, 1, st), "lossy step"))
-					return false;
-				advance_ring();
-			}
-			++frames;
-			return true;
-		}
-
-		// what the kernels of the next frame need (the ring indices as they are now)
-		LossyStep make_step(const uint16_t *tmp, const uint16_t *img, uint16_t *dst, bool add_loss, int low_value_error, int high_value_error,
-							double std_factor, int *d_errors, int nstreams = 1)
-		{
-			LossyStep p;
-			p.hist_px = lossy_hist_px(w * hl, nstreams), p.reserved = 0;
-			p.tmp = tmp, p.img = img, p.out = dst;
-			p.st = dev;
-			p.hist = d_hist.as<uint32_t>(), p.stats = d_stats.as<long long>();
-			p.budget = d_budget.as<LossyBudget>(), p.decision = d_decision.as<LossyDecision>();
-			p.errors_out = d_errors;
-			p.tickets = d_tickets.as<unsigned int>();
-			p.s = w * hl, p.full = w * h;
-			p.add_loss = add_loss ? 1 : 0, p.low_value_error = low_value_error, p.high_value_error = high_value_error;
-			p.std_factor = std_factor;
-			p.next_tmp = p.next_img = nullptr, p.next_background = nullptr, p.next_errors_out = nullptr;
-			p.do_update = 1, p.reserved2 = 0;
-			return p;
-		}
-		// the shadow arrays of the speculative form, allocated when a stream is first offered to it: as the state's own, ring included
-		bool reserve_shadow()
-		{
-			if (shadow.refT)
-				return true;
-			const size_t full = (size_t)w * h, s = (size_t)w * hl;
-			auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-			const size_t ring = (size_t)std::max(dev.running_average, 1) * s * 2 + 16;
-			const size_t total = 3 * up(full * 2 + 16) + up(s * 4 + 16) + 2 * up(s * 2 + 16) + up(ring);
-			if (!d_shadow.reserve(total))
-				return false;
-			char *p = d_shadow.as<char>();
-			shadow = dev;
-			shadow.refT = reinterpret_cast<uint16_t *>(p), p += up(full * 2 + 16);
-			shadow.prevT = reinterpret_cast<uint16_t *>(p), p += up(full * 2 + 16);
-			shadow.lastDL = reinterpret_cast<uint16_t *>(p), p += up(full * 2 + 16);
-			shadow.ra_sums = reinterpret_cast<uint32_t *>(p), p += up(s * 4 + 16);
-			shadow.ra_const_value = reinterpret_cast<uint16_t *>(p), p += up(s * 2 + 16);
-			shadow.ra_const_count = reinterpret_cast<int16_t *>(p), p += up(s * 2 + 16);
-			shadow.ra_images = reinterpret_cast<uint16_t *>(p);
-			return true;
-		}
-		void advance_ring()
-		{
-			if (dev.running_average > 0)
-			{
-				if (dev.ra_count == dev.running_average)
-					dev.ra_head = (dev.ra_head + 1) % dev.running_average;
-				else
-					++dev.ra_count;
-			}
-		}
-	};
-
-	// handle for the device-resident form of the bounded-loss step (rir_lossy_*)
-	struct LossyObject : public Object
-	{
-		const char *type_name() const override { return "LossyStream"; }
-		LossyState st;
-		int low = 6, high = 2;
-		double std_factor = 5;
-		bool remove_bad_pixels = false;
-		DeviceBuffer batch_errs; // int[nframes][2] of the last rir_lossy_step_device call
-		DeviceBuffer multi_table; // rir_lossy_step_multi_device: the steps of the call (this object leads it)
-		DeviceBuffer run_exchange; // the run kernel's ticket, error word and exchange words
-		DeviceBuffer run_hist, run_tickets, run_bg; // runs of frames: histogram slices and tickets of a group of frames, backgrounds of the call
-	DeviceBuffer const_ok, const_partials;		// constant-budget form: one word per group of the last call (1 = stepped by it), the tail frames' sums
-	int const_groups = 0;						// groups of the last run call that were OFFERED to the constant-budget form (0: it was not eligible)
-	// speculative form (lossy_kernels.h: LossySpec): the budget tables, sums and statistics of a group (reused group after group), the control
-	// words of every group and stream of the last call, and - for good - the back-off words of the calls this stream leads
-	DeviceBuffer spec_budgets, spec_rows, spec_sd, spec_ctl, spec_backoff, spec_tickets, spec_dplane;
-	PinnedBuffer spec_backoff_host;				// the back-off words again, where the host can look without waiting (lossy_kernels.h: LossySpec::backoff_host)
-	int spec_groups = 0, spec_streams = 0;		// groups (and streams) of the last run call that went through the speculative launches (0: not eligible)
-		PinnedBuffer multi_stage;
-		hipEvent_t multi_copied = nullptr; // the copy out of multi_stage of the last call (whatever its stream) has completed
-		// A resident run that gave up a wait has advanced the stream's state with invalid frames: the failure is STICKY - every
-		// later step / status of a stream that took part in such a call fails until the stream is destroyed.  The error word lives
-		// with the call's leading stream and says "some call since the last check"; so the leader numbers the calls it led and
-		// keeps the ranges found invalid, and every member remembers who led its last run call and that call's number.
-		unsigned int run_epoch = 0, run_arrivals = 0; // residency control block in run_exchange's header (resident_device.h): launches / workgroups so far
-		bool failed = false;
-		uint64_t led_calls = 0, led_clean = 0;					   // as a leader: run calls led / of those, known good at the last check
-		std::vector<std::pair<uint64_t, uint64_t>> led_bad;		   // calls in (first, second] are invalid
-		std::weak_ptr<Object> lead;								   // leader of the last run call this stream took part in, when that was another stream
-		bool led_by_other = false;								   // ... which `lead` then names (a leader that has been destroyed leaves no record)
-		uint64_t lead_call = 0;									   // that call's number with the leader (0: no run call yet)
-		LossyObject *leader()
-		{
-			if (lead_call == 0)
-				return nullptr;
-			if (!led_by_other)
-				return this;
-			// a foreign leader that is gone took its books with it: lead_call is a number of ITS numbering and must not be read against this
-			// object's own ranges - "no record" (a call that was checked while its leader lived has filed its verdict with every member: is_failed())
-			auto l = lead.lock();
-			return l ? dynamic_cast<LossyObject *>(l.get()) : nullptr;
-		}
-		bool is_failed()
-		{
-			if (failed)
-				return true;
-			if (LossyObject *l = leader())
-				for (const auto &r : l->led_bad)
-					if (lead_call > r.first && lead_call <= r.second)
-						failed = true;
-			return failed;
-		}
-		// files what a read of the error word (after a wait on the stream the calls were queued on) has shown
-		void checked(unsigned int gave_up, hipStream_t st)
-		{
-			if (gave_up)
-			{
-				led_bad.emplace_back(led_clean, led_calls);
-				(void)hipMemsetAsync(run_exchange.as<unsigned int>() + 16, 0, 4, st);
-			}
-			led_clean = led_calls;
-		}
-		~LossyObject() override
-		{
-			if (multi_copied)
-				(void)hipEventDestroy(multi_copied);
-		}
-	};
-
 	// ---- saver -------------------------------------------------------------------------------
 	// reference: struct H264 (video_io.cpp:651-657) + H264_Saver (h264.cpp:1662-1939)
-	// (defined with the rir_lossy_* entry points)
-	int lossy_step_streams(LossyObject *const *os, int nstreams, const unsigned short *const *d_in, unsigned short *const *d_out, int nframes, int add_loss,
-						   int *const *d_errs, int *low_errors, int *high_errors, hipStream_t st, bool force_per_frame = false);
 
 	struct SaverObject : public Object
 	{
@@ -662,6 +393,8 @@ namespace
 					(void)hipEventDestroy(e);
 		}
 
+		// what a frame is stepped under now (set_parameter)
+		LossyParams loss_params(bool add_loss) const { return LossyParams{add_loss, removeBadPixels, lowValueError, highValueError, stdFactor}; }
 		// the loss-injection state is created on the first lossy call (after the lazy open)
 		bool lossy_ready()
 		{
@@ -721,7 +454,7 @@ namespace
 				return frame_added(ts, attrs);
 			}
 			if (!run_deferred_loss() ||
-				!lossy->queue_host_frame(slot, false, removeBadPixels, lowValueError, highValueError, stdFactor, d_err_slots.as<int>() + 2 * deferred.size()))
+				!lossy->queue_host_frame(slot, loss_params(false), d_err_slots.as<int>() + 2 * deferred.size()))
 				return false;
 			if (first)
 			{
@@ -841,15 +574,12 @@ namespace
 				return true;
 			std::vector<int> e(deferred.size() * 2);
 			hipStream_t st = default_stream();
-			unsigned int gave_up = 0; // the run kernel's error word (lossy_step_streams): a wait between workgroups that hit its clock
-			unsigned int poison = 0;  // ... or a launch that did not become resident and was called off (resident_device.h): its frames were not stepped
-			const bool have_run = lossy_obj && lossy_obj->run_exchange.ptr;
+			unsigned int words[2] = {0, 0}; // the run kernel's error word and the poison word (LossyObject::queue_verdict_read)
+			const bool have_run = lossy_obj && lossy_obj->has_run();
 			if (!hip_ok(hipMemcpyAsync(e.data(), d_err_slots.ptr, e.size() * sizeof(int), hipMemcpyDeviceToHost, st), "D2H") ||
-				(have_run && (!hip_ok(hipMemcpyAsync(&gave_up, lossy_obj->run_exchange.as<unsigned int>() + 16, 4, hipMemcpyDeviceToHost, st), "D2H") ||
-							  !hip_ok(hipMemcpyAsync(&poison, lossy_obj->run_exchange.as<unsigned int>() + kLossyRunCtlWord + 2, 4, hipMemcpyDeviceToHost, st), "D2H"))) ||
-				!hip_ok(wait_stream(st), "sync"))
+				(have_run && !lossy_obj->queue_verdict_read(words, st)) || !hip_ok(wait_stream(st), "sync"))
 				return false;
-			const bool ok = file_errors(deferred, e.data(), gave_up | poison, have_run);
+			const bool ok = file_errors(deferred, e.data(), words[0] | words[1], have_run);
 			deferred.clear();
 			return ok;
 		}
@@ -860,7 +590,7 @@ namespace
 			if (!img || !usable() || !open() || !lossy_ready())
 				return false;
 			int lo = 0, hi = 0;
-			if (!resolve_errors() || !lossy->step(img, lossy_out.data(), true, removeBadPixels, lowValueError, highValueError, stdFactor, lo, hi))
+			if (!resolve_errors() || !lossy->step(img, lossy_out.data(), loss_params(true), lo, hi))
 				return false;
 			low_errors.push_back((unsigned short)lo);
 			high_errors.push_back((unsigned short)hi);
@@ -1070,15 +800,13 @@ namespace
 			flying.defs.clear();
 			if (!deferred.empty())
 			{ // (slots 0 .. deferred.size() of d_err_slots: the frames of this chunk; the copy runs before any kernel of the next chunk)
-				const bool have_run = lossy_obj && lossy_obj->run_exchange.ptr;
+				const bool have_run = lossy_obj && lossy_obj->has_run();
 				const size_t eb = deferred.size() * 2 * sizeof(int);
 				if (!h_errs.reserve((size_t)ERR_SLOTS * 2 * sizeof(int) + 16))
 					return false;
 				unsigned int *words = reinterpret_cast<unsigned int *>(h_errs.as<char>() + (size_t)ERR_SLOTS * 2 * sizeof(int));
 				words[0] = words[1] = 0;
-				if (!hip_ok(hipMemcpyAsync(h_errs.ptr, d_err_slots.ptr, eb, hipMemcpyDeviceToHost, st), "D2H") ||
-					(have_run && (!hip_ok(hipMemcpyAsync(words, lossy_obj->run_exchange.as<unsigned int>() + 16, 4, hipMemcpyDeviceToHost, st), "D2H") ||
-								  !hip_ok(hipMemcpyAsync(words + 1, lossy_obj->run_exchange.as<unsigned int>() + kLossyRunCtlWord + 2, 4, hipMemcpyDeviceToHost, st), "D2H"))))
+				if (!hip_ok(hipMemcpyAsync(h_errs.ptr, d_err_slots.ptr, eb, hipMemcpyDeviceToHost, st), "D2H") || (have_run && !lossy_obj->queue_verdict_read(words, st)))
 					return false;
 				flying.defs.swap(deferred);
 				flying.have_run = have_run;
@@ -3516,701 +3244,6 @@ RIR_EXPORT int h264_add_loss(int file, unsigned short *img)
 		return -1;
 	}
 	return guarded("h264_add_loss", -1, [&] { return s->add_loss(img) ? 0 : -1; });
-}
-
-// ---- bounded-loss step on a device-resident stream ---------------------------------------------------------------
-// The loss injection of H264_Saver::addImageLossyNoCamera / addLoss (h264.cpp:2253-2607) without the saver around it:
-// frames in HBM in, frames in HBM out, one state object per stream.
-RIR_EXPORT int rir_lossy_create(int width, int height, int lossy_height, int low_value_error, int high_value_error, double std_factor,
-								int running_average, int subtract_min, int remove_bad_pixels)
-{
-	if (!device_ready())
-		return 0;
-	if (width <= 0 || height <= 0 || lossy_height < 0)
-	{
-		log_error("rir_lossy_create: invalid argument");
-		return 0;
-	}
-	auto o = std::make_shared<LossyObject>();
-	o->low = low_value_error, o->high = high_value_error, o->std_factor = std_factor, o->remove_bad_pixels = remove_bad_pixels != 0;
-	if (!o->st.prepare(width, height, lossy_height, running_average, subtract_min != 0))
-		return 0;
-	return register_object(o);
-}
-
-// A parameter change on a stream in use (H264_Saver::setParameter lowValueError / highValueError / stdFactor, h264.cpp:1709-1781): applies
-// from the next frame on; the history the budget is computed from (firstStdDevs, the 40-frame window) stays.
-RIR_EXPORT int rir_lossy_set_errors(int handle, int low_value_error, int high_value_error, double std_factor)
-{
-	auto o = lookup_as<LossyObject>(handle);
-	if (!o)
-	{
-		log_error("rir_lossy_set_errors: invalid handle");
-		return -1;
-	}
-	o->low = low_value_error, o->high = high_value_error, o->std_factor = std_factor;
-	return 0;
-}
-
-// d_in, d_out: uint16 [nframes][height][width], distinct buffers; low_errors / high_errors: HOST int[nframes] (may be NULL).
-// Frames are processed in order (the state is sequential); add_loss != 0 selects the addLoss variant.
-RIR_EXPORT int rir_lossy_step_device(int handle, const unsigned short *d_in, unsigned short *d_out, int nframes, int add_loss, int *low_errors,
-									 int *high_errors, void *stream)
-{
-	auto o = lookup_as<LossyObject>(handle);
-	if (!o || !d_in || !d_out || d_in == d_out || nframes <= 0)
-	{
-		log_error("rir_lossy_step_device: invalid argument");
-		return -1;
-	}
-	{
-		const size_t span = (size_t)nframes * (size_t)o->st.w * (size_t)o->st.h;
-		if (d_in < d_out + span && d_out < d_in + span)
-		{
-			log_error("rir_lossy_step_device: input and output frames overlap");
-			return -1;
-		}
-	}
-	// a batch without bad-pixel repair is a run of frames: one launch per frame instead of three (rir_lossy_step_multi_device)
-	if (!o->remove_bad_pixels && nframes >= 3)
-	{
-		const unsigned short *in1[1] = {d_in};
-		unsigned short *out1[1] = {d_out};
-		return rir_lossy_step_multi_device(&handle, 1, in1, out1, nframes, add_loss, low_errors, high_errors, stream);
-	}
-	// every frame is queued without waiting (statistics, budget and update all run on the device); the budgets of the batch
-	// come back in one copy at the end - or not at all when the caller does not ask for them: then nothing here waits
-	const size_t npx = (size_t)o->st.w * o->st.h;
-	hipStream_t st = (hipStream_t)stream;
-	const bool want = low_errors || high_errors;
-	if (want && !o->batch_errs.reserve((size_t)nframes * 2 * sizeof(int)))
-		return -1;
-	for (int i = 0; i < nframes; ++i)
-		if (!o->st.queue_frame(d_in + (size_t)i * npx, d_out + (size_t)i * npx, add_loss != 0, o->remove_bad_pixels, o->low, o->high, o->std_factor,
-							   want ? o->batch_errs.as<int>() + 2 * i : nullptr, st))
-			return -1;
-	if (want)
-	{
-		std::vector<int> e((size_t)nframes * 2);
-		if (!hip_ok(hipMemcpyAsync(e.data(), o->batch_errs.ptr, e.size() * sizeof(int), hipMemcpyDeviceToHost, st), "D2H") ||
-			!hip_ok(wait_stream(st), "sync"))
-			return -1;
-		for (int i = 0; i < nframes; ++i)
-		{
-			if (low_errors)
-				low_errors[i] = e[2 * i];
-			if (high_errors)
-				high_errors[i] = e[2 * i + 1];
-		}
-	}
-	return 0;
-}
-
-// The same step for `nstreams` INDEPENDENT streams (one state object each, equal geometry and history length) with the streams
-// sharing every launch: frame f of all streams = three launches whose grids carry the stream in their second dimension
-// (the loss state is sequential in time, so streams - not frames - are what runs side by side).
-// d_in[i] / d_out[i]: uint16 [nframes][h][w] of stream i (HOST arrays of nstreams device pointers); low_errors / high_errors:
-// HOST int[nstreams][nframes] or NULL (then nothing waits).
-// The step of `nframes` frames for the streams os[0..nstreams) (checked by the callers: equal geometry and history length, no
-// bad-pixel repair).  d_errs: NULL, or per stream a DEVICE int[nframes][2] that receives the budgets (nothing is read back
-// then); otherwise low_errors / high_errors: HOST int[nstreams][nframes] or NULL.
-namespace
-{
-int lossy_step_streams(LossyObject *const *os, int nstreams, const unsigned short *const *d_in, unsigned short *const *d_out, int nframes, int add_loss,
-					   int *const *d_errs, int *low_errors, int *high_errors, hipStream_t st, bool force_per_frame)
-{
-	const size_t npx = (size_t)os[0]->st.w * os[0]->st.h;
-	const bool want = low_errors || high_errors;
-	LossyObject &lead = *os[0]; // owns the scratch of the call: the table of steps and the budgets
-	for (int i = 0; i < nstreams; ++i)
-		if (os[i]->is_failed())
-		{
-			log_error("bounded-loss step: a run of frames of this stream gave up earlier - its state is invalid, destroy the stream");
-			return -1;
-		}
-	if (want && !d_errs && !lead.batch_errs.reserve((size_t)nstreams * nframes * 2 * sizeof(int)))
-		return -1;
-	// where the budget of frame f of stream i goes on the device: the caller's array, the call's own (read back below), or nowhere
-	auto errs_of = [&](int i, int f) {
-		return d_errs ? d_errs[i] + (size_t)f * 2 : want ? lead.batch_errs.as<int>() + ((size_t)i * nframes + f) * 2 : (int *)nullptr;
-	};
-	int f0 = 0;
-	if (os[0]->st.frames == 0)
-	{ // first frame of every stream: stored as it is, seeds the state - one small launch per stream, once in a stream's life
-		for (int i = 0; i < nstreams; ++i)
-			if (!os[i]->st.queue_frame(d_in[i], d_out[i], add_loss != 0, false, os[i]->low, os[i]->high, os[i]->std_factor,
-									   errs_of(i, 0), st))
-				return -1;
-		f0 = 1;
-	}
-	const int nsteps = nframes - f0;
-	// resident launches of this call (resident_device.h): their epochs group by group, and the host side of every stream's state as it
-	// was before each group - what a launch that did not become resident (it has written nothing) is repeated from
-	struct Snap
-	{
-		int ra_count, ra_head;
-		int64_t frames;
-	};
-	std::vector<unsigned int> run_epochs;	// [ngroups]: epoch of the group's first launch
-	std::vector<Snap> snaps;				// [ngroups][nstreams]
-	int run_group = 0, run_launches_per_group = 0;
-	const int s_px = os[0]->st.w * os[0]->st.hl, full_px = os[0]->st.w * os[0]->st.h;
-	// runs: one launch per frame (lossy_frame_kernel) + one histogram launch per group of frames; needs whole groups of 8 pixels
-	const bool runs = nsteps >= 2 && s_px > 0 && s_px % 8 == 0 && full_px % 8 == 0;
-	if (nsteps > 0)
-	{
-		lead.const_groups = 0, lead.spec_groups = 0; // (the books of rir_lossy_path_stats / rir_lossy_spec_stats: of THIS call, whatever path it takes)
-		// the descriptions of all launches of the call go to the device in one copy (page-locked staging: the copy is asynchronous
-		// and the host buffer must outlive it - it is kept by the leading stream's object)
-		// persistent: the whole group of frames in one launch (lossy_run_kernel) when the chip holds a stream's workgroups at once
-		const int run_wgs = lossy_run_workgroups(full_px);
-		bool errors_fit = true; // (the run kernel hands a decision on as two 24-bit fields)
-		for (int i = 0; i < nstreams; ++i)
-			errors_fit = errors_fit && os[i]->low < (1 << 24) && os[i]->high < (1 << 24);
-		// (more streams than the chip holds at once go through the resident kernel a batch of streams after the other: 6 streams of
-		// 640x512 per launch keep 0.49 M frames/s whatever the number of streams; a launch per frame for all of them does 0.30-0.43 M)
-		const char *max_env = getenv("RIR_LOSSY_RUN_MAX_WORKGROUPS"); // (tests: a smaller limit, to go through the batches with small frames)
-		const int capacity = lossy_run_capacity();						 // what THIS device holds of the run kernel at once (0: unknown)
-		const int max_wgs = max_env && atoi(max_env) > 0 ? std::min(atoi(max_env), capacity) : capacity;
-		// the run kernel has a second form (part of the pixel state parked in LDS, one more wave per SIMD): more streams per launch, each
-		// a little slower - taken when it saves a launch (runtime.h; RIR_LOSSY_RUN_FORM=5 / 6: one form only, for tests and measurements)
-		const int cap6 = lossy_run_capacity(true), max6 = max_env && atoi(max_env) > 0 ? std::min(atoi(max_env), cap6) : cap6;
-		const char *form = getenv("RIR_LOSSY_RUN_FORM");
-		bool parked = false;
-		ResidentPlan plan = form ? resident_plan(atoi(form) == 6 ? max6 : max_wgs, run_wgs, nstreams) : resident_plan_two_forms(max_wgs, max6, run_wgs, nstreams, &parked);
-		if (form)
-			parked = atoi(form) == 6; // (units_per_launch 0: a stream does not fit - launch per frame)
-		const bool persistent = runs && errors_fit && plan.units_per_launch > 0 && !force_per_frame && !getenv("RIR_LOSSY_LAUNCH_PER_FRAME");
-		// streams per launch of the resident kernel: the launches the plan needs, filled evenly (32 streams at 9 per launch: 8, 8, 8, 8 - not 9, 9, 9, 5)
-		const int batch = persistent ? resident_batch(plan, nstreams) : nstreams;
-		// The constant-budget form (lossy_kernels.hip: lossy_const_run_kernel): with stdFactor == 0 for every stream of the call each group is
-		// first offered to an ordinary launch that needs no hand-offs between workgroups (decided below, on the device, group by group).
-		bool const_form = persistent && !getenv("RIR_LOSSY_NO_CONST");
-		{ // (only in the build with the test hooks: the forms of the kernel that small test frames would never take)
-			const char *pairs = test_hook("RIR_LOSSY_CONST_PAIRS");
-			lossy_const_force_pairs(pairs ? atoi(pairs) : 0);
-		}
-		for (int i = 0; i < nstreams; ++i)
-			const_form = const_form && os[i]->std_factor == 0.0;
-		// The speculative form (lossy_kernels.h: LossySpec): budgets that follow the statistics (stdFactor != 0, the reference's default) are guessed -
-		// the configured errors, what a scene that does not move gets - and verified on the device; a group whose guess does not verify within
-		// `spec_passes` corrections is left to the resident kernel, exactly as a declined constant-budget group is.
-		bool spec_form = persistent && !const_form && !getenv("RIR_LOSSY_NO_SPEC");
-		for (int i = 0; i < nstreams; ++i)
-			spec_form = spec_form && os[i]->low <= 65535 && os[i]->high <= 65535; // (the budget table holds 16-bit fields)
-		int spec_passes = 3;
-		if (const char *pe = getenv("RIR_LOSSY_SPEC_PASSES"))
-			spec_passes = std::max(1, std::min(16, atoi(pe)));
-		if (getenv("RIR_LOSSY_SPEC_FIRST_ONLY")) // (comparison: a pass corrects the first wrong budget only - bit 8 of the launch's pass count)
-			spec_passes |= 256;
-		if (getenv("RIR_LOSSY_SPEC_NO_GIVE_UP")) // (measurements: every pass that is allowed is made)
-			spec_passes |= 512;
-		const bool stream_form = const_form || spec_form; // a streaming kernel steps whole groups: long ones
-		// frames per histogram launch (one 64 KB histogram slice per frame and stream).  A group costs four small launches beside its
-		// frames, so streams that may take the constant-budget form - 0.1 us per stream-frame - get groups four times as long (up to
-		// 512 MB of slices, allocated as needed; 32 streams x 200 frames: 64-frame groups 0.83 M frames/s, one group 1.2 M)
-		int group = std::min(kLossyConstMaxFrames, std::max(1, (persistent ? (stream_form ? 8192 : 2048) : 512) / nstreams));
-		// (the constant-budget kernel addresses a group's frames with 32-bit offsets below 2^31: groups of large frames are cut to fit -
-		// 64 = the longest ring, 8 = the most frames it keeps in flight; lossy_const_run_kernel decides for itself, this only keeps it fast)
-		if (stream_form)
-			group = (int)std::max<long long>(1, std::min<long long>(group, 0x7fffffffll / ((long long)npx * 2) - 64 - 8));
-		const int ngroups = runs ? (nsteps + group - 1) / group : 0;
-		const size_t nfused = persistent ? 0 : runs ? (size_t)(nsteps + 1) * nstreams : (size_t)nsteps * nstreams, nbg = runs ? (size_t)nsteps * nstreams : 0,
-					 nhist = persistent ? 0 : nbg; // (the resident / constant-budget path takes its backgrounds straight from the runs' descriptions: no per-frame table)
-		const size_t run_off = (nfused + nhist) * sizeof(LossyStep); // (a multiple of 8)
-		const size_t spec_off = run_off + (persistent ? (size_t)ngroups * nstreams * sizeof(LossyRun) : 0);
-		static_assert(sizeof(LossyRun) % 8 == 0 && sizeof(LossySpec) % 8 == 0, "the tables of a call lie behind each other in one buffer");
-		const size_t nb = spec_off + (persistent && spec_form ? (size_t)ngroups * nstreams * sizeof(LossySpec) : 0);
-		if (!lead.multi_table.reserve(nb) || !lead.multi_stage.reserve(nb))
-			return -1;
-		// an earlier call's copy out of the staging buffer may still be in flight - on whatever stream that call was given
-		if (lead.multi_copied && !hip_ok(hipEventSynchronize(lead.multi_copied), "event"))
-			return -1;
-		if (!lead.multi_copied && !hip_ok(hipEventCreateWithFlags(&lead.multi_copied, hipEventDisableTiming), "event"))
-			return -1;
-		LossyStep *hs = lead.multi_stage.as<LossyStep>();
-		const LossyStep *dt = lead.multi_table.as<LossyStep>();
-		if (!runs)
-		{
-			for (int f = f0; f < nframes; ++f)
-				for (int i = 0; i < nstreams; ++i)
-				{
-					LossyState &ls = os[i]->st;
-					hs[(size_t)(f - f0) * nstreams + i] = ls.make_step(d_in[i] + (size_t)f * npx, d_in[i] + (size_t)f * npx, d_out[i] + (size_t)f * npx, add_loss != 0,
-																		 os[i]->low, os[i]->high, os[i]->std_factor, errs_of(i, f), nstreams);
-					ls.advance_ring();
-					++ls.frames;
-				}
-			if (!hip_ok(hipMemcpyAsync(lead.multi_table.ptr, hs, nb, hipMemcpyHostToDevice, st), "H2D") || !hip_ok(hipEventRecord(lead.multi_copied, st), "event"))
-				return -1;
-			for (int f = 0; f < nsteps; ++f)
-				if (!hip_ok(launch_lossy_step(hs + (size_t)f * nstreams, dt + (size_t)f * nstreams, nstreams, st), "lossy step"))
-					return -1;
-		}
-		else
-		{
-			// histogram scratch: one zeroed 16 384-bin slice and one ticket per frame of a group (the kernels leave them zeroed)
-			const size_t slices = (size_t)std::min(nsteps, group) * nstreams;
-			const size_t hist_cap = lead.run_hist.cap, tick_cap = lead.run_tickets.cap;
-			if (!lead.run_hist.reserve(slices * 16384 * 4) || !lead.run_tickets.reserve(slices * 4) || !lead.run_bg.reserve(nbg * sizeof(long long)))
-				return -1;
-			if (lead.run_hist.cap != hist_cap && !hip_ok(hipMemsetAsync(lead.run_hist.ptr, 0, lead.run_hist.cap, st), "memset"))
-				return -1;
-			if (lead.run_tickets.cap != tick_cap && !hip_ok(hipMemsetAsync(lead.run_tickets.ptr, 0, lead.run_tickets.cap, st), "memset"))
-				return -1;
-			long long *bg = lead.run_bg.as<long long>();
-			LossyStep *hh = hs + nfused;
-			if (persistent)
-			{
-				// scratch of the run kernel: [ticket, error word | 256 B][streams][2][run_wgs][slot_words] exchange words (zeroed before every launch)
-				constexpr int slot_words = 8;
-				const size_t exch_words = (size_t)2 * run_wgs * slot_words + 16, exch_bytes = (size_t)nstreams * exch_words * 8;
-				// workgroup 0 of a stream collects and decides (leader 0, every workgroup doing it, was measured slower at every stream count)
-				constexpr int leader = 1;
-				const size_t exch_cap = lead.run_exchange.cap;
-				if (!lead.run_exchange.reserve(256 + exch_bytes))
-					return -1;
-				if (lead.run_exchange.cap != exch_cap)
-				{
-					if (!hip_ok(hipMemsetAsync(lead.run_exchange.ptr, 0, 256, st), "memset"))
-						return -1;
-					lead.run_arrivals = 0; // (a fresh control block)
-				}
-				// The constant-budget form (lossy_kernels.hip: lossy_const_run_kernel): with stdFactor == 0 for every stream of the call each
-				// group is first offered to an ordinary launch that needs no hand-offs between workgroups; it declines - on the device, nothing
-				// waits for the host - when a frame's class may be empty or a NaN sits in a window, and the resident launch behind it, which
-				// otherwise finds the group done and leaves, steps it.
-				const size_t part_words = (size_t)kLossyConstSlots * lossy_const_workgroups(full_px, nstreams) * 4;
-				lead.const_groups = 0;
-				if (const_form)
-				{
-					if (!lead.const_ok.reserve((size_t)ngroups * 4) || !lead.const_partials.reserve((size_t)nstreams * part_words * 8) ||
-						!hip_ok(hipMemsetAsync(lead.const_ok.ptr, 0, (size_t)ngroups * 4, st), "memset"))
-						return -1;
-					lead.const_groups = ngroups;
-				}
-				lead.spec_groups = 0;
-				bool spec_plane = false;
-				const int spec_slabs = lossy_spec_stat_workgroups(s_px);
-				const size_t spec_group = (size_t)std::min(nsteps, group);
-				if (spec_form)
-				{
-					const size_t bk_cap = lead.spec_backoff.cap, tk_cap = lead.spec_tickets.cap;
-					if (!lead.const_ok.reserve((size_t)ngroups * 4) || !hip_ok(hipMemsetAsync(lead.const_ok.ptr, 0, (size_t)ngroups * 4, st), "memset") ||
-						!lead.spec_budgets.reserve((size_t)nstreams * (spec_group + 8) * 4) || !lead.spec_rows.reserve((size_t)nstreams * spec_group * spec_slabs * 32) ||
-						!lead.spec_sd.reserve((size_t)nstreams * spec_group * 16) || !lead.spec_ctl.reserve((size_t)ngroups * nstreams * 32) ||
-						!hip_ok(hipMemsetAsync(lead.spec_ctl.ptr, 0, (size_t)ngroups * nstreams * 32, st), "memset") || !lead.spec_backoff.reserve(8) ||
-						!lead.spec_tickets.reserve((size_t)nstreams * spec_group * 4))
-						return -1;
-					// the byte plane the streaming kernel leaves for the sums kernel (lossy_kernels.h: LossySpec::dplane), a byte per pixel and frame of a group;
-					// RIR_LOSSY_SPEC_NO_PLANE (measurements): none - the sums are taken from the frames, as they are when the memory is not to be had
-					spec_plane = !getenv("RIR_LOSSY_SPEC_NO_PLANE") && lead.spec_dplane.reserve((size_t)nstreams * spec_group * (size_t)s_px);
-					if (lead.spec_tickets.cap != tk_cap && !hip_ok(hipMemsetAsync(lead.spec_tickets.ptr, 0, lead.spec_tickets.cap, st), "memset"))
-						return -1;
-					if (lead.spec_backoff.cap != bk_cap && !hip_ok(hipMemsetAsync(lead.spec_backoff.ptr, 0, 8, st), "memset"))
-						return -1;
-					if (!lead.spec_backoff_host.ptr)
-					{
-						if (!lead.spec_backoff_host.reserve(64))
-							return -1;
-						std::memset(lead.spec_backoff_host.ptr, 0, 64);
-					}
-					for (int i = 0; i < nstreams; ++i)
-						if (!os[i]->st.reserve_shadow())
-							return -1;
-					lead.spec_groups = ngroups, lead.spec_streams = nstreams;
-				}
-				unsigned int *d_ticket = lead.run_exchange.as<unsigned int>(), *d_error = d_ticket + 16;
-				unsigned long long *d_exch = reinterpret_cast<unsigned long long *>(lead.run_exchange.as<char>() + 256);
-				LossyRun *hr = reinterpret_cast<LossyRun *>(reinterpret_cast<char *>(hs) + run_off);
-				const LossyRun *dr = reinterpret_cast<const LossyRun *>(lead.multi_table.as<char>() + run_off);
-				LossySpec *hsp = reinterpret_cast<LossySpec *>(reinterpret_cast<char *>(hs) + spec_off);
-				const LossySpec *dsp = reinterpret_cast<const LossySpec *>(lead.multi_table.as<char>() + spec_off);
-				for (int g = 0; g < ngroups; ++g)
-				{
-					const int k0 = g * group, in_group = std::min(group, nsteps - k0);
-					for (int i = 0; i < nstreams; ++i)
-					{
-						LossyState &ls = os[i]->st;
-						snaps.push_back(Snap{ls.dev.ra_count, ls.dev.ra_head, (int64_t)ls.frames});
-						LossyRun r{};
-						r.in = d_in[i] + (size_t)(f0 + k0) * npx, r.out = d_out[i] + (size_t)(f0 + k0) * npx;
-						r.st = ls.dev;
-						r.bg = bg + (size_t)k0 * nstreams + i, r.bg_stride = nstreams;
-						r.budget = ls.d_budget.as<LossyBudget>(), r.decision = ls.d_decision.as<LossyDecision>();
-						r.errors_out = errs_of(i, f0 + k0);
-						r.exchange = d_exch + (size_t)i * exch_words, r.error_word = d_error, r.slot_words = slot_words, r.leader = leader;
-						r.frame_px = (long long)npx, r.nsteps = in_group;
-						r.s = s_px, r.full = full_px;
-						r.add_loss = add_loss ? 1 : 0, r.low_value_error = os[i]->low, r.high_value_error = os[i]->high, r.std_factor = os[i]->std_factor;
-						r.partials = const_form ? lead.const_partials.as<unsigned long long>() + (size_t)i * part_words : nullptr;
-						hr[(size_t)g * nstreams + i] = r;
-						if (spec_form)
-						{
-							LossySpec sp{};
-							sp.shadow = ls.shadow;
-							sp.shadow.ra_count = ls.dev.ra_count, sp.shadow.ra_head = ls.dev.ra_head, sp.shadow.running_average = ls.dev.running_average;
-							sp.budgets = lead.spec_budgets.as<uint32_t>() + (size_t)i * (spec_group + 8);
-							sp.rows = lead.spec_rows.as<unsigned long long>() + (size_t)i * spec_group * spec_slabs * 4;
-							sp.sd = lead.spec_sd.as<double>() + (size_t)i * spec_group * 2;
-							sp.tickets = lead.spec_tickets.as<unsigned int>() + (size_t)i * spec_group;
-							sp.ctl = lead.spec_ctl.as<unsigned int>() + ((size_t)g * nstreams + i) * 8;
-							sp.backoff = lead.spec_backoff.as<unsigned int>();
-							sp.backoff_host = lead.spec_backoff_host.as<unsigned int>();
-							sp.dplane = spec_plane ? lead.spec_dplane.as<uint8_t>() + (size_t)i * spec_group * (size_t)s_px : nullptr;
-							hsp[(size_t)g * nstreams + i] = sp;
-						}
-						for (int k = k0; k < k0 + in_group; ++k)
-						{ // (the host side of the stream's state as it will be after the group)
-							ls.advance_ring();
-							++ls.frames;
-						}
-					}
-				}
-				if (!hip_ok(hipMemcpyAsync(lead.multi_table.ptr, hs, nb, hipMemcpyHostToDevice, st), "H2D") || !hip_ok(hipEventRecord(lead.multi_copied, st), "event"))
-					return -1;
-				// the call is on the leader's books before anything is queued: whatever happens from here on, a raised error word
-				// is charged to it
-				++lead.led_calls;
-				for (int i = 0; i < nstreams; ++i)
-				{
-					os[i]->lead_call = lead.led_calls;
-					os[i]->led_by_other = i != 0;
-					if (i == 0)
-						os[i]->lead.reset();
-					else
-						os[i]->lead = lead.weak_from_this();
-				}
-				if (test_hook("RIR_DEBUG_LOSSY_GIVE_UP") && !hip_ok(hipMemsetAsync(d_error, 1, 4, st), "memset")) // (tests: as if a wait had hit its clock)
-					return -1;
-				// A stream that backs off (its groups kept failing: budgets that move) is not offered its next groups: the device's counter says how
-				// many, the host looks at its page-locked copy - without waiting, so the value may be a call or two old: then fewer groups are left
-				// out here and the device skips them itself - and does not even queue their launches (eleven small ones per group).
-				int host_skipped = 0;
-				if (spec_form)
-				{
-					const unsigned int left = *reinterpret_cast<volatile unsigned int *>(lead.spec_backoff_host.ptr);
-					host_skipped = (int)std::min<unsigned int>(left, (unsigned int)ngroups);
-					if (host_skipped > 0 && !hip_ok(launch_lossy_spec_skipped(lead.spec_backoff.as<unsigned int>(), lead.spec_backoff_host.as<unsigned int>(),
-																			  (unsigned int)host_skipped, st),
-													"lossy speculative skip"))
-						return -1;
-				}
-				for (int g = 0; g < ngroups; ++g)
-				{
-					const int k0 = g * group, in_group = std::min(group, nsteps - k0);
-					if (!hip_ok(launch_lossy_backgrounds_of_runs(dr + (size_t)g * nstreams, nstreams, in_group, lead.run_hist.as<uint32_t>(), lead.run_tickets.as<unsigned int>(), s_px,
-																 lossy_hist_px(s_px, in_group * nstreams), st),
-								"lossy backgrounds") ||
-						!hip_ok(hipMemsetAsync(d_exch, 0, exch_bytes, st), "memset"))
-						return -1;
-					const unsigned int *d_ok = stream_form ? lead.const_ok.as<unsigned int>() + g : nullptr;
-					bool any_ra = false;
-					for (int i = 0; i < nstreams; ++i)
-						any_ra = any_ra || os[i]->st.dev.running_average > 0;
-					if (const_form && !hip_ok(launch_lossy_const(dr + (size_t)g * nstreams, nstreams, full_px, any_ra, add_loss != 0, lead.const_ok.as<unsigned int>() + g,
-																  d_ticket + kLossyRunCtlWord + 2, st),
-											  "lossy constant-budget run"))
-						return -1;
-					if (spec_form && g >= host_skipped)
-					{ // guess, (step, sums, verify) x passes, commit: every launch returns at once when the one before left it nothing to do
-						if (!hip_ok(launch_lossy_spec_begin(dr + (size_t)g * nstreams, dsp + (size_t)g * nstreams, nstreams, spec_passes, lead.const_ok.as<unsigned int>() + g,
-															 d_ticket + kLossyRunCtlWord + 2, st),
-									"lossy speculative run"))
-							return -1;
-						for (int pass = 0; pass < (spec_passes & 0xff); ++pass)
-							if (!hip_ok(launch_lossy_spec_pass(dr + (size_t)g * nstreams, dsp + (size_t)g * nstreams, nstreams, s_px, full_px, in_group, any_ra, add_loss != 0, st),
-										"lossy speculative pass"))
-								return -1;
-						if (!hip_ok(launch_lossy_spec_commit(dr + (size_t)g * nstreams, dsp + (size_t)g * nstreams, nstreams, s_px, full_px, lead.const_ok.as<unsigned int>() + g, st),
-									"lossy speculative commit"))
-							return -1;
-					}
-					for (int s0 = 0; s0 < nstreams; s0 += batch)
-					{
-						const int nl = std::min(batch, nstreams - s0);
-						const unsigned int epoch = ++lead.run_epoch;
-						if (s0 == 0)
-							run_epochs.push_back(epoch);
-						if (test_hook("RIR_DEBUG_LOSSY_BAIL") && atoi(test_hook("RIR_DEBUG_LOSSY_BAIL")) == g)
-						{ // (tests: as if group g's launch had not become resident: its decision is BAIL before anybody arrives)
-							const unsigned int w_ = ((epoch & 0x3fffffffu) << 2) | 2u;
-							if (!hip_ok(hipMemcpyAsync(d_ticket + kLossyRunCtlWord + 1, &w_, 4, hipMemcpyHostToDevice, st), "H2D") || !hip_ok(hipStreamSynchronize(st), "sync"))
-								return -1;
-						}
-						if (!hip_ok(launch_lossy_run(dr + (size_t)g * nstreams + s0, nl, full_px, d_ticket, epoch, lead.run_arrivals, parked, st, d_ok), "lossy run"))
-							return -1;
-						lead.run_arrivals += (unsigned int)(nl * run_wgs);
-					}
-				}
-				run_group = group, run_launches_per_group = (nstreams + batch - 1) / batch;
-			}
-			else
-			{
-			for (int k = 0; k <= nsteps; ++k) // launch k updates frame f0 + k - 1 (k > 0) and takes the sums of frame f0 + k (k < nsteps)
-				for (int i = 0; i < nstreams; ++i)
-				{
-					LossyState &ls = os[i]->st;
-					LossyStep p;
-					if (k == 0)
-					{
-						p = ls.make_step(nullptr, nullptr, nullptr, add_loss != 0, os[i]->low, os[i]->high, os[i]->std_factor, nullptr, nstreams);
-						p.do_update = 0;
-					}
-					else
-					{
-						const size_t f = (size_t)(f0 + k - 1);
-						p = ls.make_step(d_in[i] + f * npx, d_in[i] + f * npx, d_out[i] + f * npx, add_loss != 0, os[i]->low, os[i]->high, os[i]->std_factor, nullptr,
-										 nstreams);
-						ls.advance_ring();
-						++ls.frames;
-					}
-					if (k < nsteps)
-					{
-						const size_t fn = (size_t)(f0 + k);
-						p.next_tmp = p.next_img = d_in[i] + fn * npx;
-						p.next_background = bg + (size_t)k * nstreams + i;
-						p.next_errors_out = errs_of(i, (int)fn);
-						LossyStep h{};
-						const int in_group = std::min(group, nsteps - k / group * group);
-						const size_t slice = (size_t)(k % group) * nstreams + i;
-						h.tmp = h.img = d_in[i] + fn * npx;
-						h.hist = lead.run_hist.as<uint32_t>() + slice * 16384;
-						h.stats = bg + (size_t)k * nstreams + i;
-						h.tickets = lead.run_tickets.as<unsigned int>() + slice;
-						h.s = s_px, h.full = full_px;
-						h.hist_px = lossy_hist_px(s_px, in_group * nstreams);
-						hh[(size_t)k * nstreams + i] = h;
-					}
-					hs[(size_t)k * nstreams + i] = p;
-				}
-			if (!hip_ok(hipMemcpyAsync(lead.multi_table.ptr, hs, nb, hipMemcpyHostToDevice, st), "H2D") || !hip_ok(hipEventRecord(lead.multi_copied, st), "event"))
-				return -1;
-			for (int k = 0; k <= nsteps; ++k)
-			{
-				if (k < nsteps && k % group == 0)
-				{
-					const int in_group = std::min(group, nsteps - k);
-					if (!hip_ok(launch_lossy_backgrounds(dt + nfused + (size_t)k * nstreams, in_group * nstreams, s_px, lossy_hist_px(s_px, in_group * nstreams), st),
-								"lossy backgrounds"))
-						return -1;
-				}
-				if (!hip_ok(launch_lossy_frame(dt + (size_t)k * nstreams, nstreams, full_px, st), "lossy frame"))
-					return -1;
-			}
-			}
-		}
-	}
-	if (want && !d_errs)
-	{
-		std::vector<int> e((size_t)nstreams * nframes * 2);
-		unsigned int gave_up = 0; // the run kernel's error word (a wait between workgroups that hit its clock)
-		unsigned int ctl[4] = {0, 0, 0, 0}; // the residency control block: arrivals, decision, poison, epoch of the first launch that bailed out
-		if ((lead.run_exchange.ptr && (!hip_ok(hipMemcpyAsync(&gave_up, lead.run_exchange.as<unsigned int>() + 16, 4, hipMemcpyDeviceToHost, st), "D2H") ||
-									   !hip_ok(hipMemcpyAsync(ctl, lead.run_exchange.as<unsigned int>() + kLossyRunCtlWord, sizeof(ctl), hipMemcpyDeviceToHost, st), "D2H"))) ||
-			!hip_ok(wait_stream(st), "sync"))
-			return -1;
-		if (ctl[2] != 0 && !run_epochs.empty())
-		{
-			// A group's launch did not become resident (ordinary kernels of other streams can keep the last workgroups from fitting:
-			// resident_device.h).  It and every launch behind it have written nothing.  The call waits here anyway, so the frames
-			// from that group on are stepped again on the launch-per-frame path - same results - from the host state of that moment.
-			int g_bad = -1;
-			for (size_t g = 0; g < run_epochs.size(); ++g)
-				if (g_bad < 0 && (int)(ctl[3] - run_epochs[g]) >= 0 && (int)(ctl[3] - run_epochs[g]) < run_launches_per_group)
-					g_bad = (int)g;
-			const unsigned int zero2[2] = {0, 0};
-			if (!hip_ok(hipMemcpyAsync(lead.run_exchange.as<unsigned int>() + kLossyRunCtlWord + 2, zero2, sizeof(zero2), hipMemcpyHostToDevice, st), "H2D") ||
-				!hip_ok(hipStreamSynchronize(st), "sync"))
-				return -1;
-			if (g_bad < 0 || run_launches_per_group != 1)
-			{ // (a poison left by an earlier, queue-only call - or streams that went in several batches and stand at different frames)
-				gave_up = 1;
-			}
-			else
-			{
-				const int fr0 = f0 + g_bad * run_group; // first frame that was not stepped
-				for (int i = 0; i < nstreams; ++i)
-				{
-					const Snap &sn = snaps[(size_t)g_bad * nstreams + i];
-					os[i]->st.dev.ra_count = sn.ra_count, os[i]->st.dev.ra_head = sn.ra_head, os[i]->st.frames = (decltype(os[i]->st.frames))sn.frames;
-				}
-				std::vector<const unsigned short *> in2((size_t)nstreams);
-				std::vector<unsigned short *> out2((size_t)nstreams);
-				std::vector<int *> errs2((size_t)nstreams);
-				for (int i = 0; i < nstreams; ++i)
-				{
-					in2[i] = d_in[i] + (size_t)fr0 * npx, out2[i] = d_out[i] + (size_t)fr0 * npx;
-					errs2[i] = lead.batch_errs.as<int>() + ((size_t)i * nframes + fr0) * 2;
-				}
-				if (lossy_step_streams(os, nstreams, in2.data(), out2.data(), nframes - fr0, add_loss, errs2.data(), nullptr, nullptr, st, true) != 0 ||
-					!hip_ok(wait_stream(st), "sync"))
-					return -1;
-			}
-		}
-		if (!hip_ok(hipMemcpyAsync(e.data(), lead.batch_errs.ptr, e.size() * sizeof(int), hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(wait_stream(st), "sync"))
-			return -1;
-		if (lead.run_exchange.ptr)
-			lead.checked(gave_up, st);
-		bool any_failed = false;
-		for (int i = 0; i < nstreams; ++i)
-			any_failed = os[i]->is_failed() || any_failed; // (every stream of the call is marked)
-		if (any_failed)
-		{
-			log_error("rir_lossy_step_multi_device: a run of frames gave up waiting (results invalid; the streams of the call take no more frames)");
-			return -1;
-		}
-		for (size_t i = 0; i < (size_t)nstreams * nframes; ++i)
-		{
-			if (low_errors)
-				low_errors[i] = e[2 * i];
-			if (high_errors)
-				high_errors[i] = e[2 * i + 1];
-		}
-	}
-	return 0;
-}
-
-
-} // namespace
-
-RIR_EXPORT int rir_lossy_step_multi_device(const int *handles, int nstreams, const unsigned short *const *d_in, unsigned short *const *d_out,
-										   int nframes, int add_loss, int *low_errors, int *high_errors, void *stream)
-{
-	if (!device_ready())
-		return -1;
-	if (!handles || nstreams <= 0 || nstreams > 65535 || !d_in || !d_out || nframes <= 0)
-	{
-		log_error("rir_lossy_step_multi_device: invalid argument");
-		return -1;
-	}
-	std::vector<std::shared_ptr<LossyObject>> os((size_t)nstreams);
-	std::vector<LossyObject *> ptrs((size_t)nstreams);
-	for (int i = 0; i < nstreams; ++i)
-	{
-		os[i] = lookup_as<LossyObject>(handles[i]);
-		if (!os[i] || !d_in[i] || !d_out[i] || d_in[i] == d_out[i])
-		{
-			log_error("rir_lossy_step_multi_device: invalid handle or buffer");
-			return -1;
-		}
-		{ // (the runs of frames read input frames again - the frame that leaves the running average - after later outputs have been written)
-			const size_t span = (size_t)nframes * (size_t)os[i]->st.w * (size_t)os[i]->st.h;
-			if (d_in[i] < d_out[i] + span && d_out[i] < d_in[i] + span)
-			{
-				log_error("rir_lossy_step_multi_device: input and output frames overlap");
-				return -1;
-			}
-		}
-		for (int k = 0; k < i; ++k)
-			if (os[k] == os[i])
-			{
-				log_error("rir_lossy_step_multi_device: a stream appears twice");
-				return -1;
-			}
-		ptrs[i] = os[i].get();
-		const LossyState &a = os[0]->st, &b = os[i]->st;
-		if (a.w != b.w || a.h != b.h || a.hl != b.hl || a.frames != b.frames || os[i]->remove_bad_pixels)
-		{
-			log_error("rir_lossy_step_multi_device: the streams must share geometry and history length (and not repair bad pixels)");
-			return -1;
-		}
-	}
-	return lossy_step_streams(ptrs.data(), nstreams, d_in, d_out, nframes, add_loss, nullptr, low_errors, high_errors, (hipStream_t)stream);
-}
-
-// Which form stepped the groups of frames of the last run call this stream LED (a call of its own, or a multi-stream call it was first in):
-// out[0] = groups offered to the constant-budget form (0: the call was not eligible - stdFactor != 0, frames stepped one by one, ...),
-// out[1] = of those, groups it stepped (the others were declined on the device and stepped by the resident kernel).  Waits for `stream`.
-RIR_EXPORT int rir_lossy_path_stats(int handle, int *out2, void *stream)
-{
-	auto o = lookup_as<LossyObject>(handle);
-	if (!o || !out2)
-	{
-		log_error("rir_lossy_path_stats: invalid argument");
-		return -1;
-	}
-	out2[0] = o->const_groups, out2[1] = 0;
-	if (o->const_groups > 0)
-	{
-		std::vector<unsigned int> w((size_t)o->const_groups);
-		if (!hip_ok(hipMemcpyAsync(w.data(), o->const_ok.ptr, w.size() * 4, hipMemcpyDeviceToHost, (hipStream_t)stream), "D2H") ||
-			!hip_ok(wait_stream((hipStream_t)stream), "sync"))
-			return -1;
-		for (unsigned int v : w)
-			out2[1] += v != 0 ? 1 : 0;
-	}
-	return 0;
-}
-
-// The speculative form's books for the last run call this stream LED: out[0] = groups that went through its launches (0: the call was not
-// eligible - stdFactor 0, frames stepped one by one, ...), out[1] = of those, groups that were offered (precondition held, no back-off),
-// out[2] = groups it committed, out[3] = passes over all groups (a group's passes: the most any of its streams took).  Waits for `stream`.
-RIR_EXPORT int rir_lossy_spec_stats(int handle, int *out4, void *stream)
-{
-	auto o = lookup_as<LossyObject>(handle);
-	if (!o || !out4)
-	{
-		log_error("rir_lossy_spec_stats: invalid argument");
-		return -1;
-	}
-	out4[0] = o->spec_groups, out4[1] = out4[2] = out4[3] = 0;
-	if (o->spec_groups > 0)
-	{
-		const size_t ng = (size_t)o->spec_groups, ns = (size_t)o->spec_streams;
-		std::vector<unsigned int> w(ng * ns * 8), okw(ng);
-		if (!hip_ok(hipMemcpyAsync(w.data(), o->spec_ctl.ptr, w.size() * 4, hipMemcpyDeviceToHost, (hipStream_t)stream), "D2H") ||
-			!hip_ok(hipMemcpyAsync(okw.data(), o->const_ok.ptr, okw.size() * 4, hipMemcpyDeviceToHost, (hipStream_t)stream), "D2H") ||
-			!hip_ok(wait_stream((hipStream_t)stream), "sync"))
-			return -1;
-		for (size_t g = 0; g < ng; ++g)
-		{
-			unsigned int passes = 0;
-			for (size_t i = 0; i < ns; ++i)
-				passes = std::max(passes, w[(g * ns + i) * 8 + 1]);
-			out4[1] += w[g * ns * 8 + 4] != 0 ? 1 : 0;
-			out4[2] += okw[g] != 0 ? 1 : 0;
-			out4[3] += (int)passes;
-		}
-	}
-	return 0;
-}
-
-// 0 when no run of frames this stream took part in has given up a wait between workgroups, -1 otherwise or on an invalid handle.
-// Waits for the work queued on `stream` (calls queued on other streams are not covered).  The failure is sticky: the stream's state
-// has been advanced by invalid frames, so from then on every status and every step of the stream - and of the streams that shared
-// the failed call - returns -1 until it is destroyed.  Calls that return budgets check this themselves; queue-only calls do not.
-RIR_EXPORT int rir_lossy_status(int handle, void *stream)
-{
-	auto o = lookup_as<LossyObject>(handle);
-	if (!o)
-	{
-		log_error("rir_lossy_status: invalid handle");
-		return -1;
-	}
-	hipStream_t st = (hipStream_t)stream;
-	// the error word is with the leader of the last run call this stream took part in (itself, for a call of its own)
-	LossyObject *l = o->leader();
-	std::shared_ptr<Object> keep = o->lead.lock(); // (keeps a foreign leader alive while it is read)
-	if (!l || !l->run_exchange.ptr)
-		return hip_ok(wait_stream(st), "sync") && !o->is_failed() ? 0 : -1;
-	unsigned int gave_up = 0, poison = 0; // a wait that hit its clock / a launch that was called off because it did not become resident
-	if (!hip_ok(hipMemcpyAsync(&gave_up, l->run_exchange.as<unsigned int>() + 16, 4, hipMemcpyDeviceToHost, st), "D2H") ||
-		!hip_ok(hipMemcpyAsync(&poison, l->run_exchange.as<unsigned int>() + kLossyRunCtlWord + 2, 4, hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(wait_stream(st), "sync"))
-		return -1;
-	l->checked(gave_up | poison, st);
-	if (o->is_failed())
-	{
-		log_error("rir_lossy_status: a run of frames gave up waiting (results invalid; the stream takes no more frames)");
-		return -1;
-	}
-	return 0;
-}
-
-RIR_EXPORT void rir_lossy_destroy(int handle)
-{
-	if (lookup_as<LossyObject>(handle))
-		remove_object(handle);
 }
 
 static int errors_out(const std::vector<unsigned short> &err, unsigned short *errors, int *size)

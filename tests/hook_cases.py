@@ -1,6 +1,6 @@
 """The cases of tests/test_gpu_resident.py that force a bail-out path through the library's TEST HOOKS (RIR_DEBUG_LOSSY_GIVE_UP,
 RIR_DEBUG_LOSSY_BAIL, RIR_DEBUG_ECC_BAIL).  The hooks are compiled into librir_amd_testhooks.so only (-DRIR_TEST_HOOKS, librir_amd/build.py), not
-into the product library: each case runs in a process of its own that loads that build (RIR_LIBRARY_VARIANT=testhooks), started by the test.
+into the product library (they are read in csrc/lossy_abi.cpp, registration_abi.cpp and the saver of video_io_abi.cpp): each case runs in a process of its own that loads that build (RIR_LIBRARY_VARIANT=testhooks), started by the test.
     RIR_LIBRARY_VARIANT=testhooks python tests/hook_cases.py <case> [argument]"""
 import contextlib
 import itertools
