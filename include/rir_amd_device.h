@@ -256,6 +256,22 @@ extern "C"
 	 * overlap, no device. */
 	int rir_morphology_device(int type, const void *d_src, void *d_dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows, void *stream);
 
+	/* Spatial rank filter of a stack d_src[nframes][h][w] into d_dst (same type and shape; extension).  type: 'H' uint16, 'B' uint8, '?' bool
+	 * (one byte, 0 / 1).  The window is a centred rectangle size_y x size_x, both odd, 1..15; 0 <= rank < size_x * size_y.  The image is
+	 * the first `rows` (0..h) rows of a frame: rows y >= `rows` are copied unchanged and no window reads them.  For y < rows,
+	 *   d_dst[n][y][x] = the element of 0-based rank `rank` (in ascending order) among the size_y * size_x values
+	 *                    d_src[n][clamp(y + dy, 0, rows - 1)][clamp(x + dx, 0, w - 1)],  |dy| <= size_y / 2, |dx| <= size_x / 2:
+	 * the window is always FULL, with coordinates replicated at the border; it is not clipped.  Per frame this is
+	 * scipy.ndimage.rank_filter(frame[:rows], rank, size=(size_y, size_x), mode="nearest"); rank size_x * size_y / 2 is scipy's
+	 * median_filter, rank 0 and rank size_x * size_y - 1 are op 0 and op 1 of rir_morphology_device (a replicated pixel changes no min or
+	 * max).  This is NOT rir_median_filter_device at 3 x 3: that one takes the median of 3 along an edge and the min of 2 in a corner.
+	 * All integer, bit for bit.  One launch that reads the stack once and writes it once: there is no workspace.  Asynchronous on
+	 * `stream`; d_dst may not overlap d_src.  nframes 0: nothing is done, 0.  -1 with the reason logged (argument errors before the device
+	 * is looked for): unknown type, an even size or one outside 1..15, rank outside 0 .. size_x * size_y - 1, rows outside 0..h, w or
+	 * h < 1, nframes < 0, a null pointer, overlap, no device. */
+	int rir_rank_filter_device(int type, const void *d_src, void *d_dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows,
+							   void *stream);
+
 	/* Per-region statistics of a uint16 stack d_frames[nframes][h][w] (extension).  d_labels: int32, one map [h][w] for every frame
 	 * (labels_per_frame 0) or one per frame [nframes][h][w] (1).  For frame f and region r < nregions (1..2^24), P = the flat indices
 	 * i = y * w + x whose label is r; labels outside [0, nregions) are ignored.  Outputs [nframes][nregions]: d_count = |P|, d_sum and

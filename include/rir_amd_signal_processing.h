@@ -71,6 +71,15 @@ extern "C"
 	 * -1 with the reason logged on a bad argument (before the device is looked for) and without a device ("no usable HIP device", dst
 	 * untouched: there is no CPU fallback). */
 	int rir_morphology(int type, const void *src, void *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows);
+	/* Spatial rank filter of a host stack src[nframes][h][w] into dst (same type and shape): rir_rank_filter_device (rir_amd_device.h) over
+	 * the stack, synchronous.  type 'H' uint16, 'B' uint8, '?' bool; sizes odd, 1..15; 0 <= rank < size_x * size_y.  With the image the
+	 * first `rows` (0..h) rows (the others are copied), dst[n][y][x] = the element of 0-based rank `rank` among the size_y * size_x values
+	 * src[n][clamp(y + dy, 0, rows - 1)][clamp(x + dx, 0, w - 1)], |dy| <= size_y / 2, |dx| <= size_x / 2: a full window with coordinates
+	 * replicated at the border, scipy.ndimage.rank_filter(..., size=(size_y, size_x), mode="nearest") per frame.  Large stacks go through
+	 * the device in slabs of at most 64 MiB (frames are independent).  dst == src is allowed, any other overlap is not.  nframes 0: 0.
+	 * -1 with the reason logged on a bad argument (before the device is looked for) and without a device ("no usable HIP device", dst
+	 * untouched: there is no CPU fallback). */
+	int rir_rank_filter(int type, const void *src, void *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows);
 	/* Per-region statistics of a host stack frames[nframes][h][w] with host label maps: rir_region_stats_device (rir_amd_device.h),
 	 * synchronous, host outputs [nframes][nregions].  The frames go through the device in slabs of at most 64 MiB; a shared map goes up
 	 * once.  0 / -1. */

@@ -21,6 +21,7 @@
 #include "pixel_quantile_kernels.h"
 #include "polygon_kernels.h"
 #include "quantile_kernels.h"
+#include "rank_kernels.h"
 #include "region_kernels.h"
 #include "runtime.h"
 #include "temporal_kernels.h"
@@ -703,6 +704,43 @@ RIR_EXPORT int rir_morphology_device(int type, const void *d_src, void *d_dst, i
 	return hip_ok(launch_morphology(type, d_src, d_dst, w, h, nframes, op, size_x, size_y, rows, as_stream(stream)), "morphology") ? 0 : -1;
 }
 
+// Spatial rank filters (rank_kernels.hip).  Every argument is checked here, before the device is looked for; the byte ranges of the source
+// and the destination may not overlap.
+namespace
+{
+	// 0, or what is wrong with the arguments of rir_rank_filter / rir_rank_filter_device
+	const char *rank_filter_args(int type, const void *src, const void *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows)
+	{
+		if (type != 'H' && type != 'B' && type != '?')
+			return "unknown type (uint16 'H', uint8 'B' or bool '?')";
+		if (size_x < 1 || size_x > 15 || size_x % 2 == 0 || size_y < 1 || size_y > 15 || size_y % 2 == 0)
+			return "size_x and size_y must be odd, 1..15";
+		if (rank < 0 || rank >= size_x * size_y)
+			return "rank must be in 0 .. size_x * size_y - 1";
+		if (w < 1 || h < 1 || nframes < 0 || rows < 0 || rows > h)
+			return "invalid shape (w, h >= 1, nframes >= 0, 0 <= rows <= h)";
+		if (!src || !dst)
+			return "null pointer";
+		return nullptr;
+	}
+} // namespace
+
+RIR_EXPORT int rir_rank_filter_device(int type, const void *d_src, void *d_dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows,
+									  void *stream)
+{
+	const char *bad = rank_filter_args(type, d_src, d_dst, w, h, nframes, rank, size_x, size_y, rows);
+	const uintptr_t bytes = (uintptr_t)w * h * (type == 'H' ? 2 : 1) * (bad ? 0 : nframes), s = (uintptr_t)d_src, d = (uintptr_t)d_dst;
+	if (!bad && s < d + bytes && d < s + bytes)
+		bad = "the source and the destination overlap";
+	if (bad)
+		return refuse(__func__, bad);
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	return hip_ok(launch_rank_filter(type, d_src, d_dst, w, h, nframes, rank, size_x, size_y, rows, as_stream(stream)), "rank_filter") ? 0 : -1;
+}
+
 // Per-region statistics (region_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an input or
 // another output.
 namespace
@@ -1333,6 +1371,36 @@ RIR_EXPORT int rir_morphology(int type, const void *src, void *dst, int w, int h
 		if (!s.up(in.ptr, static_cast<const char *>(src) + frame * o, frame * count) ||
 			rir_morphology_device(type, in.ptr, out.ptr, w, h, count, op, size_x, size_y, rows, s.st) != 0 ||
 			!s.down(static_cast<char *>(dst) + frame * o, out.ptr, frame * count) || !s.wait("morphology"))
+			return s.fail();
+	}
+	return 0;
+}
+
+// A spatial rank filter of a host stack (frames are independent: any split gives the same bits).  dst may be src.
+RIR_EXPORT int rir_rank_filter(int type, const void *src, void *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows)
+{
+	const char *bad = rank_filter_args(type, src, dst, w, h, nframes, rank, size_x, size_y, rows);
+	const size_t frame = (size_t)w * h * (type == 'H' ? 2 : 1);
+	const uintptr_t bytes = bad ? 0 : frame * (size_t)nframes, from = (uintptr_t)src, to = (uintptr_t)dst;
+	if (!bad && from != to && from < to + bytes && to < from + bytes)
+		bad = "the source and the destination overlap (dst == src is allowed)";
+	if (bad)
+		return refuse(__func__, bad);
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	const int slab = Stager::slab(nframes, {frame});
+	DeviceBuffer in, out;
+	if (!in.reserve(frame * slab) || !out.reserve(frame * slab))
+		return -1;
+	Stager s;
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int count = std::min(slab, nframes - o);
+		if (!s.up(in.ptr, static_cast<const char *>(src) + frame * o, frame * count) ||
+			rir_rank_filter_device(type, in.ptr, out.ptr, w, h, count, rank, size_x, size_y, rows, s.st) != 0 ||
+			!s.down(static_cast<char *>(dst) + frame * o, out.ptr, frame * count) || !s.wait("rank_filter"))
 			return s.fail();
 	}
 	return 0;

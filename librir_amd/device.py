@@ -13,7 +13,7 @@ from .low_level.misc import _lib, last_error
 from .signal_processing.rir_signal_processing import (PixelStats, RegionGeometry, RegionQuantiles, RegionStats,  # noqa: F401 (API)
                                                       _pixel_quantiles_args, _pixel_stats_args, _polygon_map_args, _region_geometry_args,
                                                       _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
-                                                      _morphology_args, _temporal_median_args)
+                                                      _morphology_args, _rank_filter_args, _temporal_median_args, percentile_rank)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -114,6 +114,7 @@ _lib.rir_remove_motion_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int
 _lib.rir_median_filter_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, _vp]
 _lib.rir_temporal_median_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp]
 _lib.rir_morphology_device.argtypes = [ct.c_int, _vp, _vp] + [ct.c_int] * 7 + [_vp]
+_lib.rir_rank_filter_device.argtypes = [ct.c_int, _vp, _vp] + [ct.c_int] * 7 + [_vp]
 _lib.rir_region_stats_device.argtypes =[_vp, _vp] + [ct.c_int] * 5 + [_vp] * 8 + [ct.c_size_t, _vp]
 _lib.rir_region_stats_workspace_bytes.argtypes = [ct.c_int] * 5
 _lib.rir_region_stats_workspace_bytes.restype = ct.c_size_t
@@ -736,6 +737,50 @@ def black_hat(frames, size, rows=None, out=None):
 def morph_gradient(frames, size, rows=None, out=None):
     """``morphology(frames, "gradient", ...)``: dilate(frames) - erode(frames)"""
     return morphology(frames, "gradient", size, rows, out)
+
+
+def rank_filter(frames, rank, size, rows=None, out=None):
+    """Spatial rank filter of a uint16, uint8 or bool stack ``frames[n][h][w]`` (or one image ``[h][w]``) with a centred rectangle ``size``
+    (an odd int, or ``(size_y, size_x)``, each 1..15) (C ABI ``rir_rank_filter_device``), one launch on the current stream: every pixel
+    becomes the element of 0-based rank ``rank`` (negative: from the end, as in scipy) among the ``size_y * size_x`` values of its window.
+    The window is always full - a position outside the image takes the nearest pixel, ``scipy.ndimage.rank_filter(..., mode="nearest")``
+    - which is not the border rule of ``median_filter`` (a smaller window along the border).  The image is the first ``rows`` rows of a
+    frame (default: all); the others are copied.  Returns a tensor of the input's dtype and shape (``out`` when given: a contiguous CUDA
+    tensor of that dtype and shape that does not overlap ``frames``)."""
+    shape = tuple(frames.shape)
+    dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
+    type_char, rank, size_y, size_x, rows = _rank_filter_args((1,) + shape if len(shape) == 2 else shape, dtype_name, rank, size, rows)
+    if out is not None and (not out.is_cuda or out.dtype != frames.dtype or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise RuntimeError("rank_filter: out must be a contiguous %s CUDA tensor of shape %s" % (frames.dtype, shape))
+    fr = _frames3(frames)
+    n, h, w = fr.shape
+    if out is None:
+        out = torch.empty(shape, dtype=fr.dtype, device=fr.device)
+    if n:
+        _check(_lib.rir_rank_filter_device(type_char, fr.data_ptr(), out.data_ptr(), w, h, n, rank, size_x, size_y, rows, _stream()),
+               "rir_rank_filter_device")
+    return out
+
+
+def _window_sizes(size):
+    """(size_y, size_x) of a window parameter that ``_rank_filter_args`` is still to check (an unusable one: (1, 1))"""
+    sizes = tuple(size) if isinstance(size, (tuple, list)) else (size, size)
+    ok = len(sizes) == 2 and all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) and s >= 1 for s in sizes)
+    return (int(sizes[0]), int(sizes[1])) if ok else (1, 1)
+
+
+def window_median(frames, size, rows=None, out=None):
+    """``rank_filter`` at rank ``size_y * size_x // 2``: the median of the full window, ``scipy.ndimage.median_filter(..., mode="nearest")``;
+    3 x 3 and 5 x 5 on frames of even width stay in registers"""
+    size_y, size_x = _window_sizes(size)
+    return rank_filter(frames, size_y * size_x // 2, size, rows, out)
+
+
+def percentile_filter(frames, percent, size, rows=None, out=None):
+    """``rank_filter`` at ``percentile_rank(percent, size_y, size_x)``: ``scipy.ndimage.percentile_filter(..., mode="nearest")``; a negative
+    percent counts from 100"""
+    size_y, size_x = _window_sizes(size)
+    return rank_filter(frames, percentile_rank(percent, size_y, size_x), size, rows, out)
 
 
 class TemporalMedian:

@@ -250,6 +250,69 @@ def morphology(images, op, size, rows=None):
     return out.reshape(img.shape)
 
 
+# ---- extension: spatial rank filters ---------------------------------------------------------------------------------------------
+_sp.rir_rank_filter.argtypes = [ct.c_int, ct.c_void_p, ct.c_void_p] + [ct.c_int] * 7
+
+
+def _rank_filter_args(shape, dtype_name, rank, size, rows):
+    """the parameters of a rank filter over a stack of `shape`, checked without a device; a negative rank counts from the end, as in scipy;
+    -> (type char, rank, size_y, size_x, rows)"""
+    if len(shape) != 3:
+        raise ValueError("rank_filter: a stack [n][h][w] expected")
+    if dtype_name not in _MORPHOLOGY_TYPES:
+        raise ValueError("rank_filter: uint16, uint8 or bool frames expected, not %s" % dtype_name)
+    sizes = tuple(size) if isinstance(size, (tuple, list)) else (size, size)
+    if len(sizes) != 2 or not all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in sizes):
+        raise ValueError("rank_filter: size must be an odd int or (size_y, size_x)")
+    for s in sizes:
+        if not 1 <= s <= 15 or s % 2 == 0:
+            raise ValueError("rank_filter: sizes must be odd, 1 to 15 (got %r)" % (size,))
+    cells = int(sizes[0]) * int(sizes[1])
+    if not isinstance(rank, (int, np.integer)) or isinstance(rank, bool):
+        raise ValueError("rank_filter: rank must be an int")
+    rank = int(rank) + cells if rank < 0 else int(rank)
+    if not 0 <= rank < cells:
+        raise ValueError("rank_filter: rank must be in %d..%d for a %d x %d window" % (-cells, cells - 1, sizes[0], sizes[1]))
+    _, h, w = shape
+    if h < 1 or w < 1:
+        raise ValueError("rank_filter: empty frames")
+    rows = h if rows is None else int(rows)
+    if not 0 <= rows <= h:
+        raise ValueError("rank_filter: rows must be in 0..h")
+    return ord(_MORPHOLOGY_TYPES[dtype_name]), rank, int(sizes[0]), int(sizes[1]), rows
+
+
+def percentile_rank(percent, size_y, size_x):
+    """The rank ``scipy.ndimage.percentile_filter`` takes in a ``size_y x size_x`` window of n cells: n - 1 at 100, otherwise
+    ``int(float(n) * percent / 100.0)``; a negative percent counts from 100.  ``ValueError`` outside [-100, 100]."""
+    cells = int(size_y) * int(size_x)
+    percent = float(percent)
+    if percent < 0.0:
+        percent += 100.0
+    if not 0.0 <= percent <= 100.0:  # (NaN fails both)
+        raise ValueError("percentile_rank: percent must be in -100..100")
+    return cells - 1 if percent == 100.0 else int(float(cells) * percent / 100.0)
+
+
+def rank_filter(images, rank, size, rows=None):
+    """Extension: spatial rank filter of a uint16, uint8 or bool stack ``images[n][h][w]`` (or one image ``[h][w]``) with a centred rectangle
+    ``size`` (an odd int, or ``(size_y, size_x)``, each 1..15) (``rir_rank_filter``): every pixel becomes the element of 0-based rank
+    ``rank`` (negative: from the end) among the values of its window, which is always full - coordinates are replicated at the border.
+    Per image this is ``scipy.ndimage.rank_filter(image, rank, size=size, mode="nearest")``; ``rank = size_y * size_x // 2`` is the median,
+    ``percentile_rank`` gives the rank of a percentile.  The image is its first ``rows`` rows (default: all); the others are copied.
+    Returns an array of the input's dtype and shape.  ``ValueError`` on bad parameters, ``RuntimeError`` when the library fails."""
+    img = np.ascontiguousarray(images)
+    if img.ndim not in (2, 3):
+        raise ValueError("rank_filter: an image [h][w] or a stack [n][h][w] expected")
+    stack = img.reshape((-1,) + img.shape[-2:])
+    type_char, rank, size_y, size_x, rows = _rank_filter_args(stack.shape, img.dtype.name, rank, size, rows)
+    out = np.empty_like(stack)
+    n, h, w = stack.shape
+    if n and _sp.rir_rank_filter(type_char, stack.ctypes.data, out.ctypes.data, w, h, n, rank, size_x, size_y, rows) < 0:
+        raise RuntimeError("An error occured while calling 'rank_filter': " + (last_error() or ""))
+    return out.reshape(img.shape)
+
+
 # ---- extension: per-region statistics ------------------------------------------------------------------------------------------
 _sp.rir_region_stats.argtypes = [ct.c_void_p, ct.c_void_p] + [ct.c_int] * 5 + [ct.c_void_p] * 7
 

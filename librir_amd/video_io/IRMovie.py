@@ -530,6 +530,45 @@ class IRMovie(object):
             morphology(fr, op, size, rows, out=out[k0:k0 + len(sel)])
         return out
 
+    def rank_filter(self, rank, size, selection=slice(None), rows=None, out=None):
+        """Spatial rank filter of the images of ``selection`` (as ``region_stats`` takes it) - ``librir_amd.device.rank_filter(frames, rank,
+        size, rows)`` over the images ``to_tensor(selection)`` gives (read-back filters applied), filtered on the device: a uint16 CUDA
+        tensor ``[len(selection)][h][w]`` (``out`` when given: a contiguous uint16 CUDA tensor of that shape).  Every pixel becomes the
+        element of 0-based rank ``rank`` (negative: from the end) of its full ``size`` window (an odd int or ``(size_y, size_x)``, each
+        1..15), coordinates replicated at the border; ``rows=None`` filters all rows, otherwise rows ``>= rows`` are copied.  The recording
+        is read in pieces of at most ``_STATS_PIECE_BYTES`` of images; images are filtered one by one, so any split gives the same bits::
+
+            background = mov.rank_filter(librir_amd.device.percentile_rank(25, 9, 9), 9)   # a low percentile under sparse hot spots
+        """
+        import torch
+
+        from ..device import _rank_filter_args, rank_filter
+
+        h, w = self.image_size
+        _rank_filter_args((1, h, w), "uint16", rank, size, rows)
+        positions = self._stats_positions(selection, "rank_filter")
+        shape = (len(positions), h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint16, device=torch.device("cuda", torch.cuda.current_device()))
+        elif not out.is_cuda or out.dtype != torch.uint16 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise RuntimeError("rank_filter: 'out' must be a C-contiguous uint16 CUDA tensor of shape %s" % (shape,))
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=out.device)
+        for k0 in range(0, len(positions), per_piece):
+            sel = positions[k0:k0 + per_piece]
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            rank_filter(fr, rank, size, rows, out=out[k0:k0 + len(sel)])
+        return out
+
+    def window_median(self, size, selection=slice(None), rows=None, out=None):
+        """``rank_filter`` at the median rank ``size_y * size_x // 2``: ``librir_amd.device.window_median`` over the images of
+        ``selection`` - a despeckle at 3 or 5, a background estimate to subtract at 9 and more"""
+        from ..device import _window_sizes
+
+        size_y, size_x = _window_sizes(size)
+        return self.rank_filter(size_y * size_x // 2, size, selection, rows, out)
+
     _QUANTILE_RESIDENT_BYTES = 1 << 30  # uint16 images that pixel_quantiles decodes into one stack
 
     def pixel_quantiles(self, percents, selection=slice(None)):
