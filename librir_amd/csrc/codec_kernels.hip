@@ -30,16 +30,27 @@
 namespace rir
 {
 
-	// Cache policy of each traffic class (aux operand of the buffer instructions: 2 = nt, "streaming").
-	// Raw frames are read once by the encoder and written once by the decoder, the sparse slots are read once by
-	// the compaction (nt loads there): marking those accesses non-temporal keeps them from evicting what the NEXT kernel
-	// of the pipeline reads (the dense stream, which should stay in L2 / Infinity Cache between compaction and decode).
-	// Measured on the headline workload (scripts/variants.py): all-default 438 us per encode+decode pass,
-	// frames nt 391 us, + compaction loads nt 351 us; nt on the stream loads or the sparse stores is worse.
+	// Cache policy of each traffic class (aux operand of the buffer instructions: 2 = nt, "streaming"; 16 = sc1, write-through to
+	// the fabric; 18 = both).  What decides it is what a kernel leaves behind: L2 is private to an XCD, so a line that is dirty in
+	// L2 when a kernel ends is written back by the release at its end - while the chip does nothing else - and the next kernel,
+	// whose workgroups run on any XCD, cannot use it where it lay.  nt is a replacement hint, not write-through.
+	//   raw frames, read once by the encoders                     nt loads: they must not evict what the next kernel reads
+	//   raw frames, written once by the decoders                  nt stores (FRAME_STORE_AUX; the packed decoder's own constant
+	//                                                             PACKED_FRAME_STORE_AUX, measured apart: DESIGN.md section 3)
+	//   the packed encoder's payload, headers, seg_pos/seg_words  read by the NEXT kernel from the Infinity Cache: PAYLOAD_STORE_AUX /
+	//                                                             TABLE_STORE_SC1, whole 128-byte lines per store instruction where
+	//                                                             the policy is write-through (a line written by two write-through
+	//                                                             instructions goes to the fabric twice)
+	//   the slots of rirb1_encode_tiles, the dense stream         default: written and read in L2-sized pieces by neighbouring launches
+	//   stream loads of the decoders                              default
+	// The legs measured on the packed step are in profiles/packed_wt_time.txt.
 	constexpr int FRAME_LOAD_AUX = 2;
 	constexpr int FRAME_STORE_AUX = 2;
+	constexpr int PACKED_FRAME_STORE_AUX = 2; // rirb1_decode_packed's frame stores
 	constexpr int SPARSE_STORE_AUX = 0;
 	constexpr int STREAM_LOAD_AUX = 0;
+	constexpr int PAYLOAD_STORE_AUX = 16;	  // rirb1_encode_packed's copy-out of a segment
+	constexpr bool TABLE_STORE_SC1 = true;	  // the staged encoders' headers, rirb1_encode_packed's seg_pos / seg_words
 
 	typedef short short2v __attribute__((ext_vector_type(2)));
 	typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
@@ -261,6 +272,7 @@ namespace rir
 		r.d[3] = v.w;
 		return r;
 	}
+	template <int AUX = FRAME_STORE_AUX>
 	__device__ __forceinline__ void buf_store8(void *tile_base, uint32_t lane_off, const Px8 &r)
 	{
 		v4u32 v;
@@ -268,7 +280,7 @@ namespace rir
 		v.y = r.d[1];
 		v.z = r.d[2];
 		v.w = r.d[3];
-		__builtin_amdgcn_raw_buffer_store_b128(v, make_rsrc(tile_base, RIRB1_TILE_PX * 2), lane_off, 0, FRAME_STORE_AUX);
+		__builtin_amdgcn_raw_buffer_store_b128(v, make_rsrc(tile_base, RIRB1_TILE_PX * 2), lane_off, 0, AUX);
 	}
 
 	// tile minimum of the 8 packed values of every lane -> wave-uniform 16-bit base
@@ -494,6 +506,18 @@ namespace rir
 		return emit_words_wide<SCALE, NONE>(r, mode, base, rw, pos, lc, tc, words);
 	}
 
+	// A word of a table the NEXT kernel reads (a header, seg_pos, seg_words).  STAGED (the single-pass encoders) and TABLE_STORE_SC1: the
+	// store is write-through (an agent-scope relaxed store is the sc1 form of the same global store instruction), so the line is not left
+	// dirty in L2 for the release at the kernel's end; otherwise the plain store.
+	template <bool STAGED, class T>
+	__device__ __forceinline__ void store_table_word(T *p, T v)
+	{
+		if (STAGED && TABLE_STORE_SC1)
+			__hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		else
+			*p = v;
+	}
+
 	// ---- where a record's words go: the two sinks of encode_run ------------------------------------------
 	// sink.emit<DIR>(residuals, mode, base, pos, ...) files the record that begins at word `pos` of what the wave has produced so far
 	// and returns its header.  GUARDED_STEPS tells the frame walk whether a record's work may sit under a condition: not the direct sink's,
@@ -687,7 +711,7 @@ namespace rir
 			const uint32_t key_mode = use_left ? RIRB1_MODE_LEFT : RIRB1_MODE_RAW;
 			const uint64_t h = sink.template emit<DIR>(r_sel, key_mode, use_left ? base_left : base_raw, pos, lc, tc, &words);
 			if (lane == 0)
-				hdr_first[0] = h;
+				store_table_word<Sink::GUARDED_STEPS>(hdr_first, h);
 			pos += words;
 		};
 		// Ring of 4 frame slots: what was loaded k-th lives in slot k % 4, three frames are in flight ahead of the one being packed.
@@ -787,7 +811,7 @@ namespace rir
 			fb = gend;
 			// lane l holds the header of step g0 + l: the record of frame g0 + l forwards, of frame nload - (g0 + l) backwards
 			if (g0 + lane < gend)
-				hdr_first[BACK ? nload - (g0 + lane) : g0 + lane] = hdr_reg;
+				store_table_word<Sink::GUARDED_STEPS>(hdr_first + (BACK ? nload - (g0 + lane) : g0 + lane), hdr_reg);
 			hdr_reg = 0;
 		}
 #undef RIR_ENC_STEP
@@ -1069,7 +1093,7 @@ namespace rir
 												   uint32_t *sh_words, uint32_t *sh_lds_words)
 	{
 		for (int f = nf + (int)threadIdx.x; f < gop; f += WAVES * 64)
-			my_hdr[f] = 0;
+			store_table_word<true>(my_hdr + f, (uint64_t)0);
 		if (lane == 0)
 		{
 			sh_words[w] = pos;
@@ -1083,21 +1107,29 @@ namespace rir
 	// produced first - in its spill area, which spill_area(need) describes (its size in words goes to `need`) and which is asked for
 	// only when there is a rest.  A forward wave's words: its area from word 0, then its region from word 0.  A backward wave's: its
 	// region (the EARLIER records, which it packed last) up to the region's end, then its area up to the area's end.
-	template <class SpillArea>
+	// AUX: the policy of its stores (0: plain pointer stores, else buffer stores with that aux operand).
+	template <int AUX, class SpillArea>
 	__device__ __forceinline__ void copy_wave_words(uint64_t *__restrict__ dst, const uint64_t *region, uint32_t cap, uint32_t n_all, uint32_t n_lds, bool back,
 													int lane, SpillArea spill_area)
 	{
 		const uint32_t n_ext = n_all - n_lds;
 		const uint64_t *src = region + (back ? cap - n_lds : 0u);
 		uint64_t *dst_lds = dst + (back ? 0u : n_ext);
+		const __amdgpu_buffer_rsrc_t out = make_rsrc(dst, n_all * 8u); // (AUX != 0)
+		auto put = [&](uint64_t *base, uint32_t j, uint64_t v) {
+			if (AUX == 0)
+				base[j] = v;
+			else
+				__builtin_amdgcn_raw_buffer_store_b64(v2u32{(uint32_t)v, (uint32_t)(v >> 32)}, out, (uint32_t)(base - dst + j) * 8u, 0, AUX);
+		};
 		uint32_t j = (uint32_t)lane;
 		for (; j + 192 < n_lds; j += 256)
 		{
 			const uint64_t v0 = src[j], v1 = src[j + 64], v2 = src[j + 128], v3 = src[j + 192];
-			dst_lds[j] = v0, dst_lds[j + 64] = v1, dst_lds[j + 128] = v2, dst_lds[j + 192] = v3;
+			put(dst_lds, j, v0), put(dst_lds, j + 64, v1), put(dst_lds, j + 128, v2), put(dst_lds, j + 192, v3);
 		}
 		for (; j < n_lds; j += 64)
-			dst_lds[j] = src[j];
+			put(dst_lds, j, src[j]);
 		if (n_ext > 0)
 		{ // what the wave flushed comes back from the workspace (sc1 loads: from L2, where its stores went)
 			uint32_t need;
@@ -1107,9 +1139,69 @@ namespace rir
 			for (uint32_t q = (uint32_t)lane; q < n_ext; q += 64)
 			{
 				const v2u32 v = __builtin_amdgcn_raw_buffer_load_b64(sp, (first + q) * 8u, 0, 16 /* sc1 */);
-				dst_ext[q] = ((uint64_t)v.y << 32) | v.x;
+				put(dst_ext, q, ((uint64_t)v.y << 32) | v.x);
 			}
 		}
+	}
+
+	// The copy-out of a segment no wave of which spilled: words [0, total) of the segment lie in the WAVES regions of `lds` (`cap` words
+	// each) - wave i's n[i] words at the bottom of its region, or at its top when back(i) - and go to dst as ONE run, cut by the 128-byte
+	// lines of memory instead of by the waves: the words in front of the first line boundary and those behind the last whole line as
+	// 8-byte stores (one instruction for both ends), the lines between as 16 bytes per lane, so that every body instruction writes eight
+	// whole lines and no line is written by two instructions.  That is what a write-through policy needs (AUX 16 / 18): a line two
+	// instructions write goes to the fabric twice, and neighbouring segments share lines only at their ends.  A lane's two words may lie
+	// in two waves' regions: a word of the segment is found from the running sums of n.  LDS is read 8 bytes at a time.
+	template <int WAVES, int AUX, class Back>
+	__device__ __forceinline__ void copy_segment_lines(uint64_t *__restrict__ dst, const uint64_t *lds, uint32_t cap, const uint32_t *n, uint32_t total, int lane,
+													   Back back)
+	{
+		uint32_t end[WAVES], delta[WAVES]; // word q < end[i] (and >= end[i - 1]) of the segment is lds[q + delta[i]]
+		uint32_t sum = 0;
+#pragma unroll
+		for (int i = 0; i < WAVES; ++i)
+		{
+			delta[i] = (uint32_t)i * cap + (back(i) ? cap - n[i] : 0u) - sum;
+			sum += n[i];
+			end[i] = sum;
+		}
+		// (as a telescoping sum, not as a chain of selects between elements of delta: the compiler turns such a chain into a select
+		// between their addresses, and the array into scratch)
+		auto word = [&](uint32_t q) {
+			uint32_t d = delta[WAVES - 1];
+#pragma unroll
+			for (int i = WAVES - 2; i >= 0; --i)
+				d += q < end[i] ? delta[i] - delta[i + 1] : 0u;
+			return lds[q + d];
+		};
+		const __amdgpu_buffer_rsrc_t out = make_rsrc(dst, total * 8u);
+		const uint32_t to_line = (16u - (uint32_t)(((uintptr_t)dst >> 3) & 15u)) & 15u;
+		const uint32_t head = min(to_line, total);			   // words in front of the first line boundary
+		const uint32_t pairs = ((total - head) >> 4) << 3;	   // 16-byte pieces of the whole lines behind it
+		const uint32_t tail0 = head + 2u * pairs, tail = total - tail0; // the rest: < 16 words
+		{ // both ends: lanes [0, head) and [16, 16 + tail)
+			const uint32_t l = (uint32_t)lane;
+			const bool on = l < 16u ? l < head : l - 16u < tail;
+			const uint32_t q = l < 16u ? l : tail0 + (l - 16u);
+			const uint64_t v = on ? word(q) : 0ull;
+			__builtin_amdgcn_raw_buffer_store_b64(v2u32{(uint32_t)v, (uint32_t)(v >> 32)}, out, on ? q * 8u : RIR_OOB, 0, AUX);
+		}
+		auto piece = [&](uint32_t j) { // (a piece past the end reads words 0 and 1 of a segment of at least 16, and is stored nowhere)
+			const uint32_t q = j < pairs ? head + 2u * j : 0u;
+			const uint64_t a = word(q), b = word(q + 1u);
+			return v4u32{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)};
+		};
+		auto put = [&](uint32_t j, const v4u32 &v) {
+			__builtin_amdgcn_raw_buffer_store_b128(v, out, j < pairs ? (head + 2u * j) * 8u : RIR_OOB, 0, AUX);
+		};
+		uint32_t j0 = 0; // (wave-uniform loops: 1 KiB, eight whole lines, per store instruction)
+		for (; j0 + 256 <= pairs; j0 += 256)
+		{
+			const uint32_t j = j0 + (uint32_t)lane;
+			const v4u32 v0 = piece(j), v1 = piece(j + 64), v2 = piece(j + 128), v3 = piece(j + 192);
+			put(j, v0), put(j + 64, v1), put(j + 128, v2), put(j + 192, v3);
+		}
+		for (; j0 < pairs; j0 += 64)
+			put(j0 + (uint32_t)lane, piece(j0 + (uint32_t)lane));
 	}
 
 	template <int WAVES>
@@ -1210,7 +1302,8 @@ namespace rir
 		for (int i = 0; i < WAVES; ++i)
 		{
 			const uint32_t n_all = sh_u32[i];
-			copy_wave_words(dst, enc_lds + (size_t)i * cap, (uint32_t)cap, n_all, sh_u32[WAVES + 2 + i], false, lane,
+			// (the ordered stream is not what the packed step reads: it keeps the per-wave copy and plain stores)
+			copy_wave_words<0>(dst, enc_lds + (size_t)i * cap, (uint32_t)cap, n_all, sh_u32[WAVES + 2 + i], false, lane,
 							[&](uint32_t &need) { return spill_area(wave_share<enc_split>(i, WAVES, nf), need); });
 			dst += n_all;
 		}
@@ -1308,13 +1401,16 @@ namespace rir
 		// wave copying its own words after one more barrier, is RIR_PACKED_COPY_ALL_WAVES in 02807a8)
 		if (w != 0)
 			return;
-		uint32_t total = 0;
-		bool lost = false; // a wave of this segment wanted an extent and got none
+		uint32_t total = 0, n_wave[WAVES];
+		bool lost = false;	  // a wave of this segment wanted an extent and got none
+		bool spilled = false; // a wave of this segment has words outside LDS
 #pragma unroll
 		for (int i = 0; i < WAVES; ++i)
 		{
-			const uint32_t n = sh_u32[i];
+			const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)sh_u32[i]);
+			n_wave[i] = n;
 			total += n;
+			spilled |= n != sh_u32[WAVES + i];
 			lost |= n > sh_u32[WAVES + i] && sh_u64[1 + i] == ~0ull;
 		}
 		unsigned long long at = 0;
@@ -1334,17 +1430,23 @@ namespace rir
 			at = capacity_words - at - total; // (unused when it does not fit)
 		if (lane == 0)
 		{
-			seg_pos[seg] = at;
-			seg_words[seg] = total;
+			store_table_word<true>(seg_pos + seg, (uint64_t)at);
+			store_table_word<true>(seg_words + seg, total);
 			sh_u64[0] = (fits && !lost) ? at : ~0ull;
 		}
 		if (!fits || lost)
 			return;
 		uint64_t *dst = stream + at;
+		if (!spilled)
+		{ // the common case (every segment of the reference's recipe): one copy of the whole segment, cut by the lines of memory
+			copy_segment_lines<WAVES, PAYLOAD_STORE_AUX>(dst, enc_lds, (uint32_t)cap, n_wave, total, lane, [](int i) { return enc_walks_back(i); });
+			return;
+		}
+		// a wave spilled: wave by wave, each from its region and its extent, under the same policy
 		for (int i = 0; i < WAVES; ++i)
 		{
-			const uint32_t n_all = sh_u32[i];
-			copy_wave_words(dst, enc_lds + (size_t)i * cap, (uint32_t)cap, n_all, sh_u32[WAVES + i], enc_walks_back(i), lane, [&](uint32_t &need) {
+			const uint32_t n_all = sh_u32[i]; // (not n_wave[i]: a register array indexed by a loop that is not unrolled is scratch)
+			copy_wave_words<PAYLOAD_STORE_AUX>(dst, enc_lds + (size_t)i * cap, (uint32_t)cap, n_all, sh_u32[WAVES + i], enc_walks_back(i), lane, [&](uint32_t &need) {
 				need = (uint32_t)wave_share<enc_split_mirrored>(i, WAVES, nf).nrec * RIRB1_REC_MAX_WORDS;
 				return make_rsrc(arena + sh_u64[1 + i], need * 8u); // its extent
 			});
@@ -1464,7 +1566,9 @@ namespace rir
 		return o;
 	}
 
-	// where decode_tile puts a reconstructed record: every frame of the chunk at its place in `frames`
+	// where decode_tile puts a reconstructed record: every frame of the chunk at its place in `frames`; AUX: the policy of the FAST stores
+	// (1 KiB per wave instruction: whole 128-byte lines when the frames are 128-byte aligned)
+	template <int AUX = FRAME_STORE_AUX>
 	struct ChunkSink
 	{
 		uint16_t *frames, *tile0;
@@ -1479,7 +1583,7 @@ namespace rir
 		__device__ __forceinline__ void put(int f, const Px8 &o)
 		{
 			if (FAST)
-				buf_store8(tile0 + (int64_t)f * npx, lane_off, o);
+				buf_store8<AUX>(tile0 + (int64_t)f * npx, lane_off, o);
 			else
 				store8(frames, frame0 + f, npx, p0, false, o);
 		}
@@ -1631,7 +1735,7 @@ namespace rir
 			in = stream + c0 + t0;
 		}
 		const bool fast = ((npx & 7) == 0) && ((int64_t)(tile + 1) * RIRB1_TILE_PX <= npx) && ((((uintptr_t)frames) & 15) == 0);
-		ChunkSink sink(frames, npx, f_begin, tile, lane);
+		ChunkSink<> sink(frames, npx, f_begin, tile, lane);
 		if (fast)
 			decode_tile<true>(my_hdr, in, seg_len, nf, true, lane, sink, error_flag);
 		else
@@ -1667,7 +1771,7 @@ namespace rir
 				atomicExch(error_flag, 1);
 			return;
 		}
-		ChunkSink sink(frames, npx, f_begin, tile, lane);
+		ChunkSink<PACKED_FRAME_STORE_AUX> sink(frames, npx, f_begin, tile, lane);
 		decode_tile<FAST>(hdr_table + slot * gop, stream + base, seg_len, nf, true, lane, sink, error_flag);
 	}
 
