@@ -320,6 +320,29 @@ extern "C"
 									int *d_count, int *d_values, void *d_work, size_t work_bytes, void *stream);
 	size_t rir_region_quantiles_workspace_bytes(int w, int h, int nframes, int labels_per_frame, int nregions, int npercents);
 
+	/* Per-region histograms of a uint16 stack d_frames[nframes][h][w] (extension), frames and label maps as rir_region_stats_device takes
+	 * them (one map [h][w], or [nframes][h][w] with labels_per_frame 1; labels outside [0, nregions) are ignored), nregions 1..65 536.
+	 * d_labels null: the whole image is region 0 - nregions must be 1 and labels_per_frame 0 - and only the frames are read, 2 bytes a
+	 * pixel instead of 6.  Only the first `rows` (0..h) rows of every frame, and of every map, are counted; the frame stride stays w * h
+	 * (the metadata rows of a WEST frame are left out as `rows` leaves them out of the filters).  Bins: nbins (1..65 536) bins of `width`
+	 * (1..65 536) levels from `lo` (0..65 535), with nregions * nbins <= 2^24; lo + nbins * width may pass 65 536, the bins beyond stay 0.
+	 * For frame f and region r, V = the values of the counted pixels of f whose label is r.  Outputs, all int32:
+	 *   d_hist[f][r][b]     = the number of v in V with lo + b * width <= v < lo + (b + 1) * width,
+	 *   d_outside[f][r][0]  = the number with v < lo,  d_outside[f][r][1] = the number with v >= lo + nbins * width,
+	 *   d_count[f][r]       = |V|,  so that count == outside[0] + sum over b of hist + outside[1] always;
+	 * an empty region has zeros everywhere.  d_count and d_outside may each be null: not wanted.  The device uses integer arithmetic only
+	 * ((v - lo) / width is a shift for a power of two, else a multiply-high by a reciprocal computed on the host, exact for every 16-bit
+	 * value) and every combination is a 32-bit integer add: bitwise reproducible, whatever the launch geometry.  The outputs are zeroed
+	 * by the call and serve as the accumulators.  d_work: device memory, 8-byte aligned, at least rir_region_histogram_workspace_bytes(...)
+	 * bytes - a small constant kept for uniformity with the other region entries; 0: arguments refused.  Asynchronous on `stream`; no
+	 * output or the workspace may overlap an input or another output.  nframes 0: nothing is done, 0; rows 0: the outputs are zeroed, 0.
+	 * 0 / -1 with the reason logged; a bad argument, a null pointer (other than d_labels, d_count, d_outside), a workspace too small and
+	 * an overlap are refused before the device is looked for; then no device.  There is no CPU fallback. */
+	int rir_region_histogram_device(const unsigned short *d_frames, const int *d_labels /* or null */, int w, int h, int rows, int nframes,
+									int labels_per_frame, int nregions, int lo, int width, int nbins, int *d_count /* or null */, int *d_hist,
+									int *d_outside /* or null */, void *d_work, size_t work_bytes, void *stream);
+	size_t rir_region_histogram_workspace_bytes(int w, int h, int rows, int nframes, int labels_per_frame, int nregions, int nbins);
+
 	/* Per-pixel statistics over time of a uint16 stack d_frames[nframes][h][w] (extension).  For pixel i = y * w + x, with v_f = d_frames[f][i],
 	 * f = 0 .. nframes - 1, and a time origin t0 >= 0, the outputs [h][w] are: d_sum[i] = the exact sum of the v_f, d_sumsq[i] = the exact sum
 	 * of their squares (int64), d_min[i] / d_max[i] = the extremes over f, d_argmin[i] / d_argmax[i] = t0 + f for the LOWEST f that holds the

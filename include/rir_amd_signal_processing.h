@@ -96,6 +96,14 @@ extern "C"
 	 * through the device in slabs of at most 64 MiB; a shared map goes up once.  0 / -1. */
 	int rir_region_quantiles(const unsigned short *frames, const int *labels, int w, int h, int nframes, int labels_per_frame, int nregions,
 							 const float *percents, int npercents, int *count, int *values);
+	/* Per-region histograms of a host stack frames[nframes][h][w] with host label maps, or none (labels null: the whole image is region 0,
+	 * nregions 1): rir_region_histogram_device (rir_amd_device.h, where the bins are defined), synchronous, host outputs
+	 * count[nframes][nregions], hist[nframes][nregions][nbins] and outside[nframes][nregions][2]; count and outside may be null.  The
+	 * frames go through the device in slabs of at most 64 MiB; a shared map goes up once.  nframes 0: 0.  -1 with the reason logged on a
+	 * bad argument (before the device is looked for) and without a device (the outputs untouched: there is no CPU fallback). */
+	int rir_region_histogram(const unsigned short *frames, const int *labels /* or null */, int w, int h, int rows, int nframes,
+							 int labels_per_frame, int nregions, int lo, int width, int nbins, int *count /* or null */, int *hist,
+							 int *outside /* or null */);
 	/* Per-pixel statistics over time of a host stack frames[nframes][h][w]: rir_pixel_stats_device (rir_amd_device.h) with t0 = 0,
 	 * synchronous, host outputs [h][w]; a group (sum, sumsq / min, max, argmin, argmax) may be null, not both.  The frames go through the
 	 * device in slabs of at most 64 MiB that accumulate there; the outputs come back once.  nframes 0: nothing is done.  0 / -1. */

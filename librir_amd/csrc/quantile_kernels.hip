@@ -16,6 +16,8 @@
 //                                  in that bucket's histogram (buckets of one region differ, so a pixel counts at most once).
 //   region_quantiles_finish        one wave per (frame, region, percent) scans the 256 low counters for the rank left.
 //
+// The walk of the two counting passes - items, frames, runs, the drain - is walk_counters of region_walk.h under the policy QtCount.
+//
 // Every combination is a 32-bit integer add (ds_add_u32 / global_atomic_add), so the result does not depend on the order the workgroups
 // run in; the only floating-point operation is the rank, qt_rank().
 #include "quantile_kernels.h"
@@ -96,6 +98,64 @@ namespace rir
 		r.cnt = 0;
 	}
 
+	// A counting pass as a policy of walk_counters (region_walk.h): the keys are QtIndex's, the counters below lds_bins are in LDS.
+	template <bool LOW>
+	struct QtCount
+	{
+		typedef int Key;
+		typedef QtRun Run;
+		static constexpr int NONE = -1;
+
+		const uint16_t *__restrict__ frames;
+		const int32_t *__restrict__ labels;
+		int64_t npx;
+		int per_frame, nregions, vec;
+		const uint2 *__restrict__ codes;
+		uint32_t *__restrict__ hist; // [n][bins]
+		uint32_t *lds;
+		int bins, lds_bins;
+		QtIndex<LOW> index;
+		const uint16_t *f; // of the open frame
+		const int32_t *l;
+		uint32_t *h;
+
+		__device__ __forceinline__ void clear()
+		{
+			for (int i = threadIdx.x; i < lds_bins; i += QT_BLOCK)
+				lds[i] = 0;
+		}
+		__device__ __forceinline__ void frame(int64_t fi)
+		{
+			f = frames + fi * npx;
+			l = labels + (per_frame ? fi * npx : 0);
+			h = hist + fi * bins;
+			index.frame(LOW ? codes + fi * nregions * 2 : nullptr);
+		}
+		template <bool CHECK>
+		__device__ __forceinline__ void keys(int64_t p, int64_t end, int (&key)[QT_PX])
+		{
+			unsigned v[QT_PX];
+			int lab[QT_PX];
+			load8<CHECK, true>(f, l, p, end, vec, -1, v, lab); // a pixel past the end gets label -1, no region: it counts nowhere
+#pragma unroll
+			for (int j = 0; j < QT_PX; ++j)
+				key[j] = index(v[j], lab[j]);
+		}
+		static __device__ __forceinline__ void add(QtRun &r, unsigned n) { r.cnt += n; }
+		__device__ __forceinline__ void flush(QtRun &r, int next) { qt_flush(r, lds, lds_bins, h, next); }
+		__device__ __forceinline__ void drain()
+		{
+			for (int i = threadIdx.x; i < lds_bins; i += QT_BLOCK)
+			{
+				const uint32_t c = lds[i];
+				if (c == 0)
+					continue;
+				walk_add<WALK_AGENT>(h + i, c);
+				lds[i] = 0;
+			}
+		}
+	};
+
 	// hist: [n][slots][256], slots = nregions (high pass) or nregions * nq (low pass); codes (low pass): [n][nregions] x 16 bytes.
 	template <bool LOW>
 	__global__ __launch_bounds__(QT_BLOCK) void region_quantiles_count(const uint16_t *__restrict__ frames, const int32_t *__restrict__ labels,
@@ -105,78 +165,11 @@ namespace rir
 	{
 		extern __shared__ uint32_t qt_lds[];
 		const int slots = LOW ? nregions * nq : nregions;
-		const int bins = slots * 256, lds_bins = min(slots, QUANTILE_LDS_MAX) * 256;
-		for (int i = threadIdx.x; i < lds_bins; i += QT_BLOCK)
-			qt_lds[i] = 0;
-		__syncthreads();
-		QtIndex<LOW> index;
-		index.nregions = nregions;
-		index.nq = nq;
-		index.frame(nullptr);
-		QtRun run{-1, 0};
-		const int64_t first = (int64_t)blockIdx.x * items / gridDim.x, last = ((int64_t)blockIdx.x + 1) * items / gridDim.x;
-		int64_t open = -1; // the frame the counters and the run belong to
-		for (int64_t item = first;; ++item)
-		{
-			const int64_t fi = item < last ? item / per_item_frame : -1;
-			if (fi != open)
-			{
-				if (open >= 0)
-				{
-					uint32_t *hf = hist + open * bins;
-					qt_flush(run, qt_lds, lds_bins, hf, -1);
-					__syncthreads();
-					for (int i = threadIdx.x; i < lds_bins; i += QT_BLOCK)
-					{
-						const uint32_t c = qt_lds[i];
-						if (c == 0)
-							continue;
-						walk_add<WALK_AGENT>(hf + i, c);
-						qt_lds[i] = 0;
-					}
-					__syncthreads();
-				}
-				open = fi;
-				if (fi >= 0)
-					index.frame(LOW ? codes + fi * nregions * 2 : nullptr);
-			}
-			if (fi < 0)
-				break; // past the range's last item
-			const int64_t lo = (item - fi * per_item_frame) * QT_ITEM, hi = min(lo + QT_ITEM, npx);
-			const uint16_t *f = frames + fi * npx;
-			const int32_t *l = labels + (per_frame ? fi * npx : 0);
-			uint32_t *h = hist + fi * bins;
-			for (int64_t s = lo; s < hi; s += QT_STEP)
-			{
-				const int64_t p = s + threadIdx.x * QT_PX;
-				unsigned v[QT_PX];
-				int lab[QT_PX];
-				if (p + QT_PX <= hi) // a pixel past the end gets label -1, no region: it counts nowhere
-					load8<false, true>(f, l, p, hi, vec, -1, v, lab);
-				else
-					load8<true, true>(f, l, p, hi, vec, -1, v, lab);
-				int idx[QT_PX];
-				bool same = true;
-#pragma unroll
-				for (int j = 0; j < QT_PX; ++j)
-				{
-					idx[j] = index(v[j], lab[j]);
-					same &= idx[j] == run.key;
-				}
-				if (same)
-				{
-					run.cnt += QT_PX;
-					continue;
-				}
-#pragma unroll
-				for (int j = 0; j < QT_PX; ++j)
-				{
-					if (idx[j] != run.key)
-						qt_flush(run, qt_lds, lds_bins, h, idx[j]);
-					run.cnt += 1;
-				}
-			}
-		}
+		QtCount<LOW> pol{frames, labels, npx, per_frame, nregions, vec, codes, hist, qt_lds, slots * 256, min(slots, QUANTILE_LDS_MAX) * 256};
+		pol.index.nregions = nregions;
+		pol.index.nq = nq;
+		pol.index.frame(nullptr);
+		walk_counters(pol, npx, items, per_item_frame);
 	}
 
 	// Wave-wide: lane l holds the counters c[0..3] = bins 4l .. 4l + 3 of one histogram.  -> the lane's exclusive prefix; *total for all.

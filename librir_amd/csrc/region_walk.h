@@ -1,6 +1,7 @@
 // The walk over labelled pixels that the per-region reducers share: statistics (region_kernels.hip) and geometry (geometry_kernels.hip) take
-// all of it, quantiles (quantile_kernels.hip) the constants, the atomics, load8 and the host helpers.  Device templates plus a little host
-// code; include from .hip files only.
+// walk_regions, the counting reducers - quantiles (quantile_kernels.hip) and histograms (histogram_kernels.hip) - walk_counters, further
+// down; all share the constants, the atomics, load8 and the host helpers.  Device templates plus a little host code; include from .hip
+// files only.
 //
 // walk_regions<LDS>(policy, ...) is a grid-stride loop over work items of WALK_ITEM pixels of one frame.  A thread takes 8 adjacent pixels
 // per step (two 16-byte loads of labels, one of values) and keeps the run of its current label in registers.  It knows where its first pixel
@@ -240,6 +241,75 @@ namespace rir
 				for (int r = threadIdx.x; r < nregions; r += WALK_BLOCK)
 					pol.drain(r);
 				__syncthreads();
+			}
+		}
+	}
+
+	// The whole kernel of a counting reducer (the passes of quantile_kernels.hip, histogram_kernels.hip): every pixel becomes the key of a
+	// counter, and a thread keeps the run of its current key in registers, so a counter is touched where the key changes.  A workgroup takes
+	// a contiguous range of the work items (`items` of them, per_item_frame to a frame of npx walked pixels), so that it meets few frames:
+	// where its range passes into another frame, and at its end, the open run is closed and the policy drains the counters it keeps in LDS.
+	// A step in which a thread's 8 keys all continue its run adds 8 to it; otherwise the 8 pixels go one by one.  The policy supplies
+	//   Key, NONE                  the key type and the key of a pixel that counts nowhere
+	//   Run                        the run type, with the key `Key key`; the kernel starts from Run{} re-opened with NONE
+	//   clear()                    zero the LDS counters (the kernel's first step, before a barrier)
+	//   frame(fi)                  point the loads and the global counters at frame fi
+	//   keys<CHECK>(p, end, k)     the keys of the 8 pixels at p; CHECK: a pixel at or past `end` gets NONE
+	//   add(run, n)                n more pixels of the run
+	//   flush(run, next)           close the run into its counter and open one of key `next`
+	//   drain()                    between two barriers: the LDS counters of the open frame to global memory, and zero them
+	template <class P>
+	__device__ __forceinline__ void walk_counters(P &pol, int64_t npx, int64_t items, int per_item_frame)
+	{
+		pol.clear();
+		__syncthreads();
+		typename P::Run run{};
+		pol.flush(run, P::NONE);
+		const int64_t first = (int64_t)blockIdx.x * items / gridDim.x, last = ((int64_t)blockIdx.x + 1) * items / gridDim.x;
+		int64_t open = -1; // the frame the counters and the run belong to
+		for (int64_t item = first;; ++item)
+		{
+			const int64_t fi = item < last ? item / per_item_frame : -1;
+			if (fi != open)
+			{
+				if (open >= 0)
+				{
+					pol.flush(run, P::NONE);
+					__syncthreads();
+					pol.drain();
+					__syncthreads();
+				}
+				open = fi;
+				if (fi >= 0)
+					pol.frame(fi);
+			}
+			if (fi < 0)
+				break; // past the range's last item
+			const int64_t lo = (item - fi * per_item_frame) * WALK_ITEM, hi = min(lo + WALK_ITEM, npx);
+			for (int64_t s = lo; s < hi; s += WALK_STEP)
+			{
+				const int64_t p = s + threadIdx.x * WALK_PX;
+				typename P::Key key[WALK_PX];
+				if (p + WALK_PX <= hi)
+					pol.template keys<false>(p, hi, key);
+				else
+					pol.template keys<true>(p, hi, key);
+				bool same = true;
+#pragma unroll
+				for (int j = 0; j < WALK_PX; ++j)
+					same &= key[j] == run.key;
+				if (same)
+				{
+					P::add(run, WALK_PX);
+					continue;
+				}
+#pragma unroll
+				for (int j = 0; j < WALK_PX; ++j)
+				{
+					if (key[j] != run.key)
+						pol.flush(run, key[j]);
+					P::add(run, 1);
+				}
 			}
 		}
 	}

@@ -15,6 +15,7 @@
 
 #include "filter_kernels.h"
 #include "geometry_kernels.h"
+#include "histogram_kernels.h"
 #include "label_kernels.h"
 #include "morphology_kernels.h"
 #include "pixel_kernels.h"
@@ -879,6 +880,51 @@ RIR_EXPORT int rir_region_quantiles_device(const unsigned short *d_frames, const
 			   : -1;
 }
 
+// Per-region histograms (histogram_kernels.hip).  Every argument is checked here, before the device is looked for; no output (workspace
+// included) may overlap an input or another output.
+namespace
+{
+	const char *const REGION_HISTOGRAM_ARGS = "invalid argument (w, h >= 1 with w * h < 2^31, 0 <= rows <= h, nframes >= 0, labels_per_frame 0 or 1, "
+											  "1 <= nregions <= 65536, 0 <= lo <= 65535, 1 <= width <= 65536, 1 <= nbins <= 65536, "
+											  "nregions * nbins <= 2^24; without labels nregions 1 and labels_per_frame 0)";
+	bool region_histogram_args(bool labelled, int w, int h, int rows, int nframes, int labels_per_frame, int nregions, int lo, int width, int nbins)
+	{
+		return region_stats_args(w, h, nframes, labels_per_frame, nregions) && rows >= 0 && rows <= h && nregions <= HISTOGRAM_MAX_REGIONS && lo >= 0 &&
+			   lo <= 65535 && width >= 1 && width <= 65536 && nbins >= 1 && nbins <= HISTOGRAM_MAX_BINS &&
+			   (long long)nregions * nbins <= HISTOGRAM_MAX_CELLS && (labelled || (nregions == 1 && labels_per_frame == 0));
+	}
+} // namespace
+
+RIR_EXPORT size_t rir_region_histogram_workspace_bytes(int w, int h, int rows, int nframes, int labels_per_frame, int nregions, int nbins)
+{
+	return region_histogram_args(true, w, h, rows, nframes, labels_per_frame, nregions, 0, 1, nbins) ? HISTOGRAM_WORK_BYTES : 0;
+}
+
+RIR_EXPORT int rir_region_histogram_device(const unsigned short *d_frames, const int *d_labels, int w, int h, int rows, int nframes, int labels_per_frame,
+											int nregions, int lo, int width, int nbins, int *d_count, int *d_hist, int *d_outside, void *d_work,
+											size_t work_bytes, void *stream)
+{
+	if (!region_histogram_args(d_labels != nullptr, w, h, rows, nframes, labels_per_frame, nregions, lo, width, nbins))
+		return refuse(__func__, REGION_HISTOGRAM_ARGS);
+	if (!d_frames || !d_hist || !d_work)
+		return refuse(__func__, "null pointer (only d_labels, d_count and d_outside may be null)");
+	if (!workspace_ok(__func__, d_work, work_bytes, HISTOGRAM_WORK_BYTES, "workspace", "rir_region_histogram_workspace_bytes()"))
+		return -1;
+	const size_t npx = (size_t)w * h, cells = (size_t)nframes * nregions;
+	if (outputs_overlap({{d_frames, npx * nframes * 2}, {d_labels, npx * (labels_per_frame ? nframes : 1) * 4}},
+						{{d_count, cells * 4}, {d_hist, cells * nbins * 4}, {d_outside, cells * 8}, {d_work, HISTOGRAM_WORK_BYTES}}))
+		return refuse(__func__, "an output or the workspace overlaps an input or another output");
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	return hip_ok(launch_region_histogram(d_frames, d_labels, (int64_t)npx, (int64_t)rows * w, nframes, labels_per_frame, nregions, lo, width, nbins,
+										  d_count, d_hist, d_outside, as_stream(stream)),
+				  "region_histogram")
+			   ? 0
+			   : -1;
+}
+
 // Per-pixel statistics over time (pixel_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap the input
 // or another output.
 namespace
@@ -1514,6 +1560,43 @@ RIR_EXPORT int rir_region_quantiles(const unsigned short *frames, const int *lab
 			rir_region_quantiles_device(fr.as<unsigned short>(), lab.as<int>(), w, h, c, labels_per_frame, nregions, percents, npercents, d_count, d_values,
 										ws.ptr, work, s.st) != 0 ||
 			!s.down(outs, o * K, c * K) || !s.wait("region_quantiles"))
+			return s.fail();
+	}
+	return 0;
+}
+
+// Per-region histograms of a host stack, staged as rir_region_stats stages its arguments; without labels no map goes up.  count and
+// outside may be null.
+RIR_EXPORT int rir_region_histogram(const unsigned short *frames, const int *labels, int w, int h, int rows, int nframes, int labels_per_frame,
+									int nregions, int lo, int width, int nbins, int *count, int *hist, int *outside)
+{
+	if (!region_histogram_args(labels != nullptr, w, h, rows, nframes, labels_per_frame, nregions, lo, width, nbins))
+		return refuse(__func__, REGION_HISTOGRAM_ARGS);
+	if (!frames || !hist)
+		return refuse(__func__, "null pointer (only labels, count and outside may be null)");
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	const size_t npx = (size_t)w * h, K = (size_t)nregions, B = (size_t)nbins;
+	const int slab = Stager::slab(nframes, {npx * 2, K * (B + 3) * 4}); // a frame; its outputs
+	const size_t cells = (size_t)slab * K;
+	DeviceBuffer fr, lab, o32, ws;
+	if (!fr.reserve(npx * 2 * slab) || (labels && !lab.reserve(npx * 4 * (labels_per_frame ? slab : 1))) || !o32.reserve(cells * (B + 3) * 4) ||
+		!ws.reserve(HISTOGRAM_WORK_BYTES))
+		return -1;
+	int *d_hist = o32.as<int>(), *d_outside = d_hist + cells * B, *d_count = d_outside + cells * 2;
+	const Out outs[] = {{count, d_count, 4}, {hist, d_hist, B * 4}, {outside, d_outside, 8}};
+	Stager s;
+	if (!s.up(lab.ptr, labels_per_frame ? nullptr : labels, npx * 4))
+		return s.fail();
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int c = std::min(slab, nframes - o);
+		if (!s.up(fr.ptr, frames + o * npx, npx * 2 * c) || !s.up(lab.ptr, labels_per_frame ? labels + o * npx : nullptr, npx * 4 * c) ||
+			rir_region_histogram_device(fr.as<unsigned short>(), labels ? lab.as<int>() : nullptr, w, h, rows, c, labels_per_frame, nregions, lo, width, nbins,
+										d_count, d_hist, d_outside, ws.ptr, HISTOGRAM_WORK_BYTES, s.st) != 0 ||
+			!s.down(outs, o * K, c * K) || !s.wait("region_histogram"))
 			return s.fail();
 	}
 	return 0;

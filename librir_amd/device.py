@@ -10,9 +10,9 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
-from .signal_processing.rir_signal_processing import (PixelStats, RegionGeometry, RegionQuantiles, RegionStats,  # noqa: F401 (API)
+from .signal_processing.rir_signal_processing import (PixelStats, RegionGeometry, RegionHistogram, RegionQuantiles, RegionStats,  # noqa: F401 (API)
                                                       _pixel_quantiles_args, _pixel_stats_args, _polygon_map_args, _region_geometry_args,
-                                                      _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
+                                                      _region_histogram_args, _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
                                                       _morphology_args, _rank_filter_args, _temporal_median_args, percentile_rank)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
@@ -124,6 +124,9 @@ _lib.rir_region_geometry_workspace_bytes.restype = ct.c_size_t
 _lib.rir_region_quantiles_device.argtypes = [_vp, _vp] + [ct.c_int] * 5 + [_vp, ct.c_int, _vp, _vp, _vp, ct.c_size_t, _vp]
 _lib.rir_region_quantiles_workspace_bytes.argtypes = [ct.c_int] * 6
 _lib.rir_region_quantiles_workspace_bytes.restype = ct.c_size_t
+_lib.rir_region_histogram_device.argtypes = [_vp, _vp] + [ct.c_int] * 9 + [_vp] * 4 + [ct.c_size_t, _vp]
+_lib.rir_region_histogram_workspace_bytes.argtypes = [ct.c_int] * 7
+_lib.rir_region_histogram_workspace_bytes.restype = ct.c_size_t
 _lib.rir_pixel_stats_device.argtypes = [_vp] + [ct.c_int] * 5 + [_vp] * 7 + [ct.c_size_t, _vp]
 _lib.rir_pixel_stats_workspace_bytes.argtypes = [ct.c_int] * 3
 _lib.rir_pixel_stats_workspace_bytes.restype = ct.c_size_t
@@ -969,6 +972,66 @@ def region_quantiles(frames, labels, percents, nregions=None):
     out = _region_quantiles_empty(n, nregions, pc.size, fr.device)
     if n:
         _region_quantiles_into(fr, lab, per_frame, nregions, pc, out)
+    return out
+
+
+def _region_histogram_inputs(frames, labels, nbins, lo, width, nregions, rows, what="region_histogram"):
+    """region_histogram's checks (labels None: no map), in the order that needs no device for the shapes, dtypes, bins, rows and nregions;
+    -> (frames, labels or None, n, h, w, per_frame, nbins, lo, width, rows)"""
+    if frames.dtype != torch.uint16:
+        raise RuntimeError("%s: uint16 frames expected, not %s" % (what, frames.dtype))
+    if labels is not None and labels.dtype != torch.int32:
+        raise RuntimeError("%s: int32 labels expected, not %s" % (what, labels.dtype))
+    n, h, w, per_frame, nbins, lo, width, rows = _region_histogram_args(tuple(frames.shape), None if labels is None else tuple(labels.shape), nbins, lo,
+                                                                        width, nregions, rows, what)
+    if not frames.is_cuda or (labels is not None and (not labels.is_cuda or frames.device != labels.device)):
+        raise RuntimeError("%s: frames%s on one CUDA device expected" % (what, "" if labels is None else " and labels"))
+    return _frames3(frames), None if labels is None else labels.contiguous(), n, h, w, per_frame, nbins, lo, width, rows
+
+
+def _region_histogram_into(fr, lab, per_frame, nregions, rows, out):
+    """queue the histograms of the first `rows` rows of fr [n][h][w] over lab (None: one region) into out (a RegionHistogram of contiguous
+    tensors, whose hist, lo and width give the bins)"""
+    n, h, w = fr.shape
+    nbins = out.hist.shape[-1]
+    work = _workspace(_lib.rir_region_histogram_workspace_bytes(w, h, rows, n, per_frame, nregions, nbins), fr.device)
+    _check(_lib.rir_region_histogram_device(fr.data_ptr(), None if lab is None else lab.data_ptr(), w, h, rows, n, per_frame, nregions, out.lo, out.width,
+                                            nbins, out.count.data_ptr(), out.hist.data_ptr(), out.outside.data_ptr(), work.data_ptr(), work.numel() * 8,
+                                            _stream()), "rir_region_histogram_device")
+
+
+def _region_histogram_empty(n, nregions, nbins, lo, width, device):
+    return RegionHistogram(torch.empty((n, nregions), dtype=torch.int32, device=device),
+                           torch.empty((n, nregions, nbins), dtype=torch.int32, device=device),
+                           torch.empty((n, nregions, 2), dtype=torch.int32, device=device), lo, width)
+
+
+def region_histogram(frames, labels, nbins, lo=0, width=1, nregions=None, rows=None):
+    """Histograms of a uint16 stack ``frames (n, h, w)`` (or one ``(h, w)`` image: a stack of one) over the regions of the int32 label map
+    ``labels`` (``(h, w)`` shared by every frame, or ``(n, h, w)``), on the current stream (C ABI ``rir_region_histogram_device``, where
+    the bins are defined): a ``RegionHistogram`` of CUDA int32 tensors - count ``[n][nregions]``, hist ``[n][nregions][nbins]`` with
+    ``nbins`` bins of ``width`` levels from ``lo``, outside ``[n][nregions][2]`` - whose ``edges()``, ``mode()``, ``cumulative()`` and
+    ``otsu()`` give the derived quantities.  Only the first ``rows`` rows of every frame and map are counted (None: all).  Labels outside
+    [0, nregions) are ignored; at most 65 536 regions and bins, nregions * nbins at most 2^24; ``nregions=None`` takes
+    ``labels.max() + 1`` (at least 1), which synchronises.  ``labels=None`` is ``histogram``."""
+    if labels is None:
+        _region_histogram_args(tuple(frames.shape), None, nbins, lo, width, nregions, rows)
+        return histogram(frames, nbins, lo, width, rows)
+    fr, lab, n, h, w, per_frame, nbins, lo, width, rows = _region_histogram_inputs(frames, labels, nbins, lo, width, nregions, rows)
+    nregions = _nregions(nregions, lab, lambda k: _region_histogram_args(tuple(frames.shape), tuple(labels.shape), nbins, lo, width, k, rows))
+    out = _region_histogram_empty(n, nregions, nbins, lo, width, fr.device)
+    if n:
+        _region_histogram_into(fr, lab, per_frame, nregions, rows, out)
+    return out
+
+
+def histogram(frames, nbins, lo=0, width=1, rows=None):
+    """``region_histogram`` without a map: the whole image (its first ``rows`` rows) is region 0, and only the frames are read - a
+    ``RegionHistogram`` with count ``[n][1]``, hist ``[n][1][nbins]`` and outside ``[n][1][2]``."""
+    fr, _, n, h, w, _, nbins, lo, width, rows = _region_histogram_inputs(frames, None, nbins, lo, width, 1, rows, "histogram")
+    out = _region_histogram_empty(n, 1, nbins, lo, width, fr.device)
+    if n:
+        _region_histogram_into(fr, None, 0, 1, rows, out)
     return out
 
 

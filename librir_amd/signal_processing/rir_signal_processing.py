@@ -557,6 +557,149 @@ def region_quantiles(images, labels, percents, nregions=None):
     return out
 
 
+# ---- extension: per-region histograms ---------------------------------------------------------------------------------------------
+_sp.rir_region_histogram.argtypes = [ct.c_void_p, ct.c_void_p] + [ct.c_int] * 9 + [ct.c_void_p] * 3
+
+MAX_HISTOGRAM_REGIONS = 1 << 16
+MAX_HISTOGRAM_BINS = 1 << 16
+MAX_HISTOGRAM_CELLS = 1 << 24
+
+
+class RegionHistogram(namedtuple("RegionHistogram", "count hist outside lo width")):
+    """Histograms per (frame, region), int32: count ``[n][nregions]``, hist ``[n][nregions][nbins]`` - bin b counts the values v with
+    lo + b * width <= v < lo + (b + 1) * width - and outside ``[n][nregions][2]``, the values below lo and those at or above
+    lo + nbins * width, so that count == outside[..., 0] + hist.sum(-1) + outside[..., 1].  ``lo`` and ``width`` are the ints of the call.
+    numpy arrays (``signal_processing.region_histogram``) or tensors (``device.region_histogram``, ``device.histogram``); the helpers
+    answer in kind."""
+
+    __slots__ = ()
+
+    def _numpy(self):
+        return isinstance(self.hist, np.ndarray)
+
+    def _bins(self, dtype):
+        """0 .. nbins - 1 beside the histograms"""
+        nbins = self.hist.shape[-1]
+        if self._numpy():
+            return np.arange(nbins, dtype=np.dtype(dtype))
+        import torch
+
+        return torch.arange(nbins, dtype=getattr(torch, dtype), device=self.hist.device)
+
+    def edges(self):
+        """int64 ``[nbins + 1]``: bin b is [edges[b], edges[b + 1])"""
+        nbins = self.hist.shape[-1]
+        if self._numpy():
+            return self.lo + np.arange(nbins + 1, dtype=np.int64) * self.width
+        import torch
+
+        return self.lo + torch.arange(nbins + 1, dtype=torch.int64, device=self.hist.device) * self.width
+
+    def _lowest_of_the_largest(self, score, nothing):
+        """per (frame, region) the lowest bin whose score is the largest, as a min over the bins that hold it: ties go to the lowest bin by
+        construction; -1 where `nothing`"""
+        nbins = self.hist.shape[-1]
+        bins = self._bins("int32")
+        if self._numpy():
+            first = np.where(score == score.max(-1, keepdims=True), bins, nbins).min(-1)
+            return np.where(nothing, -1, first).astype(np.int32)
+        import torch
+
+        first = torch.where(score == score.amax(-1, keepdim=True), bins, torch.full_like(bins, nbins)).amin(-1)
+        return torch.where(nothing, torch.full_like(first, -1), first)
+
+    def mode(self):
+        """int32 ``[n][nregions]``: the lowest bin among the fullest; -1 where every bin is empty"""
+        return self._lowest_of_the_largest(self.hist, self.hist.max(-1) == 0 if self._numpy() else self.hist.amax(-1) == 0)
+
+    def cumulative(self):
+        """int64 ``[n][nregions][nbins]``: the counts of the bins up to and including each"""
+        if self._numpy():
+            return np.cumsum(self.hist, -1, dtype=np.int64)
+        import torch
+
+        return torch.cumsum(self.hist, -1, dtype=torch.int64)
+
+    def otsu(self):
+        """float64 ``[n][nregions]``: Otsu's threshold as a bin - the bin t that maximises the between-class variance of the classes
+        "bins <= t" and "bins > t", the lowest such t (the values of the upper class start at edges()[t + 1]); -1 where fewer than two
+        bins are occupied.  With c = cumulative(), N = c[-1], m[t] = sum of b * hist[b] over b <= t and M = m[-1], the variance is
+        (M * c[t] - m[t] * N)^2 / (c[t] * (N - c[t])) up to the factor N^2: the counts are exact, the products and the quotient float64."""
+        c = _f64(self.cumulative())
+        m = _f64(self.hist) * self._bins("float64")
+        m = np.cumsum(m, -1) if self._numpy() else m.cumsum(-1)
+        total, moment = c[..., -1:], m[..., -1:]
+        split = c * (total - c)
+        few = (self.hist > 0).sum(-1) < 2
+        if self._numpy():
+            with np.errstate(invalid="ignore", divide="ignore"):
+                score = np.where(split > 0, (moment * c - m * total) ** 2 / split, -1.0)
+        else:
+            import torch
+
+            score = torch.where(split > 0, (moment * c - m * total) ** 2 / split, torch.full_like(split, -1.0))
+        return _f64(self._lowest_of_the_largest(score, few))
+
+
+def _region_histogram_bins(nbins, lo, width, nregions=1, what="region_histogram"):
+    """the bins of a histogram call, checked without a device; -> (nbins, lo, width) as ints"""
+    for name, v, first, last in (("nbins", nbins, 1, MAX_HISTOGRAM_BINS), ("lo", lo, 0, 65535), ("width", width, 1, 65536)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not first <= v <= last:
+            raise ValueError("%s: %s must be an int in %d..%d (got %r)" % (what, name, first, last, v))
+    if nregions is not None and int(nregions) * int(nbins) > MAX_HISTOGRAM_CELLS:
+        raise ValueError("%s: nregions * nbins must be at most 2^24 (got %d * %d)" % (what, nregions, nbins))
+    return int(nbins), int(lo), int(width)
+
+
+def _histogram_rows(rows, h, what="region_histogram"):
+    """rows None is h; -> rows as an int in 0..h"""
+    if rows is None:
+        return h
+    if isinstance(rows, bool) or not isinstance(rows, (int, np.integer)) or not 0 <= rows <= h:
+        raise ValueError("%s: rows must be an int in 0..%d (got %r)" % (what, h, rows))
+    return int(rows)
+
+
+def _region_histogram_args(frames_shape, labels_shape, nbins, lo=0, width=1, nregions=None, rows=None, what="region_histogram"):
+    """the shapes and bins of a region_histogram call, checked without a device; labels_shape None: no map, one region.
+    -> (n, h, w, labels_per_frame, nbins, lo, width, rows).  nregions None is left to the caller."""
+    if labels_shape is None:
+        if nregions not in (None, 1):
+            raise ValueError("%s: without labels there is one region (got nregions %r)" % (what, nregions))
+        nregions = 1
+        n, h, w, per_frame = _region_stats_args(frames_shape, tuple(frames_shape)[-2:], nregions, what)
+    else:
+        n, h, w, per_frame = _region_stats_args(frames_shape, labels_shape, nregions, what, MAX_HISTOGRAM_REGIONS)
+    nbins, lo, width = _region_histogram_bins(nbins, lo, width, nregions, what)
+    return n, h, w, per_frame, nbins, lo, width, _histogram_rows(rows, h, what)
+
+
+def region_histogram(images, labels, nbins, lo=0, width=1, nregions=None, rows=None):
+    """Extension: histograms of a uint16 stack ``images[n][h][w]`` (or one ``(h, w)`` image) over the regions of the int32 label map
+    ``labels`` (``(h, w)`` shared by every image, or ``(n, h, w)``; None: the whole image is region 0), ``nbins`` bins of ``width``
+    levels from ``lo``: a ``RegionHistogram`` of numpy arrays (``rir_region_histogram``).  Only the first ``rows`` rows of every image
+    and map are counted (None: all).  Labels outside [0, nregions) are ignored; ``nregions=None`` takes labels.max() + 1 (at least 1); at
+    most 65 536 regions and bins, nregions * nbins at most 2^24.  ``ValueError`` on bad shapes, bins, rows or ``nregions``,
+    ``RuntimeError`` on other dtypes and when the library fails."""
+    img = np.ascontiguousarray(images)
+    lab = None if labels is None else np.ascontiguousarray(labels)
+    if img.dtype != np.uint16:
+        raise RuntimeError("region_histogram: uint16 images expected, not %s" % img.dtype)
+    if lab is not None and lab.dtype != np.int32:
+        raise RuntimeError("region_histogram: int32 labels expected, not %s" % lab.dtype)
+    shapes = (img.shape, None if lab is None else lab.shape)
+    n, h, w, per_frame, nbins, lo, width, rows = _region_histogram_args(*shapes, nbins, lo, width, nregions, rows)
+    if nregions is None:
+        nregions = 1 if lab is None else max(1, int(lab.max()) + 1 if lab.size else 1)
+        _region_histogram_args(*shapes, nbins, lo, width, nregions, rows)
+    k = int(nregions)
+    out = RegionHistogram(np.zeros((n, k), np.int32), np.zeros((n, k, nbins), np.int32), np.zeros((n, k, 2), np.int32), lo, width)
+    if n and _sp.rir_region_histogram(img.ctypes.data, None if lab is None else lab.ctypes.data, w, h, rows, n, per_frame, k, lo, width, nbins,
+                                      out.count.ctypes.data, out.hist.ctypes.data, out.outside.ctypes.data) < 0:
+        raise RuntimeError("An error occured while calling 'region_histogram': " + (last_error() or ""))
+    return out
+
+
 # ---- extension: per-pixel statistics over time ----------------------------------------------------------------------------------
 _sp.rir_pixel_stats.argtypes = [ct.c_void_p] + [ct.c_int] * 3 + [ct.c_void_p] * 6
 

@@ -436,6 +436,56 @@ class IRMovie(object):
             _region_quantiles_into(fr, lab, 0, int(nregions), pc, type(out)(*(t[k0:k0 + len(sel)] for t in out)))
         return out
 
+    def region_histogram(self, labels, nbins, lo=0, width=1, selection=slice(None), nregions=None, rows=None):
+        """Histograms of the images of ``selection`` over the regions of one int32 label map ``labels`` (h, w), numpy or CUDA (None: the
+        whole image is region 0), ``nbins`` bins of ``width`` levels from ``lo`` over the first ``rows`` rows (None: all) - what
+        ``librir_amd.device.region_histogram`` over the images ``movie[selection]`` gives (read-back filters applied): a
+        ``RegionHistogram`` of CUDA tensors, count ``[len(selection)][nregions]``, hist ``[..][nbins]`` and outside ``[..][2]``.  Labels,
+        selection, ``nregions`` and the pieces the recording is read in are those of ``region_stats``."""
+        import torch
+
+        from ..device import _region_histogram_empty, _region_histogram_inputs, _region_histogram_into
+
+        h, w = self.image_size
+        what = "region_histogram" if labels is not None else "histogram"
+        if isinstance(labels, np.ndarray):
+            if labels.dtype != np.int32:
+                raise RuntimeError("region_histogram: int32 labels expected, not %s" % labels.dtype)
+            labels = torch.from_numpy(np.ascontiguousarray(labels)).to(torch.device("cuda", torch.cuda.current_device()))
+        if labels is not None and labels.dim() != 2:
+            raise ValueError("region_histogram: one label map (h, w) expected, not shape %s" % (tuple(labels.shape),))
+        device = labels.device if labels is not None else torch.device("cuda", torch.cuda.current_device())
+        probe = torch.empty((0, h, w), dtype=torch.uint16, device=device)
+        if labels is None:
+            nregions = 1
+        _, lab, _, _, _, _, nbins, lo, width, rows = _region_histogram_inputs(probe, labels, nbins, lo, width, nregions, rows, what)
+        if nregions is None:
+            nregions = max(1, int(lab.max()) + 1)
+            _region_histogram_inputs(probe, labels, nbins, lo, width, nregions, rows, what)
+        positions = self._stats_positions(selection, what)
+        out = _region_histogram_empty(len(positions), int(nregions), nbins, lo, width, device)
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=device)
+        for k0 in range(0, len(positions), per_piece):
+            sel = positions[k0:k0 + per_piece]
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            _region_histogram_into(fr, lab, 0, int(nregions), rows, type(out)(*(t[k0:k0 + len(sel)] for t in out[:3]), lo, width))
+        return out
+
+    def histogram(self, nbins, lo=0, width=1, selection=slice(None), rows=None):
+        """``region_histogram`` without a map: the whole image (its first ``rows`` rows) is region 0 - what
+        ``librir_amd.device.histogram`` over the images ``movie[selection]`` gives."""
+        return self.region_histogram(None, nbins, lo, width, selection, 1, rows)
+
+    def background_levels(self, selection=slice(None), rows=None):
+        """The background level of every image of ``selection`` as the bounded-loss recorder defines it (reference ``get_background``,
+        h264.cpp:1955-1990): of the 16 384 bins of v >> 2 the first of the fullest, as the level ``(bin << 2) + 1`` - an int32 CUDA tensor
+        ``[len(selection)]``; -1 * 4 + 1 = -3 for an image without counted pixels (``rows`` 0)."""
+        import torch
+
+        return (self.histogram(16384, 0, 4, selection, rows).mode()[:, 0] * 4 + 1).to(torch.int32)
+
     def polygon_stats(self, polygons, selection=slice(None), shifts=None, values=None):
         """Statistics of the images of ``selection`` (as ``region_stats`` takes it) over polygon regions of interest
         (``librir_amd.device.polygon_map`` takes ``polygons`` and ``values`` the same way): a ``RegionStats`` of CUDA tensors
