@@ -1,7 +1,8 @@
-"""GPU: the walk over labelled pixels that region_stats, region_geometry and region_quantiles share (csrc/region_walk.h), at its own
-boundaries - item and step edges, the pixel-by-pixel loads, label changes at every offset of a thread's 8 pixels, the wave-wide flush on
-both sides of geometry's threshold, labels outside the range at a flush - in both forms of each reducer.  Every reducer runs on the same
-inputs, bit for bit against its oracle."""
+"""GPU: the two walks over labelled pixels of csrc/region_walk.h at their own boundaries - walk_regions, which region_stats and
+region_geometry share, and walk_counters, which region_quantiles, region_histogram and histogram share: item and step edges, the
+pixel-by-pixel loads, label changes at every offset of a thread's 8 pixels, the wave-wide flush on both sides of geometry's threshold,
+labels outside the range at a flush - in both forms of each reducer.  Every reducer runs on the same inputs, bit for bit against its
+oracle; the histogram also without a map, on the same frames, and over the map of zeros that is its twin."""
 import os
 import re
 
@@ -9,6 +10,7 @@ import numpy as np
 import pytest
 
 from test_region_geometry_cpu import FIELDS as GEOMETRY_FIELDS, region_geometry_oracle
+from test_region_histogram_cpu import region_histogram_oracle
 from test_region_quantiles_cpu import region_quantiles_oracle
 from test_region_stats_cpu import FIELDS as STATS_FIELDS, region_stats_oracle
 
@@ -22,6 +24,8 @@ with open(os.path.join(ROOT, "librir_amd", "csrc", "quantile_kernels.h")) as _f:
 # it from 22 regions), of geometry (geometry_kernels.h GEOMETRY_LDS_MAX) and of statistics (region_kernels.h REGION_LDS_MAX)
 GLOBAL_FORMS = (QUANTILE_LDS_MAX + 1, 2 * QUANTILE_LDS_MAX + 1, 1024 + 1, 4096 + 1)
 PERCENTS = (0.0, 0.5, 1.0)
+BINNINGS = ((0, 256, 256), (1, 7, 255))
+HISTOGRAM_FIELDS = ("count", "hist", "outside")
 N = 2
 INT32_MIN = -(2 ** 31)
 STEP = 2048  # pixels per workgroup and step: 256 threads x 8 pixels; an item is 8 steps
@@ -57,8 +61,9 @@ def same(fields, got, exp, what):
 
 
 def all_reducers(frames, labels, ks=(3,), what="", tensors=None):
-    """statistics, geometry (weighted and labels only) and quantiles of `frames` over `labels` with k regions, for every k, against the
-    oracles; tensors: the (frames, labels) device tensors to pass, where a test made its own"""
+    """statistics, geometry (weighted and labels only), quantiles and histograms of `frames` over `labels` with k regions, for every k,
+    against the oracles, and the histograms of `frames` without a map and over a map of zeros; tensors: the (frames, labels) device tensors
+    to pass, where a test made its own"""
     from librir_amd import device as D
 
     f, lab = tensors if tensors is not None else (dev16(frames), dev32(labels))
@@ -68,6 +73,14 @@ def all_reducers(frames, labels, ks=(3,), what="", tensors=None):
         same(GEOMETRY_FIELDS, D.region_geometry(lab, k), region_geometry_oracle(labels, k), (what, k, "geometry, labels only"))
         exp = dict(zip(("count", "values"), region_quantiles_oracle(frames, labels, k, PERCENTS)))
         same(("count", "values"), D.region_quantiles(f, lab, PERCENTS, k), exp, (what, k, "quantiles"))
+        for lo, width, nbins in BINNINGS:
+            exp = dict(zip(HISTOGRAM_FIELDS, region_histogram_oracle(frames, labels, k, lo, width, nbins)))
+            same(HISTOGRAM_FIELDS, D.region_histogram(f, lab, nbins, lo, width, k)[:3], exp, (what, k, "histogram", lo, width, nbins))
+    zeros = torch.zeros(tuple(f.shape[-2:]), dtype=torch.int32, device="cuda")
+    for lo, width, nbins in BINNINGS:
+        exp = dict(zip(HISTOGRAM_FIELDS, region_histogram_oracle(frames, None, 1, lo, width, nbins)))
+        same(HISTOGRAM_FIELDS, D.histogram(f, nbins, lo, width)[:3], exp, (what, "histogram, no map", lo, width, nbins))
+        same(HISTOGRAM_FIELDS, D.region_histogram(f, zeros, nbins, lo, width, 1)[:3], exp, (what, "histogram, a map of zeros", lo, width, nbins))
 
 
 @pytest.mark.parametrize("h,w", [(127, 129), (128, 128), (5, 3277), (3, 10923), (1, 2047), (1, 2048), (1, 2049), (8, 257)])
