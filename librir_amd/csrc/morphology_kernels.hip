@@ -7,9 +7,8 @@
 // outside the image is neutral for whichever stage looks at it - for the SECOND stage too, where the first stage's value at such a
 // position (a min / max over the clamped part of a window that has no centre) must not be seen.
 //
-//   morph_wave_kernel<T, R, OP>  squares 3x3, 5x5, 7x7 on frames of even width: the wave-tile scheme of wave_tile.h with TWO columns
-//                                per lane - a dword of two uint16 pixels (two uint8 pixels widened on load) - so every load, store and
-//                                min / max works on a pair (v_pk_min_u16 / v_pk_max_u16); no LDS, no barrier.
+//   morph_wave_kernel<T, R, OP>  squares 3x3, 5x5, 7x7 on frames of even width: the pair tile of pair_tile.h, two columns per lane in
+//                                registers.
 //   morph_tile_kernel<T, RMAX>   every other size and every odd width: a workgroup tile with its halo in LDS, a row pass and a column pass
 //                                per stage, radii as run-time bounds (<= RMAX = 1, 3, 5 or 7) clipped to the image.
 //
@@ -21,17 +20,16 @@
 #include <algorithm>
 
 #include "morphology_kernels.h"
-#include "wave_tile.h"
+#include "pair_tile.h"
 
 namespace rir
 {
 	constexpr bool morph_two_stages(int op) { return op == MORPH_OPEN || op == MORPH_CLOSE || op == MORPH_TOPHAT || op == MORPH_BLACKHAT; }
 
 	// ---- squares 3, 5, 7: two columns per lane, in registers ------------------------------------------------------------------------------
-	// A wave owns 128 columns x (TY + 2 HALO) rows, lane i the column pair (x0 + 2i, x0 + 2i + 1) as one dword per row - the frame read as
-	// an image of w / 2 dwords through load_column, which gives 0 for every pair outside the image (w is even: a pair is inside or outside
-	// as a whole).  A stage is a vertical min / max over 2R + 1 registers, then a horizontal one over the pairs shifted by -R .. R pixels:
-	// an even shift is the neighbouring lane's pair (DPP wave shift), an odd one two neighbouring pairs funnel-shifted by 16 bits.
+	// A wave's pair tile (pair_tile.h) is loaded with HALO rows above and below - the frame read as an image of w / 2 dwords through
+	// load_column, which gives 0 for every pair outside the image (w is even: a pair is inside or outside as a whole).  A stage is a vertical
+	// min / max over 2R + 1 registers, then a horizontal one over the pairs shifted by -R .. R pixels.
 	// HALO = R (one stage) or 2R (two) pixels on every side; the outer ceil(HALO / 2) lanes of each side have no output.
 	// Stores are plain, not streaming: a tile row is 248 / 240 / 232 bytes, so neighbouring tiles share 128-byte lines, which the default
 	// policy completes in L2 (with the streaming policy every partial line goes to memory on its own: see the fused chain's store policy).
@@ -39,18 +37,6 @@ namespace rir
 
 	constexpr int morph_halo(int r, int op) { return morph_two_stages(op) ? 2 * r : r; }
 	constexpr int morph_halo_lanes(int r, int op) { return (morph_halo(r, op) + 1) / 2; }
-
-	typedef unsigned short v2u16 __attribute__((ext_vector_type(2)));
-	template <bool MAX>
-	__device__ __forceinline__ uint32_t pk_pick(uint32_t a, uint32_t b)
-	{
-		const v2u16 x = __builtin_bit_cast(v2u16, a), y = __builtin_bit_cast(v2u16, b);
-		return __builtin_bit_cast(uint32_t, MAX ? __builtin_elementwise_max(x, y) : __builtin_elementwise_min(x, y));
-	}
-	__device__ __forceinline__ uint32_t pk_sub(uint32_t a, uint32_t b)
-	{
-		return __builtin_bit_cast(uint32_t, (v2u16)(__builtin_bit_cast(v2u16, a) - __builtin_bit_cast(v2u16, b)));
-	}
 
 	// one flat (2R + 1)^2 stage: N rows of pairs in, N - 2R rows out (all 64 lanes take part in the shifts; what is shifted in at the wave's
 	// ends only ever reaches halo lanes)
@@ -65,14 +51,13 @@ namespace rir
 			for (int d = 1; d <= 2 * R; ++d)
 				c = pk_pick<MAX>(c, a[j + d]);
 			const uint32_t prev = wave_shr1(c), next = wave_shl1(c); // columns (x - 2, x - 1) and (x + 2, x + 3)
-			// shifted by -1: (x - 1, x); by +1: (x + 1, x + 2)
-			uint32_t m = pk_pick<MAX>(c, pk_pick<MAX>(__builtin_amdgcn_alignbit(c, prev, 16), __builtin_amdgcn_alignbit(next, c, 16)));
+			uint32_t m = pk_pick<MAX>(c, pk_pick<MAX>(left_pair(c, prev), right_pair(c, next)));
 			if constexpr (R >= 2)
 				m = pk_pick<MAX>(m, pk_pick<MAX>(prev, next));
 			if constexpr (R >= 3)
 			{
 				const uint32_t prev2 = wave_shr1(prev), next2 = wave_shl1(next);
-				m = pk_pick<MAX>(m, pk_pick<MAX>(__builtin_amdgcn_alignbit(prev, prev2, 16), __builtin_amdgcn_alignbit(next2, next, 16)));
+				m = pk_pick<MAX>(m, pk_pick<MAX>(left_pair(prev, prev2), right_pair(next, next2)));
 			}
 			o[j] = m;
 		}
@@ -87,51 +72,31 @@ namespace rir
 			a[i] = (xin && ytop + i >= 0 && ytop + i < rows) ? a[i] : fill;
 	}
 
-	template <class T>
-	struct PairOf;
-	template <>
-	struct PairOf<uint16_t>
-	{
-		typedef uint32_t type;
-		__device__ static uint32_t widen(uint32_t raw) { return raw; }
-		__device__ static uint32_t narrow(uint32_t v) { return v; }
-	};
-	template <>
-	struct PairOf<uint8_t>
-	{
-		typedef uint16_t type;
-		__device__ static uint32_t widen(uint32_t raw) { return (raw | (raw << 8)) & 0x00ff00ffu; }
-		__device__ static uint16_t narrow(uint32_t v) { return (uint16_t)((v & 0xffu) | ((v >> 8) & 0xff00u)); }
-	};
-
 	template <class T, int R, int OP>
 	__global__ __launch_bounds__(256) void morph_wave_kernel(const T *__restrict__ src, T *__restrict__ dst, int w, int h, int rows)
 	{
-		typedef typename PairOf<T>::type P;
-		constexpr int TY = MORPH_TY, HALO = morph_halo(R, OP), HL = morph_halo_lanes(R, OP), OUTL = 64 - 2 * HL, NR = TY + 2 * HALO;
+		constexpr int TY = MORPH_TY, HALO = morph_halo(R, OP), HL = morph_halo_lanes(R, OP), NR = TY + 2 * HALO;
 		constexpr uint32_t TOP = 0xffffffffu; // above every pixel of a pair: neutral for a min
+		typedef typename PixelPair<T>::type P;
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-		const TileId id = tile_decode<true>(); // (tile rows are not line-aligned)
-		const int wp = w >> 1;				   // pairs per row
-		const int xp0 = id.bx * OUTL - HL, xp = xp0 + lane;
-		const int y0 = (id.by * 4 + wv) * TY;
+		const PairTile<T, TY, HL> t(lane, wv, w);
+		const int y0 = t.y0;
 		if (y0 >= h)
 			return;
-		const int64_t fbase = (int64_t)id.n * w * h;
-		const P *s = reinterpret_cast<const P *>(src + fbase);
-		P *d = reinterpret_cast<P *>(dst + fbase);
-		const bool xin = xp >= 0 && xp < wp;
-		const bool out_lane = lane >= HL && lane < 64 - HL && xp < wp;
+		const P *s = t.frame(src, w, h);
+		P *d = t.frame(dst, w, h);
+		const bool xin = t.xp >= 0 && t.xp < t.wp;
+		const bool out_lane = lane >= HL && lane < 64 - HL && t.xp < t.wp;
 		if (y0 < rows)
 		{
 			raw_px_t<P> raw[NR];
 			// (the image is the first `rows` rows: what lies below reads as outside)
-			const bool inside = load_column<NR, P, true, true>(s, wp, rows, xp0, lane, y0 - HALO, raw);
+			const bool inside = load_column<NR, P, true, true>(s, t.wp, rows, t.xp0, lane, y0 - HALO, raw);
 			uint32_t v[NR]; // 0 outside the image: neutral for a max
 #pragma unroll
 			for (int i = 0; i < NR; ++i)
-				v[i] = PairOf<T>::widen(raw[i]);
+				v[i] = PixelPair<T>::widen(raw[i]);
 			uint32_t res[TY];
 			if constexpr (OP == MORPH_DILATE)
 				morph_stage<true, R, NR>(v, res);
@@ -176,17 +141,9 @@ namespace rir
 						res[j] = pk_sub(res[j], v[j + HALO]);
 				}
 			}
-			if (out_lane)
-			{
-#pragma unroll
-				for (int j = 0; j < TY; ++j)
-					if (y0 + j < rows)
-						d[(int64_t)(y0 + j) * wp + xp] = PairOf<T>::narrow(res[j]);
-			}
+			t.store(d, res, rows, out_lane);
 		}
-		if (out_lane)
-			for (int y = max(y0, rows); y < min(y0 + TY, h); ++y)
-				d[(int64_t)y * wp + xp] = s[(int64_t)y * wp + xp];
+		t.copy_rest(s, d, h, rows, out_lane);
 	}
 
 	// ---- every other size: a workgroup tile in LDS ------------------------------------------------------------------------------------
@@ -303,10 +260,10 @@ namespace rir
 			// the loads of a thread are in flight together - under a condition each of them waits for the one before)
 			for (int c = tid & 63; c < g.rw; c += 64)
 			{
-				const T *col = s + min(max(g.gx0 + c, 0), w - 1);
+				const T *col = s + nearest(g.gx0 + c, w);
 #pragma unroll 8
 				for (int r = tid >> 6; r < g.rh; r += 4)
-					A[r * g.rw + c] = (uint16_t)col[(int64_t)min(max(g.gy0 + r, 0), rows - 1) * w];
+					A[r * g.rw + c] = (uint16_t)col[(int64_t)nearest(g.gy0 + r, rows) * w];
 			}
 			__syncthreads();
 			uint16_t *first;
@@ -357,15 +314,11 @@ namespace rir
 	}
 
 	// ---- launchers ---------------------------------------------------------------------------------------------------------------------
-	constexpr int MAX_GRID_Z = 65535;
-
 	template <class T, int R, int OP>
 	static void launch_wave(const T *src, T *dst, int w, int h, int nframes, int rows, hipStream_t st)
 	{
-		constexpr int OUTL = 64 - 2 * morph_halo_lanes(R, OP);
-		const int wp = w / 2;
-		dim3 block(256), grid((unsigned)((wp + OUTL - 1) / OUTL), (unsigned)((h + 4 * MORPH_TY - 1) / (4 * MORPH_TY)), (unsigned)nframes);
-		hipLaunchKernelGGL((morph_wave_kernel<T, R, OP>), grid, block, 0, st, src, dst, w, h, rows);
+		hipLaunchKernelGGL((morph_wave_kernel<T, R, OP>), (pair_wave_grid<MORPH_TY, morph_halo_lanes(R, OP)>(w / 2, h, nframes)), dim3(256), 0, st, src, dst, w,
+						   h, rows);
 	}
 	template <class T, int R>
 	static void launch_wave_op(const T *src, T *dst, int w, int h, int nframes, int op, int rows, hipStream_t st)
@@ -393,14 +346,8 @@ namespace rir
 	static hipError_t launch_morphology_t(const T *src, T *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows, hipStream_t st)
 	{
 		// the pair kernel: a square 3, 5 or 7 on rows of whole, aligned pairs
-		const bool pairs = size_x == size_y && size_x >= 3 && size_x <= 7 && (w & 1) == 0 &&
-						   (((uintptr_t)src | (uintptr_t)dst) & (2 * sizeof(T) - 1)) == 0;
-		const int64_t frame = (int64_t)w * h;
-		for (int f0 = 0; f0 < nframes; f0 += MAX_GRID_Z)
-		{
-			const int n = std::min(MAX_GRID_Z, nframes - f0);
-			const T *s = src + frame * f0;
-			T *d = dst + frame * f0;
+		const bool pairs = size_x == size_y && size_x >= 3 && size_x <= 7 && rows_of_pairs(src, dst, w);
+		return for_frame_chunks(src, dst, w, h, nframes, [=](const T *s, T *d, int n) {
 			if (pairs && size_x == 3)
 				launch_wave_op<T, 1>(s, d, w, h, n, op, rows, st);
 			else if (pairs && size_x == 5)
@@ -421,11 +368,7 @@ namespace rir
 				else
 					hipLaunchKernelGGL((morph_tile_kernel<T, 7>), grid, block, lds, st, s, d, w, h, rows, op, rx, ry);
 			}
-			const hipError_t e = hipGetLastError();
-			if (e != hipSuccess)
-				return e;
-		}
-		return hipSuccess;
+		});
 	}
 
 	hipError_t launch_morphology(int type, const void *src, void *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows,
@@ -433,15 +376,7 @@ namespace rir
 	{
 		if (op < 0 || op >= MORPH_OPS)
 			return hipErrorInvalidValue;
-		switch (type)
-		{
-		case 'H':
-			return launch_morphology_t<uint16_t>((const uint16_t *)src, (uint16_t *)dst, w, h, nframes, op, size_x, size_y, rows, st);
-		case 'B':
-		case '?': // (0 / 1 bytes: min, max and the differences of bytes are those of bools)
-			return launch_morphology_t<uint8_t>((const uint8_t *)src, (uint8_t *)dst, w, h, nframes, op, size_x, size_y, rows, st);
-		default:
-			return hipErrorInvalidValue;
-		}
+		// (bool frames as bytes: min, max and the differences of 0 / 1 bytes are those of bools)
+		return with_pixel_type(type, src, dst, [=](auto *s, auto *d) { return launch_morphology_t(s, d, w, h, nframes, op, size_x, size_y, rows, st); });
 	}
 } // namespace rir

@@ -7,9 +7,8 @@
 // shrinks its window along the border, the morphology unit clips it (which for a min or a max is the same as replicating, so ranks 0 and
 // n - 1 are handed to launch_morphology; there is no third min / max kernel).
 //
-//   rank_median_wave_kernel<T, R>  the medians of 3x3 and 5x5 on frames of even width: the wave-tile scheme of wave_tile.h with two columns
-//                                  per lane (a dword of two uint16 pixels, two uint8 pixels widened on load), so every load, store and
-//                                  min / max works on a pair (v_pk_min_u16 / v_pk_max_u16); no LDS, no barrier.
+//   rank_median_wave_kernel<T, R>  the medians of 3x3 and 5x5 on frames of even width: the pair tile of pair_tile.h, two columns per lane
+//                                  in registers.
 //   rank_tile_kernel<T, RY>        every other size and rank, and every odd width: a workgroup tile with its halo in LDS, as bit planes;
 //                                  each thread selects the values of 8 outputs by a binary search on the value, counting the window's
 //                                  cells below the candidate a window row at a time.
@@ -22,63 +21,30 @@
 #include <algorithm>
 
 #include "morphology_kernels.h"
+#include "pair_tile.h"
 #include "rank_kernels.h"
 #include "rank_select.h"
-#include "wave_tile.h"
 
 namespace rir
 {
 	// ---- medians of 3x3 and 5x5: two columns per lane, in registers ------------------------------------------------------------------------
-	// A wave owns 124 columns x TY rows, lane i the column pair (x0 + 2i, x0 + 2i + 1) as one dword per row; the outer lane of each side has
-	// no output.  Neighbouring columns come from the neighbouring lanes: an even shift is the next lane's pair (DPP wave shift), an odd one
-	// two neighbouring pairs funnel-shifted by 16 bits.
+	// A wave's pair tile (pair_tile.h) with one halo lane on each side: 2 pixels, enough for 3x3 and 5x5.
 	//   3x3: each column triple is sorted once (min, median, max of 3); the median of 9 is med3(max of the three column minima, median of the
 	//        three column medians, min of the three column maxima), as in median3x3_kernel - on pairs, 30 instructions per pair.
 	//   5x5: the five shifted copies of every loaded row are kept (5 x (TY + 4) registers); the 25 values of an output go through the
 	//        selection network of rank_select.h, 129 exchanges = 258 packed instructions per pair.
-	typedef unsigned short rank_v2u16 __attribute__((ext_vector_type(2)));
-	struct PackedPairOps
-	{
-		__device__ static __forceinline__ uint32_t lo(uint32_t a, uint32_t b)
-		{
-			return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(rank_v2u16, a), __builtin_bit_cast(rank_v2u16, b)));
-		}
-		__device__ static __forceinline__ uint32_t hi(uint32_t a, uint32_t b)
-		{
-			return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(rank_v2u16, a), __builtin_bit_cast(rank_v2u16, b)));
-		}
-	};
-
-	// a pair of pixels in memory, and as two uint16 halves of a dword
-	template <class T>
-	struct RankPair;
-	template <>
-	struct RankPair<uint16_t>
-	{
-		typedef uint32_t type;
-		__device__ static uint32_t widen(uint32_t raw) { return raw; }
-		__device__ static uint32_t narrow(uint32_t v) { return v; }
-	};
-	template <>
-	struct RankPair<uint8_t>
-	{
-		typedef uint16_t type;
-		__device__ static uint32_t widen(uint32_t raw) { return (raw | (raw << 8)) & 0x00ff00ffu; }
-		__device__ static uint16_t narrow(uint32_t v) { return (uint16_t)((v & 0xffu) | ((v >> 8) & 0xff00u)); }
-	};
-
 	// A lane's pair column with REPLICATED borders: v[i] = the pixels (2 xp, 2 xp + 1) of row ytop + i of an image of wp pairs x rows rows,
 	// every coordinate clamped into the image - a pair left of the image is the first pixel of the row twice, a pair right of it the last
 	// pixel twice.  The loads are unconditional, at clamped addresses (the shape of load_column's branch for frames of 2 GiB and more), and
 	// all in flight together; the row offsets are wave-uniform.  x_edge (wave-uniform): some lane of the wave lies outside the image.
 	template <int NR, class T>
-	__device__ __forceinline__ void load_pairs_replicated(const typename RankPair<T>::type *__restrict__ s, int wp, int rows, int xp, int ytop, bool x_edge,
+	__device__ __forceinline__ void load_pairs_replicated(const typename PixelPair<T>::type *__restrict__ s, int wp, int rows, int xp, int ytop, bool x_edge,
 														  uint32_t (&v)[NR])
 	{
-		const typename RankPair<T>::type *col = s + min(max(xp, 0), wp - 1);
+		const typename PixelPair<T>::type *col = s + nearest(xp, wp);
 #pragma unroll
 		for (int i = 0; i < NR; ++i)
-			v[i] = RankPair<T>::widen(col[(int64_t)min(max(ytop + i, 0), rows - 1) * wp]);
+			v[i] = PixelPair<T>::widen(col[(int64_t)nearest(ytop + i, rows) * wp]);
 		if (x_edge)
 		{
 #pragma unroll
@@ -87,39 +53,27 @@ namespace rir
 		}
 	}
 
-	// the pairs one pixel to the left and to the right of c = (x, x + 1): (x - 1, x) and (x + 1, x + 2); prev = (x - 2, x - 1), next = (x + 2, x + 3)
-	__device__ __forceinline__ void odd_shifts(uint32_t c, uint32_t prev, uint32_t next, uint32_t &left, uint32_t &right)
-	{
-		left = __builtin_amdgcn_alignbit(c, prev, 16);
-		right = __builtin_amdgcn_alignbit(next, c, 16);
-	}
-
-	constexpr int RANK_OUT_LANES = 62; // one halo lane on each side: 2 pixels, enough for 3x3 and 5x5
 	constexpr int rank_wave_ty(int r) { return r == 1 ? 16 : 8; }
 
 	template <class T, int R>
 	__global__ __launch_bounds__(256) void rank_median_wave_kernel(const T *__restrict__ src, T *__restrict__ dst, int w, int h, int rows)
 	{
 		static_assert(R == 1 || R == 2, "3x3 or 5x5");
-		typedef typename RankPair<T>::type P;
-		typedef PackedPairOps O;
+		typedef PackedPair O;
 		constexpr int TY = rank_wave_ty(R), NR = TY + 2 * R;
+		typedef typename PixelPair<T>::type P;
 		const int lane = threadIdx.x & 63;
 		const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-		const TileId id = tile_decode<true>(); // (tile rows are not line-aligned)
-		const int wp = w >> 1;				   // pairs per row
-		const int xp0 = id.bx * RANK_OUT_LANES - 1, xp = xp0 + lane;
-		const int y0 = (id.by * 4 + wv) * TY;
-		if (y0 >= h)
+		const PairTile<T, TY, 1> t(lane, wv, w);
+		if (t.y0 >= h)
 			return;
-		const int64_t fbase = (int64_t)id.n * w * h;
-		const P *s = reinterpret_cast<const P *>(src + fbase);
-		P *d = reinterpret_cast<P *>(dst + fbase);
-		const bool out_lane = lane >= 1 && lane <= RANK_OUT_LANES && xp < wp;
-		if (y0 < rows)
+		const P *s = t.frame(src, w, h);
+		P *d = t.frame(dst, w, h);
+		const bool out_lane = lane >= 1 && lane < 63 && t.xp < t.wp;
+		if (t.y0 < rows)
 		{
 			uint32_t v[NR], res[TY];
-			load_pairs_replicated<NR, T>(s, wp, rows, xp, y0 - R, xp0 < 0 || xp0 + 63 >= wp, v);
+			load_pairs_replicated<NR, T>(s, t.wp, rows, t.xp, t.y0 - R, t.xp0 < 0 || t.xp0 + 63 >= t.wp, v);
 			// (all 64 lanes take part in the shifts; what is shifted in at the wave's ends only ever reaches the two halo lanes)
 			if constexpr (R == 1)
 			{
@@ -128,10 +82,9 @@ namespace rir
 				{
 					const uint32_t ab_lo = O::lo(v[j], v[j + 1]), ab_hi = O::hi(v[j], v[j + 1]);
 					const uint32_t lo = O::lo(ab_lo, v[j + 2]), hi = O::hi(ab_hi, v[j + 2]), mi = O::hi(ab_lo, O::lo(ab_hi, v[j + 2]));
-					uint32_t lo_l, lo_r, mi_l, mi_r, hi_l, hi_r;
-					odd_shifts(lo, wave_shr1(lo), wave_shl1(lo), lo_l, lo_r);
-					odd_shifts(mi, wave_shr1(mi), wave_shl1(mi), mi_l, mi_r);
-					odd_shifts(hi, wave_shr1(hi), wave_shl1(hi), hi_l, hi_r);
+					const uint32_t lo_l = left_pair(lo, wave_shr1(lo)), lo_r = right_pair(lo, wave_shl1(lo));
+					const uint32_t mi_l = left_pair(mi, wave_shr1(mi)), mi_r = right_pair(mi, wave_shl1(mi));
+					const uint32_t hi_l = left_pair(hi, wave_shr1(hi)), hi_r = right_pair(hi, wave_shl1(hi));
 					res[j] = rank_med3<O>(O::hi(O::hi(lo_l, lo), lo_r), rank_med3<O>(mi_l, mi, mi_r), O::lo(O::lo(hi_l, hi), hi_r));
 				}
 			}
@@ -144,7 +97,8 @@ namespace rir
 					a[2][i] = v[i];
 					a[0][i] = wave_shr1(v[i]);
 					a[4][i] = wave_shl1(v[i]);
-					odd_shifts(v[i], a[0][i], a[4][i], a[1][i], a[3][i]);
+					a[1][i] = left_pair(v[i], a[0][i]);
+					a[3][i] = right_pair(v[i], a[4][i]);
 				}
 #pragma unroll
 				for (int j = 0; j < TY; ++j)
@@ -158,24 +112,16 @@ namespace rir
 					res[j] = rank_median<O, 25>(in);
 				}
 			}
-			if (out_lane)
-			{
-#pragma unroll
-				for (int j = 0; j < TY; ++j)
-					if (y0 + j < rows)
-						d[(int64_t)(y0 + j) * wp + xp] = RankPair<T>::narrow(res[j]);
-			}
+			t.store(d, res, rows, out_lane);
 		}
-		if (out_lane)
-			for (int y = max(y0, rows); y < min(y0 + TY, h); ++y)
-				d[(int64_t)y * wp + xp] = s[(int64_t)y * wp + xp];
+		t.copy_rest(s, d, h, rows, out_lane);
 	}
 
 	// ---- every other size and rank: a workgroup tile in LDS, as bit planes --------------------------------------------------------------
 	// A workgroup owns RT_TW x RT_TH outputs and loads them with a halo of (size_x / 2, size_y / 2), each cell from the nearest pixel of the
-	// image - morph_tile_kernel's clamped loader, whose cells are here what the definition asks for: unconditional loads, all of a wave's in
-	// flight together.  The cells are not kept: a wave turns each row of 64 cells into one 64-bit mask per value bit (a compare across the
-	// wave is that mask), so LDS holds the region as bit PLANES - plane b, row r: RT_WORDS dwords, bit x = bit b of the cell at column x.
+	// image (pair_tile.h's nearest(), as in morph_tile_kernel's loader, whose cells are here what the definition asks for): unconditional
+	// loads, all of a wave's in flight together.  The cells are not kept: a wave turns each row of 64 cells into one 64-bit mask per value
+	// bit (a compare across the wave is that mask), so LDS holds the region as bit PLANES - plane b, row r: RT_WORDS dwords, bit x = bit b of the cell at column x.
 	// A thread then finds the values of its outputs by a binary search on the value, most significant bit first.  With c = v | bit, the bit
 	// is set exactly when at most `rank` cells of the window lie below c; those are the `below` cells known to lie below v's prefix plus,
 	// among the cells whose higher bits equal that prefix (the candidates, a mask of size_x bits per window row), the ones whose bit b is 0.
@@ -208,13 +154,13 @@ namespace rir
 		if (y0 < rows) // (the same for the whole workgroup)
 		{
 			// region row r = wv + 4 i of this wave: columns `lane` and 64 + `lane` (the second one a halo column for the first lanes only)
-			const int xa = min(max(x0 - rx + lane, 0), w - 1), xb = min(max(x0 - rx + 64 + lane, 0), w - 1);
+			const int xa = nearest(x0 - rx + lane, w), xb = nearest(x0 - rx + 64 + lane, w);
 			const bool second = lane < 2 * rx;
 			uint32_t a[LR], bq[LR];
 #pragma unroll
 			for (int i = 0; i < LR; ++i)
 			{
-				const T *row = s + (int64_t)min(max(y0 - RY + wv + 4 * i, 0), rows - 1) * w;
+				const T *row = s + (int64_t)nearest(y0 - RY + wv + 4 * i, rows) * w;
 				a[i] = row[xa];
 				bq[i] = row[xb];
 			}
@@ -289,15 +235,10 @@ namespace rir
 	}
 
 	// ---- launchers ---------------------------------------------------------------------------------------------------------------------
-	constexpr int RANK_MAX_GRID_Z = 65535;
-
 	template <class T, int R>
 	static void launch_median_wave(const T *src, T *dst, int w, int h, int n, int rows, hipStream_t st)
 	{
-		constexpr int TY = rank_wave_ty(R);
-		const int wp = w / 2;
-		dim3 block(256), grid((unsigned)((wp + RANK_OUT_LANES - 1) / RANK_OUT_LANES), (unsigned)((h + 4 * TY - 1) / (4 * TY)), (unsigned)n);
-		hipLaunchKernelGGL((rank_median_wave_kernel<T, R>), grid, block, 0, st, src, dst, w, h, rows);
+		hipLaunchKernelGGL((rank_median_wave_kernel<T, R>), (pair_wave_grid<rank_wave_ty(R), 1>(w / 2, h, n)), dim3(256), 0, st, src, dst, w, h, rows);
 	}
 
 	template <class T, int RY>
@@ -311,15 +252,9 @@ namespace rir
 	static hipError_t launch_rank_t(const T *src, T *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows, int top, hipStream_t st)
 	{
 		// the pair kernels: the median of a 3x3 or 5x5 square on rows of whole, aligned pairs
-		const bool pairs = size_x == size_y && (size_x == 3 || size_x == 5) && rank == size_x * size_y / 2 && (w & 1) == 0 &&
-						   (((uintptr_t)src | (uintptr_t)dst) & (2 * sizeof(T) - 1)) == 0;
-		const int64_t frame = (int64_t)w * h;
+		const bool pairs = size_x == size_y && (size_x == 3 || size_x == 5) && rank == size_x * size_y / 2 && rows_of_pairs(src, dst, w);
 		const int rx = size_x / 2;
-		for (int f0 = 0; f0 < nframes; f0 += RANK_MAX_GRID_Z)
-		{
-			const int n = std::min(RANK_MAX_GRID_Z, nframes - f0);
-			const T *s = src + frame * f0;
-			T *d = dst + frame * f0;
+		return for_frame_chunks(src, dst, w, h, nframes, [=](const T *s, T *d, int n) {
 			if (pairs && size_x == 3)
 				launch_median_wave<T, 1>(s, d, w, h, n, rows, st);
 			else if (pairs)
@@ -352,23 +287,16 @@ namespace rir
 					launch_tile<T, 7>(s, d, w, h, n, rows, rx, rank, top, st);
 					break;
 				}
-			const hipError_t e = hipGetLastError();
-			if (e != hipSuccess)
-				return e;
-		}
-		return hipSuccess;
+		});
 	}
 
 	hipError_t launch_rank_filter(int type, const void *src, void *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows,
 								  hipStream_t st)
 	{
-		if (type != 'H' && type != 'B' && type != '?')
-			return hipErrorInvalidValue;
 		// the two extreme ranks are the min and the max, which a replicated pixel does not change: the morphology unit's clipped windows
 		if (rank == 0 || rank == size_x * size_y - 1)
 			return launch_morphology(type, src, dst, w, h, nframes, rank == 0 ? MORPH_ERODE : MORPH_DILATE, size_x, size_y, rows, st);
-		if (type == 'H')
-			return launch_rank_t<uint16_t>((const uint16_t *)src, (uint16_t *)dst, w, h, nframes, rank, size_x, size_y, rows, 15, st);
-		return launch_rank_t<uint8_t>((const uint8_t *)src, (uint8_t *)dst, w, h, nframes, rank, size_x, size_y, rows, type == 'B' ? 7 : 0, st);
+		const int top = type == 'H' ? 15 : type == 'B' ? 7 : 0; // the highest value bit
+		return with_pixel_type(type, src, dst, [=](auto *s, auto *d) { return launch_rank_t(s, d, w, h, nframes, rank, size_x, size_y, rows, top, st); });
 	}
 } // namespace rir

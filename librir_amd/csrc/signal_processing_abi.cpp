@@ -668,78 +668,78 @@ RIR_EXPORT int rir_temporal_median_device(const unsigned short *d_src, unsigned 
 			   : -1;
 }
 
-// Flat morphology (morphology_kernels.hip).  Every argument is checked here, before the device is looked for; the byte ranges of the source
-// and the destination may not overlap.
+// The window filters: flat morphology (morphology_kernels.hip) and the spatial rank filters (rank_kernels.hip).  Every argument is checked
+// here, before the device is looked for; the byte ranges of the source and the destination may not overlap.
 namespace
 {
-	// 0, or what is wrong with the arguments of rir_morphology / rir_morphology_device
-	const char *morphology_args(int type, const void *src, const void *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows)
+	bool window_type(int type) { return type == 'H' || type == 'B' || type == '?'; }
+	bool window_sizes(int size_x, int size_y) { return size_x >= 1 && size_x <= 15 && size_x % 2 == 1 && size_y >= 1 && size_y <= 15 && size_y % 2 == 1; }
+
+	// 0, or what is wrong with the arguments that the window filters share, in the order in which they are tested
+	const char *window_filter_args(int type, const void *src, const void *dst, int w, int h, int nframes, int size_x, int size_y, int rows)
 	{
-		if (type != 'H' && type != 'B' && type != '?')
+		if (!window_type(type))
 			return "unknown type (uint16 'H', uint8 'B' or bool '?')";
-		if (op < 0 || op >= MORPH_OPS)
-			return "unknown op (0 erode, 1 dilate, 2 open, 3 close, 4 tophat, 5 blackhat, 6 gradient)";
-		if (size_x < 1 || size_x > 15 || size_x % 2 == 0 || size_y < 1 || size_y > 15 || size_y % 2 == 0)
+		if (!window_sizes(size_x, size_y))
 			return "size_x and size_y must be odd, 1..15";
 		if (w < 1 || h < 1 || nframes < 0 || rows < 0 || rows > h)
 			return "invalid shape (w, h >= 1, nframes >= 0, 0 <= rows <= h)";
 		if (!src || !dst)
 			return "null pointer";
 		return nullptr;
+	}
+	// the same for rir_morphology / rir_morphology_device: the op is tested right after the type
+	const char *morphology_args(int type, const void *src, const void *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows)
+	{
+		if (window_type(type) && (op < 0 || op >= MORPH_OPS))
+			return "unknown op (0 erode, 1 dilate, 2 open, 3 close, 4 tophat, 5 blackhat, 6 gradient)";
+		return window_filter_args(type, src, dst, w, h, nframes, size_x, size_y, rows);
+	}
+	// and for rir_rank_filter / rir_rank_filter_device: the rank is tested right after the sizes
+	const char *rank_filter_args(int type, const void *src, const void *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows)
+	{
+		if (window_type(type) && window_sizes(size_x, size_y) && (rank < 0 || rank >= size_x * size_y))
+			return "rank must be in 0 .. size_x * size_y - 1";
+		return window_filter_args(type, src, dst, w, h, nframes, size_x, size_y, rows);
+	}
+
+	// `bad`, or that the byte ranges of the nframes source and destination frames overlap (a host entry works in place: dst == src is allowed)
+	const char *or_overlap(const char *bad, int type, const void *src, const void *dst, int w, int h, int nframes, bool same_allowed)
+	{
+		const uintptr_t bytes = bad ? 0 : (uintptr_t)w * h * (type == 'H' ? 2 : 1) * nframes, s = (uintptr_t)src, d = (uintptr_t)dst;
+		if (bad || (same_allowed && s == d) || !(s < d + bytes && d < s + bytes))
+			return bad;
+		return same_allowed ? "the source and the destination overlap (dst == src is allowed)" : "the source and the destination overlap";
+	}
+
+	// A device entry of a window filter, `bad` being what its check found: refused before the device is looked for; no frames is no work.
+	template <class Launch>
+	int window_filter_device(const char *who, const char *what, const char *bad, int type, const void *d_src, void *d_dst, int w, int h, int nframes,
+							 Launch launch)
+	{
+		bad = or_overlap(bad, type, d_src, d_dst, w, h, nframes, false);
+		if (bad)
+			return refuse(who, bad);
+		if (nframes == 0)
+			return 0;
+		if (!device_ready())
+			return -1;
+		return hip_ok(launch(), what) ? 0 : -1;
 	}
 } // namespace
 
 RIR_EXPORT int rir_morphology_device(int type, const void *d_src, void *d_dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows,
 									 void *stream)
 {
-	const char *bad = morphology_args(type, d_src, d_dst, w, h, nframes, op, size_x, size_y, rows);
-	const uintptr_t bytes = (uintptr_t)w * h * (type == 'H' ? 2 : 1) * (bad ? 0 : nframes), s = (uintptr_t)d_src, d = (uintptr_t)d_dst;
-	if (!bad && s < d + bytes && d < s + bytes)
-		bad = "the source and the destination overlap";
-	if (bad)
-		return refuse(__func__, bad);
-	if (nframes == 0)
-		return 0;
-	if (!device_ready())
-		return -1;
-	return hip_ok(launch_morphology(type, d_src, d_dst, w, h, nframes, op, size_x, size_y, rows, as_stream(stream)), "morphology") ? 0 : -1;
+	return window_filter_device(__func__, "morphology", morphology_args(type, d_src, d_dst, w, h, nframes, op, size_x, size_y, rows), type, d_src, d_dst, w,
+								h, nframes, [=] { return launch_morphology(type, d_src, d_dst, w, h, nframes, op, size_x, size_y, rows, as_stream(stream)); });
 }
-
-// Spatial rank filters (rank_kernels.hip).  Every argument is checked here, before the device is looked for; the byte ranges of the source
-// and the destination may not overlap.
-namespace
-{
-	// 0, or what is wrong with the arguments of rir_rank_filter / rir_rank_filter_device
-	const char *rank_filter_args(int type, const void *src, const void *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows)
-	{
-		if (type != 'H' && type != 'B' && type != '?')
-			return "unknown type (uint16 'H', uint8 'B' or bool '?')";
-		if (size_x < 1 || size_x > 15 || size_x % 2 == 0 || size_y < 1 || size_y > 15 || size_y % 2 == 0)
-			return "size_x and size_y must be odd, 1..15";
-		if (rank < 0 || rank >= size_x * size_y)
-			return "rank must be in 0 .. size_x * size_y - 1";
-		if (w < 1 || h < 1 || nframes < 0 || rows < 0 || rows > h)
-			return "invalid shape (w, h >= 1, nframes >= 0, 0 <= rows <= h)";
-		if (!src || !dst)
-			return "null pointer";
-		return nullptr;
-	}
-} // namespace
 
 RIR_EXPORT int rir_rank_filter_device(int type, const void *d_src, void *d_dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows,
 									  void *stream)
 {
-	const char *bad = rank_filter_args(type, d_src, d_dst, w, h, nframes, rank, size_x, size_y, rows);
-	const uintptr_t bytes = (uintptr_t)w * h * (type == 'H' ? 2 : 1) * (bad ? 0 : nframes), s = (uintptr_t)d_src, d = (uintptr_t)d_dst;
-	if (!bad && s < d + bytes && d < s + bytes)
-		bad = "the source and the destination overlap";
-	if (bad)
-		return refuse(__func__, bad);
-	if (nframes == 0)
-		return 0;
-	if (!device_ready())
-		return -1;
-	return hip_ok(launch_rank_filter(type, d_src, d_dst, w, h, nframes, rank, size_x, size_y, rows, as_stream(stream)), "rank_filter") ? 0 : -1;
+	return window_filter_device(__func__, "rank_filter", rank_filter_args(type, d_src, d_dst, w, h, nframes, rank, size_x, size_y, rows), type, d_src, d_dst,
+								w, h, nframes, [=] { return launch_rank_filter(type, d_src, d_dst, w, h, nframes, rank, size_x, size_y, rows, as_stream(stream)); });
 }
 
 // Per-region statistics (region_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an input or
@@ -1392,64 +1392,52 @@ RIR_EXPORT int rir_temporal_median(const unsigned short *src, unsigned short *ds
 	return 0;
 }
 
-// Flat morphology of a host stack (frames are independent: any split gives the same bits).  dst may be src.
+// The window filters of a host stack (frames are independent: any split gives the same bits; dst may be src): `bad` is what the entry's check
+// found, filter(in, out, count, stream) its device entry over one slab.
+namespace
+{
+	template <class Filter>
+	int window_filter_host(const char *who, const char *what, const char *bad, int type, const void *src, void *dst, int w, int h, int nframes,
+						   Filter filter)
+	{
+		bad = or_overlap(bad, type, src, dst, w, h, nframes, true);
+		if (bad)
+			return refuse(who, bad);
+		if (nframes == 0)
+			return 0;
+		if (!device_ready())
+			return -1;
+		const size_t frame = (size_t)w * h * (type == 'H' ? 2 : 1);
+		const int slab = Stager::slab(nframes, {frame});
+		DeviceBuffer in, out;
+		if (!in.reserve(frame * slab) || !out.reserve(frame * slab))
+			return -1;
+		Stager s;
+		for (int o = 0; o < nframes; o += slab)
+		{
+			const int count = std::min(slab, nframes - o);
+			if (!s.up(in.ptr, static_cast<const char *>(src) + frame * o, frame * count) || filter(in.ptr, out.ptr, count, s.st) != 0 ||
+				!s.down(static_cast<char *>(dst) + frame * o, out.ptr, frame * count) || !s.wait(what))
+				return s.fail();
+		}
+		return 0;
+	}
+} // namespace
+
 RIR_EXPORT int rir_morphology(int type, const void *src, void *dst, int w, int h, int nframes, int op, int size_x, int size_y, int rows)
 {
-	const char *bad = morphology_args(type, src, dst, w, h, nframes, op, size_x, size_y, rows);
-	const size_t frame = (size_t)w * h * (type == 'H' ? 2 : 1);
-	const uintptr_t bytes = bad ? 0 : frame * (size_t)nframes, from = (uintptr_t)src, to = (uintptr_t)dst;
-	if (!bad && from != to && from < to + bytes && to < from + bytes)
-		bad = "the source and the destination overlap (dst == src is allowed)";
-	if (bad)
-		return refuse(__func__, bad);
-	if (nframes == 0)
-		return 0;
-	if (!device_ready())
-		return -1;
-	const int slab = Stager::slab(nframes, {frame});
-	DeviceBuffer in, out;
-	if (!in.reserve(frame * slab) || !out.reserve(frame * slab))
-		return -1;
-	Stager s;
-	for (int o = 0; o < nframes; o += slab)
-	{
-		const int count = std::min(slab, nframes - o);
-		if (!s.up(in.ptr, static_cast<const char *>(src) + frame * o, frame * count) ||
-			rir_morphology_device(type, in.ptr, out.ptr, w, h, count, op, size_x, size_y, rows, s.st) != 0 ||
-			!s.down(static_cast<char *>(dst) + frame * o, out.ptr, frame * count) || !s.wait("morphology"))
-			return s.fail();
-	}
-	return 0;
+	return window_filter_host(__func__, "morphology", morphology_args(type, src, dst, w, h, nframes, op, size_x, size_y, rows), type, src, dst, w, h, nframes,
+							  [=](const void *in, void *out, int count, void *st) {
+								  return rir_morphology_device(type, in, out, w, h, count, op, size_x, size_y, rows, st);
+							  });
 }
 
-// A spatial rank filter of a host stack (frames are independent: any split gives the same bits).  dst may be src.
 RIR_EXPORT int rir_rank_filter(int type, const void *src, void *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows)
 {
-	const char *bad = rank_filter_args(type, src, dst, w, h, nframes, rank, size_x, size_y, rows);
-	const size_t frame = (size_t)w * h * (type == 'H' ? 2 : 1);
-	const uintptr_t bytes = bad ? 0 : frame * (size_t)nframes, from = (uintptr_t)src, to = (uintptr_t)dst;
-	if (!bad && from != to && from < to + bytes && to < from + bytes)
-		bad = "the source and the destination overlap (dst == src is allowed)";
-	if (bad)
-		return refuse(__func__, bad);
-	if (nframes == 0)
-		return 0;
-	if (!device_ready())
-		return -1;
-	const int slab = Stager::slab(nframes, {frame});
-	DeviceBuffer in, out;
-	if (!in.reserve(frame * slab) || !out.reserve(frame * slab))
-		return -1;
-	Stager s;
-	for (int o = 0; o < nframes; o += slab)
-	{
-		const int count = std::min(slab, nframes - o);
-		if (!s.up(in.ptr, static_cast<const char *>(src) + frame * o, frame * count) ||
-			rir_rank_filter_device(type, in.ptr, out.ptr, w, h, count, rank, size_x, size_y, rows, s.st) != 0 ||
-			!s.down(static_cast<char *>(dst) + frame * o, out.ptr, frame * count) || !s.wait("rank_filter"))
-			return s.fail();
-	}
-	return 0;
+	return window_filter_host(__func__, "rank_filter", rank_filter_args(type, src, dst, w, h, nframes, rank, size_x, size_y, rows), type, src, dst, w, h,
+							  nframes, [=](const void *in, void *out, int count, void *st) {
+								  return rir_rank_filter_device(type, in, out, w, h, count, rank, size_x, size_y, rows, st);
+							  });
 }
 
 // Per-region statistics of a host stack: a shared label map goes up once, per-frame maps go up with their frames; a slab is also bounded by

@@ -1,5 +1,6 @@
-// The wave-tile scheme shared by the frame-buffer units (filter_kernels.hip, morphology_kernels.hip) — gfx950 (CDNA4).  Device code only:
-// include it from a .hip unit, inside no namespace.  Everything here is __forceinline__, so each unit's kernels carry their own copy.
+// The wave-tile scheme shared by the frame-buffer units — gfx950 (CDNA4): filter_kernels.hip includes it itself, morphology_kernels.hip and
+// rank_kernels.hip through pair_tile.h, which adds the form with two columns per lane.  Device code only: include it from a .hip unit,
+// inside no namespace.  Everything here is __forceinline__, so each unit's kernels carry their own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,7 +22,8 @@ namespace rir
 	}
 
 	// ---- the wave-tile scheme -------------------------------------------------------------------
-	// translate, the two gaussians, the fused chain, the 3x3 median and the 3x3 / 5x5 / 7x7 morphology work the same way: a WAVE owns a
+	// translate, the two gaussians, the fused chain, the 3x3 median, the 3x3 / 5x5 / 7x7 morphology and the 3x3 / 5x5 window medians work the
+	// same way: a WAVE owns a
 	// tile of 64 columns x TY rows, a lane one column - its pixels in registers, fetched with one raw-buffer load per row - and the
 	// neighbouring columns come from the neighbouring lanes through DPP wave shifts: no LDS, no barrier.  The parts of the scheme are
 	// written once, here.

@@ -13,7 +13,8 @@ from .low_level.misc import _lib, last_error
 from .signal_processing.rir_signal_processing import (PixelStats, RegionGeometry, RegionHistogram, RegionQuantiles, RegionStats,  # noqa: F401 (API)
                                                       _pixel_quantiles_args, _pixel_stats_args, _polygon_map_args, _region_geometry_args,
                                                       _region_histogram_args, _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
-                                                      _morphology_args, _rank_filter_args, _temporal_median_args, percentile_rank)
+                                                      _morphology_args, _rank_filter_args, _temporal_median_args, _window_size,
+                                                      percentile_rank)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -685,6 +686,23 @@ def temporal_median(frames, window, threshold=0, rows=None, first=0, count=None,
     return out
 
 
+def _window_filter(name, check, entry, frames, own, size, rows, out):
+    """``morphology`` and ``rank_filter``: the device entry of the C ABI over ``frames`` with the parameters that ``check`` passes, ``own``
+    being the op or the rank"""
+    shape = tuple(frames.shape)
+    dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
+    type_char, own, size_y, size_x, rows = check((1,) + shape if len(shape) == 2 else shape, dtype_name, own, size, rows)
+    if out is not None and (not out.is_cuda or out.dtype != frames.dtype or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise RuntimeError("%s: out must be a contiguous %s CUDA tensor of shape %s" % (name, frames.dtype, shape))
+    fr = _frames3(frames)
+    n, h, w = fr.shape
+    if out is None:
+        out = torch.empty(shape, dtype=fr.dtype, device=fr.device)
+    if n:
+        _check(entry(type_char, fr.data_ptr(), out.data_ptr(), w, h, n, own, size_x, size_y, rows, _stream()), "rir_%s_device" % name)
+    return out
+
+
 def morphology(frames, op, size, rows=None, out=None):
     """Flat morphology of a uint16, uint8 or bool stack ``frames[n][h][w]`` (or one image ``[h][w]``) with a centred rectangle ``size`` (an
     odd int, or ``(size_y, size_x)``, each 1..15) (C ABI ``rir_morphology_device``), one launch on the current stream.  ``op``: "erode" /
@@ -692,19 +710,7 @@ def morphology(frames, op, size, rows=None, out=None):
     "tophat" (frames - open), "blackhat" (close - frames), "gradient" (dilate - erode).  The image is the first ``rows`` rows of a frame
     (default: all); the others are copied.  Returns a tensor of the input's dtype and shape (``out`` when given: a contiguous CUDA tensor
     of that dtype and shape that does not overlap ``frames``)."""
-    shape = tuple(frames.shape)
-    dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
-    type_char, op_number, size_y, size_x, rows = _morphology_args((1,) + shape if len(shape) == 2 else shape, dtype_name, op, size, rows)
-    if out is not None and (not out.is_cuda or out.dtype != frames.dtype or tuple(out.shape) != shape or not out.is_contiguous()):
-        raise RuntimeError("morphology: out must be a contiguous %s CUDA tensor of shape %s" % (frames.dtype, shape))
-    fr = _frames3(frames)
-    n, h, w = fr.shape
-    if out is None:
-        out = torch.empty(shape, dtype=fr.dtype, device=fr.device)
-    if n:
-        _check(_lib.rir_morphology_device(type_char, fr.data_ptr(), out.data_ptr(), w, h, n, op_number, size_x, size_y, rows, _stream()),
-               "rir_morphology_device")
-    return out
+    return _window_filter("morphology", _morphology_args, _lib.rir_morphology_device, frames, op, size, rows, out)
 
 
 def erode(frames, size, rows=None, out=None):
@@ -750,26 +756,15 @@ def rank_filter(frames, rank, size, rows=None, out=None):
     - which is not the border rule of ``median_filter`` (a smaller window along the border).  The image is the first ``rows`` rows of a
     frame (default: all); the others are copied.  Returns a tensor of the input's dtype and shape (``out`` when given: a contiguous CUDA
     tensor of that dtype and shape that does not overlap ``frames``)."""
-    shape = tuple(frames.shape)
-    dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
-    type_char, rank, size_y, size_x, rows = _rank_filter_args((1,) + shape if len(shape) == 2 else shape, dtype_name, rank, size, rows)
-    if out is not None and (not out.is_cuda or out.dtype != frames.dtype or tuple(out.shape) != shape or not out.is_contiguous()):
-        raise RuntimeError("rank_filter: out must be a contiguous %s CUDA tensor of shape %s" % (frames.dtype, shape))
-    fr = _frames3(frames)
-    n, h, w = fr.shape
-    if out is None:
-        out = torch.empty(shape, dtype=fr.dtype, device=fr.device)
-    if n:
-        _check(_lib.rir_rank_filter_device(type_char, fr.data_ptr(), out.data_ptr(), w, h, n, rank, size_x, size_y, rows, _stream()),
-               "rir_rank_filter_device")
-    return out
+    return _window_filter("rank_filter", _rank_filter_args, _lib.rir_rank_filter_device, frames, rank, size, rows, out)
 
 
 def _window_sizes(size):
     """(size_y, size_x) of a window parameter that ``_rank_filter_args`` is still to check (an unusable one: (1, 1))"""
-    sizes = tuple(size) if isinstance(size, (tuple, list)) else (size, size)
-    ok = len(sizes) == 2 and all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) and s >= 1 for s in sizes)
-    return (int(sizes[0]), int(sizes[1])) if ok else (1, 1)
+    try:
+        return _window_size("", size)
+    except ValueError:
+        return 1, 1
 
 
 def window_median(frames, size, rows=None, out=None):

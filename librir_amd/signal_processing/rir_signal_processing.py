@@ -208,27 +208,46 @@ MORPHOLOGY_OPS = ("erode", "dilate", "open", "close", "tophat", "blackhat", "gra
 _MORPHOLOGY_TYPES = {"uint16": "H", "uint8": "B", "bool": "?"}
 
 
-def _morphology_args(shape, dtype_name, op, size, rows):
-    """the parameters of a morphology call over a stack of `shape`, checked without a device; -> (type char, op number, size_y, size_x, rows)"""
+# The parameters that the window filters (morphology, the rank filters) share, checked without a device.  Each filter has one parameter of its
+# own, tested at its own place among these - the op right after the type, the rank once the sizes are known - so the checks are three pieces
+# that _morphology_args and _rank_filter_args call in their order; every piece raises ValueError with the filter's name in front.
+def _window_type(name, shape, dtype_name):
+    """-> the type char of the C ABI for a stack of `shape`"""
     if len(shape) != 3:
-        raise ValueError("morphology: a stack [n][h][w] expected")
+        raise ValueError("%s: a stack [n][h][w] expected" % name)
     if dtype_name not in _MORPHOLOGY_TYPES:
-        raise ValueError("morphology: uint16, uint8 or bool frames expected, not %s" % dtype_name)
-    if op not in MORPHOLOGY_OPS:
-        raise ValueError("morphology: op must be one of %s (got %r)" % (", ".join(MORPHOLOGY_OPS), op))
+        raise ValueError("%s: uint16, uint8 or bool frames expected, not %s" % (name, dtype_name))
+    return ord(_MORPHOLOGY_TYPES[dtype_name])
+
+
+def _window_size(name, size):
+    """-> (size_y, size_x) of a window parameter: an odd int for a square, or a pair of them, each 1..15"""
     sizes = tuple(size) if isinstance(size, (tuple, list)) else (size, size)
     if len(sizes) != 2 or not all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in sizes):
-        raise ValueError("morphology: size must be an odd int or (size_y, size_x)")
-    for s in sizes:
-        if not 1 <= s <= 15 or s % 2 == 0:
-            raise ValueError("morphology: sizes must be odd, 1 to 15 (got %r)" % (size,))
+        raise ValueError("%s: size must be an odd int or (size_y, size_x)" % name)
+    if not all(1 <= s <= 15 and s % 2 == 1 for s in sizes):
+        raise ValueError("%s: sizes must be odd, 1 to 15 (got %r)" % (name, size))
+    return int(sizes[0]), int(sizes[1])
+
+
+def _window_rows(name, shape, rows):
+    """-> the rows of the image within frames of `shape`: all of them for None"""
     _, h, w = shape
     if h < 1 or w < 1:
-        raise ValueError("morphology: empty frames")
+        raise ValueError("%s: empty frames" % name)
     rows = h if rows is None else int(rows)
     if not 0 <= rows <= h:
-        raise ValueError("morphology: rows must be in 0..h")
-    return ord(_MORPHOLOGY_TYPES[dtype_name]), MORPHOLOGY_OPS.index(op), int(sizes[0]), int(sizes[1]), rows
+        raise ValueError("%s: rows must be in 0..h" % name)
+    return rows
+
+
+def _morphology_args(shape, dtype_name, op, size, rows):
+    """the parameters of a morphology call over a stack of `shape`, checked without a device; -> (type char, op number, size_y, size_x, rows)"""
+    type_char = _window_type("morphology", shape, dtype_name)
+    if op not in MORPHOLOGY_OPS:
+        raise ValueError("morphology: op must be one of %s (got %r)" % (", ".join(MORPHOLOGY_OPS), op))
+    size_y, size_x = _window_size("morphology", size)
+    return type_char, MORPHOLOGY_OPS.index(op), size_y, size_x, _window_rows("morphology", shape, rows)
 
 
 def morphology(images, op, size, rows=None):
@@ -257,29 +276,15 @@ _sp.rir_rank_filter.argtypes = [ct.c_int, ct.c_void_p, ct.c_void_p] + [ct.c_int]
 def _rank_filter_args(shape, dtype_name, rank, size, rows):
     """the parameters of a rank filter over a stack of `shape`, checked without a device; a negative rank counts from the end, as in scipy;
     -> (type char, rank, size_y, size_x, rows)"""
-    if len(shape) != 3:
-        raise ValueError("rank_filter: a stack [n][h][w] expected")
-    if dtype_name not in _MORPHOLOGY_TYPES:
-        raise ValueError("rank_filter: uint16, uint8 or bool frames expected, not %s" % dtype_name)
-    sizes = tuple(size) if isinstance(size, (tuple, list)) else (size, size)
-    if len(sizes) != 2 or not all(isinstance(s, (int, np.integer)) and not isinstance(s, bool) for s in sizes):
-        raise ValueError("rank_filter: size must be an odd int or (size_y, size_x)")
-    for s in sizes:
-        if not 1 <= s <= 15 or s % 2 == 0:
-            raise ValueError("rank_filter: sizes must be odd, 1 to 15 (got %r)" % (size,))
-    cells = int(sizes[0]) * int(sizes[1])
+    type_char = _window_type("rank_filter", shape, dtype_name)
+    size_y, size_x = _window_size("rank_filter", size)
+    cells = size_y * size_x
     if not isinstance(rank, (int, np.integer)) or isinstance(rank, bool):
         raise ValueError("rank_filter: rank must be an int")
     rank = int(rank) + cells if rank < 0 else int(rank)
     if not 0 <= rank < cells:
-        raise ValueError("rank_filter: rank must be in %d..%d for a %d x %d window" % (-cells, cells - 1, sizes[0], sizes[1]))
-    _, h, w = shape
-    if h < 1 or w < 1:
-        raise ValueError("rank_filter: empty frames")
-    rows = h if rows is None else int(rows)
-    if not 0 <= rows <= h:
-        raise ValueError("rank_filter: rows must be in 0..h")
-    return ord(_MORPHOLOGY_TYPES[dtype_name]), rank, int(sizes[0]), int(sizes[1]), rows
+        raise ValueError("rank_filter: rank must be in %d..%d for a %d x %d window" % (-cells, cells - 1, size_y, size_x))
+    return type_char, rank, size_y, size_x, _window_rows("rank_filter", shape, rows)
 
 
 def percentile_rank(percent, size_y, size_x):

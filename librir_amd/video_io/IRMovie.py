@@ -559,25 +559,30 @@ class IRMovie(object):
             mask = librir_amd.device.morph_open(mask, 3)            # drop single-pixel noise ...
             labels = librir_amd.device.label_images(mask)           # ... before labelling and track_components
         """
-        import torch
-
         from ..device import _morphology_args, morphology
 
+        return self._window_filter("morphology", _morphology_args, morphology, op, size, selection, rows, out)
+
+    def _window_filter(self, name, check, filter, own, size, selection, rows, out):
+        """``morphology`` and ``rank_filter``: ``filter`` of ``librir_amd.device`` over the images of ``selection``, read in pieces, with the
+        parameters that ``check`` passes; ``own`` is the op or the rank"""
+        import torch
+
         h, w = self.image_size
-        _morphology_args((1, h, w), "uint16", op, size, rows)
-        positions = self._stats_positions(selection, "morphology")
+        check((1, h, w), "uint16", own, size, rows)
+        positions = self._stats_positions(selection, name)
         shape = (len(positions), h, w)
         if out is None:
             out = torch.empty(shape, dtype=torch.uint16, device=torch.device("cuda", torch.cuda.current_device()))
         elif not out.is_cuda or out.dtype != torch.uint16 or tuple(out.shape) != shape or not out.is_contiguous():
-            raise RuntimeError("morphology: 'out' must be a C-contiguous uint16 CUDA tensor of shape %s" % (shape,))
+            raise RuntimeError("%s: 'out' must be a C-contiguous uint16 CUDA tensor of shape %s" % (name, shape))
         per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
         piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=out.device)
         for k0 in range(0, len(positions), per_piece):
             sel = positions[k0:k0 + per_piece]
             fr = piece[:len(sel)]
             self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
-            morphology(fr, op, size, rows, out=out[k0:k0 + len(sel)])
+            filter(fr, own, size, rows, out=out[k0:k0 + len(sel)])
         return out
 
     def rank_filter(self, rank, size, selection=slice(None), rows=None, out=None):
@@ -590,26 +595,9 @@ class IRMovie(object):
 
             background = mov.rank_filter(librir_amd.device.percentile_rank(25, 9, 9), 9)   # a low percentile under sparse hot spots
         """
-        import torch
-
         from ..device import _rank_filter_args, rank_filter
 
-        h, w = self.image_size
-        _rank_filter_args((1, h, w), "uint16", rank, size, rows)
-        positions = self._stats_positions(selection, "rank_filter")
-        shape = (len(positions), h, w)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint16, device=torch.device("cuda", torch.cuda.current_device()))
-        elif not out.is_cuda or out.dtype != torch.uint16 or tuple(out.shape) != shape or not out.is_contiguous():
-            raise RuntimeError("rank_filter: 'out' must be a C-contiguous uint16 CUDA tensor of shape %s" % (shape,))
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=out.device)
-        for k0 in range(0, len(positions), per_piece):
-            sel = positions[k0:k0 + per_piece]
-            fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
-            rank_filter(fr, rank, size, rows, out=out[k0:k0 + len(sel)])
-        return out
+        return self._window_filter("rank_filter", _rank_filter_args, rank_filter, rank, size, selection, rows, out)
 
     def window_median(self, size, selection=slice(None), rows=None, out=None):
         """``rank_filter`` at the median rank ``size_y * size_x // 2``: ``librir_amd.device.window_median`` over the images of

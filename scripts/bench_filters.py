@@ -47,6 +47,7 @@ for op in ("erode", "open", "tophat"):
 for size in (3, 5, 9):
     rec("window_median %dx%d" % (size, size), timeit(lambda: D.window_median(t16, size, out=morph_out)), 4 * WH)
     rec("percentile_filter 25 %% %dx%d" % (size, size), timeit(lambda: D.percentile_filter(t16, 25, size, out=morph_out)), 4 * WH)
+rec("window_median 5x5 uint8", timeit(lambda: D.window_median(t8, 5, out=morph_out8)), 2 * WH)
 sh = torch.zeros((n, 2), dtype=torch.float32, device="cuda"); sh[:, 0] = 1.25; sh[:, 1] = -2.5
 rec("remove_motion (read-back)", timeit(lambda: D.remove_motion(t16, sh, rows=h - 3)), 4 * WH)
 t0 = time.perf_counter(); bp2 = D.BadPixels(t16[0]); torch.cuda.synchronize(); print("bad_pixels_create (detector, once per stream): %.2f ms" % ((time.perf_counter() - t0) * 1e3))
