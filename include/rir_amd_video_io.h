@@ -115,6 +115,17 @@ extern "C"
 	 * is queued on `stream` (a hipStream_t, NULL: the null stream).  Returns count once the images are in d_out; -1 on failure: a bad
 	 * argument, out_bytes < count x h x w x element size, a corrupted chunk, no device. */
 	int rir_load_images_device(int camera, int first, int count, int step, int dtype, void *d_out, long long out_bytes, void *stream);
+	/* The window of h rows of w pixels at row y0, column x0 of the same images: d_out is [count][h][w] C-contiguous, bit for bit
+	 * rir_load_images_device's result cut to [:, y0:y0+h, x0:x0+w] - read-back filters, MIN_T, the camera's state left alone, the order
+	 * after `stream` and the dtypes are that call's.  With no read-back filter switched on only the window is read: of every chunk of a RIRB
+	 * file the record headers, tile offsets and payload of the run of 512-pixel tiles the window's rows lie in (three shorter reads), which
+	 * is all that crosses the link and all that is decoded - so a corruption of a chunk outside these tiles is not seen by a windowed read;
+	 * of raw and ZFile images, read whole on the host, only the window's rows are uploaded.  With bad-pixel repair or motion correction on
+	 * the images are made whole on the device, as the filters need them, and the window is copied out.  Returns count; 0 for count == 0;
+	 * -1 on failure (nothing is written before a launch): a bad camera, step < 1, images outside the file, a window outside the image or
+	 * with h < 1 or w < 1, an unknown dtype, out_bytes < count x h x w x element size, a NULL d_out, corrupted tile offsets, no device. */
+	int rir_load_window_device(int camera, int first, int count, int step, int y0, int x0, int h, int w, int dtype, void *d_out, long long out_bytes,
+							   void *stream);
 	/* `count` uint16 frames [count][h][w] in device memory appended to an open lossless saver, after the frames added before them (host
 	 * frames staged by h264_add_image_lossless included), with the time stamps timestamps_ns[count] and no per-image attributes.  The
 	 * frames are read after the work queued on `stream`; the call returns when the caller may reuse d_frames (chunks are encoded and

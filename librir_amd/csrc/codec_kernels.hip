@@ -1895,6 +1895,185 @@ namespace rir
 		decode_tile<FAST>(hdr_table + ((int64_t)chunk * ntiles + tile) * gop, stream + c0 + t0, seg_len, (int)walk, walk == e.nframes, lane, sink, error_flag);
 	}
 
+	// ---- windowed decode into the caller's buffer (rir_load_window_device) ------------------------------------------------
+	// Where decode_tile puts a record of the windowed decode: SelectSink's choice of frames and its MIN_T, but of a stored frame only the
+	// pixels inside the window, in an output frame of h x w.  A lane's eight pixels keep their place from frame to frame, so where they
+	// go is worked out once, before the walk (rirb1_decode_window): relative to `cur`, the first window row this tile touches in the
+	// output frame the next stored frame goes to - a frame only moves `cur` on.
+	//   FAST     the eight pixels lie in one window row or outside the window: `off`, their byte offset (RIR_OOB outside); the store of
+	//            a lane outside, as of a skipped frame, points out of range
+	//   general  `off` is the element pixel 0 would go to (modulo 2^32: a lane may begin above the tile's first window row); pixel k is
+	//            stored when bit k of `code` is set, at element off + k - rows * gap, rows (bits 8 + 3k .. 10 + 3k of `code`) being the
+	//            frame rows between pixel 0 and pixel k, each of which skips gap = W - w elements of the output
+	template <bool F32>
+	struct WindowSink
+	{
+		char *cur;
+		int64_t fbytes;	 // bytes of an output frame
+		uint32_t room;	 // bytes of the output frame this tile's rows take from `cur` on
+		int next, step;	 // next local frame to store, distance to the one after it
+		uint32_t off, code, gap;
+		uint32_t min_t;
+		int nmin; // pixels of this lane's eight that get min_t
+		__device__ __forceinline__ Px8 add_min(Px8 o) const
+		{
+			if (min_t)
+			{
+#pragma unroll
+				for (int k = 0; k < 4; ++k)
+					o.d[k] = pk_add16(o.d[k], (2 * k < nmin ? min_t : 0u) | (2 * k + 1 < nmin ? min_t << 16 : 0u));
+			}
+			return o;
+		}
+		template <bool FAST>
+		__device__ __forceinline__ void put(int f, const Px8 &r)
+		{
+			const bool sel = f == next; // (wave-uniform)
+			const Px8 o = add_min(r);
+			if (FAST)
+			{
+				const __amdgpu_buffer_rsrc_t rs = make_rsrc(cur, room);
+				const uint32_t at = sel ? off : RIR_OOB;
+				if (F32)
+				{
+					v4u32 a, b;
+					a.x = __builtin_bit_cast(uint32_t, (float)(o.d[0] & 0xffffu)), a.y = __builtin_bit_cast(uint32_t, (float)(o.d[0] >> 16));
+					a.z = __builtin_bit_cast(uint32_t, (float)(o.d[1] & 0xffffu)), a.w = __builtin_bit_cast(uint32_t, (float)(o.d[1] >> 16));
+					b.x = __builtin_bit_cast(uint32_t, (float)(o.d[2] & 0xffffu)), b.y = __builtin_bit_cast(uint32_t, (float)(o.d[2] >> 16));
+					b.z = __builtin_bit_cast(uint32_t, (float)(o.d[3] & 0xffffu)), b.w = __builtin_bit_cast(uint32_t, (float)(o.d[3] >> 16));
+					__builtin_amdgcn_raw_buffer_store_b128(a, rs, at, 0, FRAME_STORE_AUX);
+					__builtin_amdgcn_raw_buffer_store_b128(b, rs, sel ? off + 16u : RIR_OOB, 0, FRAME_STORE_AUX); // (off = RIR_OOB: + 16 is out of range too)
+				}
+				else
+				{
+					v4u32 v;
+					v.x = o.d[0], v.y = o.d[1], v.z = o.d[2], v.w = o.d[3];
+					__builtin_amdgcn_raw_buffer_store_b128(v, rs, at, 0, FRAME_STORE_AUX);
+				}
+			}
+			else
+			{
+				const __amdgpu_buffer_rsrc_t rs = make_rsrc(cur, room);
+				// the eight places are worked out again for every frame: kept across the walk they would cost more registers than a wave
+				// has at this residency (the compiler would, so the two words they come from are hidden from it)
+				uint32_t d0 = off, cd = code;
+				asm volatile("" : "+v"(d0), "+v"(cd));
+				const uint32_t on = sel ? cd : 0u;
+#pragma unroll
+				for (int k = 0; k < 8; ++k)
+				{
+					const uint32_t v = (o.d[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+					// (a pixel outside may have a meaningless place, before `cur` say: it is not looked at)
+					const uint32_t at = ((on >> k) & 1u) ? (d0 + (uint32_t)k - ((cd >> (8 + 3 * k)) & 7u) * gap) * (F32 ? 4u : 2u) : RIR_OOB;
+					if (F32)
+						__builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, (float)v), rs, at, 0, FRAME_STORE_AUX);
+					else
+						__builtin_amdgcn_raw_buffer_store_b16((short)v, rs, at, 0, FRAME_STORE_AUX);
+				}
+			}
+			if (sel)
+				next += step, cur += fbytes;
+		}
+	};
+
+	// grid = (ceil((tile_end - tile0) / 4), entries), block = 256: rirb1_decode_select for a window of the frame.  `win` is the window of
+	// frames of npx pixels in rows of fw, `out` is [out_frames][win.h][win.w].  The tables are the dense form's, restricted to the tiles
+	// [t_lo, t_lo + ntiles_win) the host read from the file: headers at hdr_table + (chunk * ntiles_win + tile - t_lo) * gop, ntiles_win + 1
+	// tile offsets a chunk, and a chunk's payload slice stream[chunk_off[chunk] ...) begins at its first tile offset.  Every check of
+	// rirb1_decode_select, restated for the slice (the segment inside the slice, the slice inside the stream, the entry's own), and the
+	// window's: inside the frame, not empty, the tiles asked for among those of the tables; a failed check raises *error_flag and
+	// stores nothing.  A tile of the run that holds no pixel of the window (rows of two tiles or more, a window in one half) returns
+	// before it reads a header or a payload word.
+	// FAST: fw, win.x0 and win.w are multiples of 8, `out` is 16-byte aligned and the tiles [tile0, tile_end) lie whole inside the frame.
+	template <bool F32, bool FAST>
+	__attribute__((amdgpu_waves_per_eu(8, 8))) __global__ __launch_bounds__(256) void rirb1_decode_window(
+		const uint64_t *__restrict__ hdr_table, const uint32_t *__restrict__ tile_off, const uint64_t *__restrict__ chunk_off, const uint64_t *__restrict__ stream,
+		uint64_t stream_words, int64_t npx, int fw, RirbWindow win, int t_lo, int ntiles_win, int tile0, int tile_end, int gop, int nchunks,
+		const RirbSelect *__restrict__ table, int out_frames, void *__restrict__ out, int min_px, uint32_t min_t, int *__restrict__ error_flag)
+	{
+		constexpr int ESZ = F32 ? 4 : 2;
+		const int lane = threadIdx.x & 63;
+		const int tile = tile0 + blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+		if (tile >= tile_end)
+			return;
+		// the frame, the window in it, the tiles of the tables (fw <= 2^24: what a tile's rows take of the output stays far below RIR_OOB)
+		bool bad = fw < 1 || fw > (1 << 24) || npx < fw || npx > 0x7fffffff || npx % fw != 0 || win.y0 < 0 || win.x0 < 0 || win.h < 1 || win.w < 1;
+		bad = bad || win.x0 > fw - win.w || win.y0 > (int)(npx / fw) - win.h || t_lo < 0 || ntiles_win < 1 || tile < t_lo || tile_end - t_lo > ntiles_win ||
+			  (int64_t)tile * RIRB1_TILE_PX >= npx;
+		if (FAST)
+			bad = bad || ((fw | win.x0 | win.w) & 7) != 0 || (((uintptr_t)out) & 15) != 0 || (int64_t)(tile + 1) * RIRB1_TILE_PX > npx;
+		if (bad)
+		{
+			if (lane == 0)
+				atomicExch(error_flag, 1);
+			return;
+		}
+		// the frame rows [ya, yb] of this tile, those of them in the window [ra, rb]; the first and the last may be cut by the tile's ends
+		const int tpx = tile * RIRB1_TILE_PX, tlast = (int)min((int64_t)tpx + RIRB1_TILE_PX, npx) - 1;
+		const int ya = tpx / fw, yb = tlast / fw;
+		const int ra = max(ya, win.y0), rb = min(yb, win.y0 + win.h - 1);
+		if (ra > rb)
+			return;
+		{
+			const int xa0 = ra == ya ? tpx - ya * fw : 0, xa1 = ra == yb ? tlast - yb * fw : fw - 1; // the tile's pixels of row ra
+			const int xb0 = rb == ya ? tpx - ya * fw : 0, xb1 = rb == yb ? tlast - yb * fw : fw - 1; // ... and of row rb
+			const int x1 = win.x0 + win.w - 1;
+			if (rb - ra < 2 && !(xa0 <= x1 && xa1 >= win.x0) && !(xb0 <= x1 && xb1 >= win.x0))
+				return; // (with a row between ra and rb the tile holds that row whole)
+		}
+		const RirbSelect e = table[blockIdx.y];
+		if (e.count == 0)
+			return;
+		const int64_t walk = (int64_t)e.first + (int64_t)(e.count - 1) * e.step + 1;
+		if (e.chunk < 0 || e.chunk >= nchunks || e.nframes <= 0 || e.nframes > gop || e.first < 0 || e.count < 0 || e.step < 1 || walk > e.nframes ||
+			e.out_first < 0 || e.out_first > out_frames - e.count)
+		{
+			if (lane == 0)
+				atomicExch(error_flag, 1);
+			return;
+		}
+		const int chunk = e.chunk;
+		const uint32_t *toff = tile_off + (int64_t)chunk * (ntiles_win + 1);
+		const uint32_t tb = toff[0], t0 = toff[tile - t_lo], t1 = toff[tile - t_lo + 1];
+		const uint64_t c0 = chunk_off[chunk], c1 = chunk_off[chunk + 1];
+		if (c0 > c1 || c1 > stream_words || t0 < tb || t1 < t0 || (uint64_t)(t1 - tb) > c1 - c0)
+		{ // (the checks of the dense form, the positions taken from the slice's first word)
+			if (lane == 0)
+				atomicExch(error_flag, 1);
+			return;
+		}
+		const uint32_t seg_len = min(t1 - t0, (uint32_t)gop * RIRB1_REC_MAX_WORDS);
+		WindowSink<F32> sink;
+		sink.fbytes = (int64_t)win.h * win.w * ESZ;
+		sink.cur = static_cast<char *>(out) + (int64_t)e.out_first * sink.fbytes + (int64_t)(ra - win.y0) * win.w * ESZ;
+		sink.room = (uint32_t)(rb - ra + 1) * (uint32_t)win.w * ESZ;
+		sink.next = e.first, sink.step = e.step;
+		sink.min_t = min_t & 0xffffu;
+		const int p0 = tpx + lane * 8;
+		sink.nmin = max(0, min(8, min_px - p0));
+		sink.gap = (uint32_t)(fw - win.w);
+		int y = p0 / fw, x = p0 - y * fw;
+		sink.off = (uint32_t)((y - ra) * win.w + (x - win.x0));
+		sink.code = 0;
+		if (FAST)
+			sink.off = (y >= ra && y <= rb && x >= win.x0 && x < win.x0 + win.w) ? sink.off * ESZ : RIR_OOB;
+		else
+		{
+			uint32_t below = 0;
+#pragma unroll
+			for (int k = 0; k < 8; ++k)
+			{
+				if (y >= ra && y <= rb && x >= win.x0 && x < win.x0 + win.w)
+					sink.code |= 1u << k;
+				sink.code |= below << (8 + 3 * k);
+				if (++x == fw)
+					x = 0, ++y, ++below;
+			}
+		}
+		decode_tile<FAST>(hdr_table + ((int64_t)chunk * ntiles_win + (tile - t_lo)) * gop, stream + c0 + (t0 - tb), seg_len, (int)walk, walk == e.nframes, lane,
+						  sink, error_flag);
+	}
+
 	// ---- host launchers --------------------------------------------------------------------------------
 
 	// The FAST-then-ragged pair of every kernel that has the two forms: launch(fast, t0, t1) for the tiles [0, nfast) that lie whole
@@ -2043,6 +2222,67 @@ namespace rir
 			launch_fast_then_ragged(out, npx, ntiles, rirb1_decode_select<true, true>, rirb1_decode_select<true, false>, go);
 		else
 			launch_fast_then_ragged(out, npx, ntiles, rirb1_decode_select<false, true>, rirb1_decode_select<false, false>, go);
+		return hipGetLastError();
+	}
+
+	// The FAST-then-ragged pair again, over the tiles [t_lo, t_lo + ntiles_win) of the window: FAST needs more than whole tiles of aligned
+	// frames here (the window's columns on 8-pixel lanes too), so the split is made here and not by launch_fast_then_ragged.
+	hipError_t launch_decode_window(const uint64_t *hdr, const uint32_t *tile_off, const uint64_t *chunk_off, const uint64_t *stream, uint64_t stream_words,
+									int64_t npx, int fw, RirbWindow win, int t_lo, int ntiles_win, int gop, int nchunks, const RirbSelect *table, int entries,
+									int out_frames, bool f32, void *out, int min_px, uint32_t min_t, int *d_error, hipStream_t st)
+	{
+		if (entries <= 0)
+			return hipSuccess;
+		if (fw < 1 || fw > (1 << 24) || npx < fw || npx > 0x7fffffff || npx % fw != 0 || win.y0 < 0 || win.x0 < 0 || win.h < 1 || win.w < 1 ||
+			win.x0 > fw - win.w || win.y0 > (int)(npx / fw) - win.h || t_lo < 0 || ntiles_win < 1 ||
+			(int64_t)(t_lo + ntiles_win - 1) * RIRB1_TILE_PX >= npx)
+			return hipErrorInvalidValue;
+		const bool aligned = (((fw | win.x0 | win.w) & 7) == 0) && ((((uintptr_t)out) & 15) == 0);
+		const int t_hi = t_lo + ntiles_win;
+		const int fast_end = aligned ? std::max(t_lo, (int)std::min<int64_t>(t_hi, npx / RIRB1_TILE_PX)) : t_lo;
+		auto go = [&](auto kernel, int t0, int t1) {
+			if (t1 > t0)
+				hipLaunchKernelGGL(kernel, dim3((t1 - t0 + 3) / 4, entries), dim3(256), 0, st, hdr, tile_off, chunk_off, stream, stream_words, npx, fw, win, t_lo,
+								   ntiles_win, t0, t1, gop, nchunks, table, out_frames, out, min_px, min_t, d_error);
+		};
+		if (f32)
+			go(rirb1_decode_window<true, true>, t_lo, fast_end), go(rirb1_decode_window<true, false>, fast_end, t_hi);
+		else
+			go(rirb1_decode_window<false, true>, t_lo, fast_end), go(rirb1_decode_window<false, false>, fast_end, t_hi);
+		return hipGetLastError();
+	}
+
+	// The window of whole frames (a windowed read behind a read-back filter, which needs whole frames): dst[f][y][x] = src[f][y0 + y][x0 + x],
+	// uint16 or (F32) the value converted exactly; one element per thread and turn
+	template <bool F32>
+	__global__ __launch_bounds__(256) void crop_window_kernel(const uint16_t *__restrict__ src, int64_t npx, int fw, int y0, int x0, int h, int w,
+															   void *__restrict__ dst, int64_t total)
+	{
+		for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x)
+		{
+			const int64_t row = i / w; // (frame, window row)
+			const int x = (int)(i - row * w);
+			const int64_t f = row / h;
+			const int y = (int)(row - f * h);
+			const uint16_t v = src[f * npx + (int64_t)(y0 + y) * fw + x0 + x];
+			if (F32)
+				static_cast<float *>(dst)[i] = (float)v;
+			else
+				static_cast<uint16_t *>(dst)[i] = v;
+		}
+	}
+	hipError_t launch_crop_window(const uint16_t *src, int fw, int fh, int y0, int x0, int h, int w, int nframes, bool f32, void *dst, hipStream_t st)
+	{
+		const int64_t total = (int64_t)nframes * h * w;
+		if (total <= 0)
+			return hipSuccess;
+		if (y0 < 0 || x0 < 0 || h < 1 || w < 1 || y0 > fh - h || x0 > fw - w)
+			return hipErrorInvalidValue;
+		const int blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);
+		if (f32)
+			hipLaunchKernelGGL(crop_window_kernel<true>, dim3(blocks), dim3(256), 0, st, src, (int64_t)fw * fh, fw, y0, x0, h, w, dst, total);
+		else
+			hipLaunchKernelGGL(crop_window_kernel<false>, dim3(blocks), dim3(256), 0, st, src, (int64_t)fw * fh, fw, y0, x0, h, w, dst, total);
 		return hipGetLastError();
 	}
 } // namespace rir

@@ -63,6 +63,20 @@ namespace rir
 	hipError_t launch_decode_select(const uint64_t *hdr, const uint32_t *tile_off, const uint64_t *chunk_off, const uint64_t *stream, uint64_t stream_words,
 									int64_t npx, int ntiles, int gop, int nchunks, const RirbSelect *table, int entries, int out_frames, bool f32, void *out,
 									int min_px, uint32_t min_t, int *d_error, hipStream_t st);
+	// The windowed decode (rirb1_decode_window): the entries of launch_decode_select, but only the window `win` of every selected frame
+	// (rows of fw pixels) is stored, `out` being [out_frames][win.h][win.w].  The tables are those of the dense form restricted to the
+	// tiles [t_lo, t_lo + ntiles_win) the window's rows lie in: ntiles_win x gop headers and ntiles_win + 1 tile offsets a chunk, and of a
+	// chunk's payload the words [tile_off[t_lo], tile_off[t_lo + ntiles_win)) - chunk_off places these slices in `stream`.
+	struct RirbWindow
+	{
+		int32_t y0, x0, h, w;
+	};
+	hipError_t launch_decode_window(const uint64_t *hdr, const uint32_t *tile_off, const uint64_t *chunk_off, const uint64_t *stream, uint64_t stream_words,
+									int64_t npx, int fw, RirbWindow win, int t_lo, int ntiles_win, int gop, int nchunks, const RirbSelect *table, int entries,
+									int out_frames, bool f32, void *out, int min_px, uint32_t min_t, int *d_error, hipStream_t st);
+	// the window (y0, x0, h, w) of nframes whole uint16 frames of fh rows of fw pixels, contiguous at dst as uint16 or (f32) float32: what a
+	// windowed read behind a read-back filter (which needs whole frames) ends on
+	hipError_t launch_crop_window(const uint16_t *src, int fw, int fh, int y0, int x0, int h, int w, int nframes, bool f32, void *dst, hipStream_t st);
 	hipError_t launch_decode_slots(const uint64_t *d_hdr, const uint32_t *d_seg_words, const uint64_t *d_slots, int64_t npx, int ntiles, int nframes,
 								   int gop, uint16_t *d_frames, int *d_error, hipStream_t st);
 	// the packed form (codec_kernels.hip: rirb1_encode_packed)

@@ -2030,32 +2030,47 @@ namespace
 					(void)hipEventDestroy(e);
 		}
 
-		// frames [k0, k0 + n) of the selection, uint16 in dio_scr, go to the output: read-back filters, then a copy or the conversion
-		bool dio_finish(int k0, int n, bool f32, void *d_out, bool do_bp, bool do_motion, hipStream_t st)
+		// frames [k0, k0 + n) of the selection, uint16 in dio_scr, go to the output: read-back filters, then a copy or the conversion.
+		// win: the output takes that window of them - cut out of the filtered frames (the filters need whole ones), or, without a filter,
+		// what the scratch holds already
+		bool dio_finish(int k0, int n, bool f32, void *d_out, bool do_bp, bool do_motion, hipStream_t st, const RirbWindow *win = nullptr)
 		{
-			const size_t npx = (size_t)width * height;
+			const size_t npx = (size_t)width * height, wpx = win ? (size_t)win->h * win->w : 0;
 			unsigned short *src = dio_scr.as<unsigned short>(), *res = src;
+			if (win && !do_bp && !do_motion)
+				return hip_ok(launch_u16_to_f32(src, static_cast<float *>(d_out) + (size_t)k0 * wpx, (int64_t)n * wpx, st), "u16 -> f32");
 			unsigned short *out16 = static_cast<unsigned short *>(d_out) + (size_t)k0 * npx;
 			if (do_bp && rir_remove_bad_pixels_device(bp_handle, src, height - 3, n, st) != 0)
 				return false;
 			if (do_motion)
 			{
-				unsigned short *dst = f32 ? src + (size_t)n * npx : out16;
+				unsigned short *dst = (f32 || win) ? src + (size_t)n * npx : out16;
 				if (rir_remove_motion_device(src, dst, width, height, height - 3, n, dio_shift.as<float>() + 2 * (size_t)k0, st) != 0)
 					return false;
 				res = dst;
 			}
+			if (win)
+				return hip_ok(launch_crop_window(res, width, height, win->y0, win->x0, win->h, win->w, n, f32,
+												 static_cast<char *>(d_out) + (size_t)k0 * wpx * (f32 ? 4 : 2), st),
+							  "window");
 			if (f32)
 				return hip_ok(launch_u16_to_f32(res, static_cast<float *>(d_out) + (size_t)k0 * npx, (int64_t)n * npx, st), "u16 -> f32");
 			return res == out16 || hip_ok(hipMemcpyAsync(out16, res, (size_t)n * npx * 2, hipMemcpyDefault, st), "D2D");
 		}
 
-		bool load_images_device(int first, int count, int step, bool f32, void *d_out, hipStream_t caller)
+		// win (rir_load_window_device): d_out takes that window of every image, [count][win->h][win->w].  Without a read-back filter only
+		// the window is read where the file allows it - of a RIRB chunk the tables and payload of the tiles [t_lo, t_lo + nw) its rows lie
+		// in (rirb1_decode_window) - and only the window goes up for the other kinds; with one the images are made whole, as without a
+		// window, and the window is cut out of the filtered images (dio_finish).
+		bool load_images_device(int first, int count, int step, bool f32, void *d_out, hipStream_t caller, const RirbWindow *win = nullptr)
 		{
 			const bool do_bp = filter_bad_pixels(), do_motion = filter_motion(), filtered = do_bp || do_motion;
 			if (filtered && height <= 3)
 				return false;
 			const size_t npx = (size_t)width * height, fbytes = npx * 2;
+			// uint16 bytes of an image as it comes to the device: whole, or the window when nothing needs more
+			const bool cut = win && !filtered;
+			const size_t ubytes = cut ? (size_t)win->h * win->w * 2 : fbytes;
 			if (!dio_st && !hip_ok(hipStreamCreateWithFlags(&dio_st, hipStreamNonBlocking), "hipStreamCreate"))
 			{
 				dio_st = nullptr;
@@ -2106,33 +2121,37 @@ namespace
 				dio_ev_set[b] = true;
 				return true;
 			};
-			const size_t scratch_frames_per = (filtered || f32) ? ((f32 && do_motion) ? 2 : 1) : 0;
+			// (a filtered window leaves the scratch through the crop: motion correction cannot write the output itself)
+			const size_t scratch_frames_per = (filtered || f32) ? (((f32 || win) && do_motion) ? 2 : 1) : 0;
 			if (kind != RIRB)
 			{ // raw frames (PCR, BIN) / one zstd frame per image (ZFile): read on the host, up in batches
-				const int per = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, kDioBatchBytes / fbytes,
-																			 scratch_frames_per ? kDioScratchBytes / (fbytes * scratch_frames_per) : (size_t)count}));
+				const int per = (int)std::max<size_t>(1, std::min<size_t>({(size_t)count, kDioBatchBytes / ubytes,
+																			 scratch_frames_per ? kDioScratchBytes / (ubytes * scratch_frames_per) : (size_t)count}));
 				std::vector<char> comp(kind == ZFILE ? z_buf.size() : 0);
-				if (scratch_frames_per && !dio_scr.reserve((size_t)per * fbytes * scratch_frames_per))
+				std::vector<unsigned short> whole(cut ? npx : 0); // the image a window's rows are copied out of
+				if (scratch_frames_per && !dio_scr.reserve((size_t)per * ubytes * scratch_frames_per))
 					return false;
 				for (int k0 = 0, bi = 0; k0 < count; k0 += per, ++bi)
 				{
 					const int b = bi & 1, n = std::min(per, count - k0);
-					if (!take_buffer(b) || !dio_h[b].reserve((size_t)n * fbytes))
+					if (!take_buffer(b) || !dio_h[b].reserve((size_t)n * ubytes))
 						return false;
 					for (int k = 0; k < n; ++k)
 					{
 						const int pos = first + (k0 + k) * step;
-						unsigned short *dst = dio_h[b].as<unsigned short>() + (size_t)k * npx;
-						const bool ok = kind == PCR ? read_at(pcr_start + pcr_transfer * (int64_t)pos, dst, fbytes) : zfile_image(pos, dst, comp);
+						unsigned short *dst = dio_h[b].as<unsigned short>() + (size_t)k * (ubytes / 2), *img = cut ? whole.data() : dst;
+						const bool ok = kind == PCR ? read_at(pcr_start + pcr_transfer * (int64_t)pos, img, fbytes) : zfile_image(pos, img, comp);
 						if (!ok)
 						{
 							log_error("rir_load_images_device: image " + std::to_string(pos) + " could not be read");
 							return false;
 						}
+						for (int y = 0; cut && y < win->h; ++y)
+							std::memcpy(dst + (size_t)y * win->w, img + (size_t)(win->y0 + y) * width + win->x0, (size_t)win->w * 2);
 					}
-					void *up = scratch_frames_per ? dio_scr.ptr : static_cast<void *>(static_cast<char *>(d_out) + (size_t)k0 * fbytes);
-					if (!hip_ok(hipMemcpyAsync(up, dio_h[b].ptr, (size_t)n * fbytes, hipMemcpyDefault, st), "H2D") ||
-						(scratch_frames_per && !dio_finish(k0, n, f32, d_out, do_bp, do_motion, st)) || !release_buffer(b))
+					void *up = scratch_frames_per ? dio_scr.ptr : static_cast<void *>(static_cast<char *>(d_out) + (size_t)k0 * ubytes);
+					if (!hip_ok(hipMemcpyAsync(up, dio_h[b].ptr, (size_t)n * ubytes, hipMemcpyDefault, st), "H2D") ||
+						(scratch_frames_per && !dio_finish(k0, n, f32, d_out, do_bp, do_motion, st, win)) || !release_buffer(b))
 						return false;
 				}
 				return hip_ok(wait_stream(st), "sync");
@@ -2143,6 +2162,7 @@ namespace
 				int c;
 				ChunkHeader ch;
 				RirbSelect e;
+				uint64_t pay_first, pay_words; // the words of the chunk's payload this read takes: all of them, or a window's tiles'
 			};
 			std::vector<Job> jobs;
 			const int64_t last = (int64_t)first + (int64_t)(count - 1) * step;
@@ -2165,6 +2185,7 @@ namespace
 				}
 				j.e.chunk = 0, j.e.nframes = (int)cn, j.e.first = (int)(first + k_lo * step - cf), j.e.count = (int)(k_hi - k_lo), j.e.step = step;
 				j.e.out_first = (int)k_lo;
+				j.pay_first = 0, j.pay_words = j.ch.payload_words;
 				covered += k_hi - k_lo;
 				jobs.push_back(j);
 			}
@@ -2174,7 +2195,33 @@ namespace
 				return false;
 			}
 			const int ntiles = cc.L.ntiles, gop = (int)hd.gop;
-			const size_t hdr_per = (size_t)ntiles * gop * 8, toff_per = ((size_t)ntiles + 1) * 4;
+			// the tiles read of every chunk: all, or (cut) those the window's rows lie in - one run, so three shorter reads a chunk.  Their
+			// tile offsets are read now: they say how much payload a chunk gives, which the batches below are cut by.  Of tile_offsets_ok
+			// a slice can check this much: offsets that do not decrease, a slice inside the chunk's payload.
+			int t_lo = 0, nw = ntiles;
+			if (cut)
+			{
+				t_lo = (int)(((int64_t)win->y0 * width + win->x0) / RIRB1_TILE_PX);
+				nw = (int)(((int64_t)(win->y0 + win->h - 1) * width + win->x0 + win->w - 1) / RIRB1_TILE_PX) + 1 - t_lo;
+			}
+			const size_t hdr_all = (size_t)ntiles * gop * 8, toff_all = ((size_t)ntiles + 1) * 4; // (what precedes the payload in the file)
+			const size_t hdr_per = (size_t)nw * gop * 8, toff_per = ((size_t)nw + 1) * 4;
+			std::vector<uint32_t> win_toff(cut ? jobs.size() * ((size_t)nw + 1) : 0);
+			for (size_t j = 0; cut && j < jobs.size(); ++j)
+			{
+				uint32_t *toff = &win_toff[j * ((size_t)nw + 1)];
+				if (!read_at(index[jobs[j].c].file_offset + sizeof(ChunkHeader) + hdr_all + (size_t)t_lo * 4, toff, toff_per))
+					return false;
+				bool ok = (uint64_t)toff[nw] <= jobs[j].ch.payload_words;
+				for (int t = 0; t < nw && ok; ++t)
+					ok = toff[t] <= toff[t + 1];
+				if (!ok)
+				{
+					log_error("RIRB file: corrupted tile offsets");
+					return false;
+				}
+				jobs[j].pay_first = toff[0], jobs[j].pay_words = toff[nw] - toff[0];
+			}
 			// the batches: chunks j0 .. j1 - 1, as many as kDioBatchChunks, kDioBatchBytes and (filtered) the scratch allow
 			struct Batch
 			{
@@ -2188,11 +2235,11 @@ namespace
 				Batch bt{j0, j0, 0, 0};
 				while (bt.j1 < jobs.size() && (int)(bt.j1 - j0) < kDioBatchChunks)
 				{
-					const size_t more = (bt.j1 - j0 + 1) * (hdr_per + toff_per + 32) + (bt.pay_words + jobs[bt.j1].ch.payload_words) * 8;
+					const size_t more = (bt.j1 - j0 + 1) * (hdr_per + toff_per + 32) + (bt.pay_words + jobs[bt.j1].pay_words) * 8;
 					const size_t scr = (size_t)(bt.sel_frames + jobs[bt.j1].e.count) * fbytes * scratch_frames_per;
 					if (bt.j1 > j0 && (more > kDioBatchBytes || scr > kDioScratchBytes))
 						break;
-					bt.pay_words += jobs[bt.j1].ch.payload_words, bt.sel_frames += jobs[bt.j1].e.count;
+					bt.pay_words += jobs[bt.j1].pay_words, bt.sel_frames += jobs[bt.j1].e.count;
 					++bt.j1;
 				}
 				max_sel = std::max(max_sel, bt.sel_frames);
@@ -2223,10 +2270,12 @@ namespace
 					uint64_t off = index[jb.c].file_offset + sizeof(ChunkHeader);
 					uint64_t *hdr = reinterpret_cast<uint64_t *>(h + o_hdr + (size_t)i * hdr_per);
 					uint32_t *toff = reinterpret_cast<uint32_t *>(h + o_toff + (size_t)i * toff_per);
-					if (!read_at_large(off, hdr, hdr_per) || !read_at(off + hdr_per, toff, toff_per) ||
-						(jb.ch.payload_words && !read_at_large(off + hdr_per + toff_per, h + o_pay + words * 8, (size_t)jb.ch.payload_words * 8)))
+					if (cut) // (read and checked above)
+						std::memcpy(toff, &win_toff[(j0 + i) * ((size_t)nw + 1)], toff_per);
+					if (!read_at_large(off + (size_t)t_lo * gop * 8, hdr, hdr_per) || (!cut && !read_at(off + hdr_all, toff, toff_per)) ||
+						(jb.pay_words && !read_at_large(off + hdr_all + toff_all + jb.pay_first * 8, h + o_pay + words * 8, (size_t)jb.pay_words * 8)))
 						return false;
-					if (!tile_offsets_ok(jb.ch, toff))
+					if (!cut && !tile_offsets_ok(jb.ch, toff))
 					{
 						log_error("RIRB file: corrupted tile offsets");
 						return false;
@@ -2235,7 +2284,7 @@ namespace
 					tab[i].chunk = i;
 					tab[i].out_first = filtered ? jb.e.out_first - k0 : jb.e.out_first;
 					coff[i] = words;
-					words += jb.ch.payload_words;
+					words += jb.pay_words;
 				}
 				coff[nb] = words;
 				reinterpret_cast<uint64_t *>(h + o_pay)[words] = 0;
@@ -2247,13 +2296,20 @@ namespace
 				if (filtered)
 					out = dio_scr.ptr, out_frames = sel_frames;
 				const bool add_min = min_T && min_T_rows > 0;
-				if (!hip_ok(launch_decode_select(reinterpret_cast<const uint64_t *>(src + o_hdr), reinterpret_cast<const uint32_t *>(src + o_toff),
-												 reinterpret_cast<const uint64_t *>(src + o_coff), reinterpret_cast<const uint64_t *>(src + o_pay), words, (int64_t)npx,
-												 ntiles, gop, nb, reinterpret_cast<const RirbSelect *>(src), nb, out_frames, f32 && !filtered, out,
-												 add_min ? width * std::min(min_T_rows, height) : 0, add_min ? (uint32_t)min_T : 0u, dio_err.as<int>(), st),
-							"decode"))
+				const int min_px = add_min ? width * std::min(min_T_rows, height) : 0;
+				const uint32_t min_t = add_min ? (uint32_t)min_T : 0u;
+				const hipError_t launched =
+					cut ? launch_decode_window(reinterpret_cast<const uint64_t *>(src + o_hdr), reinterpret_cast<const uint32_t *>(src + o_toff),
+											   reinterpret_cast<const uint64_t *>(src + o_coff), reinterpret_cast<const uint64_t *>(src + o_pay), words, (int64_t)npx,
+											   width, *win, t_lo, nw, gop, nb, reinterpret_cast<const RirbSelect *>(src), nb, out_frames, f32, out, min_px, min_t,
+											   dio_err.as<int>(), st)
+						: launch_decode_select(reinterpret_cast<const uint64_t *>(src + o_hdr), reinterpret_cast<const uint32_t *>(src + o_toff),
+											   reinterpret_cast<const uint64_t *>(src + o_coff), reinterpret_cast<const uint64_t *>(src + o_pay), words, (int64_t)npx,
+											   ntiles, gop, nb, reinterpret_cast<const RirbSelect *>(src), nb, out_frames, f32 && !filtered, out, min_px, min_t,
+											   dio_err.as<int>(), st);
+				if (!hip_ok(launched, "decode"))
 					return false;
-				if ((filtered && !dio_finish(k0, sel_frames, f32, d_out, do_bp, do_motion, st)) || !release_buffer(b))
+				if ((filtered && !dio_finish(k0, sel_frames, f32, d_out, do_bp, do_motion, st, win)) || !release_buffer(b))
 					return false;
 			}
 			if (!hip_ok(hipMemcpyAsync(dio_err_h.ptr, dio_err.ptr, sizeof(int), hipMemcpyDeviceToHost, st), "D2H") || !hip_ok(wait_stream(st), "sync"))
@@ -2868,6 +2924,36 @@ RIR_EXPORT int rir_load_images_device(int cam, int first, int count, int step, i
 		return -1;
 	return guarded("rir_load_images_device", -1,
 				   [&] { return c->load_images_device(first, count, step, esz == 4, d_out, static_cast<hipStream_t>(stream)) ? count : -1; });
+}
+
+// Extension: the window of h rows of w pixels at (y0, x0) of the images rir_load_images_device gives, [count][h][w] in d_out - bit for bit
+// that call's result cut to the window.  Without a read-back filter only the window's tiles of a recording of this library are read, sent
+// and decoded (a corruption elsewhere in the chunks is not seen); with one the images are made whole first.  Returns count, -1 on failure.
+RIR_EXPORT int rir_load_window_device(int cam, int first, int count, int step, int y0, int x0, int h, int w, int dtype, void *d_out, long long out_bytes,
+									  void *stream)
+{
+	auto c = camera(cam);
+	if (!c)
+	{
+		log_error("rir_load_window_device: NULL camera");
+		return -1;
+	}
+	const long long esz = dtype == 'H' ? 2 : dtype == 'f' ? 4 : 0;
+	const int64_t last = (int64_t)first + (int64_t)(count - 1) * step;
+	if (esz == 0 || count < 0 || step < 1 || (count > 0 && (first < 0 || last >= c->count || !d_out)) || y0 < 0 || x0 < 0 || h < 1 || w < 1 ||
+		y0 > c->height - h || x0 > c->width - w || out_bytes < (long long)count * h * w * esz)
+	{
+		log_error("rir_load_window_device: invalid argument (dtype 'H' or 'f', step >= 1, images inside the file, a window of at least one pixel inside "
+				  "the image, an output of count windows)");
+		return -1;
+	}
+	if (count == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	const RirbWindow win{y0, x0, h, w};
+	return guarded("rir_load_window_device", -1,
+				   [&] { return c->load_images_device(first, count, step, esz == 4, d_out, static_cast<hipStream_t>(stream), &win) ? count : -1; });
 }
 
 // Extension: `count` uint16 frames [count][h][w] of device memory, queued on `stream`, appended to an open lossless saver without

@@ -265,18 +265,41 @@ class IRMovie(object):
         self._current = pos
         return image
 
-    def to_tensor(self, selection=slice(None), dtype=None, out=None, temporal_median=None, median_threshold=0):
+    def _window(self, window, what):
+        """``window`` as four Python ints ``(y0, x0, h, w)``, checked against the image size"""
+        if not isinstance(window, (tuple, list)) or len(window) != 4 or not all(type(v) is int for v in window):
+            raise ValueError("%s: window=(y0, x0, h, w), four ints, expected, not %r" % (what, window))
+        y0, x0, h, w = window
+        H, W = self.image_size
+        if h < 1 or w < 1 or y0 < 0 or x0 < 0 or y0 + h > H or x0 + w > W:
+            raise ValueError("%s: window %r is empty or not inside the %d x %d image" % (what, tuple(window), H, W))
+        return y0, x0, h, w
+
+    def _load_device(self, first, count, step, out, window):
+        if window is None:
+            _abi.load_images_device(self.handle, first, count, step, out)
+        else:
+            _abi.load_window_device(self.handle, first, count, step, window, out)
+
+    def to_tensor(self, selection=slice(None), dtype=None, out=None, temporal_median=None, median_threshold=0, window=None):
         """Images of ``selection`` (an int, or a slice with a positive step; negative bounds as ``movie[...]`` takes them) as a CUDA
         tensor ``[n][h][w]`` of ``dtype`` (``torch.uint16``, the default, or ``torch.float32``) on the current CUDA device - the images
         ``movie[selection]`` gives, bit for bit, decoded on the device: only the compressed chunks of a recording of this library cross
         the link.  ``out``: a preallocated C-contiguous CUDA tensor of that shape and dtype.  The current image (``load_pos``) and its
         attributes stay what they were.
 
+        ``window=(y0, x0, h, w)`` (Python ints, inside the image): the result is ``[n][h][w]``, bit for bit
+        ``to_tensor(...)[:, y0:y0+h, x0:x0+w]``.  With no read-back filter on, only the 512-pixel tiles of a recording of this library
+        that the window's rows lie in are read, sent and decoded; with one, the images are made whole on the device and cut there.
+
         ``temporal_median=W`` (odd, 1..63): each selected image p becomes the temporal median of the images p - W//2 .. p + W//2 of the
         recording as ``movie[...]`` gives them (read-back filters applied first; the window is truncated only at the recording's first and
         last image), taken where it differs from image p by more than ``median_threshold`` - ``librir_amd.device.temporal_median``.  The
         recording is read in pieces with W//2 images of halo on either side: the temporary device memory holds at most
-        max(64 MiB, W images) of uint16 input, plus as many uint16 output images for a float32 result, whatever the selection's length."""
+        max(64 MiB, W images) of uint16 input, plus as many uint16 output images for a float32 result, whatever the selection's length
+        (with a window the pieces are read through it and counted in window bytes)."""
+        if window is not None:  # (before anything touches the device)
+            window = self._window(window, "to_tensor")
         import torch
 
         dtype = torch.uint16 if dtype is None else dtype
@@ -301,7 +324,7 @@ class IRMovie(object):
             positions, _ = self._positions(selection)
         else:
             raise TypeError("to_tensor: an int or a slice expected")
-        h, w = self.image_size
+        h, w = self.image_size if window is None else window[2:]
         shape = (len(positions), h, w)
         if out is None:
             out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
@@ -311,27 +334,27 @@ class IRMovie(object):
             if positions.start < 0 or positions[-1] >= total:
                 raise IndexError("to_tensor: images %s out of range (%d images)" % (positions, total))
             if temporal_median is None:
-                _abi.load_images_device(self.handle, positions.start, len(positions), positions.step, out)
+                self._load_device(positions.start, len(positions), positions.step, out, window)
             else:
-                self._median_to_tensor(positions, int(temporal_median), int(median_threshold), out)
+                self._median_to_tensor(positions, int(temporal_median), int(median_threshold), out, window)
         return out
 
     _MEDIAN_PIECE_BYTES = 64 << 20  # uint16 input images read at once by to_tensor(temporal_median=...)
 
-    def _median_to_tensor(self, positions, window, threshold, out):
+    def _median_to_tensor(self, positions, window, threshold, out, crop=None):
         import torch
 
         from ..device import temporal_median
 
         r, total, step = window // 2, self.images, positions.step
-        h, w = self.image_size
+        h, w = self.image_size if crop is None else crop[2:]
         budget = max(window, self._MEDIAN_PIECE_BYTES // (2 * h * w))  # input images per piece
         per_piece = max(1, (budget - 2 * r - 1) // step + 1)  # outputs per piece: their images, halo included, fit the budget
         for k0 in range(0, len(positions), per_piece):
             sel = positions[k0:k0 + per_piece]
             lo, hi = max(0, sel[0] - r), min(total, sel[-1] + r + 1)
             stack = torch.empty((hi - lo, h, w), dtype=torch.uint16, device=out.device)
-            _abi.load_images_device(self.handle, lo, hi - lo, 1, stack)
+            self._load_device(lo, hi - lo, 1, stack, crop)
             dst = out[k0:k0 + len(sel)]
             if out.dtype == torch.uint16:
                 temporal_median(stack, window, threshold, first=sel[0] - lo, count=len(sel), step=step, out=dst)
@@ -345,11 +368,19 @@ class IRMovie(object):
         numpy or CUDA, uploaded once - ``librir_amd.device.region_stats`` over the images ``movie[selection]`` gives (read-back filters
         applied): a ``RegionStats`` of CUDA tensors ``[len(selection)][nregions]``.  ``nregions=None`` takes labels.max() + 1.  The
         recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of images, so the device memory used does not grow with the selection."""
+        return self.region_stats_window(labels, None, selection, nregions)
+
+    def region_stats_window(self, labels, window, selection=slice(None), nregions=None):
+        """``region_stats`` of the window ``(y0, x0, h, w)`` of the images, read through it (``to_tensor(window=...)``): ``labels`` is the
+        (h, w) of the window, the result that of ``librir_amd.device.region_stats`` on ``to_tensor(selection)[:, y0:y0+h, x0:x0+w]``, the
+        pieces are counted in window bytes.  ``window=None``: the whole image."""
+        if window is not None:
+            window = self._window(window, "region_stats")
         import torch
 
         from ..device import _region_inputs, _region_stats_empty, _region_stats_into
 
-        h, w = self.image_size
+        h, w = self.image_size if window is None else window[2:]
         if isinstance(labels, np.ndarray):
             if labels.dtype != np.int32:
                 raise RuntimeError("region_stats: int32 labels expected, not %s" % labels.dtype)
@@ -366,7 +397,7 @@ class IRMovie(object):
         for k0 in range(0, len(positions), per_piece):
             sel = positions[k0:k0 + per_piece]
             fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr, window=window)
             _region_stats_into(fr, lab, 0, int(nregions), type(out)(*(t[k0:k0 + len(sel)] for t in out)))
         return out
 
@@ -528,11 +559,19 @@ class IRMovie(object):
         and sum of squares (``sums``), the min, the max and where each first occurs (``extremes``).  ``argmin`` / ``argmax`` index into the
         selection: k means image ``movie[selection][k]``.  The recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of images
         into one accumulator, so the device memory used does not grow with the selection."""
+        return self.pixel_stats_window(None, selection, sums, extremes)
+
+    def pixel_stats_window(self, window, selection=slice(None), sums=True, extremes=True):
+        """``pixel_stats`` of the window ``(y0, x0, h, w)`` of the images, read through it (``to_tensor(window=...)``): tensors ``[h][w]`` of
+        the window, the result that of ``librir_amd.device.pixel_stats`` on ``to_tensor(selection)[:, y0:y0+h, x0:x0+w]``, the pieces are
+        counted in window bytes.  ``window=None``: the whole image."""
+        if window is not None:
+            window = self._window(window, "pixel_stats")
         import torch
 
         from ..device import PixelStatsAccumulator
 
-        h, w = self.image_size
+        h, w = self.image_size if window is None else window[2:]
         positions = self._stats_positions(selection, "pixel_stats")
         device = torch.device("cuda", torch.cuda.current_device())
         acc = PixelStatsAccumulator(sums, extremes, shape=(h, w), device=device)
@@ -541,7 +580,7 @@ class IRMovie(object):
         for k0 in range(0, len(positions), per_piece):
             sel = positions[k0:k0 + per_piece]
             fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr, window=window)
             acc.push(fr, k0)
         return acc.result()
 

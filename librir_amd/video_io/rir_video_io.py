@@ -22,6 +22,7 @@ _v.open_camera_from_memory.argtypes = [_vp, ct.c_int64, _ip]
 _v.video_file_format.argtypes = [ct.c_char_p]
 _v.rir_transcode_images.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p, ct.c_int]
 _v.rir_load_images_device.argtypes = [ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_void_p, ct.c_longlong, ct.c_void_p]
+_v.rir_load_window_device.argtypes = [ct.c_int] * 9 + [ct.c_void_p, ct.c_longlong, ct.c_void_p]
 _v.rir_add_images_device.argtypes = [ct.c_int, ct.c_void_p, ct.c_int, ct.c_void_p, ct.c_void_p]
 _v.get_image_time.argtypes = [ct.c_int, ct.c_int, ct.POINTER(ct.c_int64)]
 _v.get_image_size.argtypes = [ct.c_int, _ip, _ip]
@@ -391,6 +392,22 @@ def load_images_device(camera, first, count, step, out, stream=None):
     r = _v.rir_load_images_device(camera, int(first), int(count), int(step), code, out.data_ptr(), out.numel() * out.element_size(), st.cuda_stream)
     if r != count:
         _fail("rir_load_images_device")
+    return out
+
+
+def load_window_device(camera, first, count, step, window, out, stream=None):
+    """Extension (``rir_load_window_device``): the window ``(y0, x0, h, w)`` of the images ``load_images_device`` gives into ``out``, a
+    C-contiguous CUDA tensor ``[count][h][w]`` of ``torch.uint16`` or ``torch.float32`` - of a recording of this library only the tiles
+    the window touches are read, sent and decoded when no read-back filter is on."""
+    import torch
+
+    code = {torch.uint16: ord("H"), torch.float32: ord("f")}[out.dtype]
+    st = torch.cuda.current_stream(out.device) if stream is None else stream
+    y0, x0, h, w = (int(v) for v in window)
+    r = _v.rir_load_window_device(camera, int(first), int(count), int(step), y0, x0, h, w, code, out.data_ptr(), out.numel() * out.element_size(),
+                                  st.cuda_stream)
+    if r != count:
+        _fail("rir_load_window_device")
     return out
 
 
