@@ -272,6 +272,33 @@ extern "C"
 	int rir_rank_filter_device(int type, const void *d_src, void *d_dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows,
 							   void *stream);
 
+	/* Exact Euclidean distance transform of a stack of masks or label maps d_src[nframes][h][w] (extension): d_dist2[nframes][h][w], int32,
+	 * the SQUARED distance of every pixel to the nearest background pixel of its frame, and - unless d_index is NULL - d_index[nframes][h][w],
+	 * int32, which pixel that is.  type: '?' bool (one byte, 0 / 1), 'B' uint8, 'H' uint16, 'i' int32.  A cell is background when it equals
+	 * `background` (which must lie in the type's range: 0..1, 0..255, 0..65535, any int), foreground otherwise.  The image is the first
+	 * `rows` (0..h) rows of a frame; rows y >= `rows` are read by nothing and get dist2 0 and index y * w + x, their own.  For an image
+	 * pixel p = (y, x):
+	 *   dist2[p] = min over the background pixels q = (qy, qx) of the image of (y - qy)^2 + (x - qx)^2      (0 on background)
+	 *   index[p] = the LOWEST flat index qy * w + qx among the background pixels at that minimum
+	 * An image without a background pixel gets dist2 RIR_DIST2_NONE and index -1 everywhere.  border 1: everything outside the image
+	 * counts as background too - dist2[p] = min(dist2[p], b^2), b = min(x + 1, w - x, y + 1, rows - y) - and index[p] = -1 where the
+	 * outside is STRICTLY nearer than every background pixel.  1 <= w, h <= 16384, so every distance fits.  Where a background pixel
+	 * exists, dist2 is round(scipy.ndimage.distance_transform_edt(src != background)^2); scipy's return_indices breaks ties differently.
+	 * With fg = src != background and r2 = floor(r^2): fg & (dist2 > r2) is the erosion of fg by the Euclidean disc of radius r with
+	 * the outside foreground (border 0) or background (border 1), and dist2 of the inverted mask <= r2 its dilation.  All integer, bit for
+	 * bit, the same bits for any split of the stack into calls.  Two launches per group of frames, work per row and per column linear in
+	 * its length, nothing on the host in between.  d_work: device memory, 8-byte aligned, at least ONE frame's share of
+	 * rir_distance_transform_workspace_bytes(w, h, nframes, want_indices) (which is nframes shares, 256 MiB worth of them at most, or 0
+	 * when w, h, nframes or want_indices are refused): the stack goes through in groups of as many frames as the workspace holds.
+	 * Asynchronous on `stream`; no output or the workspace may overlap the input or another output.  nframes 0: nothing is done, 0.
+	 * -1 with the reason logged (argument errors before the device is looked for): unknown type, background outside the type's range,
+	 * border not 0 / 1, rows outside 0..h, w or h outside 1..16384, nframes < 0, a null d_src, d_dist2 or d_work, overlap, a workspace
+	 * that is too small or misaligned, no device. */
+#define RIR_DIST2_NONE 0x7fffffff
+	size_t rir_distance_transform_workspace_bytes(int w, int h, int nframes, int want_indices);
+	int rir_distance_transform_device(int type, const void *d_src, int w, int h, int nframes, int background, int border, int rows, int *d_dist2,
+									  int *d_index /* may be NULL */, void *d_work, size_t work_bytes, void *stream);
+
 	/* Per-region statistics of a uint16 stack d_frames[nframes][h][w] (extension).  d_labels: int32, one map [h][w] for every frame
 	 * (labels_per_frame 0) or one per frame [nframes][h][w] (1).  For frame f and region r < nregions (1..2^24), P = the flat indices
 	 * i = y * w + x whose label is r; labels outside [0, nregions) are ignored.  Outputs [nframes][nregions]: d_count = |P|, d_sum and

@@ -80,6 +80,15 @@ extern "C"
 	 * -1 with the reason logged on a bad argument (before the device is looked for) and without a device ("no usable HIP device", dst
 	 * untouched: there is no CPU fallback). */
 	int rir_rank_filter(int type, const void *src, void *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows);
+	/* Exact Euclidean distance transform of a host stack src[nframes][h][w]: rir_distance_transform_device (rir_amd_device.h, where the rule
+	 * is defined) over the stack, synchronous.  type '?' bool, 'B' uint8, 'H' uint16, 'i' int32; a cell equal to `background` is
+	 * background; dist2[nframes][h][w] (int32) is the squared distance to the nearest background pixel among the first `rows` (0..h) rows
+	 * of the frame - with border 1 also to the outside of the image -, RIR_DIST2_NONE where there is none; index (int32, may be NULL) the
+	 * lowest flat index y * w + x of such a pixel, -1 where there is none or the outside is strictly nearer.  1 <= w, h <= 16384.  Large
+	 * stacks go through the device in slabs sized by a frame's input, outputs and workspace, 64 MiB each at most (frames are independent).
+	 * No output may overlap the input or the other output.  nframes 0: 0.  -1 with the reason logged on a bad argument (before the device
+	 * is looked for) and without a device ("no usable HIP device", outputs untouched: there is no CPU fallback). */
+	int rir_distance_transform(int type, const void *src, int w, int h, int nframes, int background, int border, int rows, int *dist2, int *index);
 	/* Per-region statistics of a host stack frames[nframes][h][w] with host label maps: rir_region_stats_device (rir_amd_device.h),
 	 * synchronous, host outputs [nframes][nregions].  The frames go through the device in slabs of at most 64 MiB; a shared map goes up
 	 * once.  0 / -1. */

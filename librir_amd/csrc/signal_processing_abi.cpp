@@ -13,6 +13,7 @@
 #include <initializer_list>
 #include <map>
 
+#include "distance_kernels.h"
 #include "filter_kernels.h"
 #include "geometry_kernels.h"
 #include "histogram_kernels.h"
@@ -742,6 +743,68 @@ RIR_EXPORT int rir_rank_filter_device(int type, const void *d_src, void *d_dst, 
 								w, h, nframes, [=] { return launch_rank_filter(type, d_src, d_dst, w, h, nframes, rank, size_x, size_y, rows, as_stream(stream)); });
 }
 
+// The exact Euclidean distance transform (distance_kernels.hip).  Every argument is checked here, before the device is looked for; no output
+// (workspace included) may overlap the input or another output.
+namespace
+{
+	constexpr size_t DISTANCE_WORK_BYTES = (size_t)256 << 20; // what the workspace query asks for at most, or one frame's need
+
+	int distance_cell_bytes(int type) { return type == '?' || type == 'B' ? 1 : type == 'H' ? 2 : type == 'i' ? 4 : 0; }
+	bool distance_geometry(int w, int h, int nframes) { return w >= 1 && w <= DISTANCE_MAX_SIDE && h >= 1 && h <= DISTANCE_MAX_SIDE && nframes >= 0; }
+
+	// 0, or what is wrong with the arguments that rir_distance_transform and rir_distance_transform_device share, in the order of the tests
+	const char *distance_transform_args(int type, const void *src, int w, int h, int nframes, int background, int border, int rows, const int *dist2,
+										const int *index)
+	{
+		const int cell = distance_cell_bytes(type);
+		if (!cell)
+			return "unknown type (bool '?', uint8 'B', uint16 'H' or int32 'i')";
+		if (cell < 4 && (background < 0 || background > (type == '?' ? 1 : type == 'B' ? 255 : 65535)))
+			return "background outside the range of the type";
+		if (border != 0 && border != 1)
+			return "border must be 0 or 1";
+		if (!distance_geometry(w, h, nframes) || rows < 0 || rows > h)
+			return "invalid shape (1 <= w, h <= 16384, nframes >= 0, 0 <= rows <= h)";
+		if (!src || !dist2)
+			return "null pointer (only the index may be null)";
+		const size_t npx = (size_t)w * h * nframes;
+		if (outputs_overlap({{src, npx * cell}}, {{dist2, npx * 4}, {index, npx * 4}}))
+			return "an output overlaps the input or the other output";
+		return nullptr;
+	}
+} // namespace
+
+RIR_EXPORT size_t rir_distance_transform_workspace_bytes(int w, int h, int nframes, int want_indices)
+{
+	if (!distance_geometry(w, h, nframes) || (want_indices != 0 && want_indices != 1))
+		return 0;
+	const size_t B = distance_frame_bytes(w, h); // (the same with and without indices: the index comes from what the passes keep anyway)
+	return B * std::min<size_t>((size_t)std::max(nframes, 1), std::max<size_t>(1, DISTANCE_WORK_BYTES / B));
+}
+
+RIR_EXPORT int rir_distance_transform_device(int type, const void *d_src, int w, int h, int nframes, int background, int border, int rows, int *d_dist2,
+											 int *d_index, void *d_work, size_t work_bytes, void *stream)
+{
+	if (const char *bad = distance_transform_args(type, d_src, w, h, nframes, background, border, rows, d_dist2, d_index))
+		return refuse(__func__, bad);
+	const size_t B = distance_frame_bytes(w, h);
+	if (!d_work)
+		return refuse(__func__, "null pointer (the workspace)");
+	if (!workspace_ok(__func__, d_work, work_bytes, B, "workspace", "one frame's share of rir_distance_transform_workspace_bytes()"))
+		return -1;
+	const size_t npx = (size_t)w * h * nframes, used = B * std::min<size_t>((size_t)nframes, work_bytes / B);
+	if (outputs_overlap({{d_src, npx * distance_cell_bytes(type)}, {d_dist2, npx * 4}, {d_index, npx * 4}}, {{d_work, used}}))
+		return refuse(__func__, "the workspace overlaps the input or an output");
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	return hip_ok(launch_distance_transform(type, d_src, w, h, nframes, background, border, rows, d_dist2, d_index, d_work, work_bytes, as_stream(stream)),
+				  "distance_transform")
+			   ? 0
+			   : -1;
+}
+
 // Per-region statistics (region_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an input or
 // another output.
 namespace
@@ -1438,6 +1501,36 @@ RIR_EXPORT int rir_rank_filter(int type, const void *src, void *dst, int w, int 
 							  nframes, [=](const void *in, void *out, int count, void *st) {
 								  return rir_rank_filter_device(type, in, out, w, h, count, rank, size_x, size_y, rows, st);
 							  });
+}
+
+// The distance transform of a host stack (frames are independent: any split gives the same bits); a slab is bounded by what a frame's input,
+// outputs and workspace take on the device.  index may be null.
+RIR_EXPORT int rir_distance_transform(int type, const void *src, int w, int h, int nframes, int background, int border, int rows, int *dist2, int *index)
+{
+	if (const char *bad = distance_transform_args(type, src, w, h, nframes, background, border, rows, dist2, index))
+		return refuse(__func__, bad);
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	const size_t npx = (size_t)w * h, frame = npx * distance_cell_bytes(type), outs_bytes = npx * 4 * (index ? 2 : 1);
+	const int slab = Stager::slab(nframes, {frame, outs_bytes, distance_frame_bytes(w, h)});
+	const size_t work = distance_frame_bytes(w, h) * slab;
+	DeviceBuffer in, o32, ws;
+	if (!in.reserve(frame * slab) || !o32.reserve(outs_bytes * slab) || !ws.reserve(work))
+		return -1;
+	int *d_dist2 = o32.as<int>(), *d_index = index ? d_dist2 + npx * slab : nullptr;
+	const Out outs[] = {{dist2, d_dist2, 4}, {index, d_index, 4}};
+	Stager s;
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int c = std::min(slab, nframes - o);
+		if (!s.up(in.ptr, static_cast<const char *>(src) + frame * o, frame * c) ||
+			rir_distance_transform_device(type, in.ptr, w, h, c, background, border, rows, d_dist2, d_index, ws.ptr, work, s.st) != 0 ||
+			!s.down(outs, o * npx, c * npx) || !s.wait("distance_transform"))
+			return s.fail();
+	}
+	return 0;
 }
 
 // Per-region statistics of a host stack: a shared label map goes up once, per-frame maps go up with their frames; a slab is also bounded by

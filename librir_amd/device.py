@@ -10,9 +10,10 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
-from .signal_processing.rir_signal_processing import (PixelStats, RegionGeometry, RegionHistogram, RegionQuantiles, RegionStats,  # noqa: F401 (API)
-                                                      _pixel_quantiles_args, _pixel_stats_args, _polygon_map_args, _region_geometry_args,
-                                                      _region_histogram_args, _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
+from .signal_processing.rir_signal_processing import (DIST2_NONE, DISTANCE_MAX_SIDE, PixelStats, RegionGeometry, RegionHistogram,  # noqa: F401 (API)
+                                                      RegionQuantiles, RegionStats, _distance_transform_args, _pixel_quantiles_args,
+                                                      _pixel_stats_args, _polygon_map_args, _region_geometry_args, _region_histogram_args,
+                                                      _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
                                                       _morphology_args, _rank_filter_args, _temporal_median_args, _window_size,
                                                       percentile_rank)
 
@@ -116,6 +117,9 @@ _lib.rir_median_filter_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int
 _lib.rir_temporal_median_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp]
 _lib.rir_morphology_device.argtypes = [ct.c_int, _vp, _vp] + [ct.c_int] * 7 + [_vp]
 _lib.rir_rank_filter_device.argtypes = [ct.c_int, _vp, _vp] + [ct.c_int] * 7 + [_vp]
+_lib.rir_distance_transform_device.argtypes = [ct.c_int, _vp] + [ct.c_int] * 6 + [_vp, _vp, _vp, ct.c_size_t, _vp]
+_lib.rir_distance_transform_workspace_bytes.argtypes = [ct.c_int] * 4
+_lib.rir_distance_transform_workspace_bytes.restype = ct.c_size_t
 _lib.rir_region_stats_device.argtypes =[_vp, _vp] + [ct.c_int] * 5 + [_vp] * 8 + [ct.c_size_t, _vp]
 _lib.rir_region_stats_workspace_bytes.argtypes = [ct.c_int] * 5
 _lib.rir_region_stats_workspace_bytes.restype = ct.c_size_t
@@ -779,6 +783,109 @@ def percentile_filter(frames, percent, size, rows=None, out=None):
     percent counts from 100"""
     size_y, size_x = _window_sizes(size)
     return rank_filter(frames, percentile_rank(percent, size_y, size_x), size, rows, out)
+
+
+_DISTANCE_WORK_BYTES = 256 << 20  # the workspace of one distance_transform call at most (or one frame's need): longer stacks go in groups
+
+
+def _distance_transform_inputs(masks, background, border, rows, out, return_indices):
+    """distance_transform's checks, the parameters first, which need no device; -> (masks [n][h][w], type char, background, border, rows,
+    dist2, index or None), the outputs of the shape of `masks`"""
+    shape = tuple(masks.shape)
+    dtype_name = np.dtype(_NP_OF[masks.dtype]).name if masks.dtype in _NP_OF else str(masks.dtype)
+    type_char, background, border, rows = _distance_transform_args((1,) + shape if len(shape) == 2 else shape, dtype_name, background, border, rows)
+    outs = (out if return_indices else (out,)) if out is not None else ()
+    if out is not None and (not isinstance(outs, (tuple, list)) or len(outs) != 1 + bool(return_indices) or any(
+            not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() for t in outs)):
+        raise RuntimeError("distance_transform: out must be %s of shape %s" % (
+            "a pair (dist2, index) of contiguous int32 CUDA tensors" if return_indices else "a contiguous int32 CUDA tensor", shape))
+    fr = _frames3(masks)
+    dist2 = outs[0] if outs else torch.empty(shape, dtype=torch.int32, device=fr.device)
+    index = None if not return_indices else outs[1] if outs else torch.empty(shape, dtype=torch.int32, device=fr.device)
+    return fr, type_char, background, border, rows, dist2, index
+
+
+def _distance_transform_into(fr, type_char, background, border, rows, dist2, index):
+    """queue the transform of fr [n][h][w] into dist2 and index (None: not wanted), contiguous int32 of n * h * w cells; the workspace is
+    that of the whole stack or _DISTANCE_WORK_BYTES worth of whole frames, and the entry walks the stack in groups that fit it"""
+    n, h, w = fr.shape
+    want = int(index is not None)
+    one, need = _lib.rir_distance_transform_workspace_bytes(w, h, 1, want), _lib.rir_distance_transform_workspace_bytes(w, h, n, want)
+    if one == 0:
+        raise RuntimeError("distance_transform: geometry refused")
+    work = _workspace(max(one, min(need, _DISTANCE_WORK_BYTES // one * one)), fr.device)
+    _check(_lib.rir_distance_transform_device(type_char, fr.data_ptr(), w, h, n, background, border, rows, dist2.data_ptr(),
+                                              None if index is None else index.data_ptr(), work.data_ptr(), work.numel() * 8, _stream()),
+           "rir_distance_transform_device")
+
+
+def distance_transform(masks, background=0, border=False, rows=None, return_indices=False, out=None):
+    """Exact Euclidean distance transform of a bool, uint8, uint16 or int32 stack ``masks[n][h][w]`` (or one image ``[h][w]``) - masks or
+    label maps - on the current stream (C ABI ``rir_distance_transform_device``, where the rule is defined): an int32 tensor of the input's
+    shape with the SQUARED distance of every pixel to the nearest pixel of its image that equals ``background``, 0 on background,
+    ``DIST2_NONE`` in an image without one.  ``border=True``: everything outside the image is background too.  The image is the first
+    ``rows`` rows of a frame (default: all); the others get 0.  ``return_indices=True``: ``(dist2, index)``, index int32, the lowest flat
+    index ``y * w + x`` among the nearest background pixels - the feature transform -, -1 where there is none or the outside is strictly
+    nearer, a pixel's own index in the rows outside the image.  ``out``: a contiguous int32 CUDA tensor of the input's shape (a pair of them
+    with ``return_indices``) that overlaps neither ``masks`` nor each other.  All integer, bit for bit; a stack whose workspace (2 bytes a
+    pixel) exceeds 256 MiB goes through in groups of frames.  ``dist2 > r * r`` under a mask is its erosion by the disc of radius r
+    (``disc_erode``); the per-region maximum of ``dist2`` under a label map is the squared inscribed radius of each region.  ``ValueError``
+    on bad parameters, before any device work."""
+    fr, type_char, background, border, rows, dist2, index = _distance_transform_inputs(masks, background, border, rows, out, return_indices)
+    if fr.shape[0]:
+        _distance_transform_into(fr, type_char, background, border, rows, dist2, index)
+    return (dist2, index) if return_indices else dist2
+
+
+def _disc_args(name, mask, radius):
+    """the checks of the disc_* forms, which need no device; -> r2 = floor(radius^2)"""
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("%s: a bool or uint8 mask expected, not %s" % (name, mask.dtype))
+    if mask.dim() not in (2, 3) or min(mask.shape[-2:]) < 1 or max(mask.shape[-2:]) > DISTANCE_MAX_SIDE:
+        raise ValueError("%s: a mask [h][w] or a stack [n][h][w] of 1..%d rows and columns expected" % (name, DISTANCE_MAX_SIDE))
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, float, np.integer, np.floating)) or not 0 <= radius < float("inf"):
+        raise ValueError("%s: radius must be a non-negative number (got %r)" % (name, radius))
+    r = float(radius)
+    return int(min(np.floor(r * r), float(DIST2_NONE - 1)))  # (no distance inside a frame reaches 2^31 - 2)
+
+
+def disc_erode(mask, radius, border=False):
+    """Erosion of a bool or uint8 mask ``[n][h][w]`` (or ``[h][w]``; non-zero is set) by the Euclidean disc of ``radius`` (any non-negative
+    number): a pixel stays set when no unset pixel lies within ``radius`` of it, ``mask & (distance_transform(mask) > floor(radius^2))`` -
+    ``scipy.ndimage.binary_erosion`` with the disc ``dy^2 + dx^2 <= radius^2`` and ``border_value=1``; ``border=True`` counts the outside
+    of the image as unset (``border_value=0``).  One distance transform, whatever the radius; radius 0 copies.  Returns a mask of the input's
+    dtype (set is 1 / True)."""
+    r2 = _disc_args("disc_erode", mask, radius)
+    if not isinstance(border, (bool, np.bool_)) and border not in (0, 1):
+        raise ValueError("disc_erode: border must be a bool")
+    if radius == 0:
+        return mask.clone()
+    return ((mask != 0) & (distance_transform(mask, border=border) > r2)).to(mask.dtype)
+
+
+def disc_dilate(mask, radius):
+    """Dilation of a bool or uint8 mask by the Euclidean disc of ``radius``: a pixel is set when a set pixel lies within ``radius`` of it,
+    ``distance_transform(mask == 0) <= floor(radius^2)`` - ``scipy.ndimage.binary_dilation`` with the disc ``dy^2 + dx^2 <= radius^2``.  The
+    transform of the inverted mask (one torch op), whatever the radius: "grow every hot spot by 12 px" is ``disc_dilate(mask, 12)``.  Radius
+    0 copies.  Returns a mask of the input's dtype."""
+    r2 = _disc_args("disc_dilate", mask, radius)
+    if radius == 0:
+        return mask.clone()
+    return (distance_transform(mask == 0) <= r2).to(mask.dtype)
+
+
+def disc_open(mask, radius):
+    """``disc_dilate(disc_erode(mask, radius), radius)``: removes what the disc does not fit into (``scipy.ndimage.binary_opening`` with the
+    disc; the erosion takes the outside of the image as set, as ``disc_erode`` does by default)"""
+    _disc_args("disc_open", mask, radius)
+    return disc_dilate(disc_erode(mask, radius), radius)
+
+
+def disc_close(mask, radius):
+    """``disc_erode(disc_dilate(mask, radius), radius)``: fills what the disc does not fit into (``scipy.ndimage.binary_closing`` with the
+    disc, the outside of the image taken as set by the erosion)"""
+    _disc_args("disc_close", mask, radius)
+    return disc_erode(disc_dilate(mask, radius), radius)
 
 
 class TemporalMedian:

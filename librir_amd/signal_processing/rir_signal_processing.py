@@ -318,6 +318,57 @@ def rank_filter(images, rank, size, rows=None):
     return out.reshape(img.shape)
 
 
+# ---- extension: exact Euclidean distance transform -------------------------------------------------------------------------------
+_sp.rir_distance_transform.argtypes = [ct.c_int, ct.c_void_p] + [ct.c_int] * 6 + [ct.c_void_p, ct.c_void_p]
+
+DIST2_NONE = 0x7FFFFFFF  # dist2 of an image without a background pixel (RIR_DIST2_NONE)
+DISTANCE_MAX_SIDE = 16384
+_DISTANCE_TYPES = {"bool": ("?", 0, 1), "uint8": ("B", 0, 255), "uint16": ("H", 0, 65535), "int32": ("i", -(1 << 31), (1 << 31) - 1)}
+
+
+def _distance_transform_args(shape, dtype_name, background=0, border=False, rows=None):
+    """the parameters of a distance transform over a stack of `shape`, checked without a device; -> (type char, background, border, rows)"""
+    if len(shape) != 3:
+        raise ValueError("distance_transform: a stack [n][h][w] expected")
+    if dtype_name not in _DISTANCE_TYPES:
+        raise ValueError("distance_transform: bool, uint8, uint16 or int32 masks expected, not %s" % dtype_name)
+    type_char, lo, hi = _DISTANCE_TYPES[dtype_name]
+    if not isinstance(background, (int, np.integer)) or (isinstance(background, (bool, np.bool_)) and dtype_name != "bool"):
+        raise ValueError("distance_transform: background must be an int")
+    if not lo <= int(background) <= hi:
+        raise ValueError("distance_transform: background %d is outside the range of %s" % (int(background), dtype_name))
+    if not isinstance(border, (bool, np.bool_)) and border not in (0, 1):
+        raise ValueError("distance_transform: border must be a bool")
+    _, h, w = shape
+    if not (1 <= h <= DISTANCE_MAX_SIDE and 1 <= w <= DISTANCE_MAX_SIDE):
+        raise ValueError("distance_transform: frames of 1..%d rows and columns expected" % DISTANCE_MAX_SIDE)
+    return ord(type_char), int(background), int(bool(border)), _window_rows("distance_transform", shape, rows)
+
+
+def distance_transform(images, background=0, border=False, rows=None, return_indices=False):
+    """Extension: exact Euclidean distance transform of a bool, uint8, uint16 or int32 stack ``images[n][h][w]`` (or one image ``[h][w]``)
+    (``rir_distance_transform``): an int32 array of the input's shape with the SQUARED distance of every pixel to the nearest pixel equal to
+    ``background`` in its image - ``round(scipy.ndimage.distance_transform_edt(images != background) ** 2)`` wherever the image has a
+    background pixel, ``DIST2_NONE`` where it has none.  ``border=True``: everything outside the image is background too.  The image is
+    its first ``rows`` rows (default: all); the others get 0.  ``return_indices=True``: ``(dist2, index)``, index the lowest flat index
+    ``y * w + x`` among the nearest background pixels, -1 where there is none or the outside is strictly nearer, a pixel's own index in
+    the rows outside the image (scipy's ``return_indices`` breaks ties differently).  At most 16 384 rows and columns.  ``ValueError`` on
+    bad parameters, ``RuntimeError`` when the library fails."""
+    img = np.ascontiguousarray(images)
+    if img.ndim not in (2, 3):
+        raise ValueError("distance_transform: an image [h][w] or a stack [n][h][w] expected")
+    stack = img.reshape((-1,) + img.shape[-2:])
+    type_char, background, border, rows = _distance_transform_args(stack.shape, img.dtype.name, background, border, rows)
+    n, h, w = stack.shape
+    dist2 = np.empty(stack.shape, np.int32)
+    index = np.empty(stack.shape, np.int32) if return_indices else None
+    if n and _sp.rir_distance_transform(type_char, stack.ctypes.data, w, h, n, background, border, rows, dist2.ctypes.data,
+                                        index.ctypes.data if return_indices else None) < 0:
+        raise RuntimeError("An error occured while calling 'distance_transform': " + (last_error() or ""))
+    dist2 = dist2.reshape(img.shape)
+    return (dist2, index.reshape(img.shape)) if return_indices else dist2
+
+
 # ---- extension: per-region statistics ------------------------------------------------------------------------------------------
 _sp.rir_region_stats.argtypes = [ct.c_void_p, ct.c_void_p] + [ct.c_int] * 5 + [ct.c_void_p] * 7
 

@@ -731,17 +731,8 @@ class IRMovie(object):
         device = torch.device("cuda", torch.cuda.current_device())
         if filtered:
             kept = _hot_spot_maps_on(kept, device)
-        elif isinstance(threshold, (int, np.integer)):
-            cut = int(threshold)
         else:
-            cut = threshold if isinstance(threshold, torch.Tensor) else np.asarray(threshold)
-            if tuple(cut.shape) != (h, w):
-                raise ValueError("track_hot_spots: an int or an (h, w) threshold expected, not shape %s" % (tuple(cut.shape),))
-            if isinstance(cut, np.ndarray):
-                cut = torch.from_numpy(np.ascontiguousarray(cut, np.float64 if cut.dtype.kind == "f" else np.int64))
-            cut = cut.to(device)
-            if not cut.is_floating_point():
-                cut = cut.to(torch.int32) if cut.dtype in (torch.uint16, torch.int16, torch.uint8, torch.int8) else cut
+            cut = self._hot_cut(threshold, device, "track_hot_spots")
         stack = torch.empty((n, h, w), dtype=torch.int32, device=device)
         counts = torch.zeros(n, dtype=torch.int32, device=device)
         per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
@@ -776,6 +767,69 @@ class IRMovie(object):
             if geometry:
                 _region_geometry_into(stack[k0:k1], fr, k1 - k0, 1, ntracks, type(geo)(*(t[k0:k1] for t in geo)))
         return (tracks, out, geo) if geometry else (tracks, out)
+
+    def _hot_cut(self, threshold, device, what):
+        """the threshold of ``image > threshold`` as the hot-spot calls take it, an int or an (h, w) array or tensor: an int, or a map on `device`"""
+        import torch
+
+        if isinstance(threshold, (int, np.integer)):
+            return int(threshold)
+        h, w = self.image_size
+        cut = threshold if isinstance(threshold, torch.Tensor) else np.asarray(threshold)
+        if tuple(cut.shape) != (h, w):
+            raise ValueError("%s: an int or an (h, w) threshold expected, not shape %s" % (what, tuple(cut.shape)))
+        if isinstance(cut, np.ndarray):
+            cut = torch.from_numpy(np.ascontiguousarray(cut, np.float64 if cut.dtype.kind == "f" else np.int64))
+        cut = cut.to(device)
+        if not cut.is_floating_point():
+            cut = cut.to(torch.int32) if cut.dtype in (torch.uint16, torch.int16, torch.uint8, torch.int8) else cut
+        return cut
+
+    def distance_transform(self, threshold, selection=slice(None), invert=False, border=False, rows=None, return_indices=False):
+        """Exact Euclidean distance transform of the hot-spot masks of the images of ``selection`` (as ``region_stats`` takes it) -
+        ``librir_amd.device.distance_transform(to_tensor(selection) > threshold, ...)``, read-back filters applied, on the device: an int32
+        CUDA tensor ``[len(selection)][h][w]`` with the SQUARED distance of every pixel to the nearest pixel that is not hot (0 outside
+        the hot spots, ``librir_amd.device.DIST2_NONE`` in an image without such a pixel), or ``(dist2, index)`` with
+        ``return_indices``, index the lowest flat index ``y * w + x`` of such a nearest pixel.  ``threshold`` is an int or an ``(h, w)``
+        array or tensor, as in ``track_hot_spots``.  ``invert=True`` gives the distance TO the hot pixels instead: of every pixel to the
+        nearest hot one, and which one that is.  ``border=True`` counts the outside of the image as a pixel to measure to; the image is
+        its first ``rows`` rows (default: all), the others get 0.  The recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of
+        images; images are transformed one by one, so any split gives the same bits.
+
+        Two idioms::
+
+            # thickness per hot spot: the largest inscribed radius, the per-region maximum of dist2 under the label map
+            dist2 = mov.distance_transform(t)
+            labels = librir_amd.device.label_images(mov.to_tensor() > t)[0]
+            regions = librir_amd.device.region_stats(dist2.clamp(max=65535).to(torch.uint16), labels)   # max: squared radius, up to 255 px
+            radius = regions.max.double().sqrt()
+
+            # merge the fragments of a spot before labelling: grow every hot spot by 3 px
+            mask = librir_amd.device.disc_dilate(mov.to_tensor() > t, 3)
+            labels = librir_amd.device.label_images(mask)[0]
+        """
+        import torch
+
+        from ..device import _distance_transform_args, distance_transform
+
+        h, w = self.image_size
+        _distance_transform_args((1, h, w), "bool", 0, border, rows)
+        positions = self._stats_positions(selection, "distance_transform")
+        n = len(positions)
+        device = torch.device("cuda", torch.cuda.current_device())
+        cut = self._hot_cut(threshold, device, "distance_transform")
+        dist2 = torch.empty((n, h, w), dtype=torch.int32, device=device)
+        index = torch.empty((n, h, w), dtype=torch.int32, device=device) if return_indices else None
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, n), h, w), dtype=torch.uint16, device=device)
+        for k0 in range(0, n, per_piece):
+            sel = positions[k0:k0 + per_piece]
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            hot = (fr.view(torch.int16).to(torch.int32) & 0xFFFF) > cut
+            k1 = k0 + len(sel)
+            distance_transform(hot, int(bool(invert)), border, rows, return_indices, out=(dist2[k0:k1], index[k0:k1]) if return_indices else dist2[k0:k1])
+        return (dist2, index) if return_indices else dist2
 
     def _stats_positions(self, selection, what="region_stats"):
         """the positions of an int or a slice with a positive step, as to_tensor takes them"""
