@@ -272,6 +272,37 @@ extern "C"
 	int rir_rank_filter_device(int type, const void *d_src, void *d_dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows,
 							   void *stream);
 
+	/* Local window statistics of a stack d_src[nframes][h][w] (extension).  type: 'H' uint16, 'B' uint8, '?' bool (one byte, 0 / 1).  The
+	 * window is a centred rectangle size_y x size_x, both odd, 1..15, of n = size_x * size_y cells, always FULL with coordinates replicated
+	 * at the border as in rir_rank_filter_device; the image is the first `rows` (0..h) rows of a frame and no window reads the others.
+	 * With v(dy, dx) = d_src[n][clamp(y + dy, 0, rows - 1)][clamp(x + dx, 0, w - 1)], |dy| <= size_y / 2, |dx| <= size_x / 2, for y < rows
+	 *   d_sum[n][y][x]   = S = the sum of the v(dy, dx)            (int32; at most 225 * 65535 = 14 745 375)
+	 *   d_sumsq[n][y][x] = Q = the sum of the v(dy, dx)^2          (int64; at most 225 * 65535^2 = 966 338 150 625)
+	 *   d_mean[n][y][x]  = (S + n / 2) / n in integer division     (the type of d_src; the mean rounded half up)
+	 * and in rows y >= `rows` the two sums are 0 and d_mean is a copy of d_src.  Each output may be null - it is then not computed -, at
+	 * least one must not be.  n Q - S^2 is n^2 times the window's population variance, in exact integers.  All integer, bit for bit.  One
+	 * launch per 65535 frames that reads the stack once and writes each output once: no workspace.  Asynchronous on `stream`; no output may
+	 * overlap d_src or another output.  nframes 0: nothing is done, 0.  -1 with the reason logged (argument errors before the device is
+	 * looked for): unknown type, an even size or one outside 1..15, rows outside 0..h, w or h < 1, nframes < 0, a null d_src, no output,
+	 * overlap, no device. */
+	int rir_local_stats_device(int type, const void *d_src, int w, int h, int nframes, int size_x, int size_y, int rows, int *d_sum, long long *d_sumsq,
+							   void *d_mean, void *stream);
+
+	/* The z-score mask of a stack d_src[nframes][h][w] (extension): d_mask[nframes][h][w], one byte 0 / 1 a pixel - what
+	 * rir_label_images_device and rir_morphology_device take.  Types, window, border and rows as rir_local_stats_device.  With v the pixel,
+	 * S and Q its window's sums, d = n v - S and V = n Q - S^2 (>= 0), k = k_num / k_den (0 <= k_num <= 255, 1 <= k_den <= 64), delta in
+	 * -65535..65535 and polarity
+	 *   0 above: d_mask = 1 where d > delta n and d^2 k_den^2 > k_num^2 V   (v - mean > delta and |v - mean| > k sigma, both strict, with
+	 *                                                                        the exact rational mean and population sigma, centre included)
+	 *   1 below: the same with -d in the first test                         2 both: above or below
+	 * and 0 elsewhere and in rows y >= `rows`.  A constant window gives 0; k_num 0 is "off the local mean by more than delta".  The limits
+	 * of the parameters keep every product inside int64; the test is exact.  One launch per 65535 frames that reads the stack once and
+	 * writes the mask once (neither sum is stored): no workspace.  Asynchronous on `stream`; d_mask may not overlap d_src.  nframes 0:
+	 * nothing is done, 0.  -1 with the reason logged (argument errors before the device is looked for): as rir_local_stats_device, and
+	 * k_num, k_den, delta or polarity outside their ranges. */
+	int rir_local_threshold_device(int type, const void *d_src, unsigned char *d_mask, int w, int h, int nframes, int size_x, int size_y, int rows,
+								   int k_num, int k_den, int delta, int polarity, void *stream);
+
 	/* Exact Euclidean distance transform of a stack of masks or label maps d_src[nframes][h][w] (extension): d_dist2[nframes][h][w], int32,
 	 * the SQUARED distance of every pixel to the nearest background pixel of its frame, and - unless d_index is NULL - d_index[nframes][h][w],
 	 * int32, which pixel that is.  type: '?' bool (one byte, 0 / 1), 'B' uint8, 'H' uint16, 'i' int32.  A cell is background when it equals

@@ -80,6 +80,17 @@ extern "C"
 	 * -1 with the reason logged on a bad argument (before the device is looked for) and without a device ("no usable HIP device", dst
 	 * untouched: there is no CPU fallback). */
 	int rir_rank_filter(int type, const void *src, void *dst, int w, int h, int nframes, int rank, int size_x, int size_y, int rows);
+	/* Local window statistics of a host stack src[nframes][h][w]: rir_local_stats_device (rir_amd_device.h, where the outputs are defined)
+	 * over the stack, synchronous.  sum (int32), sumsq (int64) and mean (the type of src) have the shape of src; each may be null, at least
+	 * one must not be, and none may overlap src or another.  Large stacks go through the device in slabs of at most 64 MiB of the widest
+	 * array (frames are independent).  nframes 0: 0.  -1 with the reason logged on a bad argument (before the device is looked for) and
+	 * without a device ("no usable HIP device", the outputs untouched: there is no CPU fallback). */
+	int rir_local_stats(int type, const void *src, int w, int h, int nframes, int size_x, int size_y, int rows, int *sum, long long *sumsq, void *mean);
+	/* The z-score mask of a host stack src[nframes][h][w] into mask[nframes][h][w] (one byte 0 / 1 a pixel): rir_local_threshold_device
+	 * (rir_amd_device.h, where the rule is defined) over the stack, synchronous, in slabs as rir_local_stats.  mask may not overlap src.
+	 * 0 / -1 as rir_local_stats. */
+	int rir_local_threshold(int type, const void *src, unsigned char *mask, int w, int h, int nframes, int size_x, int size_y, int rows, int k_num,
+							int k_den, int delta, int polarity);
 	/* Exact Euclidean distance transform of a host stack src[nframes][h][w]: rir_distance_transform_device (rir_amd_device.h, where the rule
 	 * is defined) over the stack, synchronous.  type '?' bool, 'B' uint8, 'H' uint16, 'i' int32; a cell equal to `background` is
 	 * background; dist2[nframes][h][w] (int32) is the squared distance to the nearest background pixel among the first `rows` (0..h) rows

@@ -18,6 +18,7 @@
 #include "geometry_kernels.h"
 #include "histogram_kernels.h"
 #include "label_kernels.h"
+#include "local_kernels.h"
 #include "morphology_kernels.h"
 #include "pixel_kernels.h"
 #include "pixel_quantile_kernels.h"
@@ -743,6 +744,74 @@ RIR_EXPORT int rir_rank_filter_device(int type, const void *d_src, void *d_dst, 
 								w, h, nframes, [=] { return launch_rank_filter(type, d_src, d_dst, w, h, nframes, rank, size_x, size_y, rows, as_stream(stream)); });
 }
 
+// The local window statistics (local_kernels.hip).  Every argument is checked here, before the device is looked for, in the order of
+// window_filter_args with the entry's own conditions at their places; no output may overlap the input or another output.
+namespace
+{
+	// 0, or what is wrong with the arguments of rir_local_stats / rir_local_stats_device: the outputs are tested after the shape and the source
+	const char *local_stats_args(int type, const void *src, int w, int h, int nframes, int size_x, int size_y, int rows, const int *sum, const long long *sumsq,
+								 const void *mean)
+	{
+		if (const char *bad = window_filter_args(type, src, src, w, h, nframes, size_x, size_y, rows))
+			return bad;
+		if (!sum && !sumsq && !mean)
+			return "no output asked for (the sum, the sum of squares and the mean are all null)";
+		const size_t npx = (size_t)w * h * nframes;
+		if (outputs_overlap({{src, npx * (type == 'H' ? 2 : 1)}}, {{sum, npx * 4}, {sumsq, npx * 8}, {mean, npx * (type == 'H' ? 2 : 1)}}))
+			return "an output overlaps the input or another output";
+		return nullptr;
+	}
+	// the same for rir_local_threshold / rir_local_threshold_device: the rule's parameters are tested right after the sizes
+	const char *local_threshold_args(int type, const void *src, const void *mask, int w, int h, int nframes, int size_x, int size_y, int rows, int k_num,
+									 int k_den, int delta, int polarity)
+	{
+		if (window_type(type) && window_sizes(size_x, size_y))
+		{
+			if (k_num < 0 || k_num > LOCAL_K_NUM_MAX || k_den < 1 || k_den > LOCAL_K_DEN_MAX)
+				return "k_num must be in 0..255 and k_den in 1..64";
+			if (delta < -LOCAL_DELTA_MAX || delta > LOCAL_DELTA_MAX)
+				return "delta must be in -65535..65535";
+			if (polarity < 0 || polarity >= LOCAL_POLARITIES)
+				return "unknown polarity (0 above, 1 below, 2 both)";
+		}
+		if (const char *bad = window_filter_args(type, src, mask, w, h, nframes, size_x, size_y, rows))
+			return bad;
+		const size_t npx = (size_t)w * h * nframes;
+		if (outputs_overlap({{src, npx * (type == 'H' ? 2 : 1)}}, {{mask, npx}}))
+			return "the mask overlaps the input";
+		return nullptr;
+	}
+} // namespace
+
+RIR_EXPORT int rir_local_stats_device(int type, const void *d_src, int w, int h, int nframes, int size_x, int size_y, int rows, int *d_sum, long long *d_sumsq,
+									  void *d_mean, void *stream)
+{
+	if (const char *bad = local_stats_args(type, d_src, w, h, nframes, size_x, size_y, rows, d_sum, d_sumsq, d_mean))
+		return refuse(__func__, bad);
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	return hip_ok(launch_local_stats(type, d_src, w, h, nframes, size_x, size_y, rows, d_sum, (int64_t *)d_sumsq, d_mean, as_stream(stream)), "local_stats")
+			   ? 0
+			   : -1;
+}
+
+RIR_EXPORT int rir_local_threshold_device(int type, const void *d_src, unsigned char *d_mask, int w, int h, int nframes, int size_x, int size_y, int rows,
+										  int k_num, int k_den, int delta, int polarity, void *stream)
+{
+	if (const char *bad = local_threshold_args(type, d_src, d_mask, w, h, nframes, size_x, size_y, rows, k_num, k_den, delta, polarity))
+		return refuse(__func__, bad);
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	return hip_ok(launch_local_threshold(type, d_src, d_mask, w, h, nframes, size_x, size_y, rows, k_num, k_den, delta, polarity, as_stream(stream)),
+				  "local_threshold")
+			   ? 0
+			   : -1;
+}
+
 // The exact Euclidean distance transform (distance_kernels.hip).  Every argument is checked here, before the device is looked for; no output
 // (workspace included) may overlap the input or another output.
 namespace
@@ -1459,6 +1528,46 @@ RIR_EXPORT int rir_temporal_median(const unsigned short *src, unsigned short *ds
 // found, filter(in, out, count, stream) its device entry over one slab.
 namespace
 {
+	struct WindowOut // an output of a window filter on a host stack: `cell` bytes per pixel; a null `host`: not asked for
+	{
+		void *host;
+		size_t cell;
+	};
+
+	// The walk: the stack goes up slab by slab - as many frames as HOST_SLAB_BYTES hold of the input and of the widest output -,
+	// filter(in, d_outs, count, stream) runs the device entry over the slab (d_outs[k]: output k of the slab, null when not asked for),
+	// and every output asked for comes down.
+	template <size_t N, class Filter>
+	int window_walk_host(const char *what, int type, const void *src, int w, int h, int nframes, const WindowOut (&outs)[N], Filter filter)
+	{
+		const size_t npx = (size_t)w * h, frame = npx * (type == 'H' ? 2 : 1);
+		size_t widest = frame;
+		for (const WindowOut &o : outs)
+			widest = std::max(widest, o.host ? npx * o.cell : 0);
+		const int slab = Stager::slab(nframes, {widest});
+		DeviceBuffer in, dev[N];
+		void *d_outs[N];
+		if (!in.reserve(frame * slab))
+			return -1;
+		for (size_t k = 0; k < N; ++k)
+		{
+			d_outs[k] = outs[k].host ? dev[k].reserve(npx * outs[k].cell * slab) : nullptr;
+			if (outs[k].host && !d_outs[k])
+				return -1;
+		}
+		Stager s;
+		for (int o = 0; o < nframes; o += slab)
+		{
+			const int count = std::min(slab, nframes - o);
+			bool ok = s.up(in.ptr, static_cast<const char *>(src) + frame * o, frame * count) && filter(in.ptr, d_outs, count, s.st) == 0;
+			for (size_t k = 0; ok && k < N; ++k)
+				ok = s.down(outs[k].host ? static_cast<char *>(outs[k].host) + npx * outs[k].cell * o : nullptr, d_outs[k], npx * outs[k].cell * count);
+			if (!ok || !s.wait(what))
+				return s.fail();
+		}
+		return 0;
+	}
+
 	template <class Filter>
 	int window_filter_host(const char *who, const char *what, const char *bad, int type, const void *src, void *dst, int w, int h, int nframes,
 						   Filter filter)
@@ -1470,20 +1579,9 @@ namespace
 			return 0;
 		if (!device_ready())
 			return -1;
-		const size_t frame = (size_t)w * h * (type == 'H' ? 2 : 1);
-		const int slab = Stager::slab(nframes, {frame});
-		DeviceBuffer in, out;
-		if (!in.reserve(frame * slab) || !out.reserve(frame * slab))
-			return -1;
-		Stager s;
-		for (int o = 0; o < nframes; o += slab)
-		{
-			const int count = std::min(slab, nframes - o);
-			if (!s.up(in.ptr, static_cast<const char *>(src) + frame * o, frame * count) || filter(in.ptr, out.ptr, count, s.st) != 0 ||
-				!s.down(static_cast<char *>(dst) + frame * o, out.ptr, frame * count) || !s.wait(what))
-				return s.fail();
-		}
-		return 0;
+		const WindowOut outs[] = {{dst, (size_t)(type == 'H' ? 2 : 1)}};
+		return window_walk_host(what, type, src, w, h, nframes, outs,
+								[&](const void *in, void *const *d_outs, int count, void *st) { return filter(in, d_outs[0], count, st); });
 	}
 } // namespace
 
@@ -1501,6 +1599,36 @@ RIR_EXPORT int rir_rank_filter(int type, const void *src, void *dst, int w, int 
 							  nframes, [=](const void *in, void *out, int count, void *st) {
 								  return rir_rank_filter_device(type, in, out, w, h, count, rank, size_x, size_y, rows, st);
 							  });
+}
+
+// The local window statistics of a host stack, through the window filters' walk with up to three outputs of their own cell sizes.
+RIR_EXPORT int rir_local_stats(int type, const void *src, int w, int h, int nframes, int size_x, int size_y, int rows, int *sum, long long *sumsq, void *mean)
+{
+	if (const char *bad = local_stats_args(type, src, w, h, nframes, size_x, size_y, rows, sum, sumsq, mean))
+		return refuse(__func__, bad);
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	const WindowOut outs[] = {{sum, 4}, {sumsq, 8}, {mean, (size_t)(type == 'H' ? 2 : 1)}};
+	return window_walk_host("local_stats", type, src, w, h, nframes, outs, [=](const void *in, void *const *d, int count, void *st) {
+		return rir_local_stats_device(type, in, w, h, count, size_x, size_y, rows, (int *)d[0], (long long *)d[1], d[2], st);
+	});
+}
+
+RIR_EXPORT int rir_local_threshold(int type, const void *src, unsigned char *mask, int w, int h, int nframes, int size_x, int size_y, int rows, int k_num,
+								   int k_den, int delta, int polarity)
+{
+	if (const char *bad = local_threshold_args(type, src, mask, w, h, nframes, size_x, size_y, rows, k_num, k_den, delta, polarity))
+		return refuse(__func__, bad);
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	const WindowOut outs[] = {{mask, 1}};
+	return window_walk_host("local_threshold", type, src, w, h, nframes, outs, [=](const void *in, void *const *d, int count, void *st) {
+		return rir_local_threshold_device(type, in, (unsigned char *)d[0], w, h, count, size_x, size_y, rows, k_num, k_den, delta, polarity, st);
+	});
 }
 
 // The distance transform of a host stack (frames are independent: any split gives the same bits); a slab is bounded by what a frame's input,

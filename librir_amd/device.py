@@ -10,12 +10,12 @@ import numpy as np
 import torch
 
 from .low_level.misc import _lib, last_error
-from .signal_processing.rir_signal_processing import (DIST2_NONE, DISTANCE_MAX_SIDE, PixelStats, RegionGeometry, RegionHistogram,  # noqa: F401 (API)
-                                                      RegionQuantiles, RegionStats, _distance_transform_args, _pixel_quantiles_args,
+from .signal_processing.rir_signal_processing import (DIST2_NONE, DISTANCE_MAX_SIDE, LocalStats, PixelStats, RegionGeometry,  # noqa: F401 (API)
+                                                      RegionHistogram, RegionQuantiles, RegionStats, _distance_transform_args, _pixel_quantiles_args,
                                                       _pixel_stats_args, _polygon_map_args, _region_geometry_args, _region_histogram_args,
                                                       _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
-                                                      _morphology_args, _rank_filter_args, _temporal_median_args, _window_size,
-                                                      percentile_rank)
+                                                      _local_stats_args, _morphology_args, _rank_filter_args, _temporal_median_args,
+                                                      _window_size, percentile_rank)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -117,6 +117,8 @@ _lib.rir_median_filter_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int
 _lib.rir_temporal_median_device.argtypes = [_vp, _vp, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, _vp]
 _lib.rir_morphology_device.argtypes = [ct.c_int, _vp, _vp] + [ct.c_int] * 7 + [_vp]
 _lib.rir_rank_filter_device.argtypes = [ct.c_int, _vp, _vp] + [ct.c_int] * 7 + [_vp]
+_lib.rir_local_stats_device.argtypes = [ct.c_int, _vp] + [ct.c_int] * 6 + [_vp] * 4
+_lib.rir_local_threshold_device.argtypes = [ct.c_int, _vp, _vp] + [ct.c_int] * 10 + [_vp]
 _lib.rir_distance_transform_device.argtypes = [ct.c_int, _vp] + [ct.c_int] * 6 + [_vp, _vp, _vp, ct.c_size_t, _vp]
 _lib.rir_distance_transform_workspace_bytes.argtypes = [ct.c_int] * 4
 _lib.rir_distance_transform_workspace_bytes.restype = ct.c_size_t
@@ -783,6 +785,94 @@ def percentile_filter(frames, percent, size, rows=None, out=None):
     percent counts from 100"""
     size_y, size_x = _window_sizes(size)
     return rank_filter(frames, percentile_rank(percent, size_y, size_x), size, rows, out)
+
+
+def _local_inputs(name, frames, size, rows, **own):
+    """the checks of ``local_stats`` / ``local_threshold`` that need no device: -> (what ``_local_stats_args`` returns for the stack - one
+    image being a stack of one -, the input's shape)"""
+    shape = tuple(frames.shape)
+    dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
+    args = _local_stats_args(name, (1,) + shape if len(shape) == 2 else shape, dtype_name, size, rows, **own)
+    return args, shape
+
+
+def _local_out(name, what, out, frames, dtype, shape):
+    """``out`` checked - a contiguous CUDA tensor of `dtype` and `shape` that does not overlap ``frames`` - or a new tensor"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=frames.device)
+    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise RuntimeError("%s: %s must be a contiguous %s CUDA tensor of shape %s" % (name, what, dtype, shape))
+    return out
+
+
+def local_stats(frames, size, rows=None, sum=True, sumsq=False, mean=False, out=None):
+    """Local window statistics of a uint16, uint8 or bool stack ``frames[n][h][w]`` (or one image ``[h][w]``, which keeps its shape) over a
+    centred rectangle ``size`` (an odd int, or ``(size_y, size_x)``, each 1..15) (C ABI ``rir_local_stats_device``), one launch on the
+    current stream: a ``LocalStats`` of tensors of the input's shape - ``sum`` (int32) the window's sum S, ``sumsq`` (int64) its sum of
+    squares Q, ``mean`` (the input's dtype) ``(S + n // 2) // n``, the mean rounded half up - with None for what was not asked for, and
+    ``n`` = size_y * size_x.  The
+    window is always full, coordinates replicated at the border (``mode="nearest"``, as ``rank_filter``).  The image is the first ``rows``
+    rows of a frame (default: all); below them the sums are 0 and the mean is the input.  ``out``: a ``LocalStats`` (or a tuple ``(sum,
+    sumsq, mean)``) with a contiguous CUDA tensor of the right dtype and shape for every output asked for, none of which overlaps
+    ``frames`` or another; they are fully overwritten.  Non-contiguous input is copied first.  All integer, bit for bit
+    (``local_variance_terms`` gives the exact variance); ``ValueError`` on bad parameters, before any device work."""
+    (type_char, size_y, size_x, rows), shape = _local_inputs("local_stats", frames, size, rows, outputs=(sum, sumsq, mean))
+    wanted = (bool(sum), bool(sumsq), bool(mean))
+    if out is not None and (not isinstance(out, (tuple, list)) or len(out) not in (3, 4)):
+        raise RuntimeError("local_stats: out must be a LocalStats or a tuple (sum, sumsq, mean)")
+    dtypes = (torch.int32, torch.int64, frames.dtype)
+    outs = [_local_out("local_stats", "out." + f, None if out is None else out[k], frames, dtypes[k], shape) if wanted[k] else None
+            for k, f in enumerate(LocalStats._fields[:3])]
+    fr = _frames3(frames)
+    n, h, w = fr.shape
+    if n:
+        _check(_lib.rir_local_stats_device(type_char, fr.data_ptr(), w, h, n, size_x, size_y, rows, *(None if t is None else t.data_ptr() for t in outs),
+                                           _stream()), "rir_local_stats_device")
+    return LocalStats(*outs, size_y * size_x)
+
+
+def box_sum(frames, size, rows=None, out=None):
+    """``local_stats(...).sum``: the int32 sum of every pixel's ``size`` window (``out``: the int32 tensor it goes to)"""
+    return local_stats(frames, size, rows, True, False, False, None if out is None else (out, None, None)).sum
+
+
+def box_mean(frames, size, rows=None, out=None):
+    """``local_stats(...).mean``: the mean of every pixel's ``size`` window, rounded half up, in the input's dtype (``out``: the tensor it
+    goes to)"""
+    return local_stats(frames, size, rows, False, False, True, None if out is None else (None, None, out)).mean
+
+
+def local_threshold(frames, size, k, delta=0, polarity="above", rows=None, out=None):
+    """The z-score mask of a uint16, uint8 or bool stack ``frames[n][h][w]`` (or one image ``[h][w]``) (C ABI ``rir_local_threshold_device``),
+    one launch on the current stream that reads the stack once and writes a byte a pixel: a ``torch.bool`` tensor of the input's shape,
+    True where the pixel lies more than ``delta`` (an int in -65535..65535) above the mean of its ``size`` window (an odd int, or ``(size_y,
+    size_x)``, each 1..15) AND more than ``k`` population standard deviations of that window (centre pixel included) off it - ``k`` an int
+    or ``(num, den)``, 0 <= num <= 255, 1 <= den <= 64.  Both tests are strict and exact: with S, Q the window's sum and sum of squares,
+    ``d = n v - S`` and ``V = n Q - S^2``, "above" is ``d > delta n and d^2 den^2 > num^2 V``; ``polarity`` "below" takes ``-d`` in the first
+    test, "both" either.  A constant window gives False; ``k = 0`` is "off the local mean by more than delta".  Window border and ``rows``
+    as ``local_stats``; rows below the image are False.  ``out``: a contiguous bool or uint8 CUDA tensor of the input's shape that does not
+    overlap ``frames`` (it receives 0 / 1 and is returned).  The mask - as uint8 through ``.view(torch.uint8)`` - is what ``label_images``
+    and ``morphology`` take: ``label_images(morph_open(local_threshold(frames, 9, 4, delta=20).view(torch.uint8), 3))``.  ``ValueError`` on
+    bad parameters, before any device work."""
+    (type_char, size_y, size_x, rows, k_num, k_den, delta, polarity), shape = _local_inputs("local_threshold", frames, size, rows, k=k, delta=delta,
+                                                                                             polarity=polarity)
+    out = _local_out("local_threshold", "out", out, frames, torch.uint8 if out is not None and out.dtype == torch.uint8 else torch.bool, shape)
+    fr = _frames3(frames)
+    n, h, w = fr.shape
+    if n:
+        _check(_lib.rir_local_threshold_device(type_char, fr.data_ptr(), out.data_ptr(), w, h, n, size_x, size_y, rows, k_num, k_den, delta, polarity,
+                                               _stream()), "rir_local_threshold_device")
+    return out
+
+
+def local_variance_terms(stats):
+    """``(n Q - S^2, n^2)`` of a ``LocalStats`` that has ``sum`` and ``sumsq`` (tensors or numpy arrays): an int64 array that is n^2 times
+    every window's population variance, exactly (at most 5.44e13), and the int n^2, n = ``stats.n`` being the window's cell count -
+    ``terms.double() / n2`` is the variance in float64 from exact integers, 0 exactly where a window is constant"""
+    if stats.sum is None or stats.sumsq is None:
+        raise ValueError("local_variance_terms: the sum and the sum of squares are needed (local_stats(..., sum=True, sumsq=True))")
+    wide = stats.sum.long() if isinstance(stats.sum, torch.Tensor) else stats.sum.astype(np.int64)
+    return stats.n * stats.sumsq - wide * wide, stats.n * stats.n
 
 
 _DISTANCE_WORK_BYTES = 256 << 20  # the workspace of one distance_transform call at most (or one frame's need): longer stacks go in groups

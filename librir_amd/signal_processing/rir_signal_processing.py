@@ -318,6 +318,77 @@ def rank_filter(images, rank, size, rows=None):
     return out.reshape(img.shape)
 
 
+# ---- extension: local window statistics ------------------------------------------------------------------------------------------
+_sp.rir_local_stats.argtypes = [ct.c_int, ct.c_void_p] + [ct.c_int] * 6 + [ct.c_void_p] * 3
+_sp.rir_local_threshold.argtypes = [ct.c_int, ct.c_void_p, ct.c_void_p] + [ct.c_int] * 10
+
+LocalStats = namedtuple("LocalStats", ["sum", "sumsq", "mean", "n"])  # an array that was not asked for is None; n: the window's cells
+LOCAL_POLARITIES = ("above", "below", "both")  # the polarity numbers of the C ABI
+LOCAL_K_NUM_MAX, LOCAL_K_DEN_MAX, LOCAL_DELTA_MAX = 255, 64, 65535  # what keeps the z-score test inside int64
+
+
+def _local_stats_args(name, shape, dtype_name, size, rows, outputs=None, k=None, delta=0, polarity="above"):
+    """the parameters of ``local_stats`` (``outputs``: the three flags sum, sumsq, mean) or ``local_threshold`` (``k``, ``delta``,
+    ``polarity``) over a stack of `shape`, checked without a device under the caller's `name`; -> (type char, size_y, size_x, rows) and,
+    for a threshold, (k_num, k_den, delta, polarity number) after them"""
+    type_char = _window_type(name, shape, dtype_name)
+    size_y, size_x = _window_size(name, size)
+    if outputs is not None:
+        if not any(outputs):
+            raise ValueError("%s: no output asked for" % name)
+        return type_char, size_y, size_x, _window_rows(name, shape, rows)
+    ks = tuple(k) if isinstance(k, (tuple, list)) else (k, 1)
+    if len(ks) != 2 or not all(isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_)) for v in ks):
+        raise ValueError("%s: k must be an int or (num, den)" % name)
+    if not (0 <= ks[0] <= LOCAL_K_NUM_MAX and 1 <= ks[1] <= LOCAL_K_DEN_MAX):
+        raise ValueError("%s: k = num / den needs 0 <= num <= %d and 1 <= den <= %d (got %r)" % (name, LOCAL_K_NUM_MAX, LOCAL_K_DEN_MAX, k))
+    if not isinstance(delta, (int, np.integer)) or isinstance(delta, (bool, np.bool_)) or not -LOCAL_DELTA_MAX <= delta <= LOCAL_DELTA_MAX:
+        raise ValueError("%s: delta must be an int in %d..%d" % (name, -LOCAL_DELTA_MAX, LOCAL_DELTA_MAX))
+    if polarity not in LOCAL_POLARITIES:
+        raise ValueError("%s: polarity must be one of %s (got %r)" % (name, ", ".join(LOCAL_POLARITIES), polarity))
+    return type_char, size_y, size_x, _window_rows(name, shape, rows), int(ks[0]), int(ks[1]), int(delta), LOCAL_POLARITIES.index(polarity)
+
+
+def _host_stack(name, images):
+    """-> (the contiguous array, its view [n][h][w]) of an image or a stack"""
+    img = np.ascontiguousarray(images)
+    if img.ndim not in (2, 3):
+        raise ValueError("%s: an image [h][w] or a stack [n][h][w] expected" % name)
+    return img, img.reshape((-1,) + img.shape[-2:])
+
+
+def local_stats(images, size, rows=None, sum=True, sumsq=False, mean=False):
+    """Extension: local window statistics of a uint16, uint8 or bool stack ``images[n][h][w]`` (or one image ``[h][w]``) over a centred
+    rectangle ``size`` (an odd int, or ``(size_y, size_x)``, each 1..15) (``rir_local_stats``): a ``LocalStats`` of arrays of the input's
+    shape - ``sum`` (int32) the window's sum, ``sumsq`` (int64) its sum of squares, ``mean`` (the input's dtype) ``(sum + n // 2) // n`` -,
+    None for what was not asked for, and the window's cell count ``n``.  The window is always full, coordinates replicated at the border: per image ``sum`` is
+    ``scipy.ndimage.correlate(image.astype(int64), ones(size), mode="nearest")``.  The image is its first ``rows`` rows (default: all);
+    below them the sums are 0 and the mean is the input.  ``ValueError`` on bad parameters, ``RuntimeError`` when the library fails."""
+    img, stack = _host_stack("local_stats", images)
+    type_char, size_y, size_x, rows = _local_stats_args("local_stats", stack.shape, img.dtype.name, size, rows, outputs=(sum, sumsq, mean))
+    outs = [np.zeros(stack.shape, dt) if want else None for want, dt in ((sum, np.int32), (sumsq, np.int64), (mean, img.dtype))]
+    n, h, w = stack.shape
+    if n and _sp.rir_local_stats(type_char, stack.ctypes.data, w, h, n, size_x, size_y, rows, *(None if o is None else o.ctypes.data for o in outs)) < 0:
+        raise RuntimeError("An error occured while calling 'local_stats': " + (last_error() or ""))
+    return LocalStats(*(None if o is None else o.reshape(img.shape) for o in outs), size_y * size_x)
+
+
+def local_threshold(images, size, k, delta=0, polarity="above", rows=None):
+    """Extension: the z-score mask of a uint16, uint8 or bool stack ``images[n][h][w]`` (or one image ``[h][w]``) (``rir_local_threshold``): a
+    bool array of the input's shape, True where the pixel lies more than ``delta`` above the mean of its ``size`` window and more than
+    ``k`` (an int, or ``(num, den)`` with 0 <= num <= 255, 1 <= den <= 64) population standard deviations of that window off it, both strict
+    and exact; ``polarity`` "below" tests below the mean, "both" either.  Window, border and ``rows`` as ``local_stats``; rows below the
+    image are False.  ``ValueError`` on bad parameters, ``RuntimeError`` when the library fails."""
+    img, stack = _host_stack("local_threshold", images)
+    type_char, size_y, size_x, rows, k_num, k_den, delta, polarity = _local_stats_args("local_threshold", stack.shape, img.dtype.name, size, rows, k=k,
+                                                                                       delta=delta, polarity=polarity)
+    out = np.zeros(stack.shape, np.bool_)
+    n, h, w = stack.shape
+    if n and _sp.rir_local_threshold(type_char, stack.ctypes.data, out.ctypes.data, w, h, n, size_x, size_y, rows, k_num, k_den, delta, polarity) < 0:
+        raise RuntimeError("An error occured while calling 'local_threshold': " + (last_error() or ""))
+    return out.reshape(img.shape)
+
+
 # ---- extension: exact Euclidean distance transform -------------------------------------------------------------------------------
 _sp.rir_distance_transform.argtypes = [ct.c_int, ct.c_void_p] + [ct.c_int] * 6 + [ct.c_void_p, ct.c_void_p]
 

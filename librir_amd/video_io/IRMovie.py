@@ -609,20 +609,7 @@ class IRMovie(object):
 
         h, w = self.image_size
         check((1, h, w), "uint16", own, size, rows)
-        positions = self._stats_positions(selection, name)
-        shape = (len(positions), h, w)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint16, device=torch.device("cuda", torch.cuda.current_device()))
-        elif not out.is_cuda or out.dtype != torch.uint16 or tuple(out.shape) != shape or not out.is_contiguous():
-            raise RuntimeError("%s: 'out' must be a C-contiguous uint16 CUDA tensor of shape %s" % (name, shape))
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=out.device)
-        for k0 in range(0, len(positions), per_piece):
-            sel = positions[k0:k0 + per_piece]
-            fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
-            filter(fr, own, size, rows, out=out[k0:k0 + len(sel)])
-        return out
+        return self._filter_pieces(name, lambda fr, out: filter(fr, own, size, rows, out=out), torch.uint16, selection, out)
 
     def rank_filter(self, rank, size, selection=slice(None), rows=None, out=None):
         """Spatial rank filter of the images of ``selection`` (as ``region_stats`` takes it) - ``librir_amd.device.rank_filter(frames, rank,
@@ -645,6 +632,58 @@ class IRMovie(object):
 
         size_y, size_x = _window_sizes(size)
         return self.rank_filter(size_y * size_x // 2, size, selection, rows, out)
+
+    def _filter_pieces(self, name, filter, dtype, selection, out):
+        """what the window filters and the local statistics share: ``filter(piece, out=...)`` of ``librir_amd.device`` over the images of
+        ``selection``, read in pieces, into a `dtype` tensor ``[len(selection)][h][w]``"""
+        import torch
+
+        h, w = self.image_size
+        positions = self._stats_positions(selection, name)
+        shape = (len(positions), h, w)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
+        elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise RuntimeError("%s: 'out' must be a C-contiguous %s CUDA tensor of shape %s" % (name, str(dtype)[6:], shape))
+        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
+        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=out.device)
+        for k0 in range(0, len(positions), per_piece):
+            sel = positions[k0:k0 + per_piece]
+            fr = piece[:len(sel)]
+            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            filter(fr, out=out[k0:k0 + len(sel)])
+        return out
+
+    def local_threshold(self, size, k, delta=0, polarity="above", selection=slice(None), rows=None, out=None):
+        """The z-score mask of the images of ``selection`` (as ``region_stats`` takes it) - ``librir_amd.device.local_threshold(frames, size,
+        k, delta, polarity, rows)`` over the images ``to_tensor(selection)`` gives (read-back filters applied), on the device: a bool CUDA
+        tensor ``[len(selection)][h][w]`` (``out`` when given: a contiguous bool CUDA tensor of that shape), True where a pixel lies more
+        than ``delta`` above the mean of its ``size`` window and more than ``k`` (an int or ``(num, den)``) local standard deviations off
+        it.  The recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of images; images are filtered one by one, so any split
+        gives the same bits.  An adaptive threshold where ``morphology("tophat", 9) > t`` has one ``t`` for the whole image::
+
+            labels = librir_amd.device.label_images(mov.local_threshold(9, 4, delta=20))   # hot spots 4 sigma and 20 counts above their surround
+        """
+        import torch
+
+        from ..device import _local_stats_args, local_threshold
+
+        h, w = self.image_size
+        _local_stats_args("local_threshold", (1, h, w), "uint16", size, rows, k=k, delta=delta, polarity=polarity)
+        return self._filter_pieces("local_threshold", lambda fr, out: local_threshold(fr, size, k, delta, polarity, rows, out=out), torch.bool, selection,
+                                  out)
+
+    def box_mean(self, size, selection=slice(None), rows=None, out=None):
+        """The local mean of the images of ``selection`` - ``librir_amd.device.box_mean(frames, size, rows)`` over the images
+        ``to_tensor(selection)`` gives: a uint16 CUDA tensor ``[len(selection)][h][w]`` (``out`` when given), every pixel the mean of its
+        full ``size`` window rounded half up, coordinates replicated at the border; read in pieces as ``local_threshold``"""
+        import torch
+
+        from ..device import _local_stats_args, box_mean
+
+        h, w = self.image_size
+        _local_stats_args("box_mean", (1, h, w), "uint16", size, rows, outputs=(False, False, True))
+        return self._filter_pieces("box_mean", lambda fr, out: box_mean(fr, size, rows, out=out), torch.uint16, selection, out)
 
     _QUANTILE_RESIDENT_BYTES = 1 << 30  # uint16 images that pixel_quantiles decodes into one stack
 
