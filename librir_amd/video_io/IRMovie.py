@@ -312,25 +312,12 @@ class IRMovie(object):
             raise ValueError("to_tensor: dtype torch.uint16 or torch.float32 expected, not %s" % (dtype,))
         if self._calibration_index != 0:
             raise ValueError("to_tensor: only digital levels (DL) are read to the device")
-        total = self.images
-        if isinstance(selection, (int, np.integer)):
-            pos = int(selection) + (total if selection < 0 else 0)
-            if not 0 <= pos < total:
-                raise IndexError("image %d out of range (%d images)" % (int(selection), total))
-            positions = range(pos, pos + 1)
-        elif isinstance(selection, slice):
-            if selection.step is not None and selection.step <= 0:
-                raise ValueError("to_tensor: a slice with a positive step expected")
-            positions, _ = self._positions(selection)
-        else:
-            raise TypeError("to_tensor: an int or a slice expected")
+        positions = self._stats_positions(selection, "to_tensor")
         h, w = self.image_size if window is None else window[2:]
         shape = (len(positions), h, w)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
-        elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-            raise RuntimeError("to_tensor: 'out' must be a C-contiguous CUDA tensor of shape %s and dtype %s" % (shape, dtype))
+        out = self._result(out, shape, dtype, "to_tensor: 'out' must be a C-contiguous CUDA tensor of shape %s and dtype %s", shape, dtype)
         if len(positions):
+            total = self.images
             if positions.start < 0 or positions[-1] >= total:
                 raise IndexError("to_tensor: images %s out of range (%d images)" % (positions, total))
             if temporal_median is None:
@@ -361,7 +348,7 @@ class IRMovie(object):
             else:
                 dst.copy_(temporal_median(stack, window, threshold, first=sel[0] - lo, count=len(sel), step=step))
 
-    _STATS_PIECE_BYTES = 64 << 20  # uint16 images read at once by region_stats
+    _STATS_PIECE_BYTES = 64 << 20  # images (and what their caller keeps beside each) that one piece of _pieces holds
 
     def region_stats(self, labels, selection=slice(None), nregions=None):
         """Statistics of the images of ``selection`` (as ``to_tensor`` takes it) over the regions of one int32 label map ``labels`` (h, w),
@@ -376,29 +363,82 @@ class IRMovie(object):
         pieces are counted in window bytes.  ``window=None``: the whole image."""
         if window is not None:
             window = self._window(window, "region_stats")
-        import torch
-
         from ..device import _region_inputs, _region_stats_empty, _region_stats_into
 
+        return self._region_reduce("region_stats", labels, nregions, selection, lambda probe, lab, k: _region_inputs(probe, lab, k)[1:2],
+                                   _region_stats_empty, lambda fr, lab, k, out: _region_stats_into(fr, lab, 0, k, out), window, two_d=False)
+
+    def _pieces(self, positions, device, window=None, bytes_per_pixel=2):
+        """The walk of every analysis over a recording: the images at ``positions`` (a range) read in pieces of at most
+        ``_STATS_PIECE_BYTES`` - read when the walk starts; ``bytes_per_pixel`` is what an image costs its caller, 2 for the image alone -
+        through ``window`` if given, whose bytes are then the ones counted.  Yields ``(k0, k1, frames)``: ``frames`` holds the images
+        ``positions[k0:k1]``, uint16 ``[k1 - k0][h][w]``, and is a view of ONE buffer on ``device`` that the next piece overwrites."""
+        import torch
+
         h, w = self.image_size if window is None else window[2:]
-        if isinstance(labels, np.ndarray):
-            if labels.dtype != np.int32:
-                raise RuntimeError("region_stats: int32 labels expected, not %s" % labels.dtype)
-            labels = torch.from_numpy(np.ascontiguousarray(labels)).to(torch.device("cuda", torch.cuda.current_device()))
-        probe = torch.empty((0, h, w), dtype=torch.uint16, device=labels.device if labels.is_cuda else "cpu")
-        _, lab, _, _, _, _ = _region_inputs(probe, labels, nregions)
-        if nregions is None:
-            nregions = max(1, int(lab.max()) + 1)
-            _region_inputs(probe, labels, nregions)
-        positions = self._stats_positions(selection)
-        out = _region_stats_empty(len(positions), int(nregions), lab.device)
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=lab.device)
+        per_piece = self._piece_images(len(positions), h, w, bytes_per_pixel)
+        if not per_piece:  # (an empty selection: nothing is read)
+            return
+        piece = torch.empty((per_piece, h, w), dtype=torch.uint16, device=device)
         for k0 in range(0, len(positions), per_piece):
             sel = positions[k0:k0 + per_piece]
             fr = piece[:len(sel)]
             self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr, window=window)
-            _region_stats_into(fr, lab, 0, int(nregions), type(out)(*(t[k0:k0 + len(sel)] for t in out)))
+            yield k0, k0 + len(sel), fr
+
+    def _piece_images(self, n, h, w, bytes_per_pixel=2):
+        """the images in a piece of ``_pieces`` over n images (h, w): what ``_STATS_PIECE_BYTES`` holds, one at least, n at most"""
+        return min(n, max(1, self._STATS_PIECE_BYTES // (bytes_per_pixel * h * w)))
+
+    @staticmethod
+    def _rows(out, k0, k1):
+        """rows k0 .. k1 of a namedtuple of tensors; what is no tensor (a histogram's lo and width) stays"""
+        return type(out)(*(t if isinstance(t, int) else t[k0:k1] for t in out))
+
+    @staticmethod
+    def _result(out, shape, dtype, message, *args):
+        """``out`` if it is a C-contiguous CUDA tensor of `shape` and `dtype` - ``RuntimeError(message % args)`` if not - or, for None, a new
+        one on the current device"""
+        import torch
+
+        if out is None:
+            return torch.empty(shape, dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
+        if not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
+            raise RuntimeError(message % args)
+        return out
+
+    def _label_map(self, what, labels, nregions, inputs, h, w, two_d):
+        """The label map of a region reducer on the device and ``nregions`` resolved.  ``labels`` is numpy (int32, uploaded to the current
+        device), a CUDA tensor, or None where the caller's checks allow it; ``two_d``: one map (h, w), refused here under `what` otherwise.
+        ``inputs(probe, labels, nregions)`` runs the caller's checks of ``librir_amd.device`` over `probe`, an empty stack of (h, w) images,
+        and returns (the map as the kernels take it, whatever else the caller needs); it runs before ``nregions=None`` is resolved to
+        labels.max() + 1 and, with that, again.  -> (what ``inputs`` returned, nregions, device)"""
+        import torch
+
+        if isinstance(labels, np.ndarray):
+            if labels.dtype != np.int32:
+                raise RuntimeError("%s: int32 labels expected, not %s" % (what, labels.dtype))
+            labels = torch.from_numpy(np.ascontiguousarray(labels)).to(torch.device("cuda", torch.cuda.current_device()))
+        if two_d and labels is not None and labels.dim() != 2:
+            raise ValueError("%s: one label map (h, w) expected, not shape %s" % (what, tuple(labels.shape)))
+        device = labels.device if labels is not None else torch.device("cuda", torch.cuda.current_device())
+        probe = torch.empty((0, h, w), dtype=torch.uint16, device=device)
+        checked = inputs(probe, labels, nregions)
+        if nregions is None:
+            nregions = max(1, int(checked[0].max()) + 1)
+            inputs(probe, labels, nregions)
+        return checked, int(nregions), device
+
+    def _region_reduce(self, what, labels, nregions, selection, inputs, empty, into, window=None, two_d=True):
+        """What the region_* methods share: the label map taken in (``_label_map`` with `what`, ``inputs`` and ``two_d``), the selection
+        parsed, the result made - ``empty(len(selection), nregions, *more, device)``, `more` being what ``inputs`` returned after the map -
+        and filled piece by piece by ``into(frames, map, nregions, rows of the result, *more)``."""
+        h, w = self.image_size if window is None else window[2:]
+        (lab, *more), nregions, device = self._label_map(what, labels, nregions, inputs, h, w, two_d)
+        positions = self._stats_positions(selection, what)
+        out = empty(len(positions), nregions, *more, device)
+        for k0, k1, fr in self._pieces(positions, device, window):
+            into(fr, lab, nregions, self._rows(out, k0, k1), *more)
         return out
 
     def region_geometry(self, labels, selection=slice(None), nregions=None):
@@ -407,32 +447,11 @@ class IRMovie(object):
         ``RegionGeometry`` of CUDA tensors ``[len(selection)][nregions]`` leading; count, bbox and moments repeat for every image, the
         weighted sums follow the recording.  Labels, selection, ``nregions`` and the pieces the recording is read in are those of
         ``region_stats``."""
-        import torch
-
         from ..device import _region_geometry_empty, _region_geometry_inputs, _region_geometry_into
 
-        h, w = self.image_size
-        if isinstance(labels, np.ndarray):
-            if labels.dtype != np.int32:
-                raise RuntimeError("region_geometry: int32 labels expected, not %s" % labels.dtype)
-            labels = torch.from_numpy(np.ascontiguousarray(labels)).to(torch.device("cuda", torch.cuda.current_device()))
-        if labels.dim() != 2:
-            raise ValueError("region_geometry: one label map (h, w) expected, not shape %s" % (tuple(labels.shape),))
-        probe = torch.empty((0, h, w), dtype=torch.uint16, device=labels.device if labels.is_cuda else "cpu")
-        lab, _, _, _, _, _ = _region_geometry_inputs(labels, probe, nregions)
-        if nregions is None:
-            nregions = max(1, int(lab.max()) + 1)
-            _region_geometry_inputs(labels, probe, nregions)
-        positions = self._stats_positions(selection, "region_geometry")
-        out = _region_geometry_empty(len(positions), int(nregions), True, lab.device)
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=lab.device)
-        for k0 in range(0, len(positions), per_piece):
-            sel = positions[k0:k0 + per_piece]
-            fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
-            _region_geometry_into(lab, fr, len(sel), 0, int(nregions), type(out)(*(t[k0:k0 + len(sel)] for t in out)))
-        return out
+        return self._region_reduce("region_geometry", labels, nregions, selection, lambda probe, lab, k: _region_geometry_inputs(lab, probe, k)[:1],
+                                   lambda n, k, device: _region_geometry_empty(n, k, True, device),
+                                   lambda fr, lab, k, out: _region_geometry_into(lab, fr, len(fr), 0, k, out))
 
     def region_quantiles(self, labels, percents, selection=slice(None), nregions=None):
         """Quantiles of the images of ``selection`` over the regions of one int32 label map ``labels`` (h, w), numpy or CUDA, at
@@ -440,32 +459,14 @@ class IRMovie(object):
         gives (read-back filters applied): a ``RegionQuantiles`` of CUDA tensors, count ``[len(selection)][nregions]`` and values
         ``[len(selection)][nregions][len(percents)]``.  Labels, selection, ``nregions`` and the pieces the recording is read in are those
         of ``region_stats``."""
-        import torch
-
         from ..device import (_region_inputs, _region_quantiles_args, _region_quantiles_empty, _region_quantiles_into,
                               _region_quantiles_percents)
 
-        h, w = self.image_size
         pc = _region_quantiles_percents(percents)
-        if isinstance(labels, np.ndarray):
-            if labels.dtype != np.int32:
-                raise RuntimeError("region_quantiles: int32 labels expected, not %s" % labels.dtype)
-            labels = torch.from_numpy(np.ascontiguousarray(labels)).to(torch.device("cuda", torch.cuda.current_device()))
-        probe = torch.empty((0, h, w), dtype=torch.uint16, device=labels.device if labels.is_cuda else "cpu")
-        _, lab, _, _, _, _ = _region_inputs(probe, labels, nregions, "region_quantiles", _region_quantiles_args)
-        if nregions is None:
-            nregions = max(1, int(lab.max()) + 1)
-            _region_inputs(probe, labels, nregions, "region_quantiles", _region_quantiles_args)
-        positions = self._stats_positions(selection, "region_quantiles")
-        out = _region_quantiles_empty(len(positions), int(nregions), pc.size, lab.device)
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=lab.device)
-        for k0 in range(0, len(positions), per_piece):
-            sel = positions[k0:k0 + per_piece]
-            fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
-            _region_quantiles_into(fr, lab, 0, int(nregions), pc, type(out)(*(t[k0:k0 + len(sel)] for t in out)))
-        return out
+        return self._region_reduce("region_quantiles", labels, nregions, selection,
+                                   lambda probe, lab, k: _region_inputs(probe, lab, k, "region_quantiles", _region_quantiles_args)[1:2],
+                                   lambda n, k, device: _region_quantiles_empty(n, k, pc.size, device),
+                                   lambda fr, lab, k, out: _region_quantiles_into(fr, lab, 0, k, pc, out), two_d=False)
 
     def region_histogram(self, labels, nbins, lo=0, width=1, selection=slice(None), nregions=None, rows=None):
         """Histograms of the images of ``selection`` over the regions of one int32 label map ``labels`` (h, w), numpy or CUDA (None: the
@@ -473,36 +474,17 @@ class IRMovie(object):
         ``librir_amd.device.region_histogram`` over the images ``movie[selection]`` gives (read-back filters applied): a
         ``RegionHistogram`` of CUDA tensors, count ``[len(selection)][nregions]``, hist ``[..][nbins]`` and outside ``[..][2]``.  Labels,
         selection, ``nregions`` and the pieces the recording is read in are those of ``region_stats``."""
-        import torch
-
         from ..device import _region_histogram_empty, _region_histogram_inputs, _region_histogram_into
 
-        h, w = self.image_size
         what = "region_histogram" if labels is not None else "histogram"
-        if isinstance(labels, np.ndarray):
-            if labels.dtype != np.int32:
-                raise RuntimeError("region_histogram: int32 labels expected, not %s" % labels.dtype)
-            labels = torch.from_numpy(np.ascontiguousarray(labels)).to(torch.device("cuda", torch.cuda.current_device()))
-        if labels is not None and labels.dim() != 2:
-            raise ValueError("region_histogram: one label map (h, w) expected, not shape %s" % (tuple(labels.shape),))
-        device = labels.device if labels is not None else torch.device("cuda", torch.cuda.current_device())
-        probe = torch.empty((0, h, w), dtype=torch.uint16, device=device)
-        if labels is None:
-            nregions = 1
-        _, lab, _, _, _, _, nbins, lo, width, rows = _region_histogram_inputs(probe, labels, nbins, lo, width, nregions, rows, what)
-        if nregions is None:
-            nregions = max(1, int(lab.max()) + 1)
-            _region_histogram_inputs(probe, labels, nbins, lo, width, nregions, rows, what)
-        positions = self._stats_positions(selection, what)
-        out = _region_histogram_empty(len(positions), int(nregions), nbins, lo, width, device)
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=device)
-        for k0 in range(0, len(positions), per_piece):
-            sel = positions[k0:k0 + per_piece]
-            fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
-            _region_histogram_into(fr, lab, 0, int(nregions), rows, type(out)(*(t[k0:k0 + len(sel)] for t in out[:3]), lo, width))
-        return out
+
+        def inputs(probe, lab, k):  # -> (the map, nbins, lo, width, rows), the four as the checks leave them
+            checked = _region_histogram_inputs(probe, lab, nbins, lo, width, k, rows, what)
+            return checked[1:2] + checked[6:]
+
+        return self._region_reduce(what, labels, 1 if labels is None else nregions, selection, inputs,
+                                   lambda n, k, nbins, lo, width, rows, device: _region_histogram_empty(n, k, nbins, lo, width, device),
+                                   lambda fr, lab, k, out, nbins, lo, width, rows: _region_histogram_into(fr, lab, 0, k, rows, out))
 
     def histogram(self, nbins, lo=0, width=1, selection=slice(None), rows=None):
         """``region_histogram`` without a map: the whole image (its first ``rows`` rows) is region 0 - what
@@ -540,17 +522,11 @@ class IRMovie(object):
         device = a.xy.device if isinstance(a.xy, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
         xy, npts, vals, moves = _polygon_inputs(a, device)
         out = _region_stats_empty(n, nregions, device)
-        per_piece = max(1, self._STATS_PIECE_BYTES // (6 * h * w))
-        piece = torch.empty((min(per_piece, n), h, w), dtype=torch.uint16, device=device)
-        maps = torch.empty((min(per_piece, n), h, w), dtype=torch.int32, device=device)
-        for k0 in range(0, n, per_piece):
-            sel = positions[k0:k0 + per_piece]
-            k1 = k0 + len(sel)
-            fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+        maps = torch.empty((self._piece_images(n, h, w, 6), h, w), dtype=torch.int32, device=device)  # (6: an image and its int32 map)
+        for k0, k1, fr in self._pieces(positions, device, bytes_per_pixel=6):
             _polygon_map_into(xy[k0:k1] if a.per_map else xy, npts[k0:k1] if a.per_map else npts, vals, None if moves is None else moves[k0:k1],
-                              a.per_map, -1, maps[:len(sel)])
-            _region_stats_into(fr, maps[:len(sel)], 1, nregions, type(out)(*(t[k0:k1] for t in out)))
+                              a.per_map, -1, maps[:k1 - k0])
+            _region_stats_into(fr, maps[:k1 - k0], 1, nregions, self._rows(out, k0, k1))
         return out
 
     def pixel_stats(self, selection=slice(None), sums=True, extremes=True):
@@ -575,12 +551,7 @@ class IRMovie(object):
         positions = self._stats_positions(selection, "pixel_stats")
         device = torch.device("cuda", torch.cuda.current_device())
         acc = PixelStatsAccumulator(sums, extremes, shape=(h, w), device=device)
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=device)
-        for k0 in range(0, len(positions), per_piece):
-            sel = positions[k0:k0 + per_piece]
-            fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr, window=window)
+        for k0, _, fr in self._pieces(positions, device, window):
             acc.push(fr, k0)
         return acc.result()
 
@@ -636,22 +607,12 @@ class IRMovie(object):
     def _filter_pieces(self, name, filter, dtype, selection, out):
         """what the window filters and the local statistics share: ``filter(piece, out=...)`` of ``librir_amd.device`` over the images of
         ``selection``, read in pieces, into a `dtype` tensor ``[len(selection)][h][w]``"""
-        import torch
-
         h, w = self.image_size
         positions = self._stats_positions(selection, name)
         shape = (len(positions), h, w)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=torch.device("cuda", torch.cuda.current_device()))
-        elif not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-            raise RuntimeError("%s: 'out' must be a C-contiguous %s CUDA tensor of shape %s" % (name, str(dtype)[6:], shape))
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, len(positions)), h, w), dtype=torch.uint16, device=out.device)
-        for k0 in range(0, len(positions), per_piece):
-            sel = positions[k0:k0 + per_piece]
-            fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
-            filter(fr, out=out[k0:k0 + len(sel)])
+        out = self._result(out, shape, dtype, "%s: 'out' must be a C-contiguous %s CUDA tensor of shape %s", name, str(dtype)[6:], shape)
+        for k0, k1, fr in self._pieces(positions, out.device):
+            filter(fr, out=out[k0:k1])
         return out
 
     def local_threshold(self, size, k, delta=0, polarity="above", selection=slice(None), rows=None, out=None):
@@ -710,13 +671,8 @@ class IRMovie(object):
                 self.to_tensor(slice(positions.start, positions.stop, positions.step), out=stack)
             return pixel_quantiles(stack, pc)
         select = PixelQuantileSelector(pc, shape=(h, w), device=device)
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, n), h, w), dtype=torch.uint16, device=device)
         for _ in range(select.passes):
-            for k0 in range(0, n, per_piece):
-                sel = positions[k0:k0 + per_piece]
-                fr = piece[:len(sel)]
-                self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
+            for _, _, fr in self._pieces(positions, device):
                 select.push(fr)
             select.next_pass()
         return select.result()
@@ -774,25 +730,15 @@ class IRMovie(object):
             cut = self._hot_cut(threshold, device, "track_hot_spots")
         stack = torch.empty((n, h, w), dtype=torch.int32, device=device)
         counts = torch.zeros(n, dtype=torch.int32, device=device)
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, n), h, w), dtype=torch.uint16, device=device)
-        xy = torch.zeros((piece.shape[0], 1, 2), dtype=torch.float64, device=device)
-        area = torch.zeros((piece.shape[0], 1), dtype=torch.int32, device=device)
+        per_piece = self._piece_images(n, h, w)
+        xy = torch.zeros((per_piece, 1, 2), dtype=torch.float64, device=device)
+        area = torch.zeros((per_piece, 1), dtype=torch.int32, device=device)
         first = torch.zeros_like(area) if filtered else None
-
-        def pieces():
-            for k0 in range(0, n, per_piece):
-                sel = positions[k0:k0 + per_piece]
-                fr = piece[:len(sel)]
-                self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
-                yield k0, k0 + len(sel), fr
-
-        for k0, k1, fr in pieces():
+        for k0, k1, fr in self._pieces(positions, device):
             if filtered:
                 _label_hot_spots_into(fr, kept, stack[k0:k1], first[:k1 - k0], area[:k1 - k0], counts[k0:k1])
                 continue
-            hot = (fr.view(torch.int16).to(torch.int32) & 0xFFFF) > cut
-            _label_images_into(hot, 0, stack[k0:k1], xy[:k1 - k0], area[:k1 - k0], counts[k0:k1])
+            _label_images_into(self._hot_mask(fr, cut), 0, stack[k0:k1], xy[:k1 - k0], area[:k1 - k0], counts[k0:k1])
         nlabels = max(1, int(counts.max())) if n else 1
         tracks = track_components(stack, counts, nlabels, table_entries, out=stack)
         if not stats and not geometry:
@@ -800,12 +746,19 @@ class IRMovie(object):
         ntracks = int(tracks.ntracks)
         out = _region_stats_empty(n, ntracks, device) if stats else None
         geo = _region_geometry_empty(n, ntracks, True, device) if geometry else None
-        for k0, k1, fr in pieces():
+        for k0, k1, fr in self._pieces(positions, device):
             if stats:
-                _region_stats_into(fr, stack[k0:k1], 1, ntracks, type(out)(*(t[k0:k1] for t in out)))
+                _region_stats_into(fr, stack[k0:k1], 1, ntracks, self._rows(out, k0, k1))
             if geometry:
-                _region_geometry_into(stack[k0:k1], fr, k1 - k0, 1, ntracks, type(geo)(*(t[k0:k1] for t in geo)))
+                _region_geometry_into(stack[k0:k1], fr, k1 - k0, 1, ntracks, self._rows(geo, k0, k1))
         return (tracks, out, geo) if geometry else (tracks, out)
+
+    @staticmethod
+    def _hot_mask(fr, cut):
+        """``fr > cut`` of uint16 images ``fr``, widened to int32 for the comparison, with the int or the map of ``_hot_cut``"""
+        import torch
+
+        return (fr.view(torch.int16).to(torch.int32) & 0xFFFF) > cut
 
     def _hot_cut(self, threshold, device, what):
         """the threshold of ``image > threshold`` as the hot-spot calls take it, an int or an (h, w) array or tensor: an int, or a map on `device`"""
@@ -859,19 +812,13 @@ class IRMovie(object):
         cut = self._hot_cut(threshold, device, "distance_transform")
         dist2 = torch.empty((n, h, w), dtype=torch.int32, device=device)
         index = torch.empty((n, h, w), dtype=torch.int32, device=device) if return_indices else None
-        per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-        piece = torch.empty((min(per_piece, n), h, w), dtype=torch.uint16, device=device)
-        for k0 in range(0, n, per_piece):
-            sel = positions[k0:k0 + per_piece]
-            fr = piece[:len(sel)]
-            self.to_tensor(slice(sel.start, sel.stop, sel.step), out=fr)
-            hot = (fr.view(torch.int16).to(torch.int32) & 0xFFFF) > cut
-            k1 = k0 + len(sel)
-            distance_transform(hot, int(bool(invert)), border, rows, return_indices, out=(dist2[k0:k1], index[k0:k1]) if return_indices else dist2[k0:k1])
+        for k0, k1, fr in self._pieces(positions, device):
+            distance_transform(self._hot_mask(fr, cut), int(bool(invert)), border, rows, return_indices,
+                               out=(dist2[k0:k1], index[k0:k1]) if return_indices else dist2[k0:k1])
         return (dist2, index) if return_indices else dist2
 
-    def _stats_positions(self, selection, what="region_stats"):
-        """the positions of an int or a slice with a positive step, as to_tensor takes them"""
+    def _stats_positions(self, selection, what):
+        """the positions of an int or a slice with a positive step, as a range; `what` is the caller's name in the refusals"""
         total = self.images
         if isinstance(selection, (int, np.integer)):
             pos = int(selection) + (total if selection < 0 else 0)
@@ -1073,14 +1020,10 @@ class IRMovie(object):
         thin = Downsampler(w, h, downsample[0], downsample[1], None, downsample[2] if len(downsample) == 3 else 1)
         try:
             device = torch.device("cuda", torch.cuda.current_device())
-            per_piece = max(1, self._STATS_PIECE_BYTES // (2 * h * w))
-            piece = torch.empty((min(per_piece, count), h, w), dtype=torch.uint16, device=device)
-            kept_buffer = torch.empty_like(piece)
-            for k0 in range(0, count, per_piece):
-                n = min(per_piece, count - k0)
+            kept_buffer = torch.empty((self._piece_images(count, h, w), h, w), dtype=torch.uint16, device=device)
+            for k0, k1, fr in self._pieces(range(start_img, start_img + count), device):
                 first = start_img + k0
-                self.to_tensor(slice(first, first + n), out=piece[:n])
-                kept = thin.push(piece[:n], [int(stamps[pos]) for pos in range(first, first + n)], out=kept_buffer[:n])
+                kept = thin.push(fr, [int(stamps[pos]) for pos in range(first, start_img + k1)], out=kept_buffer[:k1 - k0])
                 images = kept.frames.cpu().numpy()
                 for image, at in zip(images, kept.positions):
                     pos = first + int(at)
