@@ -330,6 +330,36 @@ extern "C"
 	int rir_distance_transform_device(int type, const void *d_src, int w, int h, int nframes, int background, int border, int rows, int *d_dist2,
 									  int *d_index /* may be NULL */, void *d_work, size_t work_bytes, void *stream);
 
+	/* Grey-level morphological reconstruction of a marker under a mask (extension): d_dst[nframes][h][w] from the stack d_mask[nframes][h][w]
+	 * and, in marker mode 0, the stack d_marker of the same type and shape.  type: 'H' uint16, 'B' uint8, '?' bool (one byte, 0 / 1), top =
+	 * the type's maximum.  Per frame; the image is the first `rows` (0..h) rows of a frame, rows y >= `rows` of d_dst are a copy of the MASK
+	 * and nothing reads them.  N(p) is p and its neighbours inside the image: the 3x3 window clipped to the image (connectivity 8) or the
+	 * cross (connectivity 4); there is no padding.  With G the mask and F the marker:
+	 *   method 0, reconstruction by dilation: F0 = min(F, G) (a marker above the mask is clamped, not refused), R the fixed point of
+	 *     F_{k+1}(p) = min(G(p), max of F_k over N(p)).  Equivalently R(p) = the maximum, over every pixel q and every connected path from q
+	 *     to p, of min(F0(q), min of G along the path) - which no order of evaluation enters.
+	 *   method 1, reconstruction by erosion, the dual: F0 = max(F, G), F_{k+1}(p) = max(G(p), min of F_k over N(p)).
+	 * marker_mode 0: F = d_marker.  1: F = G - param saturating at 0 (dilation), G + param saturating at top (erosion), param in 0..top; no
+	 * marker stack is stored or read.  2: F = G on row 0, row rows - 1, column 0 and column w - 1, elsewhere 0 (dilation) or top (erosion).
+	 * d_marker must be NULL unless the mode is 0.  output 0: R.  1: the difference, G - R (dilation) or R - G (erosion), never negative.
+	 * So f - R(f - h, f) = (method 0, mode 1, param h, output 1) is the h-dome, which keeps what stands more than h above its surround
+	 * whatever its extent, (method 1, mode 2, output 0) fills the holes and basins that do not reach the border, and (method 0, mode 2,
+	 * output 1) removes what is connected to it.  All integer, bit for bit, the same bits for any split of the stack into calls or groups.
+	 * Rounds of one launch each: a workgroup converges a tile of 64 x 32 pixels in LDS and raises its frame's flag when a pixel moved, in
+	 * place over d_dst; the host reads the flags between rounds and stops after a round that wrote nothing - at most w * rows + 2 rounds,
+	 * beyond which the call fails with "did not converge" (a correct kernel cannot get there).  The call is therefore SYNCHRONOUS with the
+	 * host: it waits for `stream` (for nothing else), and cannot be captured into a graph.  *rounds (host memory, may be NULL): the rounds
+	 * the call took, the largest number over its groups of frames.  d_work: device memory, 8-byte aligned, at least ONE frame's share of
+	 * rir_reconstruct_workspace_bytes(type, w, h, nframes) (which is nframes shares, or 0 when its arguments are refused): the stack goes
+	 * through in groups of as many frames as the workspace holds.  d_dst and the workspace may overlap neither input; d_marker == d_mask
+	 * is allowed and gives the mask back.  nframes 0: nothing is done, 0.  -1 with the reason logged (argument errors before the device is
+	 * looked for): unknown type, method, connectivity, marker mode or output, param outside 0..top, rows outside 0..h, w or h < 1 or
+	 * w * h >= 2^31, nframes < 0, a null d_mask, d_dst or d_work, a marker with mode 1 or 2 or none with mode 0, overlap, a workspace that
+	 * is too small or misaligned, no device. */
+	size_t rir_reconstruct_workspace_bytes(int type, int w, int h, int nframes);
+	int rir_reconstruct_device(int type, const void *d_mask, const void *d_marker, void *d_dst, int w, int h, int nframes, int method, int connectivity,
+							   int marker_mode, int param, int output, int rows, void *d_work, size_t work_bytes, int *rounds, void *stream);
+
 	/* Per-region statistics of a uint16 stack d_frames[nframes][h][w] (extension).  d_labels: int32, one map [h][w] for every frame
 	 * (labels_per_frame 0) or one per frame [nframes][h][w] (1).  For frame f and region r < nregions (1..2^24), P = the flat indices
 	 * i = y * w + x whose label is r; labels outside [0, nregions) are ignored.  Outputs [nframes][nregions]: d_count = |P|, d_sum and

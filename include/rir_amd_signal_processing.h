@@ -100,6 +100,16 @@ extern "C"
 	 * No output may overlap the input or the other output.  nframes 0: 0.  -1 with the reason logged on a bad argument (before the device
 	 * is looked for) and without a device ("no usable HIP device", outputs untouched: there is no CPU fallback). */
 	int rir_distance_transform(int type, const void *src, int w, int h, int nframes, int background, int border, int rows, int *dist2, int *index);
+	/* Grey-level morphological reconstruction of host stacks: rir_reconstruct_device (rir_amd_device.h, where the rule is defined) over
+	 * mask[nframes][h][w] and, in marker mode 0, marker[nframes][h][w], synchronous.  type 'H' uint16, 'B' uint8, '?' bool; method 0
+	 * dilation, 1 erosion; connectivity 4 or 8; marker_mode 0 explicit (marker must be NULL otherwise), 1 the mask shifted by param
+	 * (0..the type's maximum, saturating), 2 the mask on the border of the image; output 0 the reconstruction R, 1 its difference to the
+	 * mask; the image is the first `rows` (0..h) rows, the others are a copy of the mask.  *rounds (may be NULL): the largest number of
+	 * rounds a slab took.  Large stacks go through the device in slabs of at most 64 MiB (frames are independent).  dst may overlap
+	 * neither input; marker == mask is allowed.  nframes 0: 0.  -1 with the reason logged on a bad argument (before the device is looked
+	 * for) and without a device ("no usable HIP device", dst untouched: there is no CPU fallback). */
+	int rir_reconstruct(int type, const void *mask, const void *marker, void *dst, int w, int h, int nframes, int method, int connectivity,
+						int marker_mode, int param, int output, int rows, int *rounds);
 	/* Per-region statistics of a host stack frames[nframes][h][w] with host label maps: rir_region_stats_device (rir_amd_device.h),
 	 * synchronous, host outputs [nframes][nregions].  The frames go through the device in slabs of at most 64 MiB; a shared map goes up
 	 * once.  0 / -1. */

@@ -25,6 +25,7 @@
 #include "polygon_kernels.h"
 #include "quantile_kernels.h"
 #include "rank_kernels.h"
+#include "reconstruct_kernels.h"
 #include "region_kernels.h"
 #include "runtime.h"
 #include "temporal_kernels.h"
@@ -874,6 +875,84 @@ RIR_EXPORT int rir_distance_transform_device(int type, const void *d_src, int w,
 			   : -1;
 }
 
+// Grey-level morphological reconstruction (reconstruct_kernels.hip).  Every argument is checked here, before the device is looked for; the
+// destination (and the workspace) may overlap neither input, the marker may be the mask.
+namespace
+{
+	constexpr size_t RECONSTRUCT_WORK_BYTES = (size_t)256 << 20; // what the workspace query asks for at most
+
+	bool reconstruct_geometry(int w, int h, int nframes) { return w >= 1 && h >= 1 && (int64_t)w * h <= 0x7fffffff && nframes >= 0; }
+
+	// 0, or what is wrong with the arguments that rir_reconstruct and rir_reconstruct_device share, in the order of the tests
+	const char *reconstruct_args(int type, const void *mask, const void *marker, const void *dst, int w, int h, int nframes, int method, int connectivity,
+								 int marker_mode, int param, int output, int rows)
+	{
+		if (!window_type(type))
+			return "unknown type (uint16 'H', uint8 'B' or bool '?')";
+		if (method != 0 && method != 1)
+			return "unknown method (0 dilation, 1 erosion)";
+		if (connectivity != 4 && connectivity != 8)
+			return "connectivity must be 4 or 8";
+		if (marker_mode < 0 || marker_mode >= RECONSTRUCT_MARKERS)
+			return "unknown marker mode (0 explicit, 1 the mask shifted by param, 2 the mask on the border)";
+		if (output != 0 && output != 1)
+			return "unknown output (0 the reconstruction, 1 its difference to the mask)";
+		if (param < 0 || param > (type == 'H' ? 65535 : type == 'B' ? 255 : 1))
+			return "param outside the range of the type";
+		if (!reconstruct_geometry(w, h, nframes) || rows < 0 || rows > h)
+			return "invalid shape (w, h >= 1, w * h < 2^31, nframes >= 0, 0 <= rows <= h)";
+		if (!mask || !dst)
+			return "null pointer";
+		if ((marker_mode == 0) != (marker != nullptr))
+			return "a marker stack goes with marker mode 0, and with no other";
+		const size_t bytes = (size_t)w * h * nframes * (type == 'H' ? 2 : 1);
+		if (outputs_overlap({{mask, bytes}, {marker, bytes}}, {{dst, bytes}}))
+			return "the destination overlaps the mask or the marker";
+		return nullptr;
+	}
+} // namespace
+
+RIR_EXPORT size_t rir_reconstruct_workspace_bytes(int type, int w, int h, int nframes)
+{
+	if (!window_type(type) || !reconstruct_geometry(w, h, nframes))
+		return 0;
+	return RECONSTRUCT_FRAME_BYTES * std::min<size_t>((size_t)std::max(nframes, 1), RECONSTRUCT_WORK_BYTES / RECONSTRUCT_FRAME_BYTES);
+}
+
+RIR_EXPORT int rir_reconstruct_device(int type, const void *d_mask, const void *d_marker, void *d_dst, int w, int h, int nframes, int method,
+									  int connectivity, int marker_mode, int param, int output, int rows, void *d_work, size_t work_bytes, int *rounds,
+									  void *stream)
+{
+	if (const char *bad = reconstruct_args(type, d_mask, d_marker, d_dst, w, h, nframes, method, connectivity, marker_mode, param, output, rows))
+		return refuse(__func__, bad);
+	if (!d_work)
+		return refuse(__func__, "null pointer (the workspace)");
+	if (!workspace_ok(__func__, d_work, work_bytes, RECONSTRUCT_FRAME_BYTES, "workspace", "one frame's share of rir_reconstruct_workspace_bytes()"))
+		return -1;
+	const size_t bytes = (size_t)w * h * nframes * (type == 'H' ? 2 : 1);
+	const size_t used = RECONSTRUCT_FRAME_BYTES * std::min<size_t>((size_t)nframes, work_bytes / RECONSTRUCT_FRAME_BYTES);
+	if (outputs_overlap({{d_mask, bytes}, {d_marker, bytes}, {d_dst, bytes}}, {{d_work, used}}))
+		return refuse(__func__, "the workspace overlaps an input or the destination");
+	if (rounds)
+		*rounds = 0;
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	thread_local PinnedBuffer h_flags; // the flags of a round, as the host reads them
+	if (!h_flags.reserve(sizeof(int) * (size_t)reconstruct_group_frames(nframes, work_bytes)))
+		return -1;
+	int took = 0;
+	bool converged = true;
+	if (!hip_ok(launch_reconstruct(type, d_mask, d_marker, d_dst, w, h, nframes, method, connectivity, marker_mode, param, output, rows, d_work, work_bytes,
+								   h_flags.as<int>(), &took, &converged, as_stream(stream)),
+				"reconstruct"))
+		return -1;
+	if (rounds)
+		*rounds = took;
+	return converged ? 0 : refuse(__func__, "did not converge within w * rows + 2 rounds");
+}
+
 // Per-region statistics (region_kernels.hip).  Every argument is checked here; no output (workspace included) may overlap an input or
 // another output.
 namespace
@@ -1657,6 +1736,42 @@ RIR_EXPORT int rir_distance_transform(int type, const void *src, int w, int h, i
 			rir_distance_transform_device(type, in.ptr, w, h, c, background, border, rows, d_dist2, d_index, ws.ptr, work, s.st) != 0 ||
 			!s.down(outs, o * npx, c * npx) || !s.wait("distance_transform"))
 			return s.fail();
+	}
+	return 0;
+}
+
+// Reconstruction of a host stack (frames are independent: any split gives the same bits): the mask, and the marker where there is one, go up
+// slab by slab, the result comes down.
+RIR_EXPORT int rir_reconstruct(int type, const void *mask, const void *marker, void *dst, int w, int h, int nframes, int method, int connectivity,
+							   int marker_mode, int param, int output, int rows, int *rounds)
+{
+	if (const char *bad = reconstruct_args(type, mask, marker, dst, w, h, nframes, method, connectivity, marker_mode, param, output, rows))
+		return refuse(__func__, bad);
+	if (rounds)
+		*rounds = 0;
+	if (nframes == 0)
+		return 0;
+	if (!device_ready())
+		return -1;
+	const size_t frame = (size_t)w * h * (type == 'H' ? 2 : 1);
+	const int slab = Stager::slab(nframes, {frame});
+	const size_t work = RECONSTRUCT_FRAME_BYTES * slab;
+	DeviceBuffer in, seed, out, ws;
+	if (!in.reserve(frame * slab) || (marker && !seed.reserve(frame * slab)) || !out.reserve(frame * slab) || !ws.reserve(work))
+		return -1;
+	Stager s;
+	for (int o = 0; o < nframes; o += slab)
+	{
+		const int c = std::min(slab, nframes - o);
+		int took = 0;
+		if (!s.up(in.ptr, static_cast<const char *>(mask) + frame * o, frame * c) ||
+			!s.up(marker ? seed.ptr : nullptr, marker ? static_cast<const char *>(marker) + frame * o : nullptr, frame * c) ||
+			rir_reconstruct_device(type, in.ptr, marker ? seed.ptr : nullptr, out.ptr, w, h, c, method, connectivity, marker_mode, param, output, rows, ws.ptr,
+								   work, &took, s.st) != 0 ||
+			!s.down(static_cast<char *>(dst) + frame * o, out.ptr, frame * c) || !s.wait("reconstruct"))
+			return s.fail();
+		if (rounds)
+			*rounds = std::max(*rounds, took);
 	}
 	return 0;
 }

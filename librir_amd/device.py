@@ -15,7 +15,8 @@ from .signal_processing.rir_signal_processing import (DIST2_NONE, DISTANCE_MAX_S
                                                       _pixel_stats_args, _polygon_map_args, _region_geometry_args, _region_histogram_args,
                                                       _region_quantiles_args, _region_quantiles_percents, _region_stats_args,
                                                       _local_stats_args, _morphology_args, _rank_filter_args, _temporal_median_args,
-                                                      _window_size, percentile_rank)
+                                                      _window_size, percentile_rank,
+                                                      RECONSTRUCT_BORDER, RECONSTRUCT_MARKER, RECONSTRUCT_SHIFT, _NO_SHIFT, _reconstruct_args)
 
 DEFAULT_GOP = 50  # reference key-frame cadence, src/cpp/video_io/h264.cpp:1662-1665
 
@@ -122,6 +123,9 @@ _lib.rir_local_threshold_device.argtypes = [ct.c_int, _vp, _vp] + [ct.c_int] * 1
 _lib.rir_distance_transform_device.argtypes = [ct.c_int, _vp] + [ct.c_int] * 6 + [_vp, _vp, _vp, ct.c_size_t, _vp]
 _lib.rir_distance_transform_workspace_bytes.argtypes = [ct.c_int] * 4
 _lib.rir_distance_transform_workspace_bytes.restype = ct.c_size_t
+_lib.rir_reconstruct_device.argtypes = [ct.c_int, _vp, _vp, _vp] + [ct.c_int] * 9 + [_vp, ct.c_size_t, ct.POINTER(ct.c_int), _vp]
+_lib.rir_reconstruct_workspace_bytes.argtypes = [ct.c_int] * 4
+_lib.rir_reconstruct_workspace_bytes.restype = ct.c_size_t
 _lib.rir_region_stats_device.argtypes =[_vp, _vp] + [ct.c_int] * 5 + [_vp] * 8 + [ct.c_size_t, _vp]
 _lib.rir_region_stats_workspace_bytes.argtypes = [ct.c_int] * 5
 _lib.rir_region_stats_workspace_bytes.restype = ct.c_size_t
@@ -976,6 +980,112 @@ def disc_close(mask, radius):
     disc, the outside of the image taken as set by the erosion)"""
     _disc_args("disc_close", mask, radius)
     return disc_erode(disc_dilate(mask, radius), radius)
+
+
+def _reconstruct(name, mask, marker, method, connectivity, rows, out, mode, h, output, return_rounds=False):
+    """the reconstruction forms: ``rir_reconstruct_device`` over ``mask`` with the parameters checked first, which needs no device"""
+    shape = tuple(mask.shape)
+    dtype_name = np.dtype(_NP_OF[mask.dtype]).name if mask.dtype in _NP_OF else str(mask.dtype)
+    type_char, method, connectivity, rows, param = _reconstruct_args(name, (1,) + shape if len(shape) == 2 else shape, dtype_name, method, connectivity,
+                                                                     rows, h)
+    if marker is not None and (not isinstance(marker, torch.Tensor) or marker.dtype != mask.dtype or tuple(marker.shape) != shape):
+        raise ValueError("%s: the marker must be a tensor of the mask's dtype and shape" % name)
+    if out is not None and (not out.is_cuda or out.dtype != mask.dtype or tuple(out.shape) != shape or not out.is_contiguous()):
+        raise RuntimeError("%s: out must be a contiguous %s CUDA tensor of shape %s" % (name, mask.dtype, shape))
+    fr = _frames3(mask)
+    seed = None if marker is None else _frames3(marker)
+    n, height, w = fr.shape
+    if out is None:
+        out = torch.empty(shape, dtype=fr.dtype, device=fr.device)
+    rounds = ct.c_int(0)
+    if n:
+        need = _lib.rir_reconstruct_workspace_bytes(type_char, w, height, n)
+        if need == 0:
+            raise RuntimeError("%s: geometry refused" % name)
+        work = _workspace(need, fr.device)
+        _check(_lib.rir_reconstruct_device(type_char, fr.data_ptr(), None if seed is None else seed.data_ptr(), out.data_ptr(), w, height, n, method,
+                                           connectivity, mode, param, output, rows, work.data_ptr(), work.numel() * 8, ct.byref(rounds), _stream()),
+               "rir_reconstruct_device")
+    return (out, rounds.value) if return_rounds else out
+
+
+def reconstruct(marker, mask, method="dilation", connectivity=8, rows=None, out=None, return_rounds=False):
+    """Grey-level morphological reconstruction of ``marker`` under ``mask``, uint16, uint8 or bool CUDA stacks ``[n][h][w]`` (or one image
+    ``[h][w]``) of the same dtype and shape (C ABI ``rir_reconstruct_device``, where the rule is defined).  ``method="dilation"``: the
+    marker, clamped to ``min(marker, mask)``, spreads under the mask until nothing changes - the fixed point of ``min(mask, dilate(f, 3))``
+    (``connectivity=8``) or of the same with the cross (4), the window clipped to the image; per pixel the best, over all paths that reach
+    it, of the lowest mask value on the path and the marker at its start.  ``method="erosion"``: the dual, from ``max(marker, mask)`` down.
+    This is ``skimage.morphology.reconstruction`` and, on bool, ``scipy.ndimage.binary_propagation(marker, structure, mask=mask)``: "keep
+    what is connected to a marker".  The image is the first ``rows`` rows of a frame (default: all); the others are a copy of the mask.
+    Bit for bit, whatever the reach: tiles converge in LDS and the call repeats rounds until one writes nothing, so it waits for the
+    current stream between rounds - it is synchronous with the host and cannot be captured into a graph.  Returns a tensor of the input's
+    dtype and shape (``out`` when given: a contiguous CUDA tensor of that dtype and shape that overlaps neither input);
+    ``return_rounds=True``: ``(result, rounds)``.  ``ValueError`` on bad parameters, before any device work."""
+    return _reconstruct("reconstruct", mask, marker, method, connectivity, rows, out, RECONSTRUCT_MARKER, _NO_SHIFT, 0, return_rounds)
+
+
+def h_maxima(frames, h, connectivity=8, rows=None, out=None):
+    """The h-maxima transform ``reconstruct(frames - h, frames)`` (the subtraction saturating at 0; no marker stack is stored): every
+    maximum cut down by ``h``, or to the level at which it joins a higher one.  ``h``: an int in 0..the dtype's maximum."""
+    return _reconstruct("h_maxima", frames, None, "dilation", connectivity, rows, out, RECONSTRUCT_SHIFT, h, 0)
+
+
+def h_dome(frames, h, connectivity=8, rows=None, out=None):
+    """The h-domes ``frames - h_maxima(frames, h)``: what stands above its surround, at most ``h`` of it, whatever the extent of the
+    structure - a top-hat without a window, for hot spots larger than any window on an uneven background.  ``h_dome(f, 0)`` is 0."""
+    return _reconstruct("h_dome", frames, None, "dilation", connectivity, rows, out, RECONSTRUCT_SHIFT, h, 1)
+
+
+def h_minima(frames, h, connectivity=8, rows=None, out=None):
+    """The dual of ``h_maxima``: ``reconstruct(frames + h, frames, "erosion")`` (the sum saturating at the dtype's maximum): every minimum
+    raised by ``h``, or to the level at which it joins a lower one"""
+    return _reconstruct("h_minima", frames, None, "erosion", connectivity, rows, out, RECONSTRUCT_SHIFT, h, 0)
+
+
+def h_basin(frames, h, connectivity=8, rows=None, out=None):
+    """The dual of ``h_dome``: ``h_minima(frames, h) - frames``, the depth, at most ``h``, of what lies below its surround"""
+    return _reconstruct("h_basin", frames, None, "erosion", connectivity, rows, out, RECONSTRUCT_SHIFT, h, 1)
+
+
+def _regional(name, method, frames, connectivity, rows, out):
+    """``regional_maxima`` and ``regional_minima``: where the difference output of a shift by 1 is not 0"""
+    shape = tuple(frames.shape)
+    if out is not None and (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.bool or tuple(out.shape) != shape):
+        dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
+        _reconstruct_args(name, (1,) + shape if len(shape) == 2 else shape, dtype_name, method, connectivity, rows)  # (bad parameters come first)
+        raise RuntimeError("%s: out must be a bool CUDA tensor of shape %s" % (name, shape))
+    depth = _reconstruct(name, frames, None, method, connectivity, rows, None, RECONSTRUCT_SHIFT, 1, 1)
+    found = torch.ne(depth.view(torch.int16) if depth.dtype == torch.uint16 else depth, 0, out=out)
+    if rows is not None:
+        found[..., int(rows):, :] = False  # (outside the image)
+    return found
+
+
+def regional_maxima(frames, connectivity=8, rows=None, out=None):
+    """The regional maxima as a bool mask, ``h_dome(frames, 1) != 0``: the plateaus with no higher neighbour.  One consequence of the
+    saturating marker: a plateau of value 0 is no maximum (a constant frame of zeros has none).  Rows outside the image are False."""
+    return _regional("regional_maxima", "dilation", frames, connectivity, rows, out)
+
+
+def regional_minima(frames, connectivity=8, rows=None, out=None):
+    """The regional minima as a bool mask, ``h_basin(frames, 1) != 0``: the plateaus with no lower neighbour.  A plateau of the dtype's
+    maximum is no minimum.  Rows outside the image are False."""
+    return _regional("regional_minima", "erosion", frames, connectivity, rows, out)
+
+
+def fill_holes(frames, connectivity=4, rows=None, out=None):
+    """Reconstruction by erosion from the image's border (the marker is the frame on its border and the dtype's maximum inside; no marker
+    stack is stored): every basin that does not reach the border is filled up to its rim.  On a bool mask at the default
+    ``connectivity=4`` - the connectivity of the BACKGROUND - this is ``scipy.ndimage.binary_fill_holes``; it mends a hot spot with a
+    saturated or repaired centre before ``region_geometry``, ``distance_transform`` or ``track_components``.  The border is that of the
+    first ``rows`` rows."""
+    return _reconstruct("fill_holes", frames, None, "erosion", connectivity, rows, out, RECONSTRUCT_BORDER, _NO_SHIFT, 0)
+
+
+def clear_border(frames, connectivity=8, rows=None, out=None):
+    """``frames - reconstruct(border marker, frames)``, the marker being the frame on the image's border and 0 inside: removes everything
+    connected to the edge of the image, grey or binary (``skimage.segmentation.clear_border`` on a bool mask)"""
+    return _reconstruct("clear_border", frames, None, "dilation", connectivity, rows, out, RECONSTRUCT_BORDER, _NO_SHIFT, 1)
 
 
 class TemporalMedian:

@@ -389,6 +389,77 @@ def local_threshold(images, size, k, delta=0, polarity="above", rows=None):
     return out.reshape(img.shape)
 
 
+# ---- extension: grey-level morphological reconstruction --------------------------------------------------------------------------
+_sp.rir_reconstruct.argtypes = [ct.c_int, ct.c_void_p, ct.c_void_p, ct.c_void_p] + [ct.c_int] * 9 + [ct.c_void_p]
+
+RECONSTRUCT_METHODS = ("dilation", "erosion")  # the method numbers of the C ABI
+RECONSTRUCT_MARKER, RECONSTRUCT_SHIFT, RECONSTRUCT_BORDER = 0, 1, 2  # its marker modes
+_TYPE_TOP = {"uint16": 65535, "uint8": 255, "bool": 1}
+_NO_SHIFT = object()  # the h of a form whose marker is no shifted mask
+
+
+def _reconstruct_args(name, shape, dtype_name, method, connectivity, rows, h=_NO_SHIFT):
+    """the parameters of a reconstruction over a stack of `shape`, checked without a device; `h` is the shift of the marker where the call
+    has one; -> (type char, method number, connectivity, rows, h or 0)"""
+    type_char = _window_type(name, shape, dtype_name)
+    if method not in RECONSTRUCT_METHODS:
+        raise ValueError("%s: method must be one of %s (got %r)" % (name, ", ".join(RECONSTRUCT_METHODS), method))
+    if isinstance(connectivity, (bool, np.bool_)) or connectivity not in (4, 8):
+        raise ValueError("%s: connectivity must be 4 or 8 (got %r)" % (name, connectivity))
+    if h is not _NO_SHIFT:
+        if not isinstance(h, (int, np.integer)) or isinstance(h, (bool, np.bool_)) or not 0 <= int(h) <= _TYPE_TOP[dtype_name]:
+            raise ValueError("%s: h must be an int in 0..%d for %s (got %r)" % (name, _TYPE_TOP[dtype_name], dtype_name, h))
+    return type_char, RECONSTRUCT_METHODS.index(method), int(connectivity), _window_rows(name, shape, rows), 0 if h is _NO_SHIFT else int(h)
+
+
+def _reconstruct_host(name, images, marker, method, connectivity, rows, mode, h, output):
+    img = np.ascontiguousarray(images)
+    if img.ndim not in (2, 3):
+        raise ValueError("%s: an image [h][w] or a stack [n][h][w] expected" % name)
+    stack = img.reshape((-1,) + img.shape[-2:])
+    type_char, method, connectivity, rows, param = _reconstruct_args(name, stack.shape, img.dtype.name, method, connectivity, rows, h)
+    seed = None
+    if marker is not None:
+        seed = np.ascontiguousarray(marker)
+        if seed.dtype != img.dtype or seed.shape != img.shape:
+            raise ValueError("%s: the marker must have the mask's dtype and shape" % name)
+    out = np.empty_like(stack)
+    n, height, w = stack.shape
+    if n and _sp.rir_reconstruct(type_char, stack.ctypes.data, None if seed is None else seed.ctypes.data, out.ctypes.data, w, height, n, method,
+                                 connectivity, mode, param, output, rows, None) < 0:
+        raise RuntimeError("An error occured while calling '%s': %s" % (name, last_error() or ""))
+    return out.reshape(img.shape)
+
+
+def reconstruct(marker, mask, method="dilation", connectivity=8, rows=None):
+    """Extension: grey-level morphological reconstruction of ``marker`` under ``mask``, uint16, uint8 or bool stacks ``[n][h][w]`` (or one
+    image ``[h][w]``) of the same dtype and shape (``rir_reconstruct``, where the rule is defined).  ``method="dilation"``: the marker,
+    clamped to ``min(marker, mask)``, spreads under the mask until nothing changes - the fixed point of ``min(mask, maximum_filter(f))`` over
+    the 3x3 window (``connectivity=8``) or the cross (4), clipped to the image: ``skimage.morphology.reconstruction``, and on bool
+    ``scipy.ndimage.binary_propagation(marker, structure, mask=mask)``.  ``method="erosion"``: the dual, from ``max(marker, mask)`` down.
+    The image is its first ``rows`` rows (default: all); the others are a copy of the mask.  Returns an array of the input's dtype and
+    shape.  ``ValueError`` on bad parameters, ``RuntimeError`` when the library fails."""
+    return _reconstruct_host("reconstruct", mask, marker, method, connectivity, rows, RECONSTRUCT_MARKER, _NO_SHIFT, 0)
+
+
+def h_maxima(images, h, connectivity=8, rows=None):
+    """Extension: the h-maxima transform ``R(images - h, images)``, reconstruction by dilation of the image lowered by ``h`` (saturating at
+    0) under itself: every maximum cut down by ``h``, or to the level at which it joins a higher one (``reconstruct``)"""
+    return _reconstruct_host("h_maxima", images, None, "dilation", connectivity, rows, RECONSTRUCT_SHIFT, h, 0)
+
+
+def h_dome(images, h, connectivity=8, rows=None):
+    """Extension: the h-domes ``images - R(images - h, images)``: what stands above its surround, at most ``h`` of it, whatever the extent
+    of the structure - a top-hat without a window (``reconstruct``)"""
+    return _reconstruct_host("h_dome", images, None, "dilation", connectivity, rows, RECONSTRUCT_SHIFT, h, 1)
+
+
+def fill_holes(images, connectivity=4, rows=None):
+    """Extension: reconstruction by erosion from the border of the image: every basin that does not reach the border is filled up to its
+    rim.  On a bool mask at the default ``connectivity=4`` (of the background) this is ``scipy.ndimage.binary_fill_holes`` (``reconstruct``)"""
+    return _reconstruct_host("fill_holes", images, None, "erosion", connectivity, rows, RECONSTRUCT_BORDER, _NO_SHIFT, 0)
+
+
 # ---- extension: exact Euclidean distance transform -------------------------------------------------------------------------------
 _sp.rir_distance_transform.argtypes = [ct.c_int, ct.c_void_p] + [ct.c_int] * 6 + [ct.c_void_p, ct.c_void_p]
 

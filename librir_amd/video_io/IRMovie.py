@@ -604,6 +604,36 @@ class IRMovie(object):
         size_y, size_x = _window_sizes(size)
         return self.rank_filter(size_y * size_x // 2, size, selection, rows, out)
 
+    def h_dome(self, h, selection=slice(None), connectivity=8, rows=None, out=None):
+        """The h-domes of the images of ``selection`` (as ``region_stats`` takes it) - ``librir_amd.device.h_dome(frames, h, connectivity,
+        rows)`` over the images ``to_tensor(selection)`` gives (read-back filters applied), on the device: a uint16 CUDA tensor
+        ``[len(selection)][h][w]`` (``out`` when given: a contiguous uint16 CUDA tensor of that shape) with what stands above its surround,
+        ``h`` of it at most - ``image - R(image - h, image)``, R the reconstruction by dilation.  Unlike ``morphology("tophat", 9)`` it has
+        no window: a strike line or a 40-pixel spot keeps its contrast.  ``connectivity`` is 8 or 4; ``rows=None`` takes all rows,
+        otherwise rows ``>= rows`` are copied.  The recording is read in pieces of at most ``_STATS_PIECE_BYTES`` of images; images are
+        independent, so any split gives the same bits::
+
+            labels = librir_amd.device.label_hot_spots(mov.h_dome(40), low=10, min_area=4)   # hot spots of any size, 10 counts of contrast
+        """
+        return self._reconstruct_form("h_dome", h, selection, connectivity, rows, out)
+
+    def h_maxima(self, h, selection=slice(None), connectivity=8, rows=None, out=None):
+        """The h-maxima transform of the images of ``selection`` - ``librir_amd.device.h_maxima(frames, h, connectivity, rows)`` over the
+        images ``to_tensor(selection)`` gives: every maximum cut down by ``h``, ``image - mov.h_dome(h)``; parameters and pieces as
+        ``h_dome``"""
+        return self._reconstruct_form("h_maxima", h, selection, connectivity, rows, out)
+
+    def _reconstruct_form(self, name, h, selection, connectivity, rows, out):
+        """``h_dome`` and ``h_maxima``: the form of that name of ``librir_amd.device`` over the images of ``selection``, read in pieces"""
+        import torch
+
+        from .. import device
+
+        height, w = self.image_size
+        device._reconstruct_args(name, (1, height, w), "uint16", "dilation", connectivity, rows, h)
+        form = getattr(device, name)
+        return self._filter_pieces(name, lambda fr, out: form(fr, h, connectivity, rows, out=out), torch.uint16, selection, out)
+
     def _filter_pieces(self, name, filter, dtype, selection, out):
         """what the window filters and the local statistics share: ``filter(piece, out=...)`` of ``librir_amd.device`` over the images of
         ``selection``, read in pieces, into a `dtype` tensor ``[len(selection)][h][w]``"""
