@@ -46,6 +46,7 @@ _NP_OF = {
     torch.float32: np.float32,
     torch.float64: np.float64,
 }
+_DTYPE_NAMES = {t: np.dtype(a).name for t, a in _NP_OF.items()}  # as the _..._args checkers of the host module name them
 
 
 class CodecLayout(ct.Structure):
@@ -209,6 +210,51 @@ def _frames3(t, dtype=None):
     if dtype is not None and t.dtype != dtype:
         raise RuntimeError("expected dtype %s" % dtype)
     return t.contiguous()
+
+
+# What the forms of the frame filters share ("The Python forms of the frame filters").
+def _stack_of(t):
+    """-> (the shape of `t`, that shape as a stack [n][h][w] - one image being a stack of one -, the numpy name of its dtype), the last two as the
+    ``_..._args`` checkers take them"""
+    shape = tuple(t.shape)
+    return shape, (1,) + shape if len(shape) == 2 else shape, _DTYPE_NAMES.get(t.dtype) or str(t.dtype)
+
+
+def _is_out(t, dtypes, shape, contiguous=True):
+    """whether `t` can take an output: a CUDA tensor of one of `dtypes` and of `shape`, contiguous unless that is not asked for"""
+    return isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in dtypes and tuple(t.shape) == shape and (not contiguous or t.is_contiguous())
+
+
+def _out_or_new(out, dtype, shape, device, message, *args):
+    """`out` checked - a contiguous CUDA tensor of `dtype` and `shape`, else ``RuntimeError(message % args)``, the form's own words - or, for
+    None, a new tensor on `device`"""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if not _is_out(out, (dtype,), shape):
+        raise RuntimeError(message % args)
+    return out
+
+
+def _workspace(need, device):
+    """an 8-byte aligned workspace of at least `need` bytes on `device`: work.data_ptr(), work.numel() * 8"""
+    return torch.empty(need // 8 + 1, dtype=torch.int64, device=device)
+
+
+def _queue(entry, n, *args):
+    """queue `entry`, a ``rir_<name>_device`` of the C ABI, over `args` on the current stream, which is its last argument; nothing for n = 0 frames"""
+    if n:
+        _check(entry(*args, _stream()), entry.__name__)
+
+
+def _queue_with_workspace(entry, workspace_bytes, query, device, n, *args, form=None, after=()):
+    """``_queue`` for an entry that takes a workspace and its size behind `args` (and `after` behind those): the workspace is what its
+    ``workspace_bytes(*query)`` asks for, on `device`; `form`: the name of a form to which 0 bytes mean that the geometry is refused"""
+    if n:
+        need = workspace_bytes(*query)
+        if form is not None and need == 0:
+            raise RuntimeError("%s: geometry refused" % form)
+        work = _workspace(need, device)
+        _queue(entry, n, *args, work.data_ptr(), work.numel() * 8, *after)
 
 
 def codec_layout(width, height, nframes, gop=DEFAULT_GOP):
@@ -686,30 +732,20 @@ def temporal_median(frames, window, threshold=0, rows=None, first=0, count=None,
     rows, count = _temporal_median_args(tuple(frames.shape), window, threshold, rows, first, count, step)
     fr = _frames3(frames, torch.uint16)
     n, h, w = fr.shape
-    if out is None:
-        out = torch.empty((count, h, w), dtype=torch.uint16, device=fr.device)
-    elif not out.is_cuda or out.dtype != torch.uint16 or tuple(out.shape) != (count, h, w) or not out.is_contiguous():
-        raise RuntimeError("temporal_median: out must be a contiguous uint16 CUDA tensor of shape %s" % ((count, h, w),))
-    if count:
-        _check(_lib.rir_temporal_median_device(fr.data_ptr(), out.data_ptr(), w, h, n, int(first), count, int(step), int(window), int(threshold), rows,
-                                               _stream()), "rir_temporal_median_device")
+    out = _out_or_new(out, torch.uint16, (count, h, w), fr.device, "temporal_median: out must be a contiguous uint16 CUDA tensor of shape %s", (count, h, w))
+    _queue(_lib.rir_temporal_median_device, count, fr.data_ptr(), out.data_ptr(), w, h, n, int(first), count, int(step), int(window), int(threshold), rows)
     return out
 
 
 def _window_filter(name, check, entry, frames, own, size, rows, out):
     """``morphology`` and ``rank_filter``: the device entry of the C ABI over ``frames`` with the parameters that ``check`` passes, ``own``
     being the op or the rank"""
-    shape = tuple(frames.shape)
-    dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
-    type_char, own, size_y, size_x, rows = check((1,) + shape if len(shape) == 2 else shape, dtype_name, own, size, rows)
-    if out is not None and (not out.is_cuda or out.dtype != frames.dtype or tuple(out.shape) != shape or not out.is_contiguous()):
-        raise RuntimeError("%s: out must be a contiguous %s CUDA tensor of shape %s" % (name, frames.dtype, shape))
+    shape, stack, dtype_name = _stack_of(frames)
+    type_char, own, size_y, size_x, rows = check(stack, dtype_name, own, size, rows)
+    out = _out_or_new(out, frames.dtype, shape, frames.device, "%s: out must be a contiguous %s CUDA tensor of shape %s", name, frames.dtype, shape)
     fr = _frames3(frames)
     n, h, w = fr.shape
-    if out is None:
-        out = torch.empty(shape, dtype=fr.dtype, device=fr.device)
-    if n:
-        _check(entry(type_char, fr.data_ptr(), out.data_ptr(), w, h, n, own, size_x, size_y, rows, _stream()), "rir_%s_device" % name)
+    _queue(entry, n, type_char, fr.data_ptr(), out.data_ptr(), w, h, n, own, size_x, size_y, rows)
     return out
 
 
@@ -791,22 +827,7 @@ def percentile_filter(frames, percent, size, rows=None, out=None):
     return rank_filter(frames, percentile_rank(percent, size_y, size_x), size, rows, out)
 
 
-def _local_inputs(name, frames, size, rows, **own):
-    """the checks of ``local_stats`` / ``local_threshold`` that need no device: -> (what ``_local_stats_args`` returns for the stack - one
-    image being a stack of one -, the input's shape)"""
-    shape = tuple(frames.shape)
-    dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
-    args = _local_stats_args(name, (1,) + shape if len(shape) == 2 else shape, dtype_name, size, rows, **own)
-    return args, shape
-
-
-def _local_out(name, what, out, frames, dtype, shape):
-    """``out`` checked - a contiguous CUDA tensor of `dtype` and `shape` that does not overlap ``frames`` - or a new tensor"""
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=frames.device)
-    if not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous():
-        raise RuntimeError("%s: %s must be a contiguous %s CUDA tensor of shape %s" % (name, what, dtype, shape))
-    return out
+_LOCAL_OUT = "%s: %s must be a contiguous %s CUDA tensor of shape %s"  # what local_stats and local_threshold say to an 'out' that does not fit
 
 
 def local_stats(frames, size, rows=None, sum=True, sumsq=False, mean=False, out=None):
@@ -820,18 +841,16 @@ def local_stats(frames, size, rows=None, sum=True, sumsq=False, mean=False, out=
     sumsq, mean)``) with a contiguous CUDA tensor of the right dtype and shape for every output asked for, none of which overlaps
     ``frames`` or another; they are fully overwritten.  Non-contiguous input is copied first.  All integer, bit for bit
     (``local_variance_terms`` gives the exact variance); ``ValueError`` on bad parameters, before any device work."""
-    (type_char, size_y, size_x, rows), shape = _local_inputs("local_stats", frames, size, rows, outputs=(sum, sumsq, mean))
-    wanted = (bool(sum), bool(sumsq), bool(mean))
+    shape, stack, dtype_name = _stack_of(frames)
+    type_char, size_y, size_x, rows = _local_stats_args("local_stats", stack, dtype_name, size, rows, outputs=(sum, sumsq, mean))
     if out is not None and (not isinstance(out, (tuple, list)) or len(out) not in (3, 4)):
         raise RuntimeError("local_stats: out must be a LocalStats or a tuple (sum, sumsq, mean)")
-    dtypes = (torch.int32, torch.int64, frames.dtype)
-    outs = [_local_out("local_stats", "out." + f, None if out is None else out[k], frames, dtypes[k], shape) if wanted[k] else None
-            for k, f in enumerate(LocalStats._fields[:3])]
+    asked = zip((sum, sumsq, mean), LocalStats._fields, (torch.int32, torch.int64, frames.dtype))
+    outs = [_out_or_new(None if out is None else out[k], dtype, shape, frames.device, _LOCAL_OUT, "local_stats", "out." + field, dtype, shape)
+            if wanted else None for k, (wanted, field, dtype) in enumerate(asked)]
     fr = _frames3(frames)
     n, h, w = fr.shape
-    if n:
-        _check(_lib.rir_local_stats_device(type_char, fr.data_ptr(), w, h, n, size_x, size_y, rows, *(None if t is None else t.data_ptr() for t in outs),
-                                           _stream()), "rir_local_stats_device")
+    _queue(_lib.rir_local_stats_device, n, type_char, fr.data_ptr(), w, h, n, size_x, size_y, rows, *(None if t is None else t.data_ptr() for t in outs))
     return LocalStats(*outs, size_y * size_x)
 
 
@@ -858,14 +877,14 @@ def local_threshold(frames, size, k, delta=0, polarity="above", rows=None, out=N
     overlap ``frames`` (it receives 0 / 1 and is returned).  The mask - as uint8 through ``.view(torch.uint8)`` - is what ``label_images``
     and ``morphology`` take: ``label_images(morph_open(local_threshold(frames, 9, 4, delta=20).view(torch.uint8), 3))``.  ``ValueError`` on
     bad parameters, before any device work."""
-    (type_char, size_y, size_x, rows, k_num, k_den, delta, polarity), shape = _local_inputs("local_threshold", frames, size, rows, k=k, delta=delta,
-                                                                                             polarity=polarity)
-    out = _local_out("local_threshold", "out", out, frames, torch.uint8 if out is not None and out.dtype == torch.uint8 else torch.bool, shape)
+    shape, stack, dtype_name = _stack_of(frames)
+    type_char, size_y, size_x, rows, k_num, k_den, delta, polarity = _local_stats_args("local_threshold", stack, dtype_name, size, rows, k=k, delta=delta,
+                                                                                       polarity=polarity)
+    dtype = torch.uint8 if isinstance(out, torch.Tensor) and out.dtype == torch.uint8 else torch.bool  # (either is taken)
+    out = _out_or_new(out, dtype, shape, frames.device, _LOCAL_OUT, "local_threshold", "out", dtype, shape)
     fr = _frames3(frames)
     n, h, w = fr.shape
-    if n:
-        _check(_lib.rir_local_threshold_device(type_char, fr.data_ptr(), out.data_ptr(), w, h, n, size_x, size_y, rows, k_num, k_den, delta, polarity,
-                                               _stream()), "rir_local_threshold_device")
+    _queue(_lib.rir_local_threshold_device, n, type_char, fr.data_ptr(), out.data_ptr(), w, h, n, size_x, size_y, rows, k_num, k_den, delta, polarity)
     return out
 
 
@@ -885,12 +904,11 @@ _DISTANCE_WORK_BYTES = 256 << 20  # the workspace of one distance_transform call
 def _distance_transform_inputs(masks, background, border, rows, out, return_indices):
     """distance_transform's checks, the parameters first, which need no device; -> (masks [n][h][w], type char, background, border, rows,
     dist2, index or None), the outputs of the shape of `masks`"""
-    shape = tuple(masks.shape)
-    dtype_name = np.dtype(_NP_OF[masks.dtype]).name if masks.dtype in _NP_OF else str(masks.dtype)
-    type_char, background, border, rows = _distance_transform_args((1,) + shape if len(shape) == 2 else shape, dtype_name, background, border, rows)
+    shape, stack, dtype_name = _stack_of(masks)
+    type_char, background, border, rows = _distance_transform_args(stack, dtype_name, background, border, rows)
     outs = (out if return_indices else (out,)) if out is not None else ()
-    if out is not None and (not isinstance(outs, (tuple, list)) or len(outs) != 1 + bool(return_indices) or any(
-            not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or tuple(t.shape) != shape or not t.is_contiguous() for t in outs)):
+    if out is not None and (not isinstance(outs, (tuple, list)) or len(outs) != 1 + bool(return_indices)
+                            or not all(_is_out(t, (torch.int32,), shape) for t in outs)):
         raise RuntimeError("distance_transform: out must be %s of shape %s" % (
             "a pair (dist2, index) of contiguous int32 CUDA tensors" if return_indices else "a contiguous int32 CUDA tensor", shape))
     fr = _frames3(masks)
@@ -907,10 +925,9 @@ def _distance_transform_into(fr, type_char, background, border, rows, dist2, ind
     one, need = _lib.rir_distance_transform_workspace_bytes(w, h, 1, want), _lib.rir_distance_transform_workspace_bytes(w, h, n, want)
     if one == 0:
         raise RuntimeError("distance_transform: geometry refused")
-    work = _workspace(max(one, min(need, _DISTANCE_WORK_BYTES // one * one)), fr.device)
-    _check(_lib.rir_distance_transform_device(type_char, fr.data_ptr(), w, h, n, background, border, rows, dist2.data_ptr(),
-                                              None if index is None else index.data_ptr(), work.data_ptr(), work.numel() * 8, _stream()),
-           "rir_distance_transform_device")
+    work = _workspace(max(one, min(need, _DISTANCE_WORK_BYTES // one * one)), fr.device)  # (its size is not the query's answer: no _queue_with_workspace)
+    _queue(_lib.rir_distance_transform_device, n, type_char, fr.data_ptr(), w, h, n, background, border, rows, dist2.data_ptr(),
+           None if index is None else index.data_ptr(), work.data_ptr(), work.numel() * 8)
 
 
 def distance_transform(masks, background=0, border=False, rows=None, return_indices=False, out=None):
@@ -984,28 +1001,18 @@ def disc_close(mask, radius):
 
 def _reconstruct(name, mask, marker, method, connectivity, rows, out, mode, h, output, return_rounds=False):
     """the reconstruction forms: ``rir_reconstruct_device`` over ``mask`` with the parameters checked first, which needs no device"""
-    shape = tuple(mask.shape)
-    dtype_name = np.dtype(_NP_OF[mask.dtype]).name if mask.dtype in _NP_OF else str(mask.dtype)
-    type_char, method, connectivity, rows, param = _reconstruct_args(name, (1,) + shape if len(shape) == 2 else shape, dtype_name, method, connectivity,
-                                                                     rows, h)
+    shape, stack, dtype_name = _stack_of(mask)
+    type_char, method, connectivity, rows, param = _reconstruct_args(name, stack, dtype_name, method, connectivity, rows, h)
     if marker is not None and (not isinstance(marker, torch.Tensor) or marker.dtype != mask.dtype or tuple(marker.shape) != shape):
         raise ValueError("%s: the marker must be a tensor of the mask's dtype and shape" % name)
-    if out is not None and (not out.is_cuda or out.dtype != mask.dtype or tuple(out.shape) != shape or not out.is_contiguous()):
-        raise RuntimeError("%s: out must be a contiguous %s CUDA tensor of shape %s" % (name, mask.dtype, shape))
+    out = _out_or_new(out, mask.dtype, shape, mask.device, "%s: out must be a contiguous %s CUDA tensor of shape %s", name, mask.dtype, shape)
     fr = _frames3(mask)
     seed = None if marker is None else _frames3(marker)
     n, height, w = fr.shape
-    if out is None:
-        out = torch.empty(shape, dtype=fr.dtype, device=fr.device)
     rounds = ct.c_int(0)
-    if n:
-        need = _lib.rir_reconstruct_workspace_bytes(type_char, w, height, n)
-        if need == 0:
-            raise RuntimeError("%s: geometry refused" % name)
-        work = _workspace(need, fr.device)
-        _check(_lib.rir_reconstruct_device(type_char, fr.data_ptr(), None if seed is None else seed.data_ptr(), out.data_ptr(), w, height, n, method,
-                                           connectivity, mode, param, output, rows, work.data_ptr(), work.numel() * 8, ct.byref(rounds), _stream()),
-               "rir_reconstruct_device")
+    _queue_with_workspace(_lib.rir_reconstruct_device, _lib.rir_reconstruct_workspace_bytes, (type_char, w, height, n), fr.device, n, type_char,
+                          fr.data_ptr(), None if seed is None else seed.data_ptr(), out.data_ptr(), w, height, n, method, connectivity, mode, param,
+                          output, rows, form=name, after=(ct.byref(rounds),))
     return (out, rounds.value) if return_rounds else out
 
 
@@ -1049,10 +1056,9 @@ def h_basin(frames, h, connectivity=8, rows=None, out=None):
 
 def _regional(name, method, frames, connectivity, rows, out):
     """``regional_maxima`` and ``regional_minima``: where the difference output of a shift by 1 is not 0"""
-    shape = tuple(frames.shape)
-    if out is not None and (not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.bool or tuple(out.shape) != shape):
-        dtype_name = np.dtype(_NP_OF[frames.dtype]).name if frames.dtype in _NP_OF else str(frames.dtype)
-        _reconstruct_args(name, (1,) + shape if len(shape) == 2 else shape, dtype_name, method, connectivity, rows)  # (bad parameters come first)
+    shape, stack, dtype_name = _stack_of(frames)
+    if out is not None and not _is_out(out, (torch.bool,), shape, contiguous=False):  # (torch.ne writes through any strides)
+        _reconstruct_args(name, stack, dtype_name, method, connectivity, rows)  # (bad parameters come first)
         raise RuntimeError("%s: out must be a bool CUDA tensor of shape %s" % (name, shape))
     depth = _reconstruct(name, frames, None, method, connectivity, rows, None, RECONSTRUCT_SHIFT, 1, 1)
     found = torch.ne(depth.view(torch.int16) if depth.dtype == torch.uint16 else depth, 0, out=out)
@@ -1171,17 +1177,11 @@ def _nregions(nregions, lab, check):
     return int(nregions)
 
 
-def _workspace(need, device):
-    """an 8-byte aligned workspace of at least `need` bytes on `device`: work.data_ptr(), work.numel() * 8"""
-    return torch.empty(need // 8 + 1, dtype=torch.int64, device=device)
-
-
 def _region_stats_into(fr, lab, per_frame, nregions, out):
     """queue the statistics of fr [n][h][w] over lab into out (a RegionStats of contiguous [n][nregions] tensors)"""
     n, h, w = fr.shape
-    work = _workspace(_lib.rir_region_stats_workspace_bytes(w, h, n, per_frame, nregions), fr.device)
-    _check(_lib.rir_region_stats_device(fr.data_ptr(), lab.data_ptr(), w, h, n, per_frame, nregions, *(t.data_ptr() for t in out), work.data_ptr(),
-                                        work.numel() * 8, _stream()), "rir_region_stats_device")
+    _queue_with_workspace(_lib.rir_region_stats_device, _lib.rir_region_stats_workspace_bytes, (w, h, n, per_frame, nregions), fr.device, n,
+                          fr.data_ptr(), lab.data_ptr(), w, h, n, per_frame, nregions, *(t.data_ptr() for t in out))
 
 
 def _region_stats_empty(n, nregions, device):
@@ -1219,10 +1219,9 @@ def _region_geometry_into(lab, fr, n, per_frame, nregions, out):
     """queue the geometry of lab ([h][w], or [n][h][w] with per_frame) weighted by fr ([n][h][w], or None) into out (a RegionGeometry of
     contiguous tensors, [n][nregions] leading)"""
     h, w = lab.shape[-2:]
-    work = _workspace(_lib.rir_region_geometry_workspace_bytes(w, h, n, per_frame, nregions, int(fr is not None)), lab.device)
-    _check(_lib.rir_region_geometry_device(lab.data_ptr(), None if fr is None else fr.data_ptr(), w, h, n, per_frame, nregions, out.count.data_ptr(),
-                                           out.bbox.data_ptr(), out.moments.data_ptr(), None if fr is None else out.weighted.data_ptr(),
-                                           work.data_ptr(), work.numel() * 8, _stream()), "rir_region_geometry_device")
+    _queue_with_workspace(_lib.rir_region_geometry_device, _lib.rir_region_geometry_workspace_bytes,
+                          (w, h, n, per_frame, nregions, int(fr is not None)), lab.device, n, lab.data_ptr(), None if fr is None else fr.data_ptr(), w, h, n, per_frame, nregions, out.count.data_ptr(), out.bbox.data_ptr(),
+                          out.moments.data_ptr(), None if fr is None else out.weighted.data_ptr())
 
 
 def _region_geometry_empty(n, nregions, weighted, device):
@@ -1250,10 +1249,8 @@ def region_geometry(labels, nregions=None, frames=None):
 def _region_quantiles_into(fr, lab, per_frame, nregions, percents, out):
     """queue the quantiles of fr [n][h][w] over lab at percents (float32 numpy) into out (a RegionQuantiles of contiguous tensors)"""
     n, h, w = fr.shape
-    work = _workspace(_lib.rir_region_quantiles_workspace_bytes(w, h, n, per_frame, nregions, percents.size), fr.device)
-    _check(_lib.rir_region_quantiles_device(fr.data_ptr(), lab.data_ptr(), w, h, n, per_frame, nregions, percents.ctypes.data, percents.size,
-                                            out.count.data_ptr(), out.values.data_ptr(), work.data_ptr(), work.numel() * 8, _stream()),
-           "rir_region_quantiles_device")
+    _queue_with_workspace(_lib.rir_region_quantiles_device, _lib.rir_region_quantiles_workspace_bytes, (w, h, n, per_frame, nregions, percents.size),
+                          fr.device, n, fr.data_ptr(), lab.data_ptr(), w, h, n, per_frame, nregions, percents.ctypes.data, percents.size, out.count.data_ptr(), out.values.data_ptr())
 
 
 def _region_quantiles_empty(n, nregions, npercents, device):
@@ -1296,10 +1293,9 @@ def _region_histogram_into(fr, lab, per_frame, nregions, rows, out):
     tensors, whose hist, lo and width give the bins)"""
     n, h, w = fr.shape
     nbins = out.hist.shape[-1]
-    work = _workspace(_lib.rir_region_histogram_workspace_bytes(w, h, rows, n, per_frame, nregions, nbins), fr.device)
-    _check(_lib.rir_region_histogram_device(fr.data_ptr(), None if lab is None else lab.data_ptr(), w, h, rows, n, per_frame, nregions, out.lo, out.width,
-                                            nbins, out.count.data_ptr(), out.hist.data_ptr(), out.outside.data_ptr(), work.data_ptr(), work.numel() * 8,
-                                            _stream()), "rir_region_histogram_device")
+    _queue_with_workspace(_lib.rir_region_histogram_device, _lib.rir_region_histogram_workspace_bytes, (w, h, rows, n, per_frame, nregions, nbins),
+                          fr.device, n, fr.data_ptr(), None if lab is None else lab.data_ptr(), w, h, rows, n, per_frame, nregions, out.lo, out.width, nbins, out.count.data_ptr(),
+                          out.hist.data_ptr(), out.outside.data_ptr())
 
 
 def _region_histogram_empty(n, nregions, nbins, lo, width, device):
@@ -1353,12 +1349,10 @@ def _polygon_map_into(xy, npts, values, shifts, per_map, background, out):
     """queue the maps out [n][h][w] (contiguous int32) of the packed polygons xy [(n)][npoly][max_pts][2], npts [(n)][npoly]"""
     n, h, w = out.shape
     npoly, max_pts = xy.shape[-3], xy.shape[-2]
-    need = _lib.rir_polygon_map_workspace_bytes(w, h, n, npoly, max_pts)
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=out.device)
-    _check(_lib.rir_polygon_map_device(xy.data_ptr() if npoly else None, npts.data_ptr() if npoly else None,
-                                       values.data_ptr() if values is not None and npoly else None, npoly, max_pts, n, per_map,
-                                       shifts.data_ptr() if shifts is not None else None, w, h, int(background), out.data_ptr(), work.data_ptr(),
-                                       work.numel() * 8, _stream()), "rir_polygon_map_device")
+    _queue_with_workspace(_lib.rir_polygon_map_device, _lib.rir_polygon_map_workspace_bytes, (w, h, n, npoly, max_pts), out.device, n,
+                          xy.data_ptr() if npoly else None, npts.data_ptr() if npoly else None,
+                          values.data_ptr() if values is not None and npoly else None, npoly, max_pts, n, per_map,
+                          shifts.data_ptr() if shifts is not None else None, w, h, int(background), out.data_ptr())
 
 
 def polygon_map(polygons, shape, values=None, background=-1, shifts=None, out=None):
@@ -1411,10 +1405,9 @@ def _pixel_stats_state(h, w, device, sums, extremes, empty):
 def _pixel_stats_into(fr, t0, accumulate, out):
     """queue the statistics of fr [n][h][w], n >= 1, into out (six contiguous [h][w] tensors or None), written or merged"""
     n, h, w = fr.shape
-    need = _lib.rir_pixel_stats_workspace_bytes(w, h, n)
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
-    _check(_lib.rir_pixel_stats_device(fr.data_ptr(), w, h, n, int(t0), int(accumulate), *(None if t is None else t.data_ptr() for t in out),
-                                       work.data_ptr(), work.numel() * 8, _stream()), "rir_pixel_stats_device")
+    _queue_with_workspace(_lib.rir_pixel_stats_device, _lib.rir_pixel_stats_workspace_bytes, (w, h, n), fr.device, n, fr.data_ptr(), w, h, n, int(t0),
+                          int(accumulate),
+                          *(None if t is None else t.data_ptr() for t in out))
 
 
 def pixel_stats(frames, sums=True, extremes=True, t0=0):
@@ -1516,8 +1509,7 @@ def pixel_quantiles(frames, percents):
     pc = _region_quantiles_percents(percents)
     fr, n, h, w = _pixel_quantile_inputs(frames)
     out = torch.empty((pc.size, h, w), dtype=torch.int32, device=fr.device)
-    need = _lib.rir_pixel_quantiles_workspace_bytes(w, h, n, pc.size)
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    work = _workspace(_lib.rir_pixel_quantiles_workspace_bytes(w, h, n, pc.size), fr.device)  # (queued for no frames too: they give -1 everywhere)
     _check(_lib.rir_pixel_quantiles_device(fr.data_ptr() if n else None, w, h, n, pc.ctypes.data, pc.size, out.data_ptr(), work.data_ptr(),
                                            work.numel() * 8, _stream()), "rir_pixel_quantiles_device")
     return out
@@ -1614,7 +1606,7 @@ def _label_args(image, background):
     need = _lib.rir_label_workspace_bytes(w, h)
     if need == 0:
         raise RuntimeError("label_image: geometry refused")
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=img.device)
+    work = _workspace(need, img.device)
     back = np.zeros(1, dtype=_NP_OF[img.dtype])
     back[0] = background
     return img, ch, h, w, work, back
@@ -1654,7 +1646,7 @@ def _label_batch_args(frames, background):
     need = _lib.rir_label_workspace_bytes_batch(w, h, n)
     if need == 0:
         raise RuntimeError("label_images: geometry refused")
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    work = _workspace(need, fr.device)
     back = np.zeros(1, dtype=_NP_OF[fr.dtype])
     back[0] = background
     return fr, ch, n, h, w, work, back
@@ -1758,7 +1750,7 @@ def _label_hot_spots_into(frames, spec, dst, first, area, count):
     if need == 0:
         raise RuntimeError("label_hot_spots: geometry refused")
     spec = _hot_spot_maps_on(spec, fr.device)
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=fr.device)
+    work = _workspace(need, fr.device)
     _check(_lib.rir_label_hot_spots_device(fr.data_ptr(), w, h, n, spec.rows, spec.low, None if spec.low_map is None else spec.low_map.data_ptr(),
                                            int(spec.use_high), spec.high, None if spec.high_map is None else spec.high_map.data_ptr(),
                                            spec.min_area, spec.max_area, int(spec.clear_border), dst.data_ptr(), first.data_ptr(), area.data_ptr(),
@@ -1863,7 +1855,7 @@ def track_components(labels, counts=None, nlabels=None, table_entries=None, rela
     need = _lib.rir_track_components_workspace_bytes(w, h, n, K)
     if need == 0:
         raise RuntimeError("track_components: geometry refused")
-    work = torch.empty(need // 8 + 1, dtype=torch.int64, device=dev)
+    work = _workspace(need, dev)
     _check(_lib.rir_track_components_device(lab.data_ptr(), None if cnt is None else cnt.data_ptr(), w, h, n, K, track_of.data_ptr(), info.data_ptr(),
                                             *(t.data_ptr() for t in tables), T, None if dst is None else dst.data_ptr(), work.data_ptr(),
                                             work.numel() * 8, _stream()), "rir_track_components_device")

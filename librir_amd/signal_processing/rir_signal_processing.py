@@ -157,6 +157,21 @@ def filter_chain(image, bad_pixels, sigma, dx, dy, strategy="nearest", backgroun
     return out
 
 
+# ---- what the extension forms share ------------------------------------------------------------------------------------------------
+def _host_stack(name, images):
+    """-> (the contiguous array, its view [n][h][w]) of an image or a stack"""
+    img = np.ascontiguousarray(images)
+    if img.ndim not in (2, 3):
+        raise ValueError("%s: an image [h][w] or a stack [n][h][w] expected" % name)
+    return img, img.reshape((-1,) + img.shape[-2:])
+
+
+def _call(name, n, entry, *args):
+    """the entry of the form `name` over `args`, unless there are n = 0 frames to go through; ``RuntimeError`` with the library's words when it fails"""
+    if n and entry(*args) < 0:
+        raise RuntimeError("An error occured while calling '%s': %s" % (name, last_error() or ""))
+
+
 # ---- extension: temporal median of a stack ------------------------------------------------------------------------------------
 _sp.rir_temporal_median.argtypes = [ct.c_void_p, ct.c_void_p, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int, ct.c_int]
 
@@ -195,9 +210,8 @@ def temporal_median(images, window, threshold=0, rows=None):
         raise RuntimeError("temporal_median: a 3-D uint16 stack expected")
     rows, _ = _temporal_median_args(img.shape, window, threshold, rows)
     out = np.empty_like(img)
-    if img.shape[0] and _sp.rir_temporal_median(img.ctypes.data, out.ctypes.data, img.shape[2], img.shape[1], img.shape[0], int(window), int(threshold),
-                                                rows) < 0:
-        raise RuntimeError("An error occured while calling 'temporal_median': " + (last_error() or ""))
+    n, h, w = img.shape
+    _call("temporal_median", n, _sp.rir_temporal_median, img.ctypes.data, out.ctypes.data, w, h, n, int(window), int(threshold), rows)
     return out
 
 
@@ -257,15 +271,11 @@ def morphology(images, op, size, rows=None):
     image), "gradient" (dilate - erode).  Per image this is ``scipy.ndimage.minimum_filter`` / ``maximum_filter(size=size,
     mode="nearest")`` composed stage by stage.  The image is its first ``rows`` rows (default: all); the others are copied.  Returns an
     array of the input's dtype and shape.  ``ValueError`` on bad parameters, ``RuntimeError`` when the library fails."""
-    img = np.ascontiguousarray(images)
-    if img.ndim not in (2, 3):
-        raise ValueError("morphology: an image [h][w] or a stack [n][h][w] expected")
-    stack = img.reshape((-1,) + img.shape[-2:])
+    img, stack = _host_stack("morphology", images)
     type_char, op_number, size_y, size_x, rows = _morphology_args(stack.shape, img.dtype.name, op, size, rows)
     out = np.empty_like(stack)
     n, h, w = stack.shape
-    if n and _sp.rir_morphology(type_char, stack.ctypes.data, out.ctypes.data, w, h, n, op_number, size_x, size_y, rows) < 0:
-        raise RuntimeError("An error occured while calling 'morphology': " + (last_error() or ""))
+    _call("morphology", n, _sp.rir_morphology, type_char, stack.ctypes.data, out.ctypes.data, w, h, n, op_number, size_x, size_y, rows)
     return out.reshape(img.shape)
 
 
@@ -306,15 +316,11 @@ def rank_filter(images, rank, size, rows=None):
     Per image this is ``scipy.ndimage.rank_filter(image, rank, size=size, mode="nearest")``; ``rank = size_y * size_x // 2`` is the median,
     ``percentile_rank`` gives the rank of a percentile.  The image is its first ``rows`` rows (default: all); the others are copied.
     Returns an array of the input's dtype and shape.  ``ValueError`` on bad parameters, ``RuntimeError`` when the library fails."""
-    img = np.ascontiguousarray(images)
-    if img.ndim not in (2, 3):
-        raise ValueError("rank_filter: an image [h][w] or a stack [n][h][w] expected")
-    stack = img.reshape((-1,) + img.shape[-2:])
+    img, stack = _host_stack("rank_filter", images)
     type_char, rank, size_y, size_x, rows = _rank_filter_args(stack.shape, img.dtype.name, rank, size, rows)
     out = np.empty_like(stack)
     n, h, w = stack.shape
-    if n and _sp.rir_rank_filter(type_char, stack.ctypes.data, out.ctypes.data, w, h, n, rank, size_x, size_y, rows) < 0:
-        raise RuntimeError("An error occured while calling 'rank_filter': " + (last_error() or ""))
+    _call("rank_filter", n, _sp.rir_rank_filter, type_char, stack.ctypes.data, out.ctypes.data, w, h, n, rank, size_x, size_y, rows)
     return out.reshape(img.shape)
 
 
@@ -349,14 +355,6 @@ def _local_stats_args(name, shape, dtype_name, size, rows, outputs=None, k=None,
     return type_char, size_y, size_x, _window_rows(name, shape, rows), int(ks[0]), int(ks[1]), int(delta), LOCAL_POLARITIES.index(polarity)
 
 
-def _host_stack(name, images):
-    """-> (the contiguous array, its view [n][h][w]) of an image or a stack"""
-    img = np.ascontiguousarray(images)
-    if img.ndim not in (2, 3):
-        raise ValueError("%s: an image [h][w] or a stack [n][h][w] expected" % name)
-    return img, img.reshape((-1,) + img.shape[-2:])
-
-
 def local_stats(images, size, rows=None, sum=True, sumsq=False, mean=False):
     """Extension: local window statistics of a uint16, uint8 or bool stack ``images[n][h][w]`` (or one image ``[h][w]``) over a centred
     rectangle ``size`` (an odd int, or ``(size_y, size_x)``, each 1..15) (``rir_local_stats``): a ``LocalStats`` of arrays of the input's
@@ -368,8 +366,8 @@ def local_stats(images, size, rows=None, sum=True, sumsq=False, mean=False):
     type_char, size_y, size_x, rows = _local_stats_args("local_stats", stack.shape, img.dtype.name, size, rows, outputs=(sum, sumsq, mean))
     outs = [np.zeros(stack.shape, dt) if want else None for want, dt in ((sum, np.int32), (sumsq, np.int64), (mean, img.dtype))]
     n, h, w = stack.shape
-    if n and _sp.rir_local_stats(type_char, stack.ctypes.data, w, h, n, size_x, size_y, rows, *(None if o is None else o.ctypes.data for o in outs)) < 0:
-        raise RuntimeError("An error occured while calling 'local_stats': " + (last_error() or ""))
+    _call("local_stats", n, _sp.rir_local_stats, type_char, stack.ctypes.data, w, h, n, size_x, size_y, rows,
+          *(None if o is None else o.ctypes.data for o in outs))
     return LocalStats(*(None if o is None else o.reshape(img.shape) for o in outs), size_y * size_x)
 
 
@@ -384,8 +382,8 @@ def local_threshold(images, size, k, delta=0, polarity="above", rows=None):
                                                                                        delta=delta, polarity=polarity)
     out = np.zeros(stack.shape, np.bool_)
     n, h, w = stack.shape
-    if n and _sp.rir_local_threshold(type_char, stack.ctypes.data, out.ctypes.data, w, h, n, size_x, size_y, rows, k_num, k_den, delta, polarity) < 0:
-        raise RuntimeError("An error occured while calling 'local_threshold': " + (last_error() or ""))
+    _call("local_threshold", n, _sp.rir_local_threshold, type_char, stack.ctypes.data, out.ctypes.data, w, h, n, size_x, size_y, rows, k_num, k_den, delta,
+          polarity)
     return out.reshape(img.shape)
 
 
@@ -413,10 +411,7 @@ def _reconstruct_args(name, shape, dtype_name, method, connectivity, rows, h=_NO
 
 
 def _reconstruct_host(name, images, marker, method, connectivity, rows, mode, h, output):
-    img = np.ascontiguousarray(images)
-    if img.ndim not in (2, 3):
-        raise ValueError("%s: an image [h][w] or a stack [n][h][w] expected" % name)
-    stack = img.reshape((-1,) + img.shape[-2:])
+    img, stack = _host_stack(name, images)
     type_char, method, connectivity, rows, param = _reconstruct_args(name, stack.shape, img.dtype.name, method, connectivity, rows, h)
     seed = None
     if marker is not None:
@@ -425,9 +420,8 @@ def _reconstruct_host(name, images, marker, method, connectivity, rows, mode, h,
             raise ValueError("%s: the marker must have the mask's dtype and shape" % name)
     out = np.empty_like(stack)
     n, height, w = stack.shape
-    if n and _sp.rir_reconstruct(type_char, stack.ctypes.data, None if seed is None else seed.ctypes.data, out.ctypes.data, w, height, n, method,
-                                 connectivity, mode, param, output, rows, None) < 0:
-        raise RuntimeError("An error occured while calling '%s': %s" % (name, last_error() or ""))
+    _call(name, n, _sp.rir_reconstruct, type_char, stack.ctypes.data, None if seed is None else seed.ctypes.data, out.ctypes.data, w, height, n, method,
+          connectivity, mode, param, output, rows, None)
     return out.reshape(img.shape)
 
 
@@ -496,17 +490,13 @@ def distance_transform(images, background=0, border=False, rows=None, return_ind
     ``y * w + x`` among the nearest background pixels, -1 where there is none or the outside is strictly nearer, a pixel's own index in
     the rows outside the image (scipy's ``return_indices`` breaks ties differently).  At most 16 384 rows and columns.  ``ValueError`` on
     bad parameters, ``RuntimeError`` when the library fails."""
-    img = np.ascontiguousarray(images)
-    if img.ndim not in (2, 3):
-        raise ValueError("distance_transform: an image [h][w] or a stack [n][h][w] expected")
-    stack = img.reshape((-1,) + img.shape[-2:])
+    img, stack = _host_stack("distance_transform", images)
     type_char, background, border, rows = _distance_transform_args(stack.shape, img.dtype.name, background, border, rows)
     n, h, w = stack.shape
     dist2 = np.empty(stack.shape, np.int32)
     index = np.empty(stack.shape, np.int32) if return_indices else None
-    if n and _sp.rir_distance_transform(type_char, stack.ctypes.data, w, h, n, background, border, rows, dist2.ctypes.data,
-                                        index.ctypes.data if return_indices else None) < 0:
-        raise RuntimeError("An error occured while calling 'distance_transform': " + (last_error() or ""))
+    _call("distance_transform", n, _sp.rir_distance_transform, type_char, stack.ctypes.data, w, h, n, background, border, rows, dist2.ctypes.data,
+          index.ctypes.data if return_indices else None)
     dist2 = dist2.reshape(img.shape)
     return (dist2, index.reshape(img.shape)) if return_indices else dist2
 
@@ -581,8 +571,7 @@ def region_stats(images, labels, nregions=None):
         _region_stats_args(img.shape, lab.shape, nregions)
     k = int(nregions)
     out = RegionStats(*(np.empty((n, k), dt) for dt in (np.int32, np.int64, np.int64, np.int32, np.int32, np.int32, np.int32)))
-    if n and _sp.rir_region_stats(img.ctypes.data, lab.ctypes.data, w, h, n, per_frame, k, *(a.ctypes.data for a in out)) < 0:
-        raise RuntimeError("An error occured while calling 'region_stats': " + (last_error() or ""))
+    _call("region_stats", n, _sp.rir_region_stats, img.ctypes.data, lab.ctypes.data, w, h, n, per_frame, k, *(a.ctypes.data for a in out))
     return out
 
 
@@ -694,9 +683,8 @@ def region_geometry(labels, nregions=None, frames=None):
     k = int(nregions)
     out = RegionGeometry(np.empty((n, k), np.int32), np.empty((n, k, 4), np.int32), np.empty((n, k, 5), np.int64),
                          None if img is None else np.empty((n, k, 3), np.int64))
-    if n and _sp.rir_region_geometry(lab.ctypes.data, None if img is None else img.ctypes.data, w, h, n, per_frame, k, out.count.ctypes.data,
-                                     out.bbox.ctypes.data, out.moments.ctypes.data, None if img is None else out.weighted.ctypes.data) < 0:
-        raise RuntimeError("An error occured while calling 'region_geometry': " + (last_error() or ""))
+    _call("region_geometry", n, _sp.rir_region_geometry, lab.ctypes.data, None if img is None else img.ctypes.data, w, h, n, per_frame, k,
+          out.count.ctypes.data, out.bbox.ctypes.data, out.moments.ctypes.data, None if img is None else out.weighted.ctypes.data)
     return out
 
 
@@ -749,9 +737,8 @@ def region_quantiles(images, labels, percents, nregions=None):
         _region_quantiles_args(img.shape, lab.shape, nregions)
     k = int(nregions)
     out = RegionQuantiles(np.empty((n, k), np.int32), np.empty((n, k, pc.size), np.int32))
-    if n and _sp.rir_region_quantiles(img.ctypes.data, lab.ctypes.data, w, h, n, per_frame, k, pc.ctypes.data, pc.size, out.count.ctypes.data,
-                                      out.values.ctypes.data) < 0:
-        raise RuntimeError("An error occured while calling 'region_quantiles': " + (last_error() or ""))
+    _call("region_quantiles", n, _sp.rir_region_quantiles, img.ctypes.data, lab.ctypes.data, w, h, n, per_frame, k, pc.ctypes.data, pc.size,
+          out.count.ctypes.data, out.values.ctypes.data)
     return out
 
 
@@ -892,9 +879,8 @@ def region_histogram(images, labels, nbins, lo=0, width=1, nregions=None, rows=N
         _region_histogram_args(*shapes, nbins, lo, width, nregions, rows)
     k = int(nregions)
     out = RegionHistogram(np.zeros((n, k), np.int32), np.zeros((n, k, nbins), np.int32), np.zeros((n, k, 2), np.int32), lo, width)
-    if n and _sp.rir_region_histogram(img.ctypes.data, None if lab is None else lab.ctypes.data, w, h, rows, n, per_frame, k, lo, width, nbins,
-                                      out.count.ctypes.data, out.hist.ctypes.data, out.outside.ctypes.data) < 0:
-        raise RuntimeError("An error occured while calling 'region_histogram': " + (last_error() or ""))
+    _call("region_histogram", n, _sp.rir_region_histogram, img.ctypes.data, None if lab is None else lab.ctypes.data, w, h, rows, n, per_frame, k, lo, width,
+          nbins, out.count.ctypes.data, out.hist.ctypes.data, out.outside.ctypes.data)
     return out
 
 
@@ -965,8 +951,7 @@ def pixel_stats(images, sums=True, extremes=True):
     n, h, w = _pixel_stats_args(img.shape, sums, extremes)
     on = (sums, sums, extremes, extremes, extremes, extremes)
     out = [np.full((h, w), 0 if k < 2 else -1, dt) if g else None for k, (g, dt) in enumerate(zip(on, _PIXEL_DTYPES))]
-    if n and _sp.rir_pixel_stats(img.ctypes.data, w, h, n, *(a.ctypes.data if a is not None else None for a in out)) < 0:
-        raise RuntimeError("An error occured while calling 'pixel_stats': " + (last_error() or ""))
+    _call("pixel_stats", n, _sp.rir_pixel_stats, img.ctypes.data, w, h, n, *(a.ctypes.data if a is not None else None for a in out))
     return PixelStats(*out, count=n)
 
 
@@ -997,8 +982,8 @@ def pixel_quantiles(images, percents):
     pc = _region_quantiles_percents(percents)
     n, h, w = _pixel_quantiles_args(img.shape)
     out = np.empty((pc.size, h, w), np.int32)
-    if _sp.rir_pixel_quantiles(img.ctypes.data if n else None, w, h, n, pc.ctypes.data, pc.size, out.ctypes.data) < 0:
-        raise RuntimeError("An error occured while calling 'pixel_quantiles': " + (last_error() or ""))
+    _call("pixel_quantiles", True, _sp.rir_pixel_quantiles, img.ctypes.data if n else None, w, h, n, pc.ctypes.data, pc.size,
+          out.ctypes.data)  # (called for no images too: it is the entry that fills in the -1)
     return out
 
 
@@ -1110,10 +1095,9 @@ def polygon_map(polygons, shape, values=None, background=-1, shifts=None, out=No
         out = np.empty(a.out_shape, np.int32)
     elif not isinstance(out, np.ndarray) or out.dtype != np.int32 or out.shape != a.out_shape or not out.flags.c_contiguous:
         raise RuntimeError("polygon_map: out must be a contiguous int32 array of shape %s" % (a.out_shape,))
-    if a.nmaps and _sp.rir_polygon_map(xy.ctypes.data if a.npoly else None, npts.ctypes.data if a.npoly else None,
-                                       a.values.ctypes.data if a.values is not None and a.npoly else None, a.npoly, a.max_pts, a.nmaps, a.per_map,
-                                       a.shifts.ctypes.data if a.shifts is not None else None, a.w, a.h, int(background), out.ctypes.data) < 0:
-        raise RuntimeError("An error occured while calling 'polygon_map': " + (last_error() or ""))
+    _call("polygon_map", a.nmaps, _sp.rir_polygon_map, xy.ctypes.data if a.npoly else None, npts.ctypes.data if a.npoly else None,
+          a.values.ctypes.data if a.values is not None and a.npoly else None, a.npoly, a.max_pts, a.nmaps, a.per_map,
+          a.shifts.ctypes.data if a.shifts is not None else None, a.w, a.h, int(background), out.ctypes.data)
     return out
 
 
