@@ -662,8 +662,8 @@ extern "C"
 	 *
 	 * rir_downsampler_create: a handle > 0 in the common handle namespace, 0 on failure (invalid argument, no device).
 	 * rir_downsampler_push_device: the next nframes images of the stream; returns the number of images kept by this push (written to
-	 * d_out[0 .. kept), capacity nframes images, which may not overlap d_frames), or -1 (invalid argument, time stamps, overlap, no
-	 * device: the state is untouched).  timestamps: HOST [nframes]; positions: HOST int[nframes], positions[k] = the index within this
+	 * d_out[0 .. kept), capacity nframes images, which may not overlap d_frames), or -1 (invalid argument, time stamps, overlap, more than
+	 * 4 194 240 images in one push with a factor above 1, no device: the state is untouched).  timestamps: HOST [nframes]; positions: HOST int[nframes], positions[k] = the index within this
 	 * push of the image that triggered output k, whose time stamp and attributes go with it; stats: HOST double[nframes] or NULL,
 	 * stats[i] = the statistic of image i, 0 for the very first image of the stream and for factor 1.  Two passes over the frames
 	 * (pair sums, then the maxima of the kept images) with the recurrence on the host between them: the call waits ONCE for `stream`,

@@ -274,6 +274,12 @@ RIR_EXPORT int rir_downsampler_push_device(int handle, const unsigned short *d_f
 	}
 	if (nframes == 0)
 		return 0;
+	if (o->factor != 1 && nframes > DS_MAX_FRAMES)
+	{
+		log_error("rir_downsampler_push_device: " + std::to_string(nframes) + " images in one push, at most " + std::to_string(DS_MAX_FRAMES) +
+				  " (65535 slabs of " + std::to_string(DS_SLAB) + " for the pair sums): push the stack in pieces");
+		return -1;
+	}
 	const size_t npx = (size_t)o->w * o->h, size = (size_t)o->w * o->lossy_height, image = npx * sizeof(uint16_t);
 	for (int i = 0; i < nframes; ++i)
 		if (i > 0 ? timestamps[i] <= timestamps[i - 1] : (o->any_stamp && timestamps[0] <= o->last_stamp))

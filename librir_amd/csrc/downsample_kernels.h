@@ -7,6 +7,7 @@
 namespace rir
 {
 	constexpr int DS_SLAB = 64; // frames a workgroup of the pair sums walks: a stack is cut along time every DS_SLAB frames
+	constexpr int DS_MAX_FRAMES = 65535 * DS_SLAB; // the frames launch_pair_sums takes: its slabs are the grid's second dimension
 
 	// One kept image (slot >= 0: image `slot` of the output) or the open trailing run (slot < 0: the carried maximum) of the max-hold:
 	// source frames first .. last of this push, and whether the maximum carried in from the push before takes part.

@@ -22,6 +22,11 @@ def cuda(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
+def gaussian_close(g, r):
+    """the float32 gaussian against the oracle's: within 2e-6 of the largest value (the order of the sums differs, not the terms)"""
+    return np.abs(g - r).max() <= 2e-6 * np.abs(r).max()
+
+
 # ---- find_median_pixel ---------------------------------------------------------------------------------------------------------------
 
 
@@ -381,7 +386,7 @@ def test_gaussian_full_range(dev, oracle):
         inputs = (cuda(fr.astype(np.float32)),) + ((cuda(fr),) if s < 2.5 else ())
         for x in inputs:
             g = dev.gaussian_filter(x, s).cpu().numpy()
-            assert np.abs(g - r).max() <= 2e-6 * np.abs(r).max(), (s, x.dtype)
+            assert gaussian_close(g, r), (s, x.dtype)
 
 
 def test_gaussian_full_range_in_reference_order(dev, oracle, reference_order):
